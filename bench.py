@@ -13,6 +13,10 @@ N ranks shard the 12 x 200k source queries evenly (strong scaling: the job is th
 same 12-view ring at every N).  value = forward source queries of all ranks / s.
 
 Contract: python bench.py --gpus N --steps K --warmup W ; one JSON line on rank 0.
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else the line has
+carried: repeated and settled windows, rooflines from a profiled re-run and a brute-force pass, a cold registration, the
+projected scaling, the 36 x 1M leg, the sequential mode and the CPU baselines.  --dump-outputs DIR writes what the last
+timed step computed as DIR/<name>.npy (inputs are seeded: the same arguments give the same inputs on every run).
 """
 from __future__ import annotations
 
@@ -80,6 +84,23 @@ def launch_ranks(n, argv, count_gpus=visible_gpus):
     return 0
 
 
+# what one pass of the timed path hands its caller (RingLUM.run: the new poses; RingLUM.last: the rest), by file name
+DUMPED_INFO = {"pair_T": "pair_transforms", "pair_n": "pair_correspondences", "pair_mse": "pair_mse", "lum_pose": "lum_pose",
+               "rows": "edge_table"}
+
+
+def dump_outputs(out_dir, poses, last):
+    """--dump-outputs: the last timed pass's results as out_dir/<name>.npy, float32 where the library returns float32, else float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"poses": np.asarray(poses, np.float64)}
+    for key, name in DUMPED_INFO.items():
+        if key in last:
+            a = np.asarray(last[key])
+            arrays[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     # stdout carries exactly ONE line (the JSON): libraries that print banners to
     # fd 1 (RCCL prints its version there) are diverted to stderr until the end
@@ -94,6 +115,10 @@ def main():
     ap.add_argument("--points", type=int, default=200000)
     ap.add_argument("--max-dist", type=float, default=4.0)
     ap.add_argument("--fma", type=int, default=0, help="1: fma distance chain instead of the spec's rounded-per-op form")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline window (the --no-* legs and --repeats below apply to it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (poses, per-pair transforms, counts, residuals, edge table) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--nn-mode", type=int, default=1, help="1: exact culled search (default); 0: exact brute force")
     ap.add_argument("--no-bruteforce-pass", action="store_true",
@@ -106,6 +131,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=5,
                     help="the timed K-step window is repeated this many times after the headline one: min/median/max as extra keys")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: this process stays a plain parent (it never imports torch nor
@@ -220,9 +247,11 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     ctx.prof_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state["poses"], reg.last)
     # the same K-step window again, `--repeats` times (each from the prior, like the headline one): spread of the number
     rep_s = []
-    for _ in range(max(args.repeats, 0)):
+    for _ in range(max(args.repeats, 0) if args.full else 0):
         reset()
         barrier()
         tr = time.perf_counter()
@@ -232,7 +261,7 @@ def main():
     # ... and K more passes that CONTINUE the last window instead of restarting from the prior: what a pass costs once the
     # registration has settled (the windows above each pay for a pass whose every seed is 2 mm off; `value` stays the first one)
     conv_s = None
-    if max(args.repeats, 0) > 0 and not use_dist:
+    if args.full and max(args.repeats, 0) > 0 and not use_dist:
         run(args.steps)
         barrier()
         tc = time.perf_counter()
@@ -362,7 +391,7 @@ def main():
     # pairs of the fused pass, would otherwise overlap on worker streams and a launch's duration would include
     # its neighbours.)
     iso = None
-    if world == 1:
+    if args.full and world == 1:
         ctx.tune(pair_streams=1, pair_groups=1)
         reset(); run(max(args.warmup, 1)); reset()          # the same warm-up as the timed region (seeded searches see the same history)
         ctx.prof_reset(); ctx.prof_enable(1)
@@ -383,7 +412,7 @@ def main():
         out["step_breakdown_ms"]["gpu_idle_ms_profiled_run"] = max(0.0, iso["ms_per_step"] - kern_ms)
     # the brute-force kernel (the plain VALU-roofline kernel) on the same pairs: one extra, untimed ring pass
     bf = None
-    if world == 1 and not args.no_bruteforce_pass:
+    if args.full and world == 1 and not args.no_bruteforce_pass:
         ctx.tune(nn_mode=0, pair_streams=1)
         reset()
         step()
@@ -447,7 +476,7 @@ def main():
                 extra["culling_factor"] = brute_equiv / (iev / args.steps)
                 extra["bruteforce_equivalent_tflops"] = FLOP_PER_EVAL * brute_equiv / (ims * 1e-3 / args.steps) / 1e12
         out["roofline"] = nn_roofline(kname, il, ims, iev, ktraffic, extra)
-    if nn_launches and not grid_dominant:      # the same kernel inside the timed region, overlapped with other pairs' kernels
+    if args.full and nn_launches and not grid_dominant:      # the same kernel inside the timed region, overlapped with other pairs' kernels
         r = nn_roofline(kname, nn_launches, nn_ms, nn_evals, ktraffic,
                         {"measured": "timed region (only the NN launches carry HIP events there; evaluations from running totals)"})
         if "roofline" in out:
@@ -456,7 +485,7 @@ def main():
             out["roofline"] = r
     if bf:
         out["roofline_bruteforce"] = bf
-    if rd_launches:
+    if args.full and rd_launches:
         out["roofline_hbm"] = {
             "kernel": "pass1 + moments2 reductions (K5/K8)", "bound": "hbm",
             "achieved": rd_bytes / (rd_ms * 1e-3) / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
@@ -473,7 +502,7 @@ def main():
     # What a registration costs from a standing start, beside the steady state above: a FRESH context, the uploads, then K
     # passes from the prior in one native call -- no prewarm, no seeds, the orderings and grids built on the way (the reference
     # builds its kd-trees inside every align, registrator.cpp:569, and cpu_baseline pays for them too)
-    if world == 1 and not args.no_secondary:
+    if args.full and world == 1 and not args.no_secondary:
         cold_ctx = mvr.Context(local_rank)
         try:
             cold_ctx.tune(nn_mode=args.nn_mode)
@@ -500,7 +529,7 @@ def main():
     # What ONE rank of a world of 2 / 4 / 8 would do per pass, measured on this one GPU (tools/rank_share_bench.py): a PROJECTION of
     # the multi-GPU critical path (the rank's chain, the pass's ncclAllReduce really issued on a communicator of one rank, the
     # absent peers' rows added behind it, the replicated solve) -- not a scaling run: the fabric and the ranks' skew are not in it
-    if world == 1 and not args.no_secondary and not args.no_projection:
+    if args.full and world == 1 and not args.no_secondary and not args.no_projection:
         import importlib.util as _ilu
         spec = _ilu.spec_from_file_location("rank_share_bench", os.path.join(ROOT, "tools", "rank_share_bench.py"))
         rsb = _ilu.module_from_spec(spec); spec.loader.exec_module(rsb)
@@ -531,9 +560,9 @@ def main():
         finally:
             pctx.close()
 
-    # BASELINE configs[4]'s shape (36 views x 1M points: the working set is far beyond the caches) as a short leg of the default line,
-    # so that the driver's record carries a number for it: a few timed passes on one GPU and the roofline fraction of the walk launches
-    if world == 1 and not args.no_secondary and not args.no_stress and V == 12 and N == 200000:
+    # BASELINE configs[4]'s shape (36 views x 1M points: the working set is far beyond the caches) as a short leg of the --full line,
+    # so that its record carries a number for it: a few timed passes on one GPU and the roofline fraction of the walk launches
+    if args.full and world == 1 and not args.no_secondary and not args.no_stress and V == 12 and N == 200000:
         Vs, Ns_ = 36, 1000000
         sctx = mvr.Context(local_rank)
         try:
@@ -599,7 +628,7 @@ def main():
                 first = [p.copy() for p in poses]
         return first, ncorr, per_sweep, order
     seq = None
-    if world == 1 and V >= 4 and not args.no_secondary:
+    if args.full and world == 1 and V >= 4 and not args.no_secondary:
         ctx.tune(nn_mode=args.nn_mode, pair_streams=6, pair_groups=2)
         sequential_sweeps(1)                                            # warm-up: allocations, orderings
         # the warm-up aligned the same scans from the same poses: the seeds it left (seq_seed) are forgotten, so that the timed
@@ -619,7 +648,7 @@ def main():
                "n_corr": seq_ncorr}
         out["secondary_sequential"] = seq
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle as orc    # checker only: the CPU restatement timed beside the GPU path
         t0 = time.perf_counter()
         clouds = [orc.transform_f64(poses0[v], scans[v]) for v in range(V)]

@@ -10,9 +10,9 @@ case "$1" in
 part1)
   timeout -k 10 700 python -m pytest tests -m gpu -x -q -p no:cacheprovider > $O/pytest_gpu.log 2>&1 || { tail -20 $O/pytest_gpu.log; exit 1; }
   tail -1 $O/pytest_gpu.log
-  timeout -k 10 400 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err || { tail -5 $O/bench_n1.err; exit 1; }
+  timeout -k 10 400 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err || { tail -5 $O/bench_n1.err; exit 1; }
   echo bench done
-  MVR_BENCH_FORCE_DIST=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 10 --warmup 3 \
+  MVR_BENCH_FORCE_DIST=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 10 --warmup 3 --full \
       --no-cpu-baseline --no-bruteforce-pass > $O/bench_torchrun_1rank_rccl.json 2> $O/torchrun.err || { tail -5 $O/torchrun.err; exit 1; }
   echo torchrun done
   ;&
@@ -25,7 +25,7 @@ stats)
   export MVR_BENCH_PREWARM=0
   for g in 1 2; do
     export MVR_PAIR_GROUPS=$g
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_g$g -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-bruteforce-pass --no-secondary --repeats 0 > $O/bench_under_rocprof_groups$g.json 2> $O/rocprof_g$g.err || { tail -5 $O/rocprof_g$g.err; exit 1; }
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_g$g -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-bruteforce-pass --no-secondary --repeats 0 > $O/bench_under_rocprof_groups$g.json 2> $O/rocprof_g$g.err || { tail -5 $O/rocprof_g$g.err; exit 1; }
     cp $(find $O/stats_g$g -name "*kernel_stats.csv" | head -1) $O/bench_n1_kernel_stats_groups$g.csv
   done
   unset MVR_PAIR_GROUPS
@@ -81,7 +81,7 @@ P
   ;;
 part3)
   # config 5's shape on one GPU: the bench line with >= 10 timed steps, the kernel statistics and the counters at ITS size
-  timeout -k 10 900 python bench.py --views 36 --points 1000000 --steps 10 --warmup 2 --repeats 2 --no-cpu-baseline > $O/bench_n1_stress_36x1M.json 2> $O/stress.err || { tail -5 $O/stress.err; exit 1; }
+  timeout -k 10 900 python bench.py --full --views 36 --points 1000000 --steps 10 --warmup 2 --repeats 2 --no-cpu-baseline > $O/bench_n1_stress_36x1M.json 2> $O/stress.err || { tail -5 $O/stress.err; exit 1; }
   echo stress done
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_36x1M -- python3 $R/tools/step_probe.py 36 1000000 12 6 > $O/step_probe_36x1M_under_rocprof.json 2> $O/rocprof_36.err || { tail -5 $O/rocprof_36.err; exit 1; }

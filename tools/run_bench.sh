@@ -1,7 +1,7 @@
 #!/bin/bash
-# the default bench line into gpurun_out/bench/<tag>.json, with a one-screen digest:  tools/run_bench.sh <tag> [bench flags]
+# the full bench line (bench.py --full) with a one-screen digest:  tools/run_bench.sh <tag> [bench flags]
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/bench; mkdir -p $O; cd $R; tag=$1; shift
-( time timeout -k 10 900 python bench.py "$@" ) > $O/$tag.json 2> $O/$tag.err; echo "rc=$?"
+( time timeout -k 10 900 python bench.py --full "$@" ) > $O/$tag.json 2> $O/$tag.err; echo "rc=$?"
 grep -v amdgpu.ids $O/$tag.err | tail -6
 python3 - $O/$tag.json <<'P'
 import json, sys

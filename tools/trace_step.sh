@@ -2,7 +2,7 @@
 # kernel timeline of one bench step (rocprofv3 --kernel-trace): tools/trace_step.sh <views> <points> [step index]
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/trace_step; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --output-format csv -d $O -- python3 $R/bench.py --views $1 --points $2 --steps 12 --warmup 3 --no-cpu-baseline --no-bruteforce-pass > $O/bench.json 2> $O/bench.err || exit 1
+rocprofv3 --kernel-trace --output-format csv -d $O -- python3 $R/bench.py --full --views $1 --points $2 --steps 12 --warmup 3 --no-cpu-baseline --no-bruteforce-pass > $O/bench.json 2> $O/bench.err || exit 1
 python3 - "$(find $O -name '*kernel_trace.csv' | head -1)" "${3:-8}" <<'P'
 import csv, sys
 rows=list(csv.DictReader(open(sys.argv[1]))); rows.sort(key=lambda r:int(r['Start_Timestamp']))
