@@ -18,6 +18,7 @@
 #include <cmath>
 #include <cstdio>
 #include <string>
+#include <vector>
 
 #include "../mvr_hip.h"
 #include "types.hpp"
@@ -163,6 +164,77 @@ class IterativeClosestPoint {
   bool converged_ = false, aligned_once_ = false;
   int state_ = MVR_CONV_NOT;
   SlotGuard src_, tgt_, out_;
+};
+
+// ---------------------------------------------------------------- normals
+namespace search {
+// pcl::search::KdTree: accepted and ignored -- the neighbour search is the library's grid walk on the GPU
+template <typename PointT>
+class KdTree {
+ public:
+  typedef std::shared_ptr<KdTree<PointT> > Ptr;
+  typedef std::shared_ptr<const KdTree<PointT> > ConstPtr;
+  explicit KdTree(bool sorted = true) { (void)sorted; }
+  void setInputCloud(const typename PointCloud<PointT>::ConstPtr &) {}
+};
+}  // namespace search
+
+// pcl::NormalEstimation<PointInT, PointOutT> (features/normal_3d.h): setKSearch XOR setRadiusSearch, setViewPoint, compute.
+// Semantics: mvr_cloud_estimate_normals (mvr_hip.h).  As PCL's Feature::compute, a call with both or neither of k / radius
+// set prints an error and leaves `output` empty.
+template <typename PointInT, typename PointOutT>
+class NormalEstimation {
+ public:
+  typedef PointCloud<PointInT> PointCloudIn;
+  typedef typename PointCloudIn::ConstPtr PointCloudConstPtr;
+  typedef PointCloud<PointOutT> PointCloudOut;
+  typedef search::KdTree<PointInT> KdTree;
+  typedef typename KdTree::Ptr KdTreePtr;
+
+  void setInputCloud(const PointCloudConstPtr &c) { input_ = c; }
+  PointCloudConstPtr getInputCloud() const { return input_; }
+  void setSearchMethod(const KdTreePtr &tree) { tree_ = tree; }
+  KdTreePtr getSearchMethod() const { return tree_; }
+  void setKSearch(int k) { k_ = k; }
+  int getKSearch() const { return k_; }
+  void setRadiusSearch(double r) { radius_ = r; }
+  double getRadiusSearch() const { return radius_; }
+  void setViewPoint(float vpx, float vpy, float vpz) { vp_[0] = vpx; vp_[1] = vpy; vp_[2] = vpz; }
+  void getViewPoint(float &vpx, float &vpy, float &vpz) const { vpx = vp_[0]; vpy = vp_[1]; vpz = vp_[2]; }
+
+  void compute(PointCloudOut &output)
+  {
+    output.clear();
+    if (!input_) { std::fprintf(stderr, "[NormalEstimation::compute] No input dataset was given!\n"); return; }
+    if ((k_ != 0) == (radius_ != 0.0)) {
+      std::fprintf(stderr, "[NormalEstimation::compute] Set exactly one of setKSearch / setRadiusSearch (k = %d, radius = %f).\n", k_, radius_);
+      return;
+    }
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.upload(s.s, *input_);
+    const size_t n = input_->size();
+    std::vector<float> curv(n ? n : 1), nrm(4 * (n ? n : 1));
+    mvr_normal_params p;
+    p.k = k_; p.radius = radius_; p.fma_dist = 0;
+    for (int j = 0; j < 3; ++j) p.viewpoint[j] = vp_[j];
+    float *cp = curv.data();
+    d.check(mvr_cloud_estimate_normals(d.ctx(), 1, &s.s, &p, &cp), "mvr_cloud_estimate_normals");
+    size_t got = 0;
+    if (n) d.check(mvr_cloud_download_normals(d.ctx(), s.s, nrm.data(), n, 16, &got), "mvr_cloud_download_normals");
+    output.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+      PointOutT &o = output.points[i];
+      o.normal_x = nrm[4 * i]; o.normal_y = nrm[4 * i + 1]; o.normal_z = nrm[4 * i + 2]; o.curvature = curv[i];
+    }
+  }
+
+ private:
+  PointCloudConstPtr input_;
+  KdTreePtr tree_;
+  int k_ = 0;
+  double radius_ = 0.0;
+  float vp_[3] = {0.f, 0.f, 0.f};
 };
 
 namespace registration {

@@ -129,6 +129,34 @@ class ScanCloud {
     return before - kept;
   }
 
+  // EXTENSION (pcl::NormalEstimation on the raw points, viewpoint at the origin -- the sensor of a raw turntable scan):
+  // k nearest neighbours (k > 0) or every point within `radius` (k = 0) per point, on the GPU.  Fills the normals and the
+  // curvature of `rich` (made from `points` first when it does not hold one record per point); `points` and the pose stay as
+  // they are.  save() and Registrator::saveRegisteredPoints then write these normals.
+  void estimateNormals(int k, double radius = 0.0)
+  {
+    Device &d = Device::instance();
+    SlotGuard s;
+    const size_t n = points.size();
+    if (rich.size() != n) {
+      io::RichCloud r(n);
+      for (size_t i = 0; i < n; ++i) { r[i].x = points.points[i].x; r[i].y = points.points[i].y; r[i].z = points.points[i].z; }
+      rich.swap(r);
+    }
+    d.upload(s.s, points);
+    mvr_normal_params p;
+    p.k = k; p.radius = radius; p.fma_dist = 0;
+    p.viewpoint[0] = p.viewpoint[1] = p.viewpoint[2] = 0.f;
+    std::vector<float> curv(n ? n : 1), nrm(4 * (n ? n : 1));
+    float *cp = curv.data();
+    d.check(mvr_cloud_estimate_normals(d.ctx(), 1, &s.s, &p, &cp), "mvr_cloud_estimate_normals");
+    size_t got = 0;
+    if (n) d.check(mvr_cloud_download_normals(d.ctx(), s.s, nrm.data(), n, 16, &got), "mvr_cloud_download_normals");
+    for (size_t i = 0; i < n; ++i) {
+      rich[i].normal_x = nrm[4 * i]; rich[i].normal_y = nrm[4 * i + 1]; rich[i].normal_z = nrm[4 * i + 2]; rich[i].curvature = curv[i];
+    }
+  }
+
   // point_cloud.cpp:305-326 / :328-347 -- `transformation.txt`: the column-vector
   // 4x4 printed row by row (matrix(j,i), i outer), "%lf " per element, one row per
   // line.  6 decimals: poses round-trip to 1e-6 only.

@@ -29,6 +29,21 @@ struct alignas(16) PointXYZ {
 };
 static_assert(sizeof(PointXYZ) == 16, "PointXYZ must match pcl::PointXYZ");
 
+// pcl::Normal: normal[4] (normal_x / y / z, padding) and curvature, 32 bytes as in PCL
+struct alignas(16) Normal {
+  union {
+    float normal[4];
+    struct { float normal_x, normal_y, normal_z; };
+  };
+  union {
+    struct { float curvature; };
+    float data_c[4];
+  };
+  Normal() : normal{0.f, 0.f, 0.f, 0.f}, data_c{0.f, 0.f, 0.f, 0.f} {}
+  Normal(float nx, float ny, float nz) : normal{nx, ny, nz, 0.f}, data_c{0.f, 0.f, 0.f, 0.f} {}
+};
+static_assert(sizeof(Normal) == 32, "Normal must match pcl::Normal");
+
 // pcl::PointCloud<PointT> (the members the reference touches: points, size,
 // at, operator[], push_back, clear, operator+=, Ptr; registrator.cpp:548-576,
 // point_cloud.cpp:290-303).

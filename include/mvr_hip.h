@@ -163,6 +163,47 @@ int  mvr_cloud_download_normals(mvr_ctx *ctx, int slot, float *nxyz, size_t cap_
  * index.  idx = UINT32_MAX and d2 = +inf when the target is empty. */
 int  mvr_nn(mvr_ctx *ctx, int q_slot, int t_slot, int fma_dist, uint32_t *idx, float *d2);
 
+/* ---- k nearest neighbours and normal estimation (EXTENSION: pcl::NormalEstimation) -----------------------
+ * Distances are the f32 expression of mvr_nn, selected by fma_dist the same way:
+ * d2 = (dx*dx + dy*dy) + dz*dz, each operation rounded (fma_dist = 1: the fma chain).
+ *
+ * k-NN of a query point q in a target cloud T: the k entries of T smallest under the key (d2, index) in
+ * lexicographic order, ascending -- ties go to the lower index, as in mvr_nn.  When T holds fewer than k
+ * points the tail entries are idx = UINT32_MAX, d2 = +inf (mvr_nn's empty-target convention).  k = 1 gives
+ * exactly mvr_nn's (idx, d2), bit for bit.  The search is exact: a uniform grid over T's current
+ * coordinates, walked shell by shell until no unvisited cell can hold a point within the k-th d2. */
+#define MVR_MAX_KNN 64
+/* exact k nearest neighbours of every point of q_slot in t_slot; idx / d2 host arrays of n_q * k, row-major
+ * (row = query index; either may be NULL).  MVR_E_ARG for k outside 1..MVR_MAX_KNN or a bad slot. */
+int  mvr_knn(mvr_ctx *ctx, int q_slot, int t_slot, int k, int fma_dist, uint32_t *idx, float *d2);
+
+/* Normal estimation of a cloud against itself (PCL NormalEstimation::computePointNormal, solvePlaneParameters,
+ * flipNormalTowardsViewpoint):
+ *  - neighbourhood, k mode: the k-NN list above, the point itself included (d2 = 0);
+ *    radius mode: every j with d2(i, j) <= (float)(radius * radius), i included, no cap on the count (PCL
+ *    max_nn = 0).  The <= on the f32 d2 is this library's rule: PCL / FLANN were not available to pin theirs.
+ *  - fewer than 3 neighbours (k < 3 included): normal = NaN, curvature = NaN, as PCL.
+ *  - covariance in f64 of the neighbours' coordinates taken relative to the query point, divided by the
+ *    neighbour count.  (Deliberately NOT PCL 1.7's single-pass f32 accumulation, which is less accurate.)
+ *  - normal = unit eigenvector of the smallest eigenvalue l0; curvature = |l0| / (l0 + l1 + l2), 0 when the
+ *    sum is 0.  A zero covariance (all neighbours at one point) gives some finite unit vector and curvature 0.
+ *  - orientation: the normal rounded to f32, cos = dot(vp - p, n) in f32, n negated when cos < 0 (strictly).
+ *  - output: the slot's normals ({nx, ny, nz, 0}, what mvr_cloud_upload_normals fills), has_normals set: they
+ *    follow the cloud through copy / transform / append / denoise like uploaded normals, point-to-plane ICP and
+ *    mvr_cloud_download_normals use them with no host round trip; curvature optionally to the host. */
+typedef struct {
+  int    k;             /* setKSearch: 1..MVR_MAX_KNN, or 0 for radius mode                      */
+  double radius;        /* setRadiusSearch: > 0, or 0 for k mode; exactly one of k / radius set   */
+  float  viewpoint[3];  /* setViewPoint (PCL default 0, 0, 0)                                     */
+  int    fma_dist;
+} mvr_normal_params;
+/* normals of `count` slots, each against itself, in one call (one launch for up to 16 slots); curvature: NULL,
+ * or `count` host pointers (an entry may be NULL) to arrays of the slot's size.  MVR_E_ARG, before any GPU work,
+ * for a NULL ctx / slots / p, both or neither of k / radius set, k > MVR_MAX_KNN, a bad slot or a slot listed
+ * twice.  An empty slot is MVR_OK (nothing to do). */
+int  mvr_cloud_estimate_normals(mvr_ctx *ctx, int count, const int *slots, const mvr_normal_params *p,
+                                float *const *curvature);
+
 /* CorrespondenceEstimation::determineReciprocalCorrespondences(corrs, max_d)
  * (registrator.cpp:496-502, 644-649); reciprocal = 0 gives
  * determineCorrespondences.  Outputs are host arrays of capacity `cap`

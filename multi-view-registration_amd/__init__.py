@@ -59,6 +59,7 @@ _share_hip_runtime_with_torch()
 _lib = C.CDLL(LIB_PATH)
 
 MAX_SLOTS = 256
+MAX_KNN = 64            # MVR_MAX_KNN
 OK, E_ARG, E_HIP, E_NOCORR, E_NOMEM, E_SINGULAR, E_RCCL = 0, -1, -2, -3, -4, -5, -6
 CONV_STATES = ("NOT_CONVERGED", "ITERATIONS", "TRANSFORM", "ABS_MSE", "REL_MSE",
                "NO_CORRESPONDENCES")
@@ -100,6 +101,11 @@ class SynthParams(C.Structure):
                 ("pivot", C.c_double * 3), ("axis", C.c_double * 3)]
 
 
+class NormalParams(C.Structure):
+    """mvr_normal_params"""
+    _fields_ = [("k", C.c_int), ("radius", C.c_double), ("viewpoint", C.c_float * 3), ("fma_dist", C.c_int)]
+
+
 _fp, _dp, _u32p, _i32p = (C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                           C.POINTER(C.c_int32))
 _vp, _sz = C.c_void_p, C.c_size_t
@@ -130,6 +136,8 @@ SIGNATURES = {
     "mvr_cloud_upload_normals": (C.c_int, [_vp, C.c_int, _fp, _sz, _sz]),
     "mvr_cloud_download_normals": (C.c_int, [_vp, C.c_int, _fp, _sz, _sz, C.POINTER(_sz)]),
     "mvr_nn": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _u32p, _fp]),
+    "mvr_knn": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _u32p, _fp]),
+    "mvr_cloud_estimate_normals": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(NormalParams), C.POINTER(_fp)]),
     "mvr_correspondences": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
                                       _i32p, _i32p, _fp, _sz, C.POINTER(_sz)]),
     "mvr_pair_moments": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
@@ -478,6 +486,29 @@ class Context:
         idx, d2 = np.empty(n, np.uint32), np.empty(n, np.float32)
         _chk(_lib.mvr_nn(self._h, q_slot, t_slot, int(fma), _p(idx, C.c_uint32), _p(d2, C.c_float)), self._h)
         return idx, d2
+
+    def knn(self, q_slot, t_slot, k, fma=False):
+        """exact k nearest neighbours of every point of q_slot in t_slot: (idx[n, k] uint32, d2[n, k] float32), each row
+        ascending by (d2, index); UINT32_MAX / +inf where the target holds fewer than k points"""
+        n = self.size(q_slot)
+        idx, d2 = np.empty((n, k), np.uint32), np.empty((n, k), np.float32)
+        _chk(_lib.mvr_knn(self._h, q_slot, t_slot, int(k), int(fma), _p(idx, C.c_uint32), _p(d2, C.c_float)), self._h)
+        return idx, d2
+
+    def estimate_normals(self, slots, k=None, radius=None, viewpoint=(0.0, 0.0, 0.0), curvature=False, fma=False):
+        """pcl::NormalEstimation of every slot against itself (one call): the normals go into the slots (download_normals,
+        point-to-plane ICP).  Exactly one of k / radius.  curvature=True returns the curvature array (a list of them when
+        `slots` is a list)."""
+        one = np.isscalar(slots)
+        sl = [int(slots)] if one else [int(s) for s in slots]
+        p = NormalParams(int(k or 0), float(radius or 0.0), (C.c_float * 3)(*[float(v) for v in viewpoint]), int(fma))
+        arr = (C.c_int * max(len(sl), 1))(*sl)
+        curv = [np.empty(self.size(s), np.float32) for s in sl] if curvature else None
+        cptr = (_fp * max(len(sl), 1))(*[_p(a, C.c_float) for a in curv]) if curvature else None
+        _chk(_lib.mvr_cloud_estimate_normals(self._h, len(sl), arr, C.byref(p), cptr), self._h)
+        if not curvature:
+            return None
+        return curv[0] if one else curv
 
     def denoise(self, slot, segment_threshold=10, triangle_length=2.5):
         """PointCloud::denoise in place.  Returns (kept original indices in output order, number of components)."""

@@ -1,0 +1,482 @@
+// csrc/mvr_knn.hip -- exact k-nearest-neighbour search and PCL-style normal estimation (gfx950).
+//
+// pcl::NormalEstimation (computePointNormal / solvePlaneParameters / flipNormalTowardsViewpoint) is a neighbour search per
+// point plus a 3 x 3 symmetric eigenproblem.  Both run here, one thread per query:
+//
+//   * grid: the uniform grid of a cloud over its OWN current coordinates (ensure_model_grid, mvr_grid.hip: compact cell
+//     starts, points in grid order with w = bits of the point's index).  The queries are taken in that grid order too, so
+//     the 64 lanes of a wave are neighbours on the surface and walk the same cells; results are scattered back by index.
+//     A cloud too small for a grid (n < 4) or without one (a shard) is searched as ONE cell over its points in index order.
+//   * k-NN walk: shells of cells outward from the query's cell (Chebyshev shell s = the cells at distance s).  The walk
+//     stops when the list is full and every unvisited cell lies beyond the current k-th distance -- the gap between the
+//     query and the visited box, taken in f64 in cell units of the grid's own f32 inverse edge, minus a margin that covers
+//     every rounding of the cell assignment and of the f32 distance.  A cell at exactly that distance is
+//     still visited: a candidate that ties the k-th d2 with a lower index must get in.  Exact, never approximate.
+//   * the k-best list: KMAX 64-bit keys (d2 bits << 32 | index: unsigned order = (d2, index) lexicographic) in registers,
+//     inserted with compile-time indices only (a runtime-indexed private array would live in scratch).  For k < KMAX the
+//     leading KMAX - k entries hold the key 0, which no insertion moves: the live list is always the TAIL, its k-th entry
+//     the last register.
+//   * normals, k mode: the list is finished first, then the neighbours' coordinates are read again (their lines are in
+//     L1 / L2 from the walk) into f64 moments about the query point; radius mode accumulates the moments while it walks.
+//   * 3 x 3 solve: cyclic Jacobi in f64 (a few sweeps reach the f64 rounding level on a 3 x 3), normal = eigenvector of the
+//     smallest eigenvalue, curvature = |l0| / (l0 + l1 + l2); the normal is rounded to f32 and flipped towards the viewpoint
+//     with PCL's f32 test (cos < 0 strictly).
+// Every slot of a call is served by one launch (concatenated query ranges, the block knows its slot); the neighbour lists of
+// the normals path never leave registers.  Compiled with -ffp-contract=off (the distance is the library's f32 expression).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "mvr_internal.h"
+
+namespace mvr {
+namespace {
+
+constexpr int kKnnThreads = 256;
+constexpr int kKnnSlots = 16;      // slots per launch (kernel argument by value)
+
+struct KnnSlot {
+  const float4 *qs;                // queries: grid order with w = bits(index) -- or, with q_by_pos, index order
+  const float4 *gt;                // target points: grid order with w = bits(index) -- or, without a grid (dir null), index order
+  const float4 *tpts;              // target points in index order (k-mode normals read the neighbours from here)
+  const uint32_t *dir, *recs;      // compact cell starts of the target grid (CellGrid); dir null: one cell [0, nt)
+  float4 *nrm;                     // normals out, by query index
+  float *curv;                     // optional: curvature out, by query index
+  uint32_t *oidx; float *od2;      // k-NN out: [nq][k] by query index
+  float lo[3], inv_h;
+  int dim[3];
+  uint32_t nq, nt, q_by_pos, blk0;
+};
+struct KnnBatch {
+  KnnSlot s[kKnnSlots];
+  int n_slots, k;
+  float r2;                        // radius mode: (float)(radius * radius)
+  float vp[3];
+};
+static_assert(sizeof(KnnBatch) <= 4096, "KnnBatch travels as a kernel argument");
+
+constexpr uint32_t kSegOcc = 0x80000000u;
+// the cell-start lookup of the compact table (the same encoding as cell_start_of in mvr_grid.hip)
+__device__ __forceinline__ uint32_t knn_cell_start(const KnnSlot &S, uint32_t c)
+{
+  const uint32_t d = S.dir[c >> 5];
+  return (d & kSegOcc) ? S.recs[((d & ~kSegOcc) << 5) + (c & 31u)] : d;
+}
+__device__ __forceinline__ int knn_cell_of(float x, float lo, float inv_h, int dim)
+{
+  // the grid build's own assignment (mvr_grid.hip: cell_of): monotone in x, clamped to the grid
+  const float f = floorf((x - lo) * inv_h);
+  return (int)fminf(fmaxf(f, 0.f), (float)(dim - 1));
+}
+template <bool FMA>
+__device__ __forceinline__ float knn_dist2(const float4 t, const float4 q)
+{
+  const float dx = t.x - q.x, dy = t.y - q.y, dz = t.z - q.z;
+  if (FMA) return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+  float r = dx * dx;
+  r = r + dy * dy;
+  r = r + dz * dz;
+  return r;
+}
+// the slot of this block (uniform: a slot's blocks are consecutive)
+__device__ __forceinline__ int knn_slot_of(const KnnBatch &b)
+{
+  int si = 0;
+  for (int j = 1; j < b.n_slots; ++j)
+    if (blockIdx.x >= b.s[j].blk0) si = j;
+  return si;
+}
+
+// the ordered list: insert `key` (which is below L[KMAX - 1]); every index is a compile-time constant
+template <int KMAX>
+__device__ __forceinline__ void knn_insert(nnkey_t (&L)[KMAX], const nnkey_t key)
+{
+#pragma unroll
+  for (int i = KMAX - 1; i > 0; --i) L[i] = key < L[i - 1] ? L[i - 1] : (key < L[i] ? key : L[i]);
+  L[0] = key < L[0] ? key : L[0];
+}
+
+// the grid positions where the cells [x0, x1] of row (y, z) begin and end (no grid: the one cell [0, nt))
+__device__ __forceinline__ void knn_row_range(const KnnSlot &S, int x0, int x1, int y, int z, uint32_t *s, uint32_t *e)
+{
+  if (!S.dir) { *s = 0u; *e = S.nt; return; }
+  const uint32_t c0 = (uint32_t)((z * S.dim[1] + y) * S.dim[0] + x0);
+  *s = knn_cell_start(S, c0);
+  *e = knn_cell_start(S, c0 + (uint32_t)(x1 - x0) + 1u);
+}
+
+// the exact k-best list of query q: KMAX - k leading zero keys, then the k best (kKeyInit where the target has fewer)
+template <int KMAX, bool FMA>
+__device__ __forceinline__ void knn_walk(const KnnSlot &S, const float4 q, const int k, nnkey_t (&L)[KMAX])
+{
+#pragma unroll
+  for (int i = 0; i < KMAX; ++i) L[i] = i < KMAX - k ? 0ull : kKeyInit;
+  if (S.nt == 0) return;
+  const bool by_pos = !S.dir;
+  const int cx = knn_cell_of(q.x, S.lo[0], S.inv_h, S.dim[0]), cy = knn_cell_of(q.y, S.lo[1], S.inv_h, S.dim[1]),
+            cz = knn_cell_of(q.z, S.lo[2], S.inv_h, S.dim[2]);
+  for (int s = 0;; ++s) {
+    const int x0 = cx - s, x1 = cx + s, y0 = cy - s, y1 = cy + s, z0 = cz - s, z1 = cz + s;
+    const int ya = max(y0, 0), yb = min(y1, S.dim[1] - 1), za = max(z0, 0), zb = min(z1, S.dim[2] - 1);
+    // the shell's rows one after the other: on a face of the shell the whole row [x0, x1], inside it the row's two end cells
+    // (ONE loop and one candidate loop: every copy of the unrolled insertion costs registers and code)
+    for (int r = 0, nr = (yb - ya + 1) * (zb - za + 1) * 2; r < nr; ++r) {
+      const int part = r & 1, y = ya + (r >> 1) % (yb - ya + 1), z = za + (r >> 1) / (yb - ya + 1);
+      const bool face = z == z0 || z == z1 || y == y0 || y == y1;
+      int a, b;
+      if (face) {
+        if (part) continue;
+        a = max(x0, 0); b = min(x1, S.dim[0] - 1);
+      } else {
+        a = b = part ? x1 : x0;
+        if (a < 0 || a >= S.dim[0]) continue;
+      }
+      uint32_t j, e;
+      knn_row_range(S, a, b, y, z, &j, &e);
+      for (; j < e; ++j) {
+        const float4 p = S.gt[j];
+        const nnkey_t key = ((nnkey_t)__float_as_uint(knn_dist2<FMA>(p, q)) << 32) | (by_pos ? j : __float_as_uint(p.w));
+        if (key < L[KMAX - 1]) knn_insert<KMAX>(L, key);
+      }
+    }
+    if (!S.dir) return;                                               // one cell: all of it seen
+    const bool lo_x = x0 > 0, hi_x = x1 < S.dim[0] - 1, lo_y = y0 > 0, hi_y = y1 < S.dim[1] - 1, lo_z = z0 > 0, hi_z = z1 < S.dim[2] - 1;
+    if (!(lo_x || hi_x || lo_y || hi_y || lo_z || hi_z)) return;      // the whole grid seen
+    const nnkey_t kth = L[KMAX - 1];
+    if (kth == kKeyInit) continue;                                    // the list is not full yet
+    // the nearest an unvisited cell can be: the gap between the query and the visited box on the sides that have cells beyond
+    // it, in cells of the grid's own f32 inverse edge (f64), less a margin every rounding fits in -- the f32 cell assignment of a
+    // point (relative 2^-22 of its offset from lo, plus an ulp of the coordinate) and the f32 distance (the 1e-5 of d2 below):
+    // 1e-6 of the magnitudes involved is ten times that
+    const double ih = (double)S.inv_h;
+    const double ux = ((double)q.x - (double)S.lo[0]) * ih, uy = ((double)q.y - (double)S.lo[1]) * ih, uz = ((double)q.z - (double)S.lo[2]) * ih;
+    double g = 1.0e300;
+    if (lo_x) g = fmin(g, ux - (double)x0);
+    if (hi_x) g = fmin(g, (double)(x1 + 1) - ux);
+    if (lo_y) g = fmin(g, uy - (double)y0);
+    if (hi_y) g = fmin(g, (double)(y1 + 1) - uy);
+    if (lo_z) g = fmin(g, uz - (double)z0);
+    if (hi_z) g = fmin(g, (double)(z1 + 1) - uz);
+    const double mag = fabs((double)q.x) + fabs((double)q.y) + fabs((double)q.z) + fabs((double)S.lo[0]) + fabs((double)S.lo[1]) +
+                       fabs((double)S.lo[2]) + (double)(S.dim[0] + S.dim[1] + S.dim[2]) / ih;
+    const double b = g / ih - (1.0e-6 * mag + 1.0e-6 / ih);
+    const double kd2 = (double)__uint_as_float((uint32_t)(kth >> 32));
+    if (b > 0.0 && b * b * (1.0 - 1.0e-5) > kd2) return;              // strictly beyond the k-th distance (NaN: never)
+  }
+}
+
+// ---- the 3 x 3 symmetric eigenproblem in f64: cyclic Jacobi (A is destroyed, V = eigenvectors in columns)
+template <int P, int Q, int R>
+__device__ __forceinline__ void jacobi_rot(double (&A)[3][3], double (&V)[3][3])
+{
+  const double apq = A[P][Q];
+  if (apq == 0.0) return;
+  const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
+  const double t = fabs(theta) > 1.0e150 ? 0.5 / theta : copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+  A[P][P] -= t * apq;
+  A[Q][Q] += t * apq;
+  A[P][Q] = A[Q][P] = 0.0;
+  const double arp = A[R][P], arq = A[R][Q];
+  A[R][P] = A[P][R] = c * arp - s * arq;
+  A[R][Q] = A[Q][R] = s * arp + c * arq;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const double vp = V[r][P], vq = V[r][Q];
+    V[r][P] = c * vp - s * vq;
+    V[r][Q] = s * vp + c * vq;
+  }
+}
+
+// f64 moments of the neighbours about the query point
+struct Moments {
+  double cnt = 0.0, sx = 0.0, sy = 0.0, sz = 0.0, xx = 0.0, xy = 0.0, xz = 0.0, yy = 0.0, yz = 0.0, zz = 0.0;
+  __device__ __forceinline__ void add(const float4 p, const float4 q)
+  {
+    const double dx = (double)p.x - (double)q.x, dy = (double)p.y - (double)q.y, dz = (double)p.z - (double)q.z;
+    cnt += 1.0; sx += dx; sy += dy; sz += dz;
+    xx += dx * dx; xy += dx * dy; xz += dx * dz; yy += dy * dy; yz += dy * dz; zz += dz * dz;
+  }
+};
+
+// moments about the query point -> unit normal (f32, oriented) and curvature; fewer than 3 neighbours: NaN
+__device__ __forceinline__ void plane_from_moments(const KnnSlot &S, const KnnBatch &b, const float4 q, const uint32_t qi, const Moments &M)
+{
+  float4 out; float curv;
+  if (M.cnt < 3.0) {
+    out = make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), 0.f);
+    curv = __builtin_nanf("");
+  } else {
+    const double inv = 1.0 / M.cnt, m0 = M.sx * inv, m1 = M.sy * inv, m2 = M.sz * inv;
+    double A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    A[0][0] = M.xx * inv - m0 * m0; A[0][1] = A[1][0] = M.xy * inv - m0 * m1; A[0][2] = A[2][0] = M.xz * inv - m0 * m2;
+    A[1][1] = M.yy * inv - m1 * m1; A[1][2] = A[2][1] = M.yz * inv - m1 * m2; A[2][2] = M.zz * inv - m2 * m2;
+    for (int sweep = 0; sweep < 12; ++sweep) {
+      const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
+      const double dia = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
+      if (!(off > 1.0e-40 * dia)) break;                      // (an all-zero matrix ends here too)
+      jacobi_rot<0, 1, 2>(A, V);
+      jacobi_rot<0, 2, 1>(A, V);
+      jacobi_rot<1, 2, 0>(A, V);
+    }
+    const double l0 = A[0][0], l1 = A[1][1], l2 = A[2][2];
+    // the column of the smallest eigenvalue, picked by 0 / 1 weights (a select between array elements becomes a select between
+    // their ADDRESSES, which sends A and V to scratch memory)
+    const double w0 = (l0 <= l1 && l0 <= l2) ? 1.0 : 0.0, w1 = (w0 == 0.0 && l1 <= l2) ? 1.0 : 0.0, w2 = 1.0 - w0 - w1;
+    const double lmin = w0 * l0 + w1 * l1 + w2 * l2;
+    const double nx = w0 * V[0][0] + w1 * V[0][1] + w2 * V[0][2], ny = w0 * V[1][0] + w1 * V[1][1] + w2 * V[1][2],
+                 nz = w0 * V[2][0] + w1 * V[2][1] + w2 * V[2][2];
+    const double nn = 1.0 / sqrt(nx * nx + ny * ny + nz * nz);
+    const double sum = l0 + l1 + l2;
+    curv = sum != 0.0 ? (float)(fabs(lmin) / sum) : 0.f;
+    float fx = (float)(nx * nn), fy = (float)(ny * nn), fz = (float)(nz * nn);
+    // flipNormalTowardsViewpoint: f32, the normal already rounded
+    const float vx = b.vp[0] - q.x, vy = b.vp[1] - q.y, vz = b.vp[2] - q.z;
+    float cs = vx * fx;
+    cs = cs + vy * fy;
+    cs = cs + vz * fz;
+    if (cs < 0.f) { fx = -fx; fy = -fy; fz = -fz; }
+    out = make_float4(fx, fy, fz, 0.f);
+  }
+  S.nrm[qi] = out;
+  if (S.curv) S.curv[qi] = curv;
+}
+
+__device__ __forceinline__ bool knn_query(const KnnSlot &S, float4 *q, uint32_t *qi)
+{
+  const uint32_t pos = (blockIdx.x - S.blk0) * kKnnThreads + threadIdx.x;
+  if (pos >= S.nq) return false;
+  *q = S.qs[pos];
+  *qi = S.q_by_pos ? pos : __float_as_uint(q->w);
+  return true;
+}
+
+// k-NN lists out to memory
+template <int KMAX, bool FMA>
+__global__ void __launch_bounds__(kKnnThreads) knn_kernel(KnnBatch b)
+{
+  const KnnSlot &S = b.s[knn_slot_of(b)];
+  float4 q; uint32_t qi;
+  if (!knn_query(S, &q, &qi)) return;
+  nnkey_t L[KMAX];
+  knn_walk<KMAX, FMA>(S, q, b.k, L);
+  uint32_t *oi = S.oidx + (size_t)qi * b.k;
+  float *od = S.od2 + (size_t)qi * b.k;
+#pragma unroll
+  for (int i = 0; i < KMAX; ++i) {
+    if (i >= KMAX - b.k) {
+      const uint32_t j = (uint32_t)L[i];
+      oi[i - (KMAX - b.k)] = j;
+      od[i - (KMAX - b.k)] = j == kNone ? __builtin_inff() : __uint_as_float((uint32_t)(L[i] >> 32));
+    }
+  }
+}
+
+// normals, k mode: the list in registers, then the moments of its entries
+template <int KMAX, bool FMA>
+__global__ void __launch_bounds__(kKnnThreads) normals_knn_kernel(KnnBatch b)
+{
+  const KnnSlot &S = b.s[knn_slot_of(b)];
+  float4 q; uint32_t qi;
+  if (!knn_query(S, &q, &qi)) return;
+  nnkey_t L[KMAX];
+  knn_walk<KMAX, FMA>(S, q, b.k, L);
+  Moments M;
+#pragma unroll
+  for (int i = 0; i < KMAX; ++i) {
+    const uint32_t j = (uint32_t)L[i];
+    if (i >= KMAX - b.k && j != kNone) M.add(S.tpts[j], q);
+  }
+  plane_from_moments(S, b, q, qi, M);
+}
+
+// normals, radius mode: every point with d2 <= r2, moments accumulated during the walk (no list)
+template <bool FMA>
+__global__ void __launch_bounds__(kKnnThreads) normals_radius_kernel(KnnBatch b)
+{
+  const KnnSlot &S = b.s[knn_slot_of(b)];
+  float4 q; uint32_t qi;
+  if (!knn_query(S, &q, &qi)) return;
+  Moments M;
+  int x0 = 0, x1 = 0, y0 = 0, y1 = 0, z0 = 0, z1 = 0;
+  if (S.dir) {
+    // the cells the ball overlaps: its radius widened by the same margins as the k-NN bound (f32 cell arithmetic is monotone)
+    const float mag = fabsf(q.x) + fabsf(q.y) + fabsf(q.z) + fabsf(S.lo[0]) + fabsf(S.lo[1]) + fabsf(S.lo[2]) +
+                      (float)(S.dim[0] + S.dim[1] + S.dim[2]) / S.inv_h;
+    const float rad = sqrtf(b.r2) * 1.0001f + 1.0e-5f * mag;
+    x0 = knn_cell_of(q.x - rad, S.lo[0], S.inv_h, S.dim[0]); x1 = knn_cell_of(q.x + rad, S.lo[0], S.inv_h, S.dim[0]);
+    y0 = knn_cell_of(q.y - rad, S.lo[1], S.inv_h, S.dim[1]); y1 = knn_cell_of(q.y + rad, S.lo[1], S.inv_h, S.dim[1]);
+    z0 = knn_cell_of(q.z - rad, S.lo[2], S.inv_h, S.dim[2]); z1 = knn_cell_of(q.z + rad, S.lo[2], S.inv_h, S.dim[2]);
+  }
+  for (int z = z0; z <= z1; ++z)
+    for (int y = y0; y <= y1; ++y) {
+      uint32_t j, e;
+      knn_row_range(S, x0, x1, y, z, &j, &e);
+      for (; j < e; ++j) {
+        const float4 p = S.gt[j];
+        if (knn_dist2<FMA>(p, q) <= b.r2) M.add(p, q);
+      }
+    }
+  plane_from_moments(S, b, q, qi, M);
+}
+
+template <bool FMA>
+void launch_knn_fma(int kmax, int mode, dim3 grid, hipStream_t st, const KnnBatch &b)
+{
+  // mode 0: k-NN lists, 1: normals k mode, 2: normals radius mode
+  if (mode == 2) { hipLaunchKernelGGL(normals_radius_kernel<FMA>, grid, dim3(kKnnThreads), 0, st, b); return; }
+  switch (kmax) {
+    case 8:  if (mode == 0) hipLaunchKernelGGL((knn_kernel<8, FMA>), grid, dim3(kKnnThreads), 0, st, b); else hipLaunchKernelGGL((normals_knn_kernel<8, FMA>), grid, dim3(kKnnThreads), 0, st, b); break;
+    case 16: if (mode == 0) hipLaunchKernelGGL((knn_kernel<16, FMA>), grid, dim3(kKnnThreads), 0, st, b); else hipLaunchKernelGGL((normals_knn_kernel<16, FMA>), grid, dim3(kKnnThreads), 0, st, b); break;
+    case 32: if (mode == 0) hipLaunchKernelGGL((knn_kernel<32, FMA>), grid, dim3(kKnnThreads), 0, st, b); else hipLaunchKernelGGL((normals_knn_kernel<32, FMA>), grid, dim3(kKnnThreads), 0, st, b); break;
+    default: if (mode == 0) hipLaunchKernelGGL((knn_kernel<64, FMA>), grid, dim3(kKnnThreads), 0, st, b); else hipLaunchKernelGGL((normals_knn_kernel<64, FMA>), grid, dim3(kKnnThreads), 0, st, b); break;
+  }
+}
+
+int kmax_bucket(int k) { return k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64; }
+
+// the search side of a slot: its grid over the current coordinates when it can have one, else one cell over the points
+int fill_target(Ctx *c, Cloud &t, KnnSlot &S)
+{
+  if (t.pts_stale) return set_error(c, MVR_E_ARG, "k-NN / normals: the cloud's points are not current (pipelined run)");
+  S.gt = t.pts; S.tpts = t.pts; S.dir = nullptr; S.recs = nullptr; S.nt = (uint32_t)t.n;
+  for (int j = 0; j < 3; ++j) { S.lo[j] = 0.f; S.dim[j] = 1; }
+  S.inv_h = 0.f;
+  if (t.n == 0) return MVR_OK;
+  bool ok = false;
+  if (int rc = ensure_model_grid(c, t, 0.0, &ok)) return rc;
+  if (!ok) return MVR_OK;
+  const CellGrid &g = *t.mgrid;
+  S.gt = g.graw; S.dir = g.dir; S.recs = g.recs; S.inv_h = g.inv_h;
+  for (int j = 0; j < 3; ++j) { S.lo[j] = g.lo[j]; S.dim[j] = g.dim[j]; }
+  return MVR_OK;
+}
+// the query side: grid order when the cloud has a grid (the lanes of a wave are then neighbours), else index order
+void fill_queries(const Cloud &q, KnnSlot &S)
+{
+  const bool grid = q.mgrid && q.mgrid_ok && q.mgrid->n == q.n && q.n > 0;
+  S.qs = grid ? q.mgrid->graw : q.pts;
+  S.q_by_pos = grid ? 0u : 1u;
+  S.nq = (uint32_t)q.n;
+}
+
+int run_batches(Ctx *c, std::vector<KnnSlot> &all, KnnBatch proto, int kmax, int mode, bool fma)
+{
+  for (size_t b0 = 0; b0 < all.size(); b0 += kKnnSlots) {
+    KnnBatch b = proto;
+    b.n_slots = (int)std::min<size_t>(kKnnSlots, all.size() - b0);
+    unsigned blocks = 0;
+    for (int j = 0; j < b.n_slots; ++j) {
+      b.s[j] = all[b0 + (size_t)j];
+      b.s[j].blk0 = blocks;
+      blocks += (b.s[j].nq + kKnnThreads - 1) / kKnnThreads;
+    }
+    if (!blocks) continue;
+    if (fma) launch_knn_fma<true>(kmax, mode, dim3(blocks), c->stream, b);
+    else launch_knn_fma<false>(kmax, mode, dim3(blocks), c->stream, b);
+    MVR_HIP_TRY(c, hipGetLastError());
+  }
+  return MVR_OK;
+}
+
+}  // namespace
+}  // namespace mvr
+
+using namespace mvr;
+
+#define API __attribute__((visibility("default")))
+#define CTX(p) reinterpret_cast<Ctx *>(p)
+
+static bool knn_slot_ok(int s) { return s >= 0 && s < MVR_MAX_SLOTS; }
+
+API int mvr_knn(mvr_ctx *ctx, int qs, int ts, int k, int fma, uint32_t *idx, float *d2)
+{
+  if (!ctx || !knn_slot_ok(qs) || !knn_slot_ok(ts) || k < 1 || k > MVR_MAX_KNN) return MVR_E_ARG;
+  Ctx *c = CTX(ctx);
+  MVR_HIP_TRY(c, hipSetDevice(c->device));
+  Cloud &q = c->slots[qs], &t = c->slots[ts];
+  if (q.n == 0) return MVR_OK;
+  if (q.n > 0x7FFFFFF0ull || t.n > 0x7FFFFFF0ull) return set_error(c, MVR_E_ARG, "mvr_knn: cloud too large");
+  KnnSlot S{};
+  if (int rc = fill_target(c, t, S)) return rc;
+  if (qs != ts && q.n >= 4 && !q.pts_stale) {      // the queries' own grid gives them their walking order
+    bool ok = false;
+    if (int rc = ensure_model_grid(c, q, 0.0, &ok)) return rc;
+  }
+  if (q.pts_stale) return set_error(c, MVR_E_ARG, "mvr_knn: the query cloud's points are not current (pipelined run)");
+  fill_queries(q, S);
+  const size_t m = q.n * (size_t)k;
+  uint32_t *didx = nullptr; float *dd2 = nullptr;
+  MVR_HIP_TRY(c, hipMalloc(&didx, m * 4));
+  if (hipMalloc(&dd2, m * 4) != hipSuccess) { (void)hipFree(didx); return set_error(c, MVR_E_NOMEM, "mvr_knn: out of device memory"); }
+  S.oidx = didx; S.od2 = dd2;
+  std::vector<KnnSlot> all{S};
+  KnnBatch proto{};
+  proto.k = k;
+  int rc = run_batches(c, all, proto, kmax_bucket(k), 0, fma != 0);
+  hipError_t e = hipSuccess;
+  if (!rc && idx) e = hipMemcpyAsync(idx, didx, m * 4, hipMemcpyDeviceToHost, c->stream);
+  if (!rc && e == hipSuccess && d2) e = hipMemcpyAsync(d2, dd2, m * 4, hipMemcpyDeviceToHost, c->stream);
+  const hipError_t e2 = hipStreamSynchronize(c->stream);
+  (void)hipFree(didx); (void)hipFree(dd2);
+  if (rc) return rc;
+  if (e != hipSuccess) return set_error(c, MVR_E_HIP, "mvr_knn copy", e);
+  if (e2 != hipSuccess) return set_error(c, MVR_E_HIP, "mvr_knn sync", e2);
+  return MVR_OK;
+}
+
+API int mvr_cloud_estimate_normals(mvr_ctx *ctx, int count, const int *slots, const mvr_normal_params *p, float *const *curvature)
+{
+  if (!ctx || !slots || !p || count < 0) return MVR_E_ARG;
+  const bool kmode = p->k != 0, rmode = p->radius != 0.0;
+  if (kmode == rmode || p->k < 0 || p->k > MVR_MAX_KNN || !(p->radius >= 0.0) || std::isinf(p->radius)) return MVR_E_ARG;
+  for (int j = 0; j < 3; ++j) if (!std::isfinite(p->viewpoint[j])) return MVR_E_ARG;
+  for (int i = 0; i < count; ++i) {
+    if (!knn_slot_ok(slots[i])) return MVR_E_ARG;
+    for (int j = 0; j < i; ++j) if (slots[j] == slots[i]) return MVR_E_ARG;
+  }
+  Ctx *c = CTX(ctx);
+  MVR_HIP_TRY(c, hipSetDevice(c->device));
+  std::vector<KnnSlot> all;
+  std::vector<int> used;
+  size_t curv_total = 0;
+  for (int i = 0; i < count; ++i) {
+    Cloud &cl = c->slots[slots[i]];
+    if (cl.n == 0) continue;
+    if (cl.n > 0x7FFFFFF0ull) return set_error(c, MVR_E_ARG, "mvr_cloud_estimate_normals: cloud too large");
+    KnnSlot S{};
+    if (int rc = fill_target(c, cl, S)) return rc;
+    fill_queries(cl, S);
+    if (curvature && curvature[i]) curv_total += cl.n;
+    all.push_back(S); used.push_back(i);
+  }
+  if (all.empty()) return MVR_OK;
+  // normal buffers (after every grid is built: ensure() may wait for the stream)
+  for (size_t j = 0; j < all.size(); ++j) {
+    Cloud &cl = c->slots[slots[used[j]]];
+    cl.has_normals = false;
+    if (int rc = ensure(c, cl.nrm, cl.nrm_cap, cl.n)) return rc;
+    all[j].nrm = cl.nrm;
+  }
+  float *dcurv = nullptr;
+  if (curv_total) MVR_HIP_TRY(c, hipMalloc(&dcurv, curv_total * 4));
+  size_t off = 0;
+  for (size_t j = 0; j < all.size(); ++j)
+    if (curvature && curvature[used[j]]) { all[j].curv = dcurv + off; off += all[j].nq; }
+  KnnBatch proto{};
+  proto.k = p->k;
+  proto.r2 = (float)(p->radius * p->radius);
+  for (int j = 0; j < 3; ++j) proto.vp[j] = p->viewpoint[j];
+  int rc = run_batches(c, all, proto, kmode ? kmax_bucket(p->k) : 8, kmode ? 1 : 2, p->fma_dist != 0);
+  hipError_t e = hipSuccess;
+  for (size_t j = 0; j < all.size() && !rc && e == hipSuccess; ++j)
+    if (all[j].curv) e = hipMemcpyAsync(curvature[used[j]], all[j].curv, (size_t)all[j].nq * 4, hipMemcpyDeviceToHost, c->stream);
+  const hipError_t e2 = hipStreamSynchronize(c->stream);
+  if (dcurv) (void)hipFree(dcurv);
+  if (rc) return rc;
+  if (e != hipSuccess) return set_error(c, MVR_E_HIP, "mvr_cloud_estimate_normals copy", e);
+  if (e2 != hipSuccess) return set_error(c, MVR_E_HIP, "mvr_cloud_estimate_normals sync", e2);
+  for (size_t j = 0; j < all.size(); ++j) c->slots[slots[used[j]]].has_normals = true;
+  return MVR_OK;
+}
