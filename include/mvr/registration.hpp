@@ -237,6 +237,51 @@ class NormalEstimation {
   float vp_[3] = {0.f, 0.f, 0.f};
 };
 
+// ---------------------------------------------------------------- voxel grid
+// pcl::VoxelGrid<PointT> (filters/voxel_grid.h) for 16-byte XYZ points: setLeafSize, setMinimumPointsNumberPerVoxel,
+// filter; downsample_all_data as PCL's default (true).  Semantics: mvr_cloud_voxel_grid (mvr_hip.h).  `output` may be the input
+// cloud itself (`vg.setInputCloud(cloud); vg.filter(*cloud);`): the input is on the device before `output` is written, which
+// is what PCL's Filter::filter gets by filtering such a call into a temporary.  A missing input or a leaf that is not finite
+// and > 0 prints an error and leaves `output` empty (untouched when it is the input); when PCL's integer indices would
+// overflow, the output is a copy of the input and PCL's warning is printed.
+template <typename PointT>
+class VoxelGrid {
+ public:
+  typedef PointCloud<PointT> PointCloudT;
+  typedef typename PointCloudT::ConstPtr PointCloudConstPtr;
+
+  void setInputCloud(const PointCloudConstPtr &c) { input_ = c; }
+  PointCloudConstPtr getInputCloud() const { return input_; }
+  void setLeafSize(float lx, float ly, float lz) { leaf_[0] = lx; leaf_[1] = ly; leaf_[2] = lz; }
+  void setMinimumPointsNumberPerVoxel(unsigned int m) { min_points_ = m; }
+  unsigned int getMinimumPointsNumberPerVoxel() const { return min_points_; }
+
+  void filter(PointCloudT &output)
+  {
+    if (!input_) { std::fprintf(stderr, "[pcl::VoxelGrid::filter] No input dataset given!\n"); output.clear(); return; }
+    for (int a = 0; a < 3; ++a)
+      if (!(std::isfinite(leaf_[a]) && leaf_[a] > 0.f)) {
+        std::fprintf(stderr, "[pcl::VoxelGrid::filter] Leaf size (%f, %f, %f) must be finite and > 0.\n", leaf_[0], leaf_[1], leaf_[2]);
+        if (&output != input_.get()) output.clear();
+        return;
+      }
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.upload(s.s, *input_);              // first: `output` may alias the input
+    size_t n = 0;
+    int passthrough = 0;
+    d.check(mvr_cloud_voxel_grid(d.ctx(), s.s, s.s, leaf_, min_points_, &n, nullptr, &passthrough), "mvr_cloud_voxel_grid");
+    if (passthrough)
+      std::fprintf(stderr, "[pcl::VoxelGrid::applyFilter] Leaf size is too small for the input dataset. Integer indices would overflow.\n");
+    d.download(s.s, output);
+  }
+
+ private:
+  PointCloudConstPtr input_;
+  float leaf_[3] = {0.f, 0.f, 0.f};
+  unsigned int min_points_ = 0;
+};
+
 namespace registration {
 
 // ------------------------------------------------- CorrespondenceEstimation

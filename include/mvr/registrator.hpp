@@ -157,6 +157,60 @@ class ScanCloud {
     }
   }
 
+  // EXTENSION (pcl::VoxelGrid with a cubic leaf, mvr_cloud_voxel_grid): `points` become the centroids of the occupied
+  // voxels, in ascending voxel index; voxels with fewer than min_points points are dropped.  When `rich` holds one record
+  // per point it is replaced too: xyz and normals come from the GPU (the rich normals go into the slot first, and the
+  // voxel's normal sum is normalised, as PCL >= 1.8); rgb is the per-channel mean truncated to an integer (PCL's
+  // AccumulatorRGBA) and curvature the f64 mean rounded to f32, both averaged on the host through the voxel map.  When
+  // PCL's integer indices would overflow, nothing changes but PCL's warning.  Returns the number of points removed.
+  size_t voxelDownsample(float leaf, unsigned min_points = 0)
+  {
+    Device &d = Device::instance();
+    SlotGuard s;
+    const size_t before = points.size();
+    const bool with_rich = before > 0 && rich.size() == before;
+    d.upload(s.s, points);
+    if (with_rich) {
+      std::vector<float> nrm(4 * before);
+      for (size_t i = 0; i < before; ++i) { nrm[4 * i] = rich[i].normal_x; nrm[4 * i + 1] = rich[i].normal_y; nrm[4 * i + 2] = rich[i].normal_z; nrm[4 * i + 3] = 0.f; }
+      d.check(mvr_cloud_upload_normals(d.ctx(), s.s, nrm.data(), before, 16), "mvr_cloud_upload_normals");
+    }
+    const float lf[3] = {leaf, leaf, leaf};
+    size_t kept = 0;
+    int passthrough = 0;
+    std::vector<uint32_t> vox(before ? before : 1);
+    d.check(mvr_cloud_voxel_grid(d.ctx(), s.s, s.s, lf, min_points, &kept, vox.data(), &passthrough), "mvr_cloud_voxel_grid");
+    if (passthrough) {
+      std::fprintf(stderr, "[pcl::VoxelGrid::applyFilter] Leaf size is too small for the input dataset. Integer indices would overflow.\n");
+      return 0;
+    }
+    d.download(s.s, points);
+    if (with_rich) {
+      std::vector<float> nrm(4 * (kept ? kept : 1));
+      size_t got = 0;
+      if (kept) d.check(mvr_cloud_download_normals(d.ctx(), s.s, nrm.data(), kept, 16, &got), "mvr_cloud_download_normals");
+      std::vector<unsigned long long> rgb(3 * kept, 0ull), cnt(kept, 0ull);
+      std::vector<double> curv(kept, 0.0);
+      for (size_t i = 0; i < before; ++i) {
+        const uint32_t o = vox[i];
+        if (o == 0xFFFFFFFFu) continue;
+        rgb[3 * o] += rich[i].r; rgb[3 * o + 1] += rich[i].g; rgb[3 * o + 2] += rich[i].b;
+        curv[o] += (double)rich[i].curvature;
+        ++cnt[o];
+      }
+      io::RichCloud r(kept);
+      for (size_t k = 0; k < kept; ++k) {
+        r[k].x = points.points[k].x; r[k].y = points.points[k].y; r[k].z = points.points[k].z;
+        r[k].r = (uint8_t)(rgb[3 * k] / cnt[k]); r[k].g = (uint8_t)(rgb[3 * k + 1] / cnt[k]); r[k].b = (uint8_t)(rgb[3 * k + 2] / cnt[k]);
+        r[k].normal_x = nrm[4 * k]; r[k].normal_y = nrm[4 * k + 1]; r[k].normal_z = nrm[4 * k + 2];
+        r[k].curvature = (float)(curv[k] / (double)cnt[k]);
+      }
+      rich.swap(r);
+    }
+    touch();
+    return before - kept;
+  }
+
   // point_cloud.cpp:305-326 / :328-347 -- `transformation.txt`: the column-vector
   // 4x4 printed row by row (matrix(j,i), i outer), "%lf " per element, one row per
   // line.  6 decimals: poses round-trip to 1e-6 only.
@@ -439,28 +493,28 @@ class Registrator {
   // Returns the number of points written, 0 on failure.
   size_t saveRegisteredPoints(int object, const std::string &folder, io::RichCloud *merged_out = nullptr)
   {
-    const int V = model_->numViews();
     io::RichCloud merged;
-    for (int v = 0; v < V; ++v) {
-      const ScanCloud &pc = model_->getPointCloud(object, v);
-      if (!pc.isRegistered()) continue;
-      const RowMatrixd &M = pc.getMatrix();
-      auto pre = [&M](float x, float y, float z, float out[3]) {              // osg::Matrixd::preMult(Vec3f): (x, y, z, 1) * M / w
-        const double w = 1.0 / (M(0, 3) * x + M(1, 3) * y + M(2, 3) * z + M(3, 3));
-        for (int k = 0; k < 3; ++k) out[k] = (float)((M(0, k) * x + M(1, k) * y + M(2, k) * z + M(3, k)) * w);
-      };
-      for (size_t j = 0; j < pc.size(); ++j) {
-        io::RichPoint q = j < pc.rich.size() ? pc.rich[j] : io::RichPoint();
-        const PCLPoint &p = pc.points.points[j];
-        float o[3];
-        pre(p.x, p.y, p.z, o); q.x = o[0]; q.y = o[1]; q.z = o[2];
-        pre(q.normal_x, q.normal_y, q.normal_z, o); q.normal_x = o[0]; q.normal_y = o[1]; q.normal_z = o[2];
-        merged.push_back(q);
-      }
-    }
+    mergeRegisteredPoints(object, merged);
     const bool ok = io::savePCDFile(folder + "/points.pcd", merged, io::PCD_BINARY_COMPRESSED) && io::savePointsASC(folder + "/points.asc", merged);
     const size_t n = merged.size();
     if (merged_out) merged_out->swap(merged);
+    return ok ? n : 0;
+  }
+
+  // EXTENSION: the same merged cloud put through ScanCloud::voxelDownsample(leaf_size) before it is written to the same two
+  // files -- twelve overlapping turntable views hold mostly duplicated surface.  Its normals are the reference's
+  // full-affine-moved normals and are averaged as they are (the voxel's sum, normalised).  merged_out receives the
+  // downsampled cloud.  Returns the number of points written, 0 on failure.
+  size_t saveRegisteredPoints(int object, const std::string &folder, float leaf_size, io::RichCloud *merged_out = nullptr)
+  {
+    ScanCloud merged;
+    mergeRegisteredPoints(object, merged.rich);
+    for (const io::RichPoint &q : merged.rich) merged.points.push_back(PCLPoint(q.x, q.y, q.z));
+    merged.voxelDownsample(leaf_size);
+    const bool ok = io::savePCDFile(folder + "/points.pcd", merged.rich, io::PCD_BINARY_COMPRESSED) &&
+                    io::savePointsASC(folder + "/points.asc", merged.rich);
+    const size_t n = merged.rich.size();
+    if (merged_out) merged_out->swap(merged.rich);
     return ok ? n : 0;
   }
 
@@ -486,6 +540,29 @@ class Registrator {
   std::vector<int> lum_ncorr;      // correspondences per ring edge of the last global pass
 
  private:
+  // the merged object of saveRegisteredPoints (registrator.cpp:344-400)
+  void mergeRegisteredPoints(int object, io::RichCloud &merged)
+  {
+    const int V = model_->numViews();
+    for (int v = 0; v < V; ++v) {
+      const ScanCloud &pc = model_->getPointCloud(object, v);
+      if (!pc.isRegistered()) continue;
+      const RowMatrixd &M = pc.getMatrix();
+      auto pre = [&M](float x, float y, float z, float out[3]) {              // osg::Matrixd::preMult(Vec3f): (x, y, z, 1) * M / w
+        const double w = 1.0 / (M(0, 3) * x + M(1, 3) * y + M(2, 3) * z + M(3, 3));
+        for (int k = 0; k < 3; ++k) out[k] = (float)((M(0, k) * x + M(1, k) * y + M(2, k) * z + M(3, k)) * w);
+      };
+      for (size_t j = 0; j < pc.size(); ++j) {
+        io::RichPoint q = j < pc.rich.size() ? pc.rich[j] : io::RichPoint();
+        const PCLPoint &p = pc.points.points[j];
+        float o[3];
+        pre(p.x, p.y, p.z, o); q.x = o[0]; q.y = o[1]; q.z = o[2];
+        pre(q.normal_x, q.normal_y, q.normal_z, o); q.normal_x = o[0]; q.normal_y = o[1]; q.normal_z = o[2];
+        merged.push_back(q);
+      }
+    }
+  }
+
   // raw scans -> device slots (once per object and per revision of its clouds); posed copies get slots of their own
   void ensureResident(int object)
   {

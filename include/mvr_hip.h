@@ -137,6 +137,40 @@ int  mvr_cloud_clear(mvr_ctx *ctx, int slot);
  * vertex (the later copies become isolated and are dropped by any segment_threshold > 1). */
 int  mvr_cloud_denoise(mvr_ctx *ctx, int slot, int segment_threshold, double triangle_length,
                        size_t *n_kept, size_t *n_components, uint32_t *kept_index);
+/* ---- voxel-grid downsampling (EXTENSION: pcl::VoxelGrid<PointXYZ>::filter with setLeafSize(lx, ly, lz),
+ * setMinimumPointsNumberPerVoxel(min_points) and downsample_all_data = true).  The reference pins no PCL version; where
+ * PCL versions differ, or PCL is undefined, the rule below is this library's rule.
+ *  1. Finite points only: a point with a non-finite coordinate belongs to no voxel (PCL's is_dense == false path);
+ *     min_p / max_p are taken over the finite points.  No finite point (or an empty cloud): empty output, MVR_OK.
+ *  2. inv[a] = 1.0f / leaf[a] in f32.  Every leaf[a] must be finite and > 0, else MVR_E_ARG before any GPU work, nothing
+ *     changed; MVR_E_ARG too for more than 0xFFFFFFF0 points, a NULL ctx / leaf or a bad slot.
+ *  3. PCL's overflow rule: d[a] = (int64)((max_p[a] - min_p[a]) * inv[a]) + 1, the difference and the product in f32.
+ *     When d0 * d1 * d2 > INT32_MAX the output is a COPY of the input (every point, non-finite ones included, normals
+ *     included), *passthrough = 1 and the call returns MVR_OK.  An axis whose f32 product is not below 2^31 (NaN
+ *     included) takes the same exit, and so does an axis where |min_p * inv| or |max_p * inv| is not below 2^62 (PCL's
+ *     int cast is undefined there): no cast overflows.  As a last guard, a voxel index (rule 4) that would not fit in 64
+ *     bits takes it too; under the bounds above div[a] stays within a small multiple of d[a], so the index needs about 40
+ *     bits and this guard does not fire.
+ *  4. Voxel index, PCL's f32 arithmetic (the products are f32 multiplies by inv, never contracted):
+ *     min_b[a] = floor(min_p[a] * inv[a]), max_b[a] likewise, as integers (64-bit here; PCL's int);
+ *     div[a] = max_b[a] - min_b[a] + 1;  ijk[a] = floor(p[a] * inv[a]) - (float)min_b[a], the f32 difference as an
+ *     integer (it is a non-negative f32 integer);  idx = ijk0 + ijk1 * div0 + ijk2 * div0 * div1 in 64 bits (where PCL's
+ *     int idx can wrap near the limit, this one does not).  A point exactly on a voxel face goes to the upper voxel.
+ *  5. A voxel with fewer than min_points points is dropped (0, the default, keeps every occupied voxel).
+ *  6. Output points in ascending idx (PCL's order).  voxel_of (optional, host, one entry per SOURCE point): the output
+ *     position of point i's voxel; UINT32_MAX for a non-finite point or a dropped voxel; the identity under rule 3.
+ *  7. Centroid, per coordinate: the f64 sum of the voxel's f32 coordinates / count, rounded to f32; w = 1.  (PCL sums
+ *     in f32; this library deliberately does not.)  Sums run in a fixed order: bit-identical from run to run.
+ *  8. Normals: when the source slot carries normals, each output normal is the f64 sum of the voxel's normals,
+ *     normalised in f64 (x / sqrt((x*x + y*y) + z*z)) and rounded to f32, w = 0 -- PCL >= 1.8's CentroidPoint /
+ *     AccumulatorNormal (PCL 1.7 left the mean unnormalised); normalising keeps the slot's unit-normal rule that
+ *     point-to-plane ICP relies on.  A zero sum stays (0, 0, 0); a NaN normal in the voxel gives NaN.  No source
+ *     normals: no output normals.
+ *  9. dst_slot may equal src_slot (in place); otherwise src_slot is left untouched.  The output is a NEW point set:
+ *     orderings, grids and pose bookkeeping are dropped, as after mvr_cloud_upload / mvr_cloud_denoise.
+ * n_out / passthrough (optional) receive the output size and the rule-3 flag. */
+int  mvr_cloud_voxel_grid(mvr_ctx *ctx, int dst_slot, int src_slot, const float leaf[3], unsigned min_points,
+                          size_t *n_out, uint32_t *voxel_of, int *passthrough);
 /* PointCloud::getTransformedPoints (point_cloud.cpp:290-303): f32 points times
  * the f64 pose (osg::Matrixd::preMult incl. the w divide), rounded to f32.
  * dst_slot may equal src_slot. */

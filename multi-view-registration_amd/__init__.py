@@ -16,6 +16,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import sys
+import warnings
 
 import numpy as np
 
@@ -126,6 +127,7 @@ SIGNATURES = {
     "mvr_cloud_copy": (C.c_int, [_vp, C.c_int, C.c_int]),
     "mvr_cloud_append": (C.c_int, [_vp, C.c_int, C.c_int]),
     "mvr_cloud_denoise": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _u32p]),
+    "mvr_cloud_voxel_grid": (C.c_int, [_vp, C.c_int, C.c_int, _fp, C.c_uint, C.POINTER(_sz), _u32p, C.POINTER(C.c_int)]),
     "mvr_cloud_set_global_base": (C.c_int, [_vp, C.c_int, _sz]),
     "mvr_cloud_append_range": (C.c_int, [_vp, C.c_int, C.c_int, _sz, _sz, _sz]),
     "mvr_nn_forward_keys": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp]),
@@ -518,6 +520,30 @@ class Context:
         _chk(_lib.mvr_cloud_denoise(self._h, slot, int(segment_threshold), float(triangle_length), C.byref(kept), C.byref(comps),
                                     _p(idx, C.c_uint32)), self._h)
         return idx[:kept.value].copy(), comps.value
+
+    def voxel_grid(self, dst, src, leaf, min_points=0, return_map=False):
+        """pcl::VoxelGrid::filter of slot src into slot dst (may be src): the centroid of every occupied voxel, in ascending
+        voxel index, averaged normals when src has normals (rules: mvr_cloud_voxel_grid in mvr_hip.h).  leaf: a scalar or
+        three values.  Returns n_out, or (n_out, voxel_of) with return_map (voxel_of[i]: output position of source point i's
+        voxel, UINT32_MAX for a non-finite point or a dropped voxel).  When PCL's integer indices would overflow, the output
+        is a copy of the input and a warning says so, as PCL's does."""
+        lf = np.asarray(leaf, np.float32).reshape(-1)
+        if lf.size == 1:
+            lf = np.repeat(lf, 3)
+        if lf.size != 3:
+            raise ValueError("leaf must be a scalar or three values")
+        lf = np.ascontiguousarray(lf)
+        n = self.size(src)
+        vmap = np.empty(max(n, 1), np.uint32) if return_map else None
+        n_out, passthrough = _sz(), C.c_int()
+        _chk(_lib.mvr_cloud_voxel_grid(self._h, int(dst), int(src), _p(lf, C.c_float), int(min_points), C.byref(n_out),
+                                       _p(vmap, C.c_uint32) if return_map else None, C.byref(passthrough)), self._h)
+        if passthrough.value:
+            warnings.warn("[pcl::VoxelGrid::applyFilter] Leaf size is too small for the input dataset. "
+                          "Integer indices would overflow.")
+        if return_map:
+            return n_out.value, vmap[:n]
+        return n_out.value
 
     # ---- target sharding over ranks (sequential mode): see seq.py
     def set_global_base(self, slot, global_begin):

@@ -113,6 +113,8 @@ int prof_drain(Ctx *c)
 
 bool slot_ok(int s) { return s >= 0 && s < MVR_MAX_SLOTS; }
 
+}  // namespace
+
 int cloud_reserve(Ctx *c, Cloud &cl, size_t cap, bool keep)
 {
   if (cl.cap >= cap) return MVR_OK;
@@ -129,6 +131,8 @@ int cloud_reserve(Ctx *c, Cloud &cl, size_t cap, bool keep)
   cl.pts = np; cl.cap = ncap;
   return MVR_OK;
 }
+
+namespace {
 
 void cloud_free(Cloud &cl)
 {
@@ -657,6 +661,17 @@ API int mvr_cloud_denoise(mvr_ctx *ctx, int slot, int segment_threshold, double 
   Ctx *c = CTX(ctx);
   MVR_HIP_TRY(c, hipSetDevice(c->device));
   return denoise_cloud(c, c->slots[slot], segment_threshold, triangle_length, n_kept, n_components, kept_index);
+}
+
+API int mvr_cloud_voxel_grid(mvr_ctx *ctx, int dst_slot, int src_slot, const float leaf[3], unsigned min_points, size_t *n_out,
+                             uint32_t *voxel_of, int *passthrough)
+{
+  if (!ctx || !leaf || !slot_ok(dst_slot) || !slot_ok(src_slot)) return MVR_E_ARG;
+  Ctx *c = CTX(ctx);
+  for (int a = 0; a < 3; ++a)
+    if (!(std::isfinite(leaf[a]) && leaf[a] > 0.0f)) return set_error(c, MVR_E_ARG, "mvr_cloud_voxel_grid: leaf sizes must be finite and > 0");
+  MVR_HIP_TRY(c, hipSetDevice(c->device));
+  return voxel_grid_cloud(c, c->slots[dst_slot], c->slots[src_slot], leaf, min_points, n_out, voxel_of, passthrough);
 }
 
 API int mvr_cloud_copy(mvr_ctx *ctx, int dst, int src)

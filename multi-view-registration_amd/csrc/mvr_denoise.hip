@@ -187,21 +187,6 @@ __global__ void gather_kernel(const float4 *__restrict__ in, const unsigned long
   if (index_out) index_out[k] = i;
 }
 
-// All scratch arrays are carved out of ONE grow-only buffer kept by the context (twelve hipMalloc + hipFree per call
-// cost more than the kernels: 5.3 ms per 204k-point scan, 1.5 ms of it on the GPU).
-struct Carver {
-  char *base = nullptr;
-  size_t off = 0;
-  template <class T> void plan(size_t count) { off = ((off + 255) & ~(size_t)255) + std::max<size_t>(count, 1) * sizeof(T); }
-  template <class T> T *take(size_t count)
-  {
-    off = (off + 255) & ~(size_t)255;
-    T *p = reinterpret_cast<T *>(base + off);
-    off += std::max<size_t>(count, 1) * sizeof(T);
-    return p;
-  }
-};
-
 }  // namespace
 
 int denoise_cloud(Ctx *c, Cloud &cl, int segment_threshold, double triangle_length, size_t *n_kept, size_t *n_components,
