@@ -1185,6 +1185,34 @@ static int pair_batch_fused(Ctx *c, Ctx *w, int n_pairs, const int *src, const i
   // (unseeded_grid: the forward searches of a pass WITHOUT seeds -- a registration's first -- walk the grid too: every query probes
   // the cells next to it, what finds nothing there goes to the listed sets; the culled kernel took 0.59 ms for such a pass)
   const bool grid_fwd = grid_ok && (seed || c->unseeded_grid);
+  // the listed sets: over the grid (a block per set stages the union of the flagged balls) while that union is a few
+  // hundred rows of cells -- with dense scans (small cells) it is thousands of points per set and the culled kernel's
+  // box hierarchy is the better tool again (36 x 1M: 5.9 ms per pass against 6.4).  grid_sets = 2 forces the grid.
+  bool sets_on_grid = grid_ok && c->cull_list && c->grid_lanes == 1 && c->grid_sets;
+  if (sets_on_grid && c->grid_sets == 1)
+    for (int k = 0; k < n_pairs && sets_on_grid; ++k) {
+      if (!qn[k]) continue;
+      const double span = (2.0 * max_dist + 4.0) / (double)c->slots[dst[k]].grid->h;      // cells across a rim set's union, roughly
+      sets_on_grid = span * span <= 300.0;
+    }
+  // Lean posing (Cloud::sorted_stale): does any kernel of this pass read a posed Hilbert-ordered copy as anything but queries, or
+  // its boxes?  Not when the forward searches walk the grid from seeds, their stragglers stay on the grid and the wide reverse
+  // queries take the wave-per-query launch.  That is also what the NEXT pass of the same pairs will do, which is what its posing
+  // launch goes by (Ctx::lean_route).  A pass that was posed lean and turns out to need the arrays gets them here, first.
+  const bool route_lean = grid_fwd && seed && sets_on_grid && c->grid_wide != 0 && !c->grid_debug && w == c;
+  if (phases & 1) c->lean_route = route_lean;
+  {
+    std::vector<Cloud *> lean;
+    for (int k = 0; k < n_pairs; ++k) for (int sl : {src[k], dst[k]}) if (c->slots[sl].sorted_stale) lean.push_back(&c->slots[sl]);
+    if (!lean.empty() && !route_lean) { if (int rc = flush_lean_sorted(c, lean.data(), (int)lean.size())) return rc; }
+  }
+  if (grid_ok)
+    for (int k = 0; k < n_pairs; ++k) {
+      const Cloud &s = c->slots[src[k]], &t = c->slots[dst[k]];
+      if (qn[k] == 0) continue;
+      if (s.sorted_stale) { gfwd[k].qraw = s.lean_raw; gfwd[k].qpose_dev = s.pose_dev; }
+      if (t.sorted_stale) { grev[k].qraw = t.lean_raw; grev[k].qpose_dev = t.pose_dev; }
+    }
   if (phases & 1) w->marked_in_search = reciprocal && (c->fused_mark == 2 || (c->fused_mark == 1 && grid_fwd));
   if (w->marked_in_search)
     for (int k = 0; k < n_pairs; ++k) if (qn[k]) { fwd[k].mark = w->bbound + off_t[k]; if (grid_ok) gfwd[k].mark = fwd[k].mark; }
@@ -1211,16 +1239,7 @@ static int pair_batch_fused(Ctx *c, Ctx *w, int n_pairs, const int *src, const i
         }
         std::fprintf(stderr, "[grid] forward: %zu queries, %zu to a wave each, %zu to the culled kernel in %zu sets\n", off_s[n_pairs], wide, cull, sets);
       }
-      // the listed sets: over the grid (a block per set stages the union of the flagged balls) while that union is a few
-      // hundred rows of cells -- with dense scans (small cells) it is thousands of points per set and the culled kernel's
-      // box hierarchy is the better tool again (36 x 1M: 5.9 ms per pass against 6.4).  grid_sets = 2 forces the grid.
-      bool sets_on_grid = c->cull_list && c->grid_lanes == 1 && c->grid_sets;
-      if (sets_on_grid && c->grid_sets == 1)
-        for (int k = 0; k < n_pairs && sets_on_grid; ++k) {
-          if (!qn[k]) continue;
-          const double span = (2.0 * max_dist + 4.0) / (double)c->slots[dst[k]].grid->h;      // cells across a rim set's union, roughly
-          sets_on_grid = span * span <= 300.0;
-        }
+      // (the listed sets: over the grid or to the culled list kernel -- sets_on_grid, decided above)
       if (c->grid_wide && sets_on_grid && c->grid_tail) {           // the wide queries and the listed sets in ONE launch
         if (int rc = launch_nn_grid_tail_batch(w, gfwd.data(), n_pairs, cap2, fma != 0)) return rc;
       } else {
@@ -1248,6 +1267,8 @@ static int pair_batch_fused(Ctx *c, Ctx *w, int n_pairs, const int *src, const i
       const Cloud &s = c->slots[src[k]], &t = c->slots[dst[k]];
       GluePair &g = gb.p[j];
       g.src = s.pts; g.tgt = t.pts; g.qs = s.sorted; g.ts = t.sorted; g.by_pos = 1;
+      if (s.sorted_stale) { g.qraw = s.lean_raw; g.qrec = s.pose_dev; }      // (posed lean: the sums launch poses the points it adds up)
+      if (t.sorted_stale) { g.traw = t.lean_raw; g.trec = t.pose_dev; }
       g.keys = w->bkeys + off_s[k]; g.rkeys = w->brkeys + off_t[k];
       g.qperm = (s.order && qn[k]) ? s.order->perm : nullptr; g.tinv = (t.order && qn[k]) ? t.order->inv : nullptr;
       g.bound = w->bbound + off_t[k];
@@ -1309,7 +1330,8 @@ API int mvr_pair_moments2_batch(mvr_ctx *ctx, int n_pairs, const int *src, const
   if (c->nn_mode != 0) {
     std::vector<Cloud *> used;
     for (int k = 0; k < n_pairs; ++k) { used.push_back(&c->slots[src[k]]); used.push_back(&c->slots[dst[k]]); }
-    if (int rc = ensure_index_batch(c, used.data(), (int)used.size())) return rc;      // one refresh launch for all views
+    // (posed copies that were posed lean stay so for the fused pass: pair_batch_fused brings them up to date when its route needs them)
+    if (int rc = ensure_index_batch(c, used.data(), (int)used.size(), c->pair_fused != 0)) return rc;      // one refresh launch for all views
     host_mark("  batch: indices");
     if (c->pair_fused && c->ring_search && c->fused_passes > 0 && max_dist * max_dist < (double)FLT_MAX) {
       // the grid search's side: every posed copy finds its set's grid (built once, from the cloud that holds the set's
@@ -1725,9 +1747,17 @@ int ring_passes(Ctx *c, int n_steps, const PassLoop &L, double timing_ms[3])
     auto leave = [&]() {      // back to by-value poses; the host's pose bookkeeping catches up with what the last chain computed
       c->pose_from_table = false; c->no_sync = false; c->skip_posed_pts = false; c->pose_tab_pending = false;
       std::vector<const float4 *> in; std::vector<float4 *> out; std::vector<size_t> nn; std::vector<double> Ts;
+      // (views that were posed lean: their Hilbert-ordered copies and boxes are written now, by the full posing launch at the poses
+      // of the last chain -- and the points in original order by the same launch where they were left out too)
+      std::vector<Cloud *> lean; std::vector<const float4 *> lean_x; std::vector<double> lean_T;
       for (int v = 0; v < V; ++v) {
         Cloud &d = c->slots[L.posed_slots[v]];
         d.pose_dev = nullptr;
+        if (d.sorted_stale) {
+          lean.push_back(&d); lean_x.push_back(d.pts_stale ? c->slots[L.raw_slots[v]].pts : nullptr);
+          lean_T.insert(lean_T.end(), last_in.begin() + 16 * (size_t)v, last_in.begin() + 16 * (size_t)v + 16);
+          d.pts_stale = false;
+        }
         if (!d.posed_by_table) continue;                 // (a rank of a sharded run poses only the views its share touches)
         const bool was_known = d.pose_known;
         d.posed_by_table = false;
@@ -1739,6 +1769,7 @@ int ring_passes(Ctx *c, int n_steps, const PassLoop &L, double timing_ms[3])
           d.pts_stale = false;
         }
       }
+      if (!lean.empty()) (void)flush_lean_sorted(c, lean.data(), (int)lean.size(), lean_T.data(), lean_x.data());
       if (!in.empty()) (void)launch_transform_f64_batch(c, (int)in.size(), in.data(), out.data(), nn.data(), Ts.data());
     };
     c->pose_from_table = true; c->skip_posed_pts = true;
@@ -2658,6 +2689,7 @@ API int mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value)
 {
   if (!ctx || !key) return MVR_E_ARG;
   Ctx *c = CTX(ctx);
+  c->lean_route = false;      // (a knob may change which kernels the next pass runs: it is posed fully and says itself what it ran)
   if (!std::strcmp(key, "nn_q")) c->nn_q = value;
   else if (!std::strcmp(key, "nn_sub")) c->nn_sub = value;
   else if (!std::strcmp(key, "nn_blocks_per_cu")) c->nn_blocks_per_cu = value;
@@ -2666,6 +2698,7 @@ API int mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value)
   else if (!std::strcmp(key, "cull_w")) c->cull_w = value;
   else if (!std::strcmp(key, "cull_slices")) c->cull_slices = value;
   else if (!std::strcmp(key, "seed_forward")) c->seed_forward = value != 0;
+  else if (!std::strcmp(key, "lean_pose")) { if (value < 0 || value > 1) return MVR_E_ARG; c->lean_pose = value; }
   else if (!std::strcmp(key, "lazy_super")) { if (value < 0 || value > 1) return MVR_E_ARG; c->lazy_super = value; }
   else if (!std::strcmp(key, "fused_mark")) { if (value < 0 || value > 2) return MVR_E_ARG; c->fused_mark = value; }
   else if (!std::strcmp(key, "ring_search")) c->ring_search = value;
@@ -2755,6 +2788,7 @@ API int mvr_ctx_stat(mvr_ctx *ctx, const char *key, double *value)
   Ctx *c = CTX(ctx);
   if (!std::strcmp(key, "piped_passes")) *value = (double)c->piped_passes;
   else if (!std::strcmp(key, "fused_passes")) *value = (double)c->fused_passes;
+  else if (!std::strcmp(key, "lean_passes")) *value = (double)c->lean_passes;
   else if (!std::strcmp(key, "blocking_events")) *value = (double)c->blocking_events;
   else if (!std::strcmp(key, "pipeline")) *value = (double)c->pipeline;
   else if (!std::strncmp(key, "stage_", 6) && c->stage_stat) {      // staged walk diagnostics: waves by outcome since grid_stage_stat was set

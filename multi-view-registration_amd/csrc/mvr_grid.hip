@@ -437,7 +437,9 @@ __global__ void __launch_bounds__(kGridThreads) MVR_GRID_OCC nn_grid_kernel(Grid
     qpos = a.qlist ? a.qlist[pos] : a.q_begin + pos;            // position in the query cloud's Hilbert order
     // (the three loads that depend on nothing but the position go out together: the prologue is a chain of dependent gathers,
     // query -> previous match -> its grid position -> its coordinates, and every link not waited for separately is a round trip less)
-    q = a.qs[qpos];
+    // (a query cloud that was posed lean: the raw point, posed here -- the same 16 bytes, the same bits as the copy held)
+    if (a.qraw) q = pose_query_f64(load_pose_uniform(a.qpose_dev), a.qraw, qpos);
+    else q = a.qs[qpos];
     const uint32_t start_bits = a.qbound ? a.qbound[qpos] : 0xFFFFFFFFu;
     const unsigned long long pkey = a.seed_from_keys ? a.keys[qpos] : kKeyInit;
     const uint32_t prev = (uint32_t)pkey;
@@ -894,15 +896,21 @@ __device__ __forceinline__ void nn_grid_wide_body(const GridBatch &batch, unsign
   for (uint32_t i = bx * kWideWaves + wv; i < n_wide; i += stride) {
     const uint32_t pos = a.wide_list[i];
     const uint32_t qpos = a.qlist ? a.qlist[pos] : a.q_begin + pos;
-    const float4 q = a.qs[qpos];
+    // (a query cloud that was posed lean: the raw point, posed here.  The record is read where it is used, once per query -- sixteen
+    // wave-uniform values kept across this loop cost the kernel a wave per SIMD)
+    float4 q = a.qraw ? pose_query_f64(a.qpose_dev->T, a.qraw, qpos) : a.qs[qpos];
+    // (the wave's one query: the same in every lane, kept as scalars -- that pays for the registers the posing takes)
+    auto uni = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+    q.x = uni(q.x); q.y = uni(q.y); q.z = uni(q.z); q.w = uni(q.w);
     float bound = cap2;
     if (a.qbound) { const uint32_t v = a.qbound[qpos]; if (v <= __float_as_uint(bound)) bound = __uint_as_float(v); }
     if (a.seed_from_keys) {
       const uint32_t prev = (uint32_t)a.keys[qpos];
       if (prev < a.nt) { const float d = gdist2<FMA>(a.gts[a.h2g[prev]], q.x, q.y, q.z); if (d <= bound) bound = d; }
     }
+    bound = uni(bound);
     const Ball ball = grid_ball(a, q, bound);
-    const float rad = ball.rad, rx = ball.rx, ry = ball.ry, rz = ball.rz;
+    const float rad = uni(ball.rad), rx = uni(ball.rx), ry = uni(ball.ry), rz = uni(ball.rz);
     const int x0 = cell_of(rx - rad, a.lo[0], a.inv_h, a.dim[0]), x1 = cell_of(rx + rad, a.lo[0], a.inv_h, a.dim[0]);
     const int y0 = cell_of(ry - rad, a.lo[1], a.inv_h, a.dim[1]), y1 = cell_of(ry + rad, a.lo[1], a.inv_h, a.dim[1]);
     const int z0 = cell_of(rz - rad, a.lo[2], a.inv_h, a.dim[2]), z1 = cell_of(rz + rad, a.lo[2], a.inv_h, a.dim[2]);
@@ -1672,7 +1680,8 @@ __device__ __forceinline__ void nn_grid_set_body(const GridBatch &batch, unsigne
         valid = a.heavy[qpos] != 0;
       }
       if (valid) {
-        q = a.qs[qpos];
+        if (a.qraw) q = pose_query_f64(a.qpose_dev->T, a.qraw, qpos);      // (posed lean: as in nn_grid_wide_body)
+        else q = a.qs[qpos];
         bool bounded = false;
         if (a.qbound) { const uint32_t v = a.qbound[qpos]; if (v <= __float_as_uint(bound)) { bound = __uint_as_float(v); bounded = true; } }
         if (a.seed_from_keys) {

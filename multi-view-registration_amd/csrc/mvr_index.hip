@@ -258,6 +258,39 @@ __global__ void __launch_bounds__(256) refresh_sorted_kernel(RefreshBatch rb)
   }
 }
 
+// the lean posing launch of a queued pass whose searches all walk the grid: gout[k] = pose * graw[k] and the device pose
+// record, nothing else -- a plain stream of 16 bytes in and 16 out per lane.  The posed Hilbert-ordered copy and its boxes are
+// left as they are (Cloud::sorted_stale): the kernels of such a pass read that copy as queries only and pose each query
+// themselves.  Same pose handling as refresh_sorted_kernel; a block takes kLeanPer x 256 consecutive points, so that as few
+// blocks as there read the pose from the host's pinned table.
+constexpr int kLeanPer = 4;
+__global__ void __launch_bounds__(256) pose_grid_lean_kernel(LeanPoseBatch lb)
+{
+  const int cloud = blockIdx.y;
+  const size_t n = lb.n[cloud];
+  const size_t base = (size_t)blockIdx.x * (256 * kLeanPer);
+  if (base >= n) return;                               // block-uniform (block 0 of a cloud with points always stays)
+  __shared__ Mat44d s_T;
+  const double *tin = lb.Tin[cloud];
+  const double *tsrc = tin ? tin : lb.Tp[cloud]->m;
+  if (threadIdx.x < 16) s_T.m[threadIdx.x] = (tin && threadIdx.x == 3) ? 0.0 : tsrc[threadIdx.x];      // (element [3] of a pinned pose: the delta, see refresh_sorted_kernel)
+  __syncthreads();
+  if (tin && blockIdx.x == 0 && threadIdx.x == 0) make_pose_rec(s_T.m, (float)tin[3], reinterpret_cast<PoseRec *>(const_cast<Mat44d *>(lb.Tp[cloud])));
+  const float4 *__restrict__ graw = lb.graw[cloud];
+  float4 *__restrict__ gout = lb.gout[cloud];
+  const Mat44d &T = s_T;
+#pragma unroll
+  for (int r = 0; r < kLeanPer; ++r) {
+    const size_t k = base + (size_t)r * 256 + threadIdx.x;
+    if (k < n) {
+      const float4 g = graw[k];
+      float4 w = pose_point_f64(T, g);
+      w.w = g.w;
+      gout[k] = w;
+    }
+  }
+}
+
 // one wave per super box: the union of 64 consecutive tile boxes
 __global__ void __launch_bounds__(64) super_box_kernel(RefreshBatch rb)
 {
@@ -553,8 +586,8 @@ bool extend_point_set(Ctx *c, Cloud &dst, size_t old_n, const Cloud &src)
   dst.set_id = c->next_set_id++;                                         // a different point set, with an ordering already
   c->orders[dst.set_id] = dst.order;
   // the sorted copy and the boxes of the points that were there stay valid (they did not move): only the tail is refreshed
-  const bool head_ok = dst.coords_valid && dst.sorted != nullptr;
-  dst.coords_valid = false;
+  const bool head_ok = dst.coords_valid && dst.sorted != nullptr && !dst.sorted_stale;      // (a copy that was posed lean holds no current head: gathered whole)
+  dst.coords_valid = false; dst.sorted_stale = false; dst.lean_raw = nullptr;
   dst.fresh_tiles = head_ok ? old_n / kCullTile : 0;
   return true;
 }
@@ -858,6 +891,31 @@ static int refresh_batch(Ctx *c, Cloud *const *clouds, int count, const float4 *
     }
     if (int rc = flush_g2h(c)) return rc;      // (the position maps of the grids this batch met for the first time: one launch)
     if (tmax == 0) continue;
+    // Lean: a pass queued ahead of its poses whose predecessor ran without any kernel that reads a posed Hilbert-ordered copy
+    // or its boxes (Ctx::lean_route: seeded grid walk, its tail and sets on the grid, wide reverse queries) will do so again --
+    // only the grid-ordered coordinates and the pose records are written, half the bytes.  All clouds of the launch or none;
+    // a pass that needs the arrays after all brings them up to date itself (flush_lean_sorted).
+    bool lean = c->lean_pose != 0 && c->lean_route && c->pose_from_table && from && Tp && !xsrc && with_grid && !c->parent;
+    for (int k = 0; k < m && lean; ++k) lean = rb.from[k] && rb.Tp[k] && rb.graw[k] && rb.gout[k] && rb.n[k] != 0;
+    if (lean) {
+      LeanPoseBatch lb;
+      size_t nmax = 0; double lwork = 0.0;
+      for (int k = 0; k < kBatchClouds; ++k) {
+        lb.graw[k] = k < m ? rb.graw[k] : nullptr; lb.gout[k] = k < m ? rb.gout[k] : nullptr; lb.n[k] = k < m ? rb.n[k] : 0;
+        lb.Tin[k] = k < m ? rb.Tin[k] : nullptr; lb.Tp[k] = k < m ? rb.Tp[k] : nullptr;
+        if (k < m) { nmax = std::max(nmax, (size_t)rb.n[k]); lwork += 32.0 * (double)rb.n[k]; }
+      }
+      ProfScope ps(c, MVR_K_GLUE, lwork);
+      hipLaunchKernelGGL(pose_grid_lean_kernel, dim3((unsigned)((nmax + 256 * kLeanPer - 1) / (256 * kLeanPer)), (unsigned)m), dim3(256), 0, c->stream, lb);
+      MVR_HIP_TRY(c, hipGetLastError());
+      for (int k = 0; k < m; ++k) {
+        Cloud *cl = clouds[base + k];
+        cl->coords_valid = true; cl->fresh_tiles = 0; cl->super_stale = false;      // (see Cloud::sorted_stale: "valid" = nothing to gather again)
+        cl->sorted_stale = true; cl->lean_raw = rb.from[k];
+      }
+      if (base == 0) ++c->lean_passes;
+      continue;
+    }
     ProfScope ps(c, MVR_K_GLUE, work);
     hipLaunchKernelGGL(refresh_sorted_kernel, dim3((unsigned)((tmax + 3) / 4), (unsigned)m), dim3(256), 0, c->stream, rb);
     // The super boxes are read by the culled kernel alone.  Posed copies that have just got their grid-ordered coordinates are
@@ -954,8 +1012,27 @@ int refresh_posed_batch(Ctx *c, int count, Cloud *const *dst, Cloud *const *src,
                                              c->ring_search != 0 && c->pair_fused);
 }
 
+int flush_lean_sorted(Ctx *c, Cloud *const *clouds, int count, const double *T, const float4 *const *xsrc)
+{
+  Ctx *owner = c->parent ? c->parent : c;      // (the clouds, their buffers and the pose table belong to the context the caller made)
+  std::vector<Cloud *> todo; std::vector<const float4 *> from, xs; std::vector<double> Ts; std::vector<const Mat44d *> Tps;
+  for (int k = 0; k < count; ++k) {
+    Cloud *cl = clouds[k];
+    if (!cl || !cl->sorted_stale || std::find(todo.begin(), todo.end(), cl) != todo.end()) continue;
+    if (!cl->lean_raw || !cl->sorted || !cl->order || cl->n == 0) { cl->sorted_stale = false; cl->lean_raw = nullptr; cl->coords_valid = false; continue; }      // (cannot happen: gathered again from pts[] by the next ensure_index)
+    todo.push_back(cl); from.push_back(cl->lean_raw); xs.push_back(xsrc ? xsrc[k] : nullptr);
+    const double *t = T ? T + (size_t)k * 16 : cl->pose;
+    Ts.insert(Ts.end(), t, t + 16);
+    Tps.push_back((owner->pose_from_table && cl->pose_dev) ? &cl->pose_dev->T : nullptr);
+  }
+  if (todo.empty()) return MVR_OK;
+  for (Cloud *cl : todo) { cl->sorted_stale = false; cl->lean_raw = nullptr; cl->coords_valid = false; }
+  return refresh_batch(owner, todo.data(), (int)todo.size(), from.data(), Ts.data(), xsrc ? xs.data() : nullptr, Tps.data(), false);
+}
+
 int ensure_index(Ctx *c, Cloud &cl)
 {
+  if (cl.sorted_stale) { Cloud *one = &cl; if (int rc = flush_lean_sorted(c, &one, 1)) return rc; }
   bool stale = false;
   if (int rc = prepare_index(c, cl, &stale)) return rc;
   if (!stale) return MVR_OK;
@@ -963,8 +1040,9 @@ int ensure_index(Ctx *c, Cloud &cl)
   return refresh_batch(c, &one, 1);
 }
 
-int ensure_index_batch(Ctx *c, Cloud *const *clouds, int count)
+int ensure_index_batch(Ctx *c, Cloud *const *clouds, int count, bool keep_lean)
 {
+  if (!keep_lean) { if (int rc = flush_lean_sorted(c, clouds, count)) return rc; }
   if (count >= 2) { if (int rc = build_orders_batch(c, clouds, count)) return rc; }
   host_mark("      index batch: orderings");
   std::vector<Cloud *> todo;

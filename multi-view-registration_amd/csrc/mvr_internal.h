@@ -141,7 +141,7 @@ struct Cloud {
   bool super_stale = false;            // sbox[] was NOT refreshed with the tile boxes (a posed copy about to be searched over its grid): flush_super_boxes() before a culled launch
   bool coords_valid = false;           // sorted[] / tlo / thi / cbox match pts[]
   size_t fresh_tiles = 0;              // with !coords_valid: that many LEADING tiles of sorted[] / boxes are still current (a cloud that only grew at its end: mvr_cloud_append with an extended ordering); any other change of the coordinates resets it
-  void stale_coords() { coords_valid = false; fresh_tiles = 0; gcoords_valid = false; mgrid_ok = false; }
+  void stale_coords() { coords_valid = false; fresh_tiles = 0; gcoords_valid = false; mgrid_ok = false; sorted_stale = false; lean_raw = nullptr; }
   // optional unit normals {nx,ny,nz,0} (point-to-plane extension, K10)
   float4 *nrm = nullptr; size_t nrm_cap = 0;
   bool has_normals = false;
@@ -172,6 +172,12 @@ struct Cloud {
   float bbox[6] = {0, 0, 0, 0, 0, 0}; uint64_t bbox_set = 0;      // with bbox_set == set_id (and canonical): the bounding box of pts[], taken when the cloud was uploaded (the grid build then needs no round trip for it)
   bool pts_stale = false;              // pts[] were left out by the last (pipelined) pose of this cloud: sorted[] / gsorted[] are current, pts[] are written when the run leaves the pipe
   bool posed_by_table = false;         // ... and the last transform of this cloud did read it (its host-side pose is filled in when the run leaves the pipe)
+  // the last (pipelined) pose of this cloud was LEAN: only gsorted[] and the device pose record were written.  sorted[] and the
+  // boxes are NOT current although coords_valid says so -- the kernels of such a pass pose their queries themselves, from
+  // lean_raw[] (the raw scan's Hilbert-ordered copy: same order, same w) and the record; whoever wants the arrays themselves
+  // calls flush_lean_sorted() first (ensure_index / ensure_index_batch do), and the run writes them when it leaves the pipe
+  bool sorted_stale = false;
+  const float4 *lean_raw = nullptr;
 };
 
 constexpr uint32_t kNone = 0xFFFFFFFFu;      // "no neighbour" index
@@ -371,6 +377,12 @@ struct Ctx {
   unsigned long long pipe_steady_sig = 0, pipe_steady_events = ~0ull;      // the registration whose last run ended in steady state, and blocking_events then
   std::vector<double> pass_ms;                        // wall time of every pass of the last ring run (end of the previous solve -> end of this one)
   unsigned long long piped_passes = 0;                // passes of this context whose chain was enqueued ahead of their poses (diagnostics)
+  // lean posing (refresh_batch, mvr_index.hip): a queued pass whose searches will all walk the grid writes only the grid-ordered
+  // coordinates and the pose record of its posed copies -- the Hilbert-ordered copy is read as QUERIES only, and every kernel of
+  // such a pass poses its query as it loads it (Cloud::sorted_stale)
+  int lean_pose = 1;                                  // tune key: 0 = every posing launch writes the Hilbert-ordered copy and its boxes
+  bool lean_route = false;                            // the last fused pass of this context ran without a kernel that reads a posed Hilbert copy or its boxes (seeded grid walk, tail and sets on the grid, wide reverse queries): the next one, same pairs, will too
+  unsigned long long lean_passes = 0;                 // passes of this context that were posed lean (stat key)
   // multi-GPU (mvr_world.cpp): an RCCL communicator (ncclComm_t; null = this context is a world of its own)
   void *comm = nullptr; bool comm_owned = false; int comm_rank = 0, comm_world = 1;
   void **comm_lender = nullptr;                       // a world's communicator is lent: where the world keeps it (cleared when it is aborted here)
@@ -471,6 +483,26 @@ __device__ __forceinline__ float4 pose_point_f64(const Mat44d &T, const float4 p
   o.w = 1.0f;
   return o;
 }
+// a pose record's matrix as sixteen wave-uniform values (scalar registers): for the kernels that pose their own queries with
+// pose_point_f64 -- the record is the same for every thread of the launch's pair
+__device__ __forceinline__ Mat44d load_pose_uniform(const PoseRec *r)
+{
+  Mat44d T;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const double v = r->T.m[j];
+    T.m[j] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+  }
+  return T;
+}
+// the query at position k of a cloud that was posed lean: exactly what the full posing launch stores in its sorted[k]
+__device__ __forceinline__ float4 pose_query_f64(const Mat44d &T, const float4 *__restrict__ raw, const size_t k)
+{
+  const float4 p = raw[k];
+  float4 v = pose_point_f64(T, p);
+  v.w = p.w;
+  return v;
+}
 // the device record of a pose (PoseRec) from its 16 doubles: inverse of x -> A x + t by cofactors, in double, as make_grid_pair
 // does on the host; the stretch for ANY invertible matrix (the host has checked e <= 1e-3 before it released the pass: note_pose's bar)
 __device__ __forceinline__ void make_pose_rec(const double *T, float delta, PoseRec *out)
@@ -524,7 +556,17 @@ int refresh_posed_batch(Ctx *c, int count, Cloud *const *dst, Cloud *const *src,
                         char *handled = nullptr);
 int launch_transform_f64_batch(Ctx *c, int count, const float4 *const *in, float4 *const *out, const size_t *n, const double *T,
                                const Mat44d *const *Tp = nullptr);
-int ensure_index_batch(Ctx *c, Cloud *const *clouds, int count);     // ensure_index for many clouds, coordinates refreshed in one launch
+// ensure_index for many clouds, coordinates refreshed in one launch.  keep_lean: clouds that were posed lean stay as they are
+// (the caller is the fused pass, which brings them up to date itself when one of its kernels reads the arrays)
+int ensure_index_batch(Ctx *c, Cloud *const *clouds, int count, bool keep_lean = false);
+// the lean posing launch: only the grid-ordered coordinates and the device pose record (32 B per point instead of 64)
+struct LeanPoseBatch {
+  const float4 *graw[kBatchClouds]; float4 *gout[kBatchClouds]; unsigned long long n[kBatchClouds];
+  const double *Tin[kBatchClouds]; const Mat44d *Tp[kBatchClouds];      // as RefreshBatch: Tin (pinned, optional) is read and block 0 fills the record Tp points into; without Tin the record itself is read
+};
+// sorted[] / boxes of the clouds that were posed lean, by the full refresh (pose: the device record while passes are queued
+// ahead, else `T`, 16 doubles per cloud, or the cloud's own host pose); with_pts: the points in original order too
+int flush_lean_sorted(Ctx *c, Cloud *const *clouds, int count, const double *T = nullptr, const float4 *const *xsrc = nullptr);
 
 // ---- kernel launchers (mvr_nn.hip / mvr_reduce.hip / mvr_index.hip) -----------
 // forward / reverse brute-force NN.  Queries: points [q_begin, q_begin+q_count)
@@ -598,6 +640,7 @@ int launch_nn_cull_list_batch(Ctx *c, const CullPair *pairs, int n_pairs, float 
 // ---- grid search (mvr_grid.hip): exact 1-NN of seeded / bounded queries, one thread per query
 struct GridPair {
   const float4 *qs = nullptr;                 // queries: a Hilbert-ordered posed cloud (w = original index)
+  const float4 *qraw = nullptr;               // a query cloud that was posed lean: its RAW Hilbert-ordered copy -- the query is pose_point_f64(qpose_dev->T, qraw[pos]), qs[] is not read
   const uint32_t *qlist = nullptr, *qcount = nullptr;     // optional: compacted query positions + their device count (key slot = list position)
   uint32_t q_begin = 0, q_count = 0;
   const float4 *gts = nullptr;                // target: posed coordinates in GRID order (w = original index)
@@ -694,6 +737,8 @@ int launch_nn_cull(Ctx *c, const Cloud &q, size_t q_begin, size_t q_count, const
 struct GluePair {
   const float4 *src = nullptr, *tgt = nullptr;            // original-order points
   const float4 *qs = nullptr, *ts = nullptr;              // the same points in index (Hilbert) order, w = original index
+  const float4 *qraw = nullptr, *traw = nullptr;          // by_pos, a cloud that was posed lean: its raw Hilbert-ordered copy and its device pose record instead (see GridPair::qraw)
+  const PoseRec *qrec = nullptr, *trec = nullptr;
   const nnkey_t *keys = nullptr, *rkeys = nullptr;        // forward keys [ns] (by original index, or by sorted position: by_pos), reverse keys [nt] (by sorted position)
   const uint32_t *qperm = nullptr, *tinv = nullptr;
   uint8_t *flags = nullptr;                               // [nt], sorted target space

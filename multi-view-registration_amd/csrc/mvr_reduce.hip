@@ -411,8 +411,15 @@ __device__ __forceinline__ void accept_moments2_body(const float4 *__restrict__ 
                                                      const uint32_t *__restrict__ slot, const uint32_t *__restrict__ qperm,
                                                      const uint32_t *__restrict__ tinv, size_t q_begin, size_t q_count, double max2,
                                                      int reciprocal, Vec3d o, unsigned block, unsigned n_blocks,
-                                                     double *__restrict__ partials)
+                                                     double *__restrict__ partials, const float4 *__restrict__ qraw = nullptr,
+                                                     const PoseRec *qrec = nullptr, const float4 *__restrict__ traw = nullptr,
+                                                     const PoseRec *trec = nullptr)
 {
+  // (BYPOS, a cloud that was posed lean: its points are posed here, from the raw Hilbert-ordered copy and the device record --
+  // the same 16 bytes per point, the same bits as the posed copy held)
+  Mat44d Tq, Tt;
+  if (BYPOS && qraw) Tq = load_pose_uniform(qrec);
+  if (BYPOS && traw) Tt = load_pose_uniform(trec);
   double acc[29];
 #pragma unroll
   for (int k = 0; k < 29; ++k) acc[k] = 0.0;
@@ -442,7 +449,7 @@ __device__ __forceinline__ void accept_moments2_body(const float4 *__restrict__ 
 #pragma unroll
     for (int u = 0; u < kUn; ++u) {
       key[u] = ~(nnkey_t)0; p4[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (ok[u]) { key[u] = keys[i[u]]; if (BYPOS) p4[u] = src[i[u]]; }
+      if (ok[u]) { key[u] = keys[i[u]]; if (BYPOS) p4[u] = qraw ? qraw[i[u]] : src[i[u]]; }
     }
 #pragma unroll
     for (int u = 0; u < kUn; ++u) {
@@ -483,7 +490,15 @@ __device__ __forceinline__ void accept_moments2_body(const float4 *__restrict__ 
 #pragma unroll
     for (int u = 0; u < kUn; ++u) {
       q4[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (ok[u]) { if (!BYPOS) p4[u] = src[i[u]]; q4[u] = tgt[tpos[u]]; }
+      if (ok[u]) { if (!BYPOS) p4[u] = src[i[u]]; q4[u] = (BYPOS && traw) ? traw[tpos[u]] : tgt[tpos[u]]; }
+    }
+    if (BYPOS && (qraw || traw)) {
+#pragma unroll
+      for (int u = 0; u < kUn; ++u) {
+        if (!ok[u]) continue;
+        if (qraw) p4[u] = pose_point_f64(Tq, p4[u]);      // (.w, the original index, has been taken above)
+        if (traw) q4[u] = pose_point_f64(Tt, q4[u]);
+      }
     }
 #pragma unroll
     for (int u = 0; u < kUn; ++u) {
@@ -528,7 +543,7 @@ __global__ void __launch_bounds__(kRT) accept_moments2_batch_kernel(GlueBatch b)
   const Vec3d o{b.origin[0], b.origin[1], b.origin[2]};
   if (a.by_pos)
     accept_moments2_body<true>(a.qs, a.ts, a.keys, a.rkeys, a.slot, nullptr, a.tinv, (size_t)a.q_begin, (size_t)a.q_count, b.max2, b.reciprocal, o,
-                               blockIdx.x, (unsigned)a.blocks, a.partials);
+                               blockIdx.x, (unsigned)a.blocks, a.partials, a.qraw, a.qrec, a.traw, a.trec);
   else
     accept_moments2_body<false>(a.src, a.tgt, a.keys, a.rkeys, a.slot, a.qperm, a.tinv, (size_t)a.q_begin, (size_t)a.q_count, b.max2, b.reciprocal, o,
                                 blockIdx.x, (unsigned)a.blocks, a.partials);
