@@ -282,6 +282,135 @@ class VoxelGrid {
   unsigned int min_points_ = 0;
 };
 
+// ---------------------------------------------------------------- outlier removal
+// pcl::StatisticalOutlierRemoval<PointT> (filters/statistical_outlier_removal.h) and pcl::RadiusOutlierRemoval<PointT>
+// (filters/radius_outlier_removal.h) for 16-byte XYZ points, PCL's member names and defaults (mean_k 1, stddev_mul 0,
+// min_neighbors 1).  Semantics: mvr_cloud_statistical_outlier_removal / mvr_cloud_radius_outlier_removal (mvr_hip.h) -- one
+// call on the GPU per filter().  `output` may be the input cloud itself, as for VoxelGrid.  filter(indices) gives the indices
+// of the output points instead; constructed with extract_removed_indices = true, getRemovedIndices() holds the complement
+// after a filter().  A missing input or a parameter outside its range prints an error and leaves the output empty
+// (untouched when it is the input).
+namespace detail {
+// the ascending complement of the ascending list `kept` in 0..n-1
+inline void complement_indices(const std::vector<uint32_t> &kept, size_t n_kept, size_t n, std::vector<int> &out)
+{
+  out.clear();
+  size_t k = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (k < n_kept && kept[k] == i) ++k;
+    else out.push_back((int)i);
+  }
+}
+}  // namespace detail
+
+template <typename PointT>
+class StatisticalOutlierRemoval {
+ public:
+  typedef PointCloud<PointT> PointCloudT;
+  typedef typename PointCloudT::ConstPtr PointCloudConstPtr;
+  typedef std::shared_ptr<const std::vector<int> > IndicesConstPtr;
+
+  explicit StatisticalOutlierRemoval(bool extract_removed_indices = false) : extract_removed_(extract_removed_indices) {}
+  void setInputCloud(const PointCloudConstPtr &c) { input_ = c; }
+  PointCloudConstPtr getInputCloud() const { return input_; }
+  void setMeanK(int k) { mean_k_ = k; }
+  int getMeanK() const { return mean_k_; }
+  void setStddevMulThresh(double m) { stddev_mul_ = m; }
+  double getStddevMulThresh() const { return stddev_mul_; }
+  void setNegative(bool negative) { negative_ = negative; }
+  bool getNegative() const { return negative_; }
+  IndicesConstPtr getRemovedIndices() const { return removed_; }
+  void getRemovedIndices(std::vector<int> &out) const { out = *removed_; }
+
+  void filter(PointCloudT &output) { run(&output, nullptr); }
+  void filter(std::vector<int> &indices) { run(nullptr, &indices); }
+
+ private:
+  void run(PointCloudT *output, std::vector<int> *indices)
+  {
+    removed_->clear();
+    if (indices) indices->clear();
+    if (!input_) { std::fprintf(stderr, "[pcl::StatisticalOutlierRemoval::filter] No input dataset given!\n"); if (output) output->clear(); return; }
+    if (mean_k_ < 1 || mean_k_ > MVR_MAX_KNN || !std::isfinite(stddev_mul_)) {
+      std::fprintf(stderr, "[pcl::StatisticalOutlierRemoval::filter] mean_k (%d) must be in 1..%d and the multiplier (%f) finite.\n", mean_k_, MVR_MAX_KNN, stddev_mul_);
+      if (output && output != input_.get()) output->clear();
+      return;
+    }
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.upload(s.s, *input_);              // first: `output` may alias the input
+    const size_t n = input_->size();
+    std::vector<uint32_t> kept(n ? n : 1);
+    size_t n_out = 0;
+    mvr_sor_params p;
+    p.mean_k = mean_k_; p.stddev_mul = stddev_mul_; p.negative = negative_ ? 1 : 0; p.fma_dist = 0;
+    d.check(mvr_cloud_statistical_outlier_removal(d.ctx(), s.s, s.s, &p, &n_out, kept.data(), nullptr, nullptr), "mvr_cloud_statistical_outlier_removal");
+    if (extract_removed_) detail::complement_indices(kept, n_out, n, *removed_);
+    if (indices) indices->assign(kept.begin(), kept.begin() + (std::ptrdiff_t)n_out);
+    if (output) d.download(s.s, *output);
+  }
+
+  PointCloudConstPtr input_;
+  int mean_k_ = 1;
+  double stddev_mul_ = 0.0;
+  bool negative_ = false, extract_removed_ = false;
+  std::shared_ptr<std::vector<int> > removed_ = std::make_shared<std::vector<int> >();
+};
+
+template <typename PointT>
+class RadiusOutlierRemoval {
+ public:
+  typedef PointCloud<PointT> PointCloudT;
+  typedef typename PointCloudT::ConstPtr PointCloudConstPtr;
+  typedef std::shared_ptr<const std::vector<int> > IndicesConstPtr;
+
+  explicit RadiusOutlierRemoval(bool extract_removed_indices = false) : extract_removed_(extract_removed_indices) {}
+  void setInputCloud(const PointCloudConstPtr &c) { input_ = c; }
+  PointCloudConstPtr getInputCloud() const { return input_; }
+  void setRadiusSearch(double r) { radius_ = r; }
+  double getRadiusSearch() const { return radius_; }
+  void setMinNeighborsInRadius(int m) { min_neighbors_ = m; }
+  int getMinNeighborsInRadius() const { return min_neighbors_; }
+  void setNegative(bool negative) { negative_ = negative; }
+  bool getNegative() const { return negative_; }
+  IndicesConstPtr getRemovedIndices() const { return removed_; }
+  void getRemovedIndices(std::vector<int> &out) const { out = *removed_; }
+
+  void filter(PointCloudT &output) { run(&output, nullptr); }
+  void filter(std::vector<int> &indices) { run(nullptr, &indices); }
+
+ private:
+  void run(PointCloudT *output, std::vector<int> *indices)
+  {
+    removed_->clear();
+    if (indices) indices->clear();
+    if (!input_) { std::fprintf(stderr, "[pcl::RadiusOutlierRemoval::filter] No input dataset given!\n"); if (output) output->clear(); return; }
+    if (!(std::isfinite(radius_) && radius_ > 0.0) || min_neighbors_ < 0) {
+      std::fprintf(stderr, "[pcl::RadiusOutlierRemoval::filter] The radius (%f) must be finite and > 0, min_neighbors (%d) >= 0.\n", radius_, min_neighbors_);
+      if (output && output != input_.get()) output->clear();
+      return;
+    }
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.upload(s.s, *input_);              // first: `output` may alias the input
+    const size_t n = input_->size();
+    std::vector<uint32_t> kept(n ? n : 1);
+    size_t n_out = 0;
+    mvr_ror_params p;
+    p.radius = radius_; p.min_neighbors = min_neighbors_; p.negative = negative_ ? 1 : 0; p.fma_dist = 0;
+    d.check(mvr_cloud_radius_outlier_removal(d.ctx(), s.s, s.s, &p, &n_out, kept.data(), nullptr), "mvr_cloud_radius_outlier_removal");
+    if (extract_removed_) detail::complement_indices(kept, n_out, n, *removed_);
+    if (indices) indices->assign(kept.begin(), kept.begin() + (std::ptrdiff_t)n_out);
+    if (output) d.download(s.s, *output);
+  }
+
+  PointCloudConstPtr input_;
+  double radius_ = 0.0;
+  int min_neighbors_ = 1;
+  bool negative_ = false, extract_removed_ = false;
+  std::shared_ptr<std::vector<int> > removed_ = std::make_shared<std::vector<int> >();
+};
+
 namespace registration {
 
 // ------------------------------------------------- CorrespondenceEstimation

@@ -211,6 +211,31 @@ class ScanCloud {
     return before - kept;
   }
 
+  // EXTENSION (pcl::StatisticalOutlierRemoval / pcl::RadiusOutlierRemoval on the raw points, on the GPU): `points` keep the
+  // inliers in their original order (rules: mvr_cloud_statistical_outlier_removal / mvr_cloud_radius_outlier_removal in
+  // mvr_hip.h); when `rich` holds one record per point, the records follow their points as in denoise().  Parameters outside
+  // their range print an error and change nothing.  Returns the number of points removed.
+  size_t removeStatisticalOutliers(int mean_k, double stddev_mul)
+  {
+    if (mean_k < 1 || mean_k > MVR_MAX_KNN || !std::isfinite(stddev_mul)) {
+      std::fprintf(stderr, "[ScanCloud::removeStatisticalOutliers] mean_k (%d) must be in 1..%d and the multiplier (%f) finite.\n", mean_k, MVR_MAX_KNN, stddev_mul);
+      return 0;
+    }
+    mvr_sor_params p;
+    p.mean_k = mean_k; p.stddev_mul = stddev_mul; p.negative = 0; p.fma_dist = 0;
+    return removeOutliers(&p, nullptr);
+  }
+  size_t removeRadiusOutliers(double radius, int min_neighbors)
+  {
+    if (!(std::isfinite(radius) && radius > 0.0) || min_neighbors < 0) {
+      std::fprintf(stderr, "[ScanCloud::removeRadiusOutliers] The radius (%f) must be finite and > 0, min_neighbors (%d) >= 0.\n", radius, min_neighbors);
+      return 0;
+    }
+    mvr_ror_params p;
+    p.radius = radius; p.min_neighbors = min_neighbors; p.negative = 0; p.fma_dist = 0;
+    return removeOutliers(nullptr, &p);
+  }
+
   // point_cloud.cpp:305-326 / :328-347 -- `transformation.txt`: the column-vector
   // 4x4 printed row by row (matrix(j,i), i outer), "%lf " per element, one row per
   // line.  6 decimals: poses round-trip to 1e-6 only.
@@ -243,6 +268,27 @@ class ScanCloud {
   }
 
  private:
+  // one of the two filters (the other pointer null) in place on `points`; `rich` follows through kept_index
+  size_t removeOutliers(const mvr_sor_params *sor, const mvr_ror_params *ror)
+  {
+    Device &d = Device::instance();
+    SlotGuard s;
+    const size_t before = points.size();
+    d.upload(s.s, points);
+    size_t kept = 0;
+    std::vector<uint32_t> index(before ? before : 1);
+    if (sor) d.check(mvr_cloud_statistical_outlier_removal(d.ctx(), s.s, s.s, sor, &kept, index.data(), nullptr, nullptr), "mvr_cloud_statistical_outlier_removal");
+    else d.check(mvr_cloud_radius_outlier_removal(d.ctx(), s.s, s.s, ror, &kept, index.data(), nullptr), "mvr_cloud_radius_outlier_removal");
+    d.download(s.s, points);
+    if (rich.size() == before) {                   // colours and normals follow their points
+      io::RichCloud r(kept);
+      for (size_t k = 0; k < kept; ++k) r[k] = rich[index[k]];
+      rich.swap(r);
+    }
+    touch();
+    return before - kept;
+  }
+
   RowMatrixd matrix_;
   std::string filename_;
   unsigned long long revision_ = 0;

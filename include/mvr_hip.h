@@ -238,6 +238,65 @@ typedef struct {
 int  mvr_cloud_estimate_normals(mvr_ctx *ctx, int count, const int *slots, const mvr_normal_params *p,
                                 float *const *curvature);
 
+/* ---- sparse outlier removal (EXTENSION: pcl::StatisticalOutlierRemoval and pcl::RadiusOutlierRemoval) ------------
+ * The reference pins no PCL version; where PCL versions differ, or PCL is loose, the rule below is this library's rule.
+ * Common to both filters:
+ *  1. Distances are the f32 expression of mvr_nn / mvr_knn, d2 = (dx*dx + dy*dy) + dz*dz, each operation rounded;
+ *     fma_dist = 1 selects the fma chain.
+ *  2. A point with a non-finite coordinate is an outlier by definition: it is nobody's neighbour, enters no statistic,
+ *     is never in the inlier output and always in the `negative` output.  (PCL keeps such a point, with a distance of 0;
+ *     here, as in mvr_cloud_voxel_grid, a NaN must not reach ICP.)
+ *  3. Output: the selected points in their ORIGINAL index order, w = 1; normals of the source slot follow their points.
+ *     dst_slot may equal src_slot; otherwise src_slot is left untouched.  The output is a NEW point set: orderings,
+ *     grids and pose bookkeeping are dropped, as after mvr_cloud_denoise.
+ *  4. negative = 1 (PCL's setNegative(true)) outputs exactly the complement.
+ *  5. kept_index (optional, host, capacity = source size) receives the original indices of the output points,
+ *     ascending; n_out (optional) their number.
+ *  6. An empty cloud is MVR_OK with an empty output.  A NULL ctx / params, a bad slot or a parameter outside its range
+ *     (below) returns MVR_E_ARG before any GPU work and writes nothing.
+ *
+ * Statistical outlier removal (setMeanK, setStddevMulThresh, setNegative):
+ *  7. mean_k in 1..MVR_MAX_KNN; stddev_mul any finite double (negative values allowed, as in PCL).
+ *  8. For a finite point i take the mean_k smallest d2 over the finite points j != i; other points at the same
+ *     location count, at d2 = 0.  (PCL asks for mean_k + 1 neighbours and skips the first: the same multiset.)
+ *     mean_dist[i] = f32( (sum, in ascending order of d2, of the correctly rounded f32 sqrt(d2), added in f64) / mean_k ):
+ *     PCL's arithmetic.
+ *  9. Fewer than mean_k other finite points: no point has a mean distance; every finite point is an inlier,
+ *     n_valid = 0, mean / stddev / threshold are NaN and mean_dist is NaN throughout.
+ * 10. Statistics over the n_valid finite points in f64, two passes, in a fixed summation order (bit-identical from run
+ *     to run): mean = sum(md) / n, stddev = sqrt(sum((md - mean)^2) / (n - 1)), threshold = mean + stddev_mul * stddev.
+ *     (PCL's one-pass form (sum(md^2) - sum(md)^2 / n) / (n - 1) can go negative when all distances are equal; this one
+ *     cannot.)  n_valid = 1 gives NaN, as PCL.
+ * 11. A finite point is an inlier iff !((double)mean_dist[i] > threshold): a NaN threshold keeps every finite point.
+ * 12. mean_dist (optional, host, one f32 per SOURCE point): NaN for a non-finite point.  stats (optional).
+ *
+ * Radius outlier removal (setRadiusSearch, setMinNeighborsInRadius, setNegative):
+ * 13. radius finite and > 0; min_neighbors >= 0.
+ * 14. count[i] = number of finite j != i with d2(i, j) <= (float)(radius * radius): the rule of the radius mode of
+ *     mvr_cloud_estimate_normals, minus the point itself.  A finite point is an inlier iff count[i] >= min_neighbors.
+ *     (PCL counts the point itself and removes when k <= min_pts: the same set.)
+ * 15. neighbor_count (optional, host, one u32 per SOURCE point): exact, 0 for a non-finite point. */
+typedef struct {
+  int    mean_k;        /* setMeanK: 1..MVR_MAX_KNN (PCL default 1)            */
+  double stddev_mul;    /* setStddevMulThresh (PCL default 0)                  */
+  int    negative;      /* setNegative                                         */
+  int    fma_dist;
+} mvr_sor_params;
+typedef struct {
+  double mean, stddev, threshold;   /* of the mean distances (rule 10)         */
+  size_t n_valid;                   /* points that have a mean distance        */
+} mvr_sor_stats;
+typedef struct {
+  double radius;        /* setRadiusSearch: finite, > 0                        */
+  int    min_neighbors; /* setMinNeighborsInRadius: >= 0 (PCL default 1)       */
+  int    negative;      /* setNegative                                         */
+  int    fma_dist;
+} mvr_ror_params;
+int  mvr_cloud_statistical_outlier_removal(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_sor_params *p, size_t *n_out,
+                                           uint32_t *kept_index, float *mean_dist, mvr_sor_stats *stats);
+int  mvr_cloud_radius_outlier_removal(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_ror_params *p, size_t *n_out,
+                                      uint32_t *kept_index, uint32_t *neighbor_count);
+
 /* CorrespondenceEstimation::determineReciprocalCorrespondences(corrs, max_d)
  * (registrator.cpp:496-502, 644-649); reciprocal = 0 gives
  * determineCorrespondences.  Outputs are host arrays of capacity `cap`

@@ -107,6 +107,21 @@ class NormalParams(C.Structure):
     _fields_ = [("k", C.c_int), ("radius", C.c_double), ("viewpoint", C.c_float * 3), ("fma_dist", C.c_int)]
 
 
+class SorParams(C.Structure):
+    """mvr_sor_params"""
+    _fields_ = [("mean_k", C.c_int), ("stddev_mul", C.c_double), ("negative", C.c_int), ("fma_dist", C.c_int)]
+
+
+class SorStats(C.Structure):
+    """mvr_sor_stats"""
+    _fields_ = [("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double), ("n_valid", C.c_size_t)]
+
+
+class RorParams(C.Structure):
+    """mvr_ror_params"""
+    _fields_ = [("radius", C.c_double), ("min_neighbors", C.c_int), ("negative", C.c_int), ("fma_dist", C.c_int)]
+
+
 _fp, _dp, _u32p, _i32p = (C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                           C.POINTER(C.c_int32))
 _vp, _sz = C.c_void_p, C.c_size_t
@@ -128,6 +143,9 @@ SIGNATURES = {
     "mvr_cloud_append": (C.c_int, [_vp, C.c_int, C.c_int]),
     "mvr_cloud_denoise": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _u32p]),
     "mvr_cloud_voxel_grid": (C.c_int, [_vp, C.c_int, C.c_int, _fp, C.c_uint, C.POINTER(_sz), _u32p, C.POINTER(C.c_int)]),
+    "mvr_cloud_statistical_outlier_removal": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(SorParams), C.POINTER(_sz), _u32p, _fp,
+                                                        C.POINTER(SorStats)]),
+    "mvr_cloud_radius_outlier_removal": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RorParams), C.POINTER(_sz), _u32p, _u32p]),
     "mvr_cloud_set_global_base": (C.c_int, [_vp, C.c_int, _sz]),
     "mvr_cloud_append_range": (C.c_int, [_vp, C.c_int, C.c_int, _sz, _sz, _sz]),
     "mvr_nn_forward_keys": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp]),
@@ -544,6 +562,52 @@ class Context:
         if return_map:
             return n_out.value, vmap[:n]
         return n_out.value
+
+    def statistical_outlier_removal(self, dst, src, mean_k, stddev_mul, negative=False, fma=False, return_index=False,
+                                    return_dist=False, return_stats=False):
+        """pcl::StatisticalOutlierRemoval::filter of slot src into slot dst (may be src): the points whose mean distance to
+        their mean_k nearest other points is not above mean + stddev_mul * stddev, in their original order (negative: the
+        complement); normals follow (rules: mvr_cloud_statistical_outlier_removal in mvr_hip.h).  Returns n_out, or a tuple
+        (n_out[, kept_index][, mean_dist][, stats]) with the return_* options: kept_index = original indices of the output
+        points, mean_dist = one f32 per SOURCE point (NaN for a non-finite point), stats = dict(mean, stddev, threshold,
+        n_valid)."""
+        n = self.size(src)
+        p = SorParams(int(mean_k), float(stddev_mul), int(bool(negative)), int(bool(fma)))
+        idx = np.empty(max(n, 1), np.uint32) if return_index else None
+        md = np.empty(max(n, 1), np.float32) if return_dist else None
+        st, n_out = SorStats(), _sz()
+        _chk(_lib.mvr_cloud_statistical_outlier_removal(self._h, int(dst), int(src), C.byref(p), C.byref(n_out),
+                                                        _p(idx, C.c_uint32) if return_index else None,
+                                                        _p(md, C.c_float) if return_dist else None, C.byref(st)), self._h)
+        out = [n_out.value]
+        if return_index:
+            out.append(idx[:n_out.value].copy())
+        if return_dist:
+            out.append(md[:n])
+        if return_stats:
+            out.append({"mean": st.mean, "stddev": st.stddev, "threshold": st.threshold, "n_valid": int(st.n_valid)})
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def radius_outlier_removal(self, dst, src, radius, min_neighbors, negative=False, fma=False, return_index=False,
+                               return_counts=False):
+        """pcl::RadiusOutlierRemoval::filter of slot src into slot dst (may be src): the points with at least min_neighbors
+        other points within radius, in their original order (negative: the complement); normals follow (rules:
+        mvr_cloud_radius_outlier_removal in mvr_hip.h).  Returns n_out, or (n_out[, kept_index][, neighbor_count]); the
+        counts are one uint32 per SOURCE point."""
+        n = self.size(src)
+        p = RorParams(float(radius), int(min_neighbors), int(bool(negative)), int(bool(fma)))
+        idx = np.empty(max(n, 1), np.uint32) if return_index else None
+        cnt = np.empty(max(n, 1), np.uint32) if return_counts else None
+        n_out = _sz()
+        _chk(_lib.mvr_cloud_radius_outlier_removal(self._h, int(dst), int(src), C.byref(p), C.byref(n_out),
+                                                   _p(idx, C.c_uint32) if return_index else None,
+                                                   _p(cnt, C.c_uint32) if return_counts else None), self._h)
+        out = [n_out.value]
+        if return_index:
+            out.append(idx[:n_out.value].copy())
+        if return_counts:
+            out.append(cnt[:n])
+        return out[0] if len(out) == 1 else tuple(out)
 
     # ---- target sharding over ranks (sequential mode): see seq.py
     def set_global_base(self, slot, global_begin):

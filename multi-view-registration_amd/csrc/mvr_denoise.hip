@@ -189,6 +189,14 @@ __global__ void gather_kernel(const float4 *__restrict__ in, const unsigned long
 
 }  // namespace
 
+int launch_gather(Ctx *c, const float4 *in, const unsigned long long *okey, size_t kept, float4 *out, uint32_t *index_out)
+{
+  if (!kept) return MVR_OK;
+  hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((kept + 255) / 256)), dim3(256), 0, c->stream, in, okey, kept, out, index_out);
+  MVR_HIP_TRY(c, hipGetLastError());
+  return MVR_OK;
+}
+
 int denoise_cloud(Ctx *c, Cloud &cl, int segment_threshold, double triangle_length, size_t *n_kept, size_t *n_components,
                   uint32_t *host_index)
 {
@@ -247,10 +255,10 @@ int denoise_cloud(Ctx *c, Cloud &cl, int segment_threshold, double triangle_leng
   MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
   const size_t kept = hc[1];
   if (kept) {
-    hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((kept + 255) / 256)), dim3(256), 0, c->stream, cl.pts, okey_b, kept, out, d_index);
+    if (int rc = launch_gather(c, cl.pts, okey_b, kept, out, d_index)) return rc;
     MVR_HIP_TRY(c, hipMemcpyAsync(cl.pts, out, kept * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     if (cl.has_normals) {
-      hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((kept + 255) / 256)), dim3(256), 0, c->stream, cl.nrm, okey_b, kept, out, (uint32_t *)nullptr);
+      if (int rc = launch_gather(c, cl.nrm, okey_b, kept, out, nullptr)) return rc;
       MVR_HIP_TRY(c, hipMemcpyAsync(cl.nrm, out, kept * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     }
     if (host_index) MVR_HIP_TRY(c, hipMemcpyAsync(host_index, d_index, kept * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));

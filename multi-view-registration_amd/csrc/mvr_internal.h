@@ -800,6 +800,9 @@ int cloud_reserve(Ctx *c, Cloud &cl, size_t cap, bool keep);
 // PointCloud::denoise (mvr_denoise.hip): the cloud is replaced by its kept points, in the reference's output order
 int denoise_cloud(Ctx *c, Cloud &cl, int segment_threshold, double triangle_length, size_t *n_kept, size_t *n_components,
                   uint32_t *host_index);
+// the tail of a filter that keeps a subset (mvr_denoise.hip: gather_kernel): out[k] = in[low word of okey[k]] for k < kept, and
+// index_out[k] (optional) = that index -- points and normals alike
+int launch_gather(Ctx *c, const float4 *in, const unsigned long long *okey, size_t kept, float4 *out, uint32_t *index_out);
 // pcl::VoxelGrid::filter (mvr_voxel.hip; rules at mvr_cloud_voxel_grid in mvr_hip.h): dst (which may be src) gets the voxel
 // centroids as a new point set
 int voxel_grid_cloud(Ctx *c, Cloud &dst, Cloud &src, const float leaf[3], unsigned min_points, size_t *n_out, uint32_t *voxel_of,

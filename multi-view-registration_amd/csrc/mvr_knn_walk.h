@@ -1,0 +1,119 @@
+// csrc/mvr_knn_walk.h -- what the kernels that walk a cloud's model grid around a query share (mvr_knn.hip: k-NN lists and
+// normals; mvr_outlier.hip: mean neighbour distances and neighbour counts): the search side of a slot, the cell lookup of the
+// compact table, the row ranges, the library's f32 distance and the f64 bound at which a shell walk may stop.  Not installed.
+#pragma once
+
+#include "mvr_internal.h"
+
+namespace mvr {
+
+struct KnnSlot {
+  const float4 *qs;                // queries: grid order with w = bits(index) -- or, with q_by_pos, index order
+  const float4 *gt;                // target points: grid order with w = bits(index) -- or, without a grid (dir null), index order
+  const float4 *tpts;              // target points in index order (k-mode normals read the neighbours from here)
+  const uint32_t *dir, *recs;      // compact cell starts of the target grid (CellGrid); dir null: one cell [0, nt)
+  float4 *nrm;                     // normals out, by query index
+  float *curv;                     // optional: curvature out, by query index
+  uint32_t *oidx; float *od2;      // k-NN out: [nq][k] by query index
+  float lo[3], inv_h;
+  int dim[3];
+  uint32_t nq, nt, q_by_pos, blk0;
+};
+
+constexpr uint32_t kSegOcc = 0x80000000u;
+// the cell-start lookup of the compact table (the same encoding as cell_start_of in mvr_grid.hip)
+__device__ __forceinline__ uint32_t knn_cell_start(const KnnSlot &S, uint32_t c)
+{
+  const uint32_t d = S.dir[c >> 5];
+  return (d & kSegOcc) ? S.recs[((d & ~kSegOcc) << 5) + (c & 31u)] : d;
+}
+__device__ __forceinline__ int knn_cell_of(float x, float lo, float inv_h, int dim)
+{
+  // the grid build's own assignment (mvr_grid.hip: cell_of): monotone in x, clamped to the grid
+  const float f = floorf((x - lo) * inv_h);
+  return (int)fminf(fmaxf(f, 0.f), (float)(dim - 1));
+}
+template <bool FMA>
+__device__ __forceinline__ float knn_dist2(const float4 t, const float4 q)
+{
+  const float dx = t.x - q.x, dy = t.y - q.y, dz = t.z - q.z;
+  if (FMA) return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+  float r = dx * dx;
+  r = r + dy * dy;
+  r = r + dz * dz;
+  return r;
+}
+
+// the grid positions where the cells [x0, x1] of row (y, z) begin and end (no grid: the one cell [0, nt))
+__device__ __forceinline__ void knn_row_range(const KnnSlot &S, int x0, int x1, int y, int z, uint32_t *s, uint32_t *e)
+{
+  if (!S.dir) { *s = 0u; *e = S.nt; return; }
+  const uint32_t c0 = (uint32_t)((z * S.dim[1] + y) * S.dim[0] + x0);
+  *s = knn_cell_start(S, c0);
+  *e = knn_cell_start(S, c0 + (uint32_t)(x1 - x0) + 1u);
+}
+
+// the nearest an unvisited cell can be once the box of cells [x0, x1] x [y0, y1] x [z0, z1] around the query is visited (lo_* /
+// hi_*: the grid has cells beyond that side): the gap between the query and the box on those sides, in cells of the grid's own
+// f32 inverse edge (f64), less a margin every rounding fits in -- the f32 cell assignment of a point (relative 2^-22 of its
+// offset from lo, plus an ulp of the coordinate) and the f32 distance (the 1e-5 of d2 the callers take off): 1e-6 of the
+// magnitudes involved is ten times that.  Squared and reduced by that 1e-5 it is compared with the k-th d2.
+__device__ __forceinline__ double knn_unvisited_bound(const KnnSlot &S, const float4 q, int x0, int x1, int y0, int y1, int z0, int z1,
+                                                      bool lo_x, bool hi_x, bool lo_y, bool hi_y, bool lo_z, bool hi_z)
+{
+  const double ih = (double)S.inv_h;
+  const double ux = ((double)q.x - (double)S.lo[0]) * ih, uy = ((double)q.y - (double)S.lo[1]) * ih, uz = ((double)q.z - (double)S.lo[2]) * ih;
+  double g = 1.0e300;
+  if (lo_x) g = fmin(g, ux - (double)x0);
+  if (hi_x) g = fmin(g, (double)(x1 + 1) - ux);
+  if (lo_y) g = fmin(g, uy - (double)y0);
+  if (hi_y) g = fmin(g, (double)(y1 + 1) - uy);
+  if (lo_z) g = fmin(g, uz - (double)z0);
+  if (hi_z) g = fmin(g, (double)(z1 + 1) - uz);
+  const double mag = fabs((double)q.x) + fabs((double)q.y) + fabs((double)q.z) + fabs((double)S.lo[0]) + fabs((double)S.lo[1]) +
+                     fabs((double)S.lo[2]) + (double)(S.dim[0] + S.dim[1] + S.dim[2]) / ih;
+  return g / ih - (1.0e-6 * mag + 1.0e-6 / ih);
+}
+
+// the cells the ball of radius sqrt(r2) around q overlaps: the radius widened by the same margins as the bound above (f32 cell
+// arithmetic is monotone); without a grid the one cell
+__device__ __forceinline__ void knn_ball_cells(const KnnSlot &S, const float4 q, float r2, int *x0, int *x1, int *y0, int *y1, int *z0, int *z1)
+{
+  *x0 = *x1 = *y0 = *y1 = *z0 = *z1 = 0;
+  if (!S.dir) return;
+  const float mag = fabsf(q.x) + fabsf(q.y) + fabsf(q.z) + fabsf(S.lo[0]) + fabsf(S.lo[1]) + fabsf(S.lo[2]) +
+                    (float)(S.dim[0] + S.dim[1] + S.dim[2]) / S.inv_h;
+  const float rad = sqrtf(r2) * 1.0001f + 1.0e-5f * mag;
+  *x0 = knn_cell_of(q.x - rad, S.lo[0], S.inv_h, S.dim[0]); *x1 = knn_cell_of(q.x + rad, S.lo[0], S.inv_h, S.dim[0]);
+  *y0 = knn_cell_of(q.y - rad, S.lo[1], S.inv_h, S.dim[1]); *y1 = knn_cell_of(q.y + rad, S.lo[1], S.inv_h, S.dim[1]);
+  *z0 = knn_cell_of(q.z - rad, S.lo[2], S.inv_h, S.dim[2]); *z1 = knn_cell_of(q.z + rad, S.lo[2], S.inv_h, S.dim[2]);
+}
+
+inline int kmax_bucket(int k) { return k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64; }
+
+// the search side of a slot: its grid over the current coordinates when it can have one, else one cell over the points
+inline int fill_target(Ctx *c, Cloud &t, KnnSlot &S)
+{
+  if (t.pts_stale) return set_error(c, MVR_E_ARG, "k-NN / normals: the cloud's points are not current (pipelined run)");
+  S.gt = t.pts; S.tpts = t.pts; S.dir = nullptr; S.recs = nullptr; S.nt = (uint32_t)t.n;
+  for (int j = 0; j < 3; ++j) { S.lo[j] = 0.f; S.dim[j] = 1; }
+  S.inv_h = 0.f;
+  if (t.n == 0) return MVR_OK;
+  bool ok = false;
+  if (int rc = ensure_model_grid(c, t, 0.0, &ok)) return rc;
+  if (!ok) return MVR_OK;
+  const CellGrid &g = *t.mgrid;
+  S.gt = g.graw; S.dir = g.dir; S.recs = g.recs; S.inv_h = g.inv_h;
+  for (int j = 0; j < 3; ++j) { S.lo[j] = g.lo[j]; S.dim[j] = g.dim[j]; }
+  return MVR_OK;
+}
+// the query side: grid order when the cloud has a grid (the lanes of a wave are then neighbours), else index order
+inline void fill_queries(const Cloud &q, KnnSlot &S)
+{
+  const bool grid = q.mgrid && q.mgrid_ok && q.mgrid->n == q.n && q.n > 0;
+  S.qs = grid ? q.mgrid->graw : q.pts;
+  S.q_by_pos = grid ? 0u : 1u;
+  S.nq = (uint32_t)q.n;
+}
+
+}  // namespace mvr
