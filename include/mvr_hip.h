@@ -134,7 +134,9 @@ int  mvr_cloud_clear(mvr_ctx *ctx, int slot);
  * by their smallest point index), points in index order -- the reference's output order.  kept_index (optional,
  * host, capacity = old size) receives the original indices of the kept points.  One documented difference: exact
  * duplicate points are ordinary members of their component here, while CGAL's insert keeps only the first of them as a
- * vertex (the later copies become isolated and are dropped by any segment_threshold > 1). */
+ * vertex (the later copies become isolated and are dropped by any segment_threshold > 1).
+ * Non-finite points: no rule.  A NaN stays out of the cell sizing (what it is linked to is unspecified); an infinite coordinate makes the
+ * cell edge infinite, which puts every point into one cell (no undefined conversion, but a quadratic search): unsupported. */
 int  mvr_cloud_denoise(mvr_ctx *ctx, int slot, int segment_threshold, double triangle_length,
                        size_t *n_kept, size_t *n_components, uint32_t *kept_index);
 /* ---- voxel-grid downsampling (EXTENSION: pcl::VoxelGrid<PointXYZ>::filter with setLeafSize(lx, ly, lz),
@@ -194,7 +196,9 @@ int  mvr_cloud_download_normals(mvr_ctx *ctx, int slot, float *nxyz, size_t cap_
 /* exact 1-NN of every point of q_slot in t_slot: tree_->nearestKSearch(p,1,..)
  * (inside icp.align registrator.cpp:569,920,1012,1024 and :502,:649).
  * idx/d2 are host arrays of n_q entries (either may be NULL).  Ties -> lowest
- * index.  idx = UINT32_MAX and d2 = +inf when the target is empty. */
+ * index.  idx = UINT32_MAX and d2 = +inf when the target is empty.
+ * Non-finite points: no rule.  The index build clamps them into its boxes without converting one to an integer, but what a
+ * search returns for a cloud that holds a NaN or an infinity is unspecified and untested; filter such clouds first. */
 int  mvr_nn(mvr_ctx *ctx, int q_slot, int t_slot, int fma_dist, uint32_t *idx, float *d2);
 
 /* ---- k nearest neighbours and normal estimation (EXTENSION: pcl::NormalEstimation) -----------------------
@@ -205,7 +209,18 @@ int  mvr_nn(mvr_ctx *ctx, int q_slot, int t_slot, int fma_dist, uint32_t *idx, f
  * lexicographic order, ascending -- ties go to the lower index, as in mvr_nn.  When T holds fewer than k
  * points the tail entries are idx = UINT32_MAX, d2 = +inf (mvr_nn's empty-target convention).  k = 1 gives
  * exactly mvr_nn's (idx, d2), bit for bit.  The search is exact: a uniform grid over T's current
- * coordinates, walked shell by shell until no unvisited cell can hold a point within the k-th d2. */
+ * coordinates, walked shell by shell until no unvisited cell can hold a point within the k-th d2.
+ *
+ * Non-finite points (a NaN or an infinity in x, y or z; scanner files with is_dense == false hold them), for mvr_knn and
+ * mvr_cloud_estimate_normals alike, with or without fma_dist, for clouds of any size:
+ *  N1. A non-finite target point is nobody's neighbour: it is never listed and enters no covariance.  More generally a
+ *      pair whose f32 d2 is not finite (which finite points reach only beyond 1e19) is not a neighbour pair.
+ *  N2. A non-finite query has no neighbours: idx = UINT32_MAX and d2 = +inf in all k entries.
+ *  N3. The tail rule above counts the FINITE target points: with fewer than k of them the tail is UINT32_MAX / +inf.
+ *  N4. A non-finite point gets a NaN normal and a NaN curvature; a finite point's normal is that of its finite
+ *      neighbours (fewer than 3 of them: NaN, as below).
+ *  N5. Non-finite points take no part in the sizing of the grid, and no query walks the grid because of one.
+ *  N6. "k = 1 equals mvr_nn" holds for clouds of finite points; mvr_nn has no rule for the others (see there). */
 #define MVR_MAX_KNN 64
 /* exact k nearest neighbours of every point of q_slot in t_slot; idx / d2 host arrays of n_q * k, row-major
  * (row = query index; either may be NULL).  MVR_E_ARG for k outside 1..MVR_MAX_KNN or a bad slot. */

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "mvr_internal.h"
+#include "mvr_grid_size.h"
 
 namespace mvr {
 
@@ -1408,29 +1409,28 @@ bool ensure_grid(Ctx *c, Cloud &canon, double reach)
 // registrator.cpp:576) searched as ONE point set -- one walk per query, where the part-by-part search (nn_parts_kernel) walks a
 // ball in each of the ~5 merged scans that cover a query's surface.  Compact form (segment directory + records), points in grid
 // order with w = the point's index in the cloud: the keys of a walk over it are the keys of a search of the merged cloud.
-int ensure_model_grid(Ctx *c, Cloud &t, double reach, bool *ok)
+int ensure_model_grid(Ctx *c, Cloud &t, double reach, bool *ok, bool *no_finite)
 {
   *ok = false;
-  if (t.n < 4 || t.n > 0x7FFFFFF0ull || !t.segs.empty() || t.pts_stale) return MVR_OK;
+  if (no_finite) *no_finite = false;
+  if (t.n < kModelGridMinPoints || t.n > kModelGridMaxPoints || !t.segs.empty() || t.pts_stale) return MVR_OK;
   if (t.mgrid && t.mgrid_ok && t.mgrid->n == t.n) { *ok = true; return MVR_OK; }
   t.mgrid.reset(); t.mgrid_ok = false;
   MVR_MAY_BLOCK(c, "the model has no grid yet");
+  // the box of the FINITE points: a NaN or an infinity takes no part in the sizing (model_grid_size refuses a box that holds
+  // one).  Non-finite points still get a cell -- cell_of clamps them to the grid -- and the walks pass over them.
   float bb[6];
-  if (int rc = cloud_bbox(c, t.pts, t.n, bb)) return rc;
+  if (int rc = cloud_bbox(c, t.pts, t.n, bb, true)) return rc;
+  ModelGridSize sz;
+  const ModelGridStatus st = model_grid_size(bb, t.n, c->seq_cell_points, &sz);
+  if (st != kModelGridOk) {          // no grid: the callers fall back to what they do for a cloud too small for one
+    if (no_finite) *no_finite = st == kModelGridEmpty;
+    return MVR_OK;
+  }
   auto g = std::make_shared<CellGrid>();
   g->n = t.n;
-  double ext[3];
-  for (int j = 0; j < 3; ++j) { g->lo[j] = bb[j]; ext[j] = std::max(1e-6, (double)bb[3 + j] - (double)bb[j]); }
-  const double area = ext[0] * ext[1] + ext[1] * ext[2] + ext[0] * ext[2];
-  double h = std::sqrt((double)std::max(1, c->seq_cell_points) * area / (double)t.n);
-  h = std::max(h, std::max(ext[0], std::max(ext[1], ext[2])) / 512.0);
-  for (;;) {
-    double cells = 1.0;
-    for (int j = 0; j < 3; ++j) { g->dim[j] = (int)std::floor(ext[j] / h) + 1; cells *= g->dim[j]; }
-    if (cells <= 32.0e6) break;
-    h *= 1.25;
-  }
-  g->h = (float)h; g->inv_h = (float)(1.0 / h);
+  for (int j = 0; j < 3; ++j) { g->lo[j] = sz.lo[j]; g->dim[j] = sz.dim[j]; }
+  g->h = sz.h; g->inv_h = sz.inv_h;
   const size_t cells = (size_t)g->dim[0] * g->dim[1] * g->dim[2], n = t.n;
   g->nseg = (uint32_t)((cells + 1 + 31) / 32);
   g->dt_shift = 1;
@@ -1442,7 +1442,7 @@ int ensure_model_grid(Ctx *c, Cloud &t, double reach, bool *ok)
   g->dir = reinterpret_cast<uint32_t *>(g->block + o_dir); g->recs = reinterpret_cast<uint32_t *>(g->block + o_recs);
   g->gperm = reinterpret_cast<uint32_t *>(g->block + o_gperm); g->graw = reinterpret_cast<float4 *>(g->block + o_graw);
   g->dt = reinterpret_cast<uint8_t *>(g->block + o_dt);
-  const int steps2 = (int)std::ceil(std::max(0.0, reach) / (2.0 * h)) + 2;
+  const int steps2 = (int)std::min((double)kGridDtMax, std::ceil(std::max(0.0, reach) / (2.0 * sz.h64))) + 2;      // (bounded before the conversion)
   g->dt_steps = std::min(kGridDtMax, std::max(2, steps2));
   std::vector<Cloud *> cc{&t}; std::vector<std::shared_ptr<CellGrid> > cg{g};
   if (int rc = build_compact_grids(c, cc, cg, c->stream)) return rc;

@@ -76,11 +76,15 @@ constexpr int kSortLoBit = MVR_SORT_LO_BIT;
 
 // ------------------------------------------------------------------ index build
 
+// FINITE: a point with a non-finite coordinate stays out of the box (fminf / fmaxf alone drop a NaN but take an infinity);
+// a cloud without a finite point leaves lo = 3e38 > hi = -3e38
+template <bool FINITE>
 __global__ void bbox_partial_kernel(const float4 *__restrict__ p, size_t n, float *__restrict__ part /* [blocks][6] */)
 {
   float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const float4 v = p[i];
+    if (FINITE && !(isfinite(v.x) && isfinite(v.y) && isfinite(v.z))) continue;
     lo[0] = fminf(lo[0], v.x); lo[1] = fminf(lo[1], v.y); lo[2] = fminf(lo[2], v.z);
     hi[0] = fmaxf(hi[0], v.x); hi[1] = fmaxf(hi[1], v.y); hi[2] = fmaxf(hi[2], v.z);
   }
@@ -557,14 +561,15 @@ void inherit_point_set(Cloud &dst, const Cloud &src)
   dst.stale_coords();
 }
 
-int cloud_bbox(Ctx *c, const float4 *pts, size_t n, float out[6])
+int cloud_bbox(Ctx *c, const float4 *pts, size_t n, float out[6], bool finite_only)
 {
   if (n == 0) return MVR_E_ARG;
   MVR_MAY_BLOCK(c, "a bounding box is read back");
   if (int rc = ensure(c, c->partials, c->partials_cap, (size_t)1024 * 32)) return rc;
   const int bb = (int)std::min<size_t>(256, (n + 255) / 256);
   float *part = reinterpret_cast<float *>(c->partials);
-  hipLaunchKernelGGL(bbox_partial_kernel, dim3(bb), dim3(256), 0, c->stream, pts, n, part);
+  if (finite_only) hipLaunchKernelGGL(bbox_partial_kernel<true>, dim3(bb), dim3(256), 0, c->stream, pts, n, part);
+  else hipLaunchKernelGGL(bbox_partial_kernel<false>, dim3(bb), dim3(256), 0, c->stream, pts, n, part);
   hipLaunchKernelGGL(bbox_final_kernel, dim3(1), dim3(64), 0, c->stream, part, bb, c->bbox);
   MVR_HIP_TRY(c, hipMemcpyAsync(out, c->bbox, 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -798,7 +803,7 @@ static int prepare_index(Ctx *c, Cloud &cl, bool *stale)
     ProfScope ps(c, MVR_K_GLUE, 40.0 * (double)n);
     const int bb = (int)std::min<size_t>(256, (n + 255) / 256);
     float *part = reinterpret_cast<float *>(c->partials);
-    hipLaunchKernelGGL(bbox_partial_kernel, dim3(bb), dim3(256), 0, c->stream, cl.pts, n, part);
+    hipLaunchKernelGGL(bbox_partial_kernel<false>, dim3(bb), dim3(256), 0, c->stream, cl.pts, n, part);
     hipLaunchKernelGGL(bbox_final_kernel, dim3(1), dim3(64), 0, c->stream, part, bb, c->bbox);
     hipLaunchKernelGGL(morton_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, cl.pts, n, c->bbox,
                        c->codes_a, c->idx_a);

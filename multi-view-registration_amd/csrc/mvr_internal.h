@@ -684,9 +684,9 @@ int launch_nn_grid_tail_batch(Ctx *c, const GridPair *pairs, int n_pairs, float 
 int launch_nn_grid_sets_batch(Ctx *c, const GridPair *pairs, int n_pairs, float cap2, bool fma);     // the 64-query sets the first launch listed (flagged queries only): a block per set over the grid     // the queries the first launch put on the wide lists
 // the set's grid (built from `canon`, a cloud holding the set's canonical coordinates) and the posed copy's grid-ordered
 // coordinates; false = not available (the caller uses the culled kernel)
-int cloud_bbox(Ctx *c, const float4 *pts, size_t n, float out[6]);      // {lo xyz, hi xyz} on the host (synchronises the stream)
+int cloud_bbox(Ctx *c, const float4 *pts, size_t n, float out[6], bool finite_only = false);      // {lo xyz, hi xyz} on the host (synchronises the stream); finite_only: over the points without a NaN or an infinity (none: lo > hi)
 bool ensure_grid(Ctx *c, Cloud &canon, double reach);
-int ensure_model_grid(Ctx *c, Cloud &t, double reach, bool *ok);      // the grid of a cloud over its own coordinates (Cloud::mgrid)
+int ensure_model_grid(Ctx *c, Cloud &t, double reach, bool *ok, bool *no_finite = nullptr);      // the grid of a cloud over its own coordinates (Cloud::mgrid); *no_finite: refused because no point of the cloud is finite
 GridPair make_model_pair(const Cloud &q, const Cloud &t, nnkey_t *keys);
 int ensure_grids(Ctx *c, Cloud *const *canon, int count, double reach, hipStream_t on, hipEvent_t after);      // the same for many sets at once, enqueued on `on` (no wait afterwards)      // reach: the search radius the distance map should be able to rule out (mm)
 int refresh_grid_coords_batch(Ctx *c, Cloud *const *posed, int count);

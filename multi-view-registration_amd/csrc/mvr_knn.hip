@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <vector>
 
 #include "mvr_internal.h"
@@ -63,13 +64,14 @@ __device__ __forceinline__ void knn_insert(nnkey_t (&L)[KMAX], const nnkey_t key
   L[0] = key < L[0] ? key : L[0];
 }
 
-// the exact k-best list of query q: KMAX - k leading zero keys, then the k best (kKeyInit where the target has fewer)
+// the exact k-best list of query q: KMAX - k leading zero keys, then the k best (kKnnKeyEmpty where the target has fewer
+// FINITE points within a finite f32 d2; a non-finite query has none: it returns at once and walks nothing)
 template <int KMAX, bool FMA>
 __device__ __forceinline__ void knn_walk(const KnnSlot &S, const float4 q, const int k, nnkey_t (&L)[KMAX])
 {
 #pragma unroll
-  for (int i = 0; i < KMAX; ++i) L[i] = i < KMAX - k ? 0ull : kKeyInit;
-  if (S.nt == 0) return;
+  for (int i = 0; i < KMAX; ++i) L[i] = i < KMAX - k ? 0ull : kKnnKeyEmpty;
+  if (S.nt == 0 || !knn_finite3(q)) return;
   const bool by_pos = !S.dir;
   const int cx = knn_cell_of(q.x, S.lo[0], S.inv_h, S.dim[0]), cy = knn_cell_of(q.y, S.lo[1], S.inv_h, S.dim[1]),
             cz = knn_cell_of(q.z, S.lo[2], S.inv_h, S.dim[2]);
@@ -101,7 +103,7 @@ __device__ __forceinline__ void knn_walk(const KnnSlot &S, const float4 q, const
     const bool lo_x = x0 > 0, hi_x = x1 < S.dim[0] - 1, lo_y = y0 > 0, hi_y = y1 < S.dim[1] - 1, lo_z = z0 > 0, hi_z = z1 < S.dim[2] - 1;
     if (!(lo_x || hi_x || lo_y || hi_y || lo_z || hi_z)) return;      // the whole grid seen
     const nnkey_t kth = L[KMAX - 1];
-    if (kth == kKeyInit) continue;                                    // the list is not full yet
+    if (kth == kKnnKeyEmpty) continue;                                // the list is not full yet
     // the nearest an unvisited cell can be (knn_unvisited_bound, mvr_knn_walk.h)
     const double b = knn_unvisited_bound(S, q, x0, x1, y0, y1, z0, z1, lo_x, hi_x, lo_y, hi_y, lo_z, hi_z);
     const double kd2 = (double)__uint_as_float((uint32_t)(kth >> 32));
@@ -209,9 +211,9 @@ __global__ void __launch_bounds__(kKnnThreads) knn_kernel(KnnBatch b)
 #pragma unroll
   for (int i = 0; i < KMAX; ++i) {
     if (i >= KMAX - b.k) {
-      const uint32_t j = (uint32_t)L[i];
-      oi[i - (KMAX - b.k)] = j;
-      od[i - (KMAX - b.k)] = j == kNone ? __builtin_inff() : __uint_as_float((uint32_t)(L[i] >> 32));
+      const bool none = L[i] == kKnnKeyEmpty;
+      oi[i - (KMAX - b.k)] = none ? kNone : (uint32_t)L[i];
+      od[i - (KMAX - b.k)] = __uint_as_float((uint32_t)(L[i] >> 32));      // (the empty key carries +inf)
     }
   }
 }
@@ -228,8 +230,7 @@ __global__ void __launch_bounds__(kKnnThreads) normals_knn_kernel(KnnBatch b)
   Moments M;
 #pragma unroll
   for (int i = 0; i < KMAX; ++i) {
-    const uint32_t j = (uint32_t)L[i];
-    if (i >= KMAX - b.k && j != kNone) M.add(S.tpts[j], q);
+    if (i >= KMAX - b.k && L[i] != kKnnKeyEmpty) M.add(S.tpts[(uint32_t)L[i]], q);
   }
   plane_from_moments(S, b, q, qi, M);
 }
@@ -242,15 +243,18 @@ __global__ void __launch_bounds__(kKnnThreads) normals_radius_kernel(KnnBatch b)
   float4 q; uint32_t qi;
   if (!knn_query(S, &q, &qi)) return;
   Moments M;
-  int x0 = 0, x1 = 0, y0 = 0, y1 = 0, z0 = 0, z1 = 0;
-  if (S.dir) knn_ball_cells(S, q, b.r2, &x0, &x1, &y0, &y1, &z0, &z1);
+  int x0 = 0, x1 = -1, y0 = 0, y1 = -1, z0 = 0, z1 = -1;      // (a non-finite query walks nothing: no neighbours, a NaN normal)
+  if (knn_finite3(q) && S.nt) {
+    x1 = y1 = z1 = 0;
+    if (S.dir) knn_ball_cells(S, q, b.r2, &x0, &x1, &y0, &y1, &z0, &z1);
+  }
   for (int z = z0; z <= z1; ++z)
     for (int y = y0; y <= y1; ++y) {
       uint32_t j, e;
       knn_row_range(S, x0, x1, y, z, &j, &e);
       for (; j < e; ++j) {
         const float4 p = S.gt[j];
-        if (knn_dist2<FMA>(p, q) <= b.r2) M.add(p, q);
+        if (knn_dist2<FMA>(p, q) <= b.r2) M.add(p, q);      // (r2 is finite: a non-finite p, with d2 = +inf or NaN, fails)
       }
     }
   plane_from_moments(S, b, q, qi, M);
@@ -374,7 +378,8 @@ API int mvr_cloud_estimate_normals(mvr_ctx *ctx, int count, const int *slots, co
     if (curvature && curvature[used[j]]) { all[j].curv = dcurv + off; off += all[j].nq; }
   KnnBatch proto{};
   proto.k = p->k;
-  proto.r2 = (float)(p->radius * p->radius);
+  // (float)(radius * radius), kept finite: a d2 of +inf -- a non-finite neighbour, or an f32 overflow -- is never <= r2
+  proto.r2 = (float)std::min(p->radius * p->radius, (double)std::numeric_limits<float>::max());
   for (int j = 0; j < 3; ++j) proto.vp[j] = p->viewpoint[j];
   int rc = run_batches(c, all, proto, kmode ? kmax_bucket(p->k) : 8, kmode ? 1 : 2, p->fma_dist != 0);
   hipError_t e = hipSuccess;

@@ -21,6 +21,11 @@ struct KnnSlot {
 };
 
 constexpr uint32_t kSegOcc = 0x80000000u;
+// the empty entry of a k-best list of (d2 bits << 32 | index) keys: d2 = +inf, index 0.  Every key with a FINITE d2 is below
+// it, every key with d2 = +inf or NaN (either sign: the bits of a NaN are above those of +inf) is not -- so the one test
+// `key < L[KMAX - 1]` of the candidate loop also keeps the non-finite target points out (mvr_hip.h: the non-finite rule).
+constexpr nnkey_t kKnnKeyEmpty = 0x7F80000000000000ull;
+__device__ __forceinline__ bool knn_finite3(const float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
 // the cell-start lookup of the compact table (the same encoding as cell_start_of in mvr_grid.hip)
 __device__ __forceinline__ uint32_t knn_cell_start(const KnnSlot &S, uint32_t c)
 {
@@ -100,7 +105,9 @@ inline int fill_target(Ctx *c, Cloud &t, KnnSlot &S)
   S.inv_h = 0.f;
   if (t.n == 0) return MVR_OK;
   bool ok = false;
-  if (int rc = ensure_model_grid(c, t, 0.0, &ok)) return rc;
+  bool no_finite = false;
+  if (int rc = ensure_model_grid(c, t, 0.0, &ok, &no_finite)) return rc;
+  if (no_finite) S.nt = 0;            // nobody's neighbour, all of them: an empty target (no query scans it)
   if (!ok) return MVR_OK;
   const CellGrid &g = *t.mgrid;
   S.gt = g.graw; S.dir = g.dir; S.recs = g.recs; S.inv_h = g.inv_h;

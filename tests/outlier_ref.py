@@ -30,6 +30,24 @@ def d2_f32(a, b, fma=False):
         return (dz.astype(L) * dz.astype(L) + t.astype(L)).astype(F32)
 
 
+def within_r2(a, b, r2, fma=False):
+    """d2_f32(a, b, fma) <= r2, elementwise.  The fma arm's 80-bit arithmetic is slow, so it is spent only where it can
+    decide: both expressions start from the same rounded differences and round three times, so each lies within 3 * 2^-24 of
+    the same exact sum and they differ by less than 1e-6 relative -- a plain d2 further than that from r2 settles the fma
+    comparison too"""
+    p = d2_f32(a, b, False)
+    if not fma:
+        return p <= r2
+    a, b = np.broadcast_arrays(np.asarray(a, F32), np.asarray(b, F32))
+    with np.errstate(invalid="ignore", over="ignore"):
+        p64, r64 = p.astype(F64), F64(r2)
+        out = p64 <= r64 * (1.0 - 1.0e-6)
+        amb = ~out & (p64 <= r64 * (1.0 + 1.0e-6))
+    if amb.any():
+        out[amb] = d2_f32(a[amb], b[amb], True) <= r2
+    return out
+
+
 def _brute_smallest(P, rows, k, fma):
     """the k smallest f32 d2 from each point P[rows] to the OTHER points of P, ascending"""
     out = np.empty((len(rows), k), F32)
@@ -122,7 +140,6 @@ def statistical(p, k, stddev_mul, negative=False, fma=False):
 
 def neighbor_counts(p, radius, fma=False):
     """count[i] = number of finite j != i with the f32 d2(i, j) <= f32(radius * radius); 0 for a non-finite point"""
-    from scipy.spatial import cKDTree
     p = np.asarray(p, F32)
     fin = finite_mask(p)
     cnt = np.zeros(len(p), np.uint32)
@@ -130,16 +147,26 @@ def neighbor_counts(p, radius, fma=False):
     if len(P) == 0:
         return cnt
     r2 = F32(radius * radius)
+    out = np.zeros(len(P), np.int64)
+    if len(P) <= 8192:                                 # small: the definition itself, every pair (no candidate set to trust)
+        step = max(1, int(2e7) // len(P))
+        for c0 in range(0, len(P), step):
+            c1 = min(len(P), c0 + step)
+            ok = within_r2(P[c0:c1, None, :], P[None, :, :], r2, fma)
+            ok[np.arange(c1 - c0), np.arange(c0, c1)] = False
+            out[c0:c1] = ok.sum(axis=1)
+        cnt[fin] = out.astype(np.uint32)
+        return cnt
+    from scipy.spatial import cKDTree
     P64 = P.astype(F64)
     tree = cKDTree(P64)
-    out = np.zeros(len(P), np.int64)
     for c0 in range(0, len(P), 50000):
         c1 = min(len(P), c0 + 50000)
         cand = tree.query_ball_point(P64[c0:c1], radius * (1.0 + 1e-4) + 1e-4, workers=-1)
         lens = np.fromiter((len(c) for c in cand), np.int64, c1 - c0)
         flat = np.fromiter((j for c in cand for j in c), np.int64, int(lens.sum()))
         row = np.repeat(np.arange(c0, c1), lens)
-        ok = (d2_f32(P[row], P[flat], fma) <= r2) & (flat != row)
+        ok = within_r2(P[row], P[flat], r2, fma) & (flat != row)
         out[c0:c1] = np.bincount(row[ok] - c0, minlength=c1 - c0)
     cnt[fin] = out.astype(np.uint32)
     return cnt

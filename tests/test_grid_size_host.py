@@ -1,0 +1,86 @@
+"""The sizing of a cloud's own grid (csrc/mvr_grid_size.h: model_grid_size, what ensure_model_grid calls) under
+AddressSanitizer + UBSan with float-cast-overflow on, compiled with the host compiler alone: ordinary boxes, zero-extent
+boxes, boxes at 1e6, n from 4 to 2^31 - 16, a dense cube that runs the enlargement loop, and boxes with NaN and infinite
+corners, which must be refused before any arithmetic (tests/cxx/grid_size_driver.cpp asserts 1 <= dim <= 513, at most 32e6
+cells and a finite positive edge in every accepted case).  And the two f32 distances of the references are one."""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import normals_ref
+import outlier_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_grid_sizing_is_clean_under_asan_and_ubsan(tmp_path):
+    cxx = shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "needs a host C++ compiler"
+    exe = str(tmp_path / "grid_size_driver")
+    cmd = [cxx, "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined,float-cast-overflow", "-fno-sanitize-recover=all",
+           "-fno-omit-frame-pointer", "-I" + os.path.join(ROOT, "multi-view-registration_amd", "csrc"),
+           os.path.join(ROOT, "tests", "cxx", "grid_size_driver.cpp"), "-o", exe]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0, out[-3000:]
+    assert "AddressSanitizer" not in out and "runtime error" not in out and "FAIL" not in out, out[-3000:]
+    m = re.search(r"accepted=(\d+) refused=(\d+) empty=(\d+) enlarged=(\d+) failures=0 max_dim=513", r.stdout)
+    assert m, r.stdout[-1000:]
+    accepted, refused, empty, enlarged = map(int, m.groups())
+    assert accepted > 2000 and refused >= 6 * 3 * 9 + 8 and empty == 2 and enlarged >= 2
+
+
+def test_the_library_source_sizes_its_grid_through_the_shared_function():
+    """ensure_model_grid holds no sizing arithmetic of its own"""
+    src = open(os.path.join(ROOT, "multi-view-registration_amd", "csrc", "mvr_grid.hip")).read()
+    body = src[src.index("int ensure_model_grid("):src.index("GridPair make_model_pair(")]
+    assert "model_grid_size(" in body and "std::floor" not in body and "cloud_bbox(c, t.pts, t.n, bb, true)" in body
+
+
+@pytest.mark.parametrize("fma", [False, True])
+def test_the_references_share_one_distance(fma):
+    """normals_ref.knn_brute (with fma) and outlier_ref.smallest_d2 / mean_dist on a small cloud with duplicates and
+    lattice ties: the k smallest d2 to the OTHER points are knn_brute's list without the point itself, bit for bit"""
+    assert normals_ref.d2_f32 is outlier_ref.d2_f32
+    rng = np.random.default_rng(3)
+    p = np.ones((400, 4), np.float32)
+    p[:, :3] = (rng.standard_normal((400, 3)) * 3 + [0, 0, 900]).astype(np.float32)
+    p[300:] = p[rng.integers(0, 300, 100)]
+    p[100:160, :3] = np.round(p[100:160, :3])
+    k = 9
+    idx, d2 = normals_ref.knn_brute(p, p, k + 1, fma=fma)
+    own = idx == np.arange(len(p), dtype=np.uint32)[:, None]
+    assert (own.sum(1) == 1).all()
+    others = d2[~own].reshape(len(p), k)
+    want = outlier_ref.smallest_d2(np.ascontiguousarray(p[:, :3]), k, fma)
+    assert np.array_equal(others.view(np.uint32), want.view(np.uint32))
+    md, nv = outlier_ref.mean_dist(p, k, fma)
+    s = np.zeros(len(p))
+    for j in range(k):
+        s += np.sqrt(others[:, j]).astype(np.float64)
+    assert nv == len(p) and np.array_equal(md.view(np.uint32), (s / k).astype(np.float32).view(np.uint32))
+    # and the two arms differ somewhere on this input: the fma arm is not the plain one under another name
+    if fma:
+        assert not np.array_equal(d2.view(np.uint32), normals_ref.knn_brute(p, p, k + 1)[1].view(np.uint32))
+
+
+def test_the_reference_applies_the_non_finite_rule():
+    """mvr_hip.h N1 - N3 in the reference itself: a non-finite target is never listed, a non-finite query gets nothing"""
+    p = np.ones((8, 4), np.float32)
+    p[:, :3] = np.arange(24, dtype=np.float32).reshape(8, 3)
+    p[2, 0] = np.nan
+    p[5, 2] = np.inf
+    p[6, 1] = -np.inf
+    idx, d2 = normals_ref.knn_brute(p, p, 6)
+    fin = normals_ref.finite_mask(p)
+    assert list(fin) == [True, True, False, True, True, False, False, True]
+    assert (idx[~fin] == normals_ref.NONE).all() and np.isposinf(d2[~fin]).all()
+    assert not np.isin(idx[fin], [2, 5, 6]).any()
+    assert (idx[fin, :5] != normals_ref.NONE).all() and (idx[fin, 5] == normals_ref.NONE).all() and np.isposinf(d2[fin, 5]).all()

@@ -2,11 +2,22 @@
 """tools/fuzz_exact.py [seconds] [seed] -- a randomised exactness campaign on the GPU: rings of 3..9 views with ragged sizes,
 random mis-calibrations, radii, frames far from the origin, a few passes each -- the edge tables and poses of the default route
 (grid walk with its probe, stragglers, pipelined loop) must equal those of the culled kernel alone and of other routings, bit for
-bit, and the brute-force kernel's in counts and to rounding in the sums (it adds in another order); and the sequential mode over three sweeps with and without the seeds.  Prints one line per failure and a summary."""
+bit, and the brute-force kernel's in counts and to rounding in the sums (it adds in another order); and the sequential mode over three sweeps with and without the seeds.  Prints one line per failure and a summary.
+tools/fuzz_exact.py --walks [trials] [seed] -- the kernels that walk a cloud's own grid instead (mvr_knn, the outlier filters'
+mean distances and counts): the random-shapes loop of tests/test_gpu_walk_fuzz.py with as many trials as asked for (default
+100), bit for bit against the brute-force references of tests/."""
 import importlib, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 mvr = importlib.import_module("multi-view-registration_amd")
+if len(sys.argv) > 1 and sys.argv[1] == "--walks":
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_gpu_walk_fuzz import run_random_shapes
+    trials, seed = (int(sys.argv[2]) if len(sys.argv) > 2 else 100), (int(sys.argv[3]) if len(sys.argv) > 3 else 1)
+    with mvr.Context(0) as ctx:
+        run_random_shapes(ctx, trials, seed, log=lambda m: print(m, flush=True))
+    print("fuzz --walks: %d trials, 0 failures" % trials)
+    sys.exit(0)
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 t_end = time.time() + budget
