@@ -411,6 +411,93 @@ class RadiusOutlierRemoval {
   std::shared_ptr<std::vector<int> > removed_ = std::make_shared<std::vector<int> >();
 };
 
+// ---------------------------------------------------------------- moving least squares
+// pcl::MovingLeastSquares<PointInT, PointOutT> (surface/mls.h) with upsampling NONE and the SIMPLE projection, PCL's member
+// names and defaults (polynomial order 2, sqr_gauss_param = the squared search radius until setSqrGaussParam is called, no
+// normals).  Semantics: mvr_cloud_mls (mvr_hip.h) -- one call on the GPU per process().  PointInT / PointOutT: any point
+// whose first three floats are x, y, z (PointXYZ, PointNormal); an output type with normal_x / curvature members receives
+// the normals (with setComputeNormals(true); oriented towards the origin, the sensor of a raw scan) and the curvature.
+// `output` may be the input cloud itself.  A missing input or a parameter outside its range prints an error and leaves the
+// output empty (untouched when it is the input).  Upsampling, the ORTHOGONAL projection, orders above 2 and cached
+// polynomials are not offered.
+namespace detail {
+template <class P>
+auto set_normal(P &o, const float *n, float curv, int) -> decltype((void)o.normal_x) { o.normal_x = n[0]; o.normal_y = n[1]; o.normal_z = n[2]; o.curvature = curv; }
+template <class P>
+void set_normal(P &, const float *, float, long) {}
+}  // namespace detail
+
+template <typename PointInT, typename PointOutT>
+class MovingLeastSquares {
+ public:
+  typedef PointCloud<PointInT> PointCloudIn;
+  typedef typename PointCloudIn::ConstPtr PointCloudInConstPtr;
+  typedef PointCloud<PointOutT> PointCloudOut;
+  typedef search::KdTree<PointInT> KdTree;
+  typedef typename KdTree::Ptr KdTreePtr;
+
+  void setInputCloud(const PointCloudInConstPtr &c) { input_ = c; }
+  PointCloudInConstPtr getInputCloud() const { return input_; }
+  void setSearchMethod(const KdTreePtr &tree) { tree_ = tree; }
+  KdTreePtr getSearchMethod() const { return tree_; }
+  void setSearchRadius(double r) { radius_ = r; if (!gauss_set_) sqr_gauss_ = r * r; }
+  double getSearchRadius() const { return radius_; }
+  void setPolynomialOrder(int order) { order_ = order; }
+  int getPolynomialOrder() const { return order_; }
+  void setPolynomialFit(bool fit) { order_ = fit ? (order_ > 1 ? order_ : 2) : 0; }      // (PCL 1.7's switch: order > 1 is the fit)
+  bool getPolynomialFit() const { return order_ > 1; }
+  void setSqrGaussParam(double g) { sqr_gauss_ = g; gauss_set_ = true; }
+  double getSqrGaussParam() const { return sqr_gauss_; }
+  void setComputeNormals(bool c) { compute_normals_ = c; }
+  PointIndicesPtr getCorrespondingIndices() const { return corresponding_; }
+
+  void process(PointCloudOut &output)
+  {
+    static_assert(sizeof(PointInT) % 4 == 0 && sizeof(PointInT) >= 12 && sizeof(PointOutT) >= 12, "points that begin with x, y, z expected");
+    corresponding_->indices.clear();
+    const bool alias = (const void *)&output == (const void *)input_.get();
+    if (!input_) { std::fprintf(stderr, "[pcl::MovingLeastSquares::process] No input dataset given!\n"); output.clear(); return; }
+    if (!(std::isfinite(radius_) && radius_ > 0.0) || !(std::isfinite(sqr_gauss_) && sqr_gauss_ > 0.0) || order_ < 0 || order_ > 2) {
+      std::fprintf(stderr, "[pcl::MovingLeastSquares::process] The search radius (%f) and the gauss parameter (%f) must be finite and > 0, the polynomial order (%d) in 0..2.\n",
+                   radius_, sqr_gauss_, order_);
+      if (!alias) output.clear();
+      return;
+    }
+    Device &d = Device::instance();
+    SlotGuard s;
+    const size_t n = input_->size();
+    // first: `output` may alias the input
+    d.check(mvr_cloud_upload(d.ctx(), s.s, n ? input_->points[0].data : nullptr, n, sizeof(PointInT)), "mvr_cloud_upload");
+    mvr_mls_params p;
+    p.radius = radius_; p.order = order_; p.sqr_gauss_param = sqr_gauss_; p.compute_normals = compute_normals_ ? 1 : 0; p.orient = 0;
+    p.viewpoint[0] = p.viewpoint[1] = p.viewpoint[2] = 0.f; p.fma_dist = 0;
+    std::vector<uint32_t> kept(n ? n : 1);
+    std::vector<float> curv(n ? n : 1);
+    size_t m = 0;
+    d.check(mvr_cloud_mls(d.ctx(), s.s, s.s, &p, &m, kept.data(), curv.data()), "mvr_cloud_mls");
+    std::vector<float> xyz(4 * (m ? m : 1)), nrm(4 * (m ? m : 1), 0.f);
+    size_t got = 0;
+    if (m) d.check(mvr_cloud_download(d.ctx(), s.s, xyz.data(), m, 16, &got), "mvr_cloud_download");
+    if (m && compute_normals_) d.check(mvr_cloud_download_normals(d.ctx(), s.s, nrm.data(), m, 16, &got), "mvr_cloud_download_normals");
+    output.clear();
+    output.resize(m);
+    for (size_t i = 0; i < m; ++i) {
+      PointOutT &o = output.points[i];
+      o.x = xyz[4 * i]; o.y = xyz[4 * i + 1]; o.z = xyz[4 * i + 2];
+      detail::set_normal(o, &nrm[4 * i], curv[i], 0);
+    }
+    corresponding_->indices.assign(kept.begin(), kept.begin() + (std::ptrdiff_t)m);
+  }
+
+ private:
+  PointCloudInConstPtr input_;
+  KdTreePtr tree_;
+  double radius_ = 0.0, sqr_gauss_ = 0.0;
+  int order_ = 2;
+  bool gauss_set_ = false, compute_normals_ = false;
+  PointIndicesPtr corresponding_ = std::make_shared<PointIndices>();
+};
+
 namespace registration {
 
 // ------------------------------------------------- CorrespondenceEstimation

@@ -236,6 +236,51 @@ class ScanCloud {
     return removeOutliers(nullptr, &p);
   }
 
+  // EXTENSION (pcl::MovingLeastSquares on the raw points, on the GPU; rules: mvr_cloud_mls in mvr_hip.h): every point with at
+  // least 3 neighbours within `radius` is moved onto the plane through them and, with order 2 and at least 6 neighbours, onto
+  // the weighted quadratic over that plane; the others are dropped.  `points` are replaced; when `rich` holds one record per
+  // point, the records follow through the kept indices and take the new coordinates.  With compute_normals the normals
+  // (oriented towards the origin, the sensor of a raw scan) and the curvature of `rich` come from the fit too (`rich` is made
+  // from `points` first when it does not hold one record per point).  Parameters outside their range print an error and
+  // change nothing.  Returns the number of points dropped.
+  size_t smooth(double radius, int order = 2, bool compute_normals = false)
+  {
+    if (!(std::isfinite(radius) && radius > 0.0) || order < 0 || order > 2) {
+      std::fprintf(stderr, "[ScanCloud::smooth] The radius (%f) must be finite and > 0, the order (%d) in 0..2.\n", radius, order);
+      return 0;
+    }
+    Device &d = Device::instance();
+    SlotGuard s;
+    const size_t before = points.size();
+    if (compute_normals && rich.size() != before) {
+      io::RichCloud r(before);
+      for (size_t i = 0; i < before; ++i) { r[i].x = points.points[i].x; r[i].y = points.points[i].y; r[i].z = points.points[i].z; }
+      rich.swap(r);
+    }
+    d.upload(s.s, points);
+    mvr_mls_params p;
+    p.radius = radius; p.order = order; p.sqr_gauss_param = 0.0; p.compute_normals = compute_normals ? 1 : 0; p.orient = 0;
+    p.viewpoint[0] = p.viewpoint[1] = p.viewpoint[2] = 0.f; p.fma_dist = 0;
+    size_t kept = 0;
+    std::vector<uint32_t> index(before ? before : 1);
+    std::vector<float> curv(before ? before : 1), nrm(4 * (before ? before : 1));
+    d.check(mvr_cloud_mls(d.ctx(), s.s, s.s, &p, &kept, index.data(), curv.data()), "mvr_cloud_mls");
+    d.download(s.s, points);
+    size_t got = 0;
+    if (compute_normals && kept) d.check(mvr_cloud_download_normals(d.ctx(), s.s, nrm.data(), kept, 16, &got), "mvr_cloud_download_normals");
+    if (rich.size() == before) {
+      io::RichCloud r(kept);
+      for (size_t k = 0; k < kept; ++k) {
+        r[k] = rich[index[k]];
+        r[k].x = points.points[k].x; r[k].y = points.points[k].y; r[k].z = points.points[k].z;
+        if (compute_normals) { r[k].normal_x = nrm[4 * k]; r[k].normal_y = nrm[4 * k + 1]; r[k].normal_z = nrm[4 * k + 2]; r[k].curvature = curv[k]; }
+      }
+      rich.swap(r);
+    }
+    touch();
+    return before - kept;
+  }
+
   // point_cloud.cpp:305-326 / :328-347 -- `transformation.txt`: the column-vector
   // 4x4 printed row by row (matrix(j,i), i outer), "%lf " per element, one row per
   // line.  6 decimals: poses round-trip to 1e-6 only.
@@ -557,6 +602,32 @@ class Registrator {
     mergeRegisteredPoints(object, merged.rich);
     for (const io::RichPoint &q : merged.rich) merged.points.push_back(PCLPoint(q.x, q.y, q.z));
     merged.voxelDownsample(leaf_size);
+    const bool ok = io::savePCDFile(folder + "/points.pcd", merged.rich, io::PCD_BINARY_COMPRESSED) &&
+                    io::savePointsASC(folder + "/points.asc", merged.rich);
+    const size_t n = merged.rich.size();
+    if (merged_out) merged_out->swap(merged.rich);
+    return ok ? n : 0;
+  }
+
+  // EXTENSION: the merged cloud smoothed by ScanCloud::smooth(mls_radius, polynomial_order) -- the layers of overlapping views
+  // carry their own sensor noise and what registration error is left; a surface fitted through the stack removes the "double
+  // walls" -- and then, with leaf_size > 0, put through ScanCloud::voxelDownsample(leaf_size), before it is written to the same
+  // two files.  Only the coordinates are smoothed: colours, the full-affine-moved normals and curvature follow their points.
+  // merged_out receives the cloud as written.  Returns the number of points written, 0 on failure; parameters outside their
+  // range are a failure: an error is printed and nothing is written.
+  size_t saveRegisteredPoints(int object, const std::string &folder, double mls_radius, int polynomial_order, float leaf_size /* 0: none */,
+                              io::RichCloud *merged_out = nullptr)
+  {
+    if (!(std::isfinite(mls_radius) && mls_radius > 0.0) || polynomial_order < 0 || polynomial_order > 2 || !(leaf_size >= 0.f) || !std::isfinite(leaf_size)) {
+      std::fprintf(stderr, "[Registrator::saveRegisteredPoints] The radius (%f) must be finite and > 0, the order (%d) in 0..2, the leaf size (%f) finite and >= 0.\n",
+                   mls_radius, polynomial_order, leaf_size);
+      return 0;
+    }
+    ScanCloud merged;
+    mergeRegisteredPoints(object, merged.rich);
+    for (const io::RichPoint &q : merged.rich) merged.points.push_back(PCLPoint(q.x, q.y, q.z));
+    merged.smooth(mls_radius, polynomial_order, false);
+    if (leaf_size > 0.f) merged.voxelDownsample(leaf_size);
     const bool ok = io::savePCDFile(folder + "/points.pcd", merged.rich, io::PCD_BINARY_COMPRESSED) &&
                     io::savePointsASC(folder + "/points.asc", merged.rich);
     const size_t n = merged.rich.size();

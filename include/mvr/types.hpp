@@ -44,6 +44,33 @@ struct alignas(16) Normal {
 };
 static_assert(sizeof(Normal) == 32, "Normal must match pcl::Normal");
 
+// pcl::PointNormal: data[4] (x, y, z, 1), normal[4] and curvature, 48 bytes as in PCL
+struct alignas(16) PointNormal {
+  union {
+    float data[4];
+    struct { float x, y, z; };
+  };
+  union {
+    float normal[4];
+    struct { float normal_x, normal_y, normal_z; };
+  };
+  union {
+    struct { float curvature; };
+    float data_c[4];
+  };
+  PointNormal() : data{0.f, 0.f, 0.f, 1.f}, normal{0.f, 0.f, 0.f, 0.f}, data_c{0.f, 0.f, 0.f, 0.f} {}
+  PointNormal(float _x, float _y, float _z) : data{_x, _y, _z, 1.f}, normal{0.f, 0.f, 0.f, 0.f}, data_c{0.f, 0.f, 0.f, 0.f} {}
+};
+static_assert(sizeof(PointNormal) == 48, "PointNormal must match pcl::PointNormal");
+
+// pcl::PointIndices (the member MovingLeastSquares::getCorrespondingIndices hands out)
+struct PointIndices {
+  typedef std::shared_ptr<PointIndices> Ptr;
+  typedef std::shared_ptr<const PointIndices> ConstPtr;
+  std::vector<int> indices;
+};
+typedef PointIndices::Ptr PointIndicesPtr;
+
 // pcl::PointCloud<PointT> (the members the reference touches: points, size,
 // at, operator[], push_back, clear, operator+=, Ptr; registrator.cpp:548-576,
 // point_cloud.cpp:290-303).

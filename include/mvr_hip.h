@@ -312,6 +312,58 @@ int  mvr_cloud_statistical_outlier_removal(mvr_ctx *ctx, int dst_slot, int src_s
 int  mvr_cloud_radius_outlier_removal(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_ror_params *p, size_t *n_out,
                                       uint32_t *kept_index, uint32_t *neighbor_count);
 
+/* ---- moving-least-squares smoothing (EXTENSION: pcl::MovingLeastSquares) -----------------------------------------
+ * The reference pins no PCL version; where PCL versions differ, or PCL is loose, the rule below is this library's rule.
+ * The model is PCL's computeMLSPointNormal with upsampling NONE and the SIMPLE projection; deviations are marked.
+ *  M1. Neighbourhood: point i's neighbours are every finite j with d2(i, j) <= (float)(radius * radius) under the f32
+ *      distance of mvr_nn / mvr_knn, i itself included -- exactly the radius mode of mvr_cloud_estimate_normals;
+ *      fma_dist = 1 selects the fma chain.
+ *  M2. A non-finite point is nobody's neighbour and is never in the output, and no query walks the grid because of one
+ *      (rules N1, N2 and N5 above).
+ *  M3. A finite point with fewer than 3 neighbours is dropped, as PCL does.  The output holds the other points in their
+ *      ORIGINAL index order, w = 1.  kept_index (optional, host, capacity = source size) receives the original indices,
+ *      ascending; n_out (optional) their number; curvature (optional, host) one f32 per OUTPUT point.
+ *  M4. Plane: the f64 mean and covariance of the neighbours' coordinates taken relative to the query point, divided by
+ *      the count (the arithmetic of mvr_cloud_estimate_normals; deliberately NOT PCL's f32 accumulation).  n = unit
+ *      eigenvector of the smallest eigenvalue l0.  The projected query is q' = q - ((q - mean) . n) n;
+ *      curvature = |l0| / (l0 + l1 + l2), 0 when the sum is 0.
+ *  M5. Polynomial: applies iff order == 2 and the neighbour count is at least 6 (PCL's polynomial_fit = order > 1).
+ *      With any orthonormal pair u, v such that u x v = n (the result does not depend on the choice: the polynomials of
+ *      total degree 2 are closed under rotation and the weights are radial), every neighbour p gives d = p - q',
+ *      (a, b, f) = (d . u, d . v, d . n) and w = exp(-(d . d) / sqr_gauss_param), all in f64 -- the distance from the
+ *      PROJECTED point, as PCL recomputes it.  The normal equations are those of the basis 1, b, b^2, a, ab, a^2 (PCL's
+ *      coefficient order c0..c5): 15 distinct monomial sums and 6 right-hand sums, solved by Cholesky in f64.  A pivot that
+ *      is not finite and positive, or a coefficient c0 / c1 / c3 that is not finite (a pivot can be positive and as small as
+ *      a denormal), abandons the fit and the plane result of M4 stands (PCL: an LLT solve whose result it
+ *      does not check).  On success q'' = q' + c0 n and, with compute_normals, the normal is
+ *      normalize(n - c3 u - c1 v).
+ *  M6. Output coordinates are the f64 result rounded to f32.  A computed normal is {nx, ny, nz, 0}: the unit vector rounded
+ *      to f32, then oriented with the f32 test of mvr_cloud_estimate_normals (negated when cos < 0, strictly) -- orient 0:
+ *      cos = dot(viewpoint - p, n) with p the SOURCE point; orient 1: cos = dot(source normal of the same point, n).  (PCL
+ *      leaves the eigenvector's sign as it falls.)  Without compute_normals the source slot's normals follow their points
+ *      unchanged, as in the outlier filters; no source normals and no compute_normals: no output normals.
+ *  M7. dst_slot may equal src_slot: every read comes from the source as it was before the call.  Otherwise src_slot is left
+ *      untouched.  The output is a NEW point set: orderings, grids and pose bookkeeping are dropped.
+ *  M8. MVR_E_ARG, before any GPU work and with nothing written, for a NULL ctx / params, a bad slot, a radius or
+ *      sqr_gauss_param that is non-finite or negative, a radius of 0, an order outside 0..2, an orient outside 0..1, a
+ *      non-finite viewpoint, orient 1 on a source slot without normals, a cloud above 0x7FFFFFF0 points, or a cloud whose
+ *      points are stale because a pipelined run is in flight.  An empty cloud is MVR_OK with an empty output.
+ *  M9. Bit-identical from run to run on one grid: one thread per query, sums in walk order, no atomics.
+ * Out of scope: PCL's upsampling methods (SAMPLE_LOCAL_PLANE, RANDOM_UNIFORM_DENSITY, VOXEL_GRID_DILATION, DISTINCT_CLOUD),
+ * the ORTHOGONAL projection, polynomial orders above 2 and per-point polynomial caching (setCacheMLSResults). */
+typedef struct {
+  double radius;           /* setSearchRadius: finite, > 0                                                              */
+  int    order;            /* setPolynomialOrder: 0..2; below 2 the plane projection alone (PCL's polynomial_fit = order > 1) */
+  double sqr_gauss_param;  /* setSqrGaussParam: finite, > 0; 0 selects PCL's default radius * radius                       */
+  int    compute_normals;  /* setComputeNormals                                                                           */
+  int    orient;           /* 0: towards `viewpoint` (the flip rule of mvr_cloud_estimate_normals);
+                              1: along the source slot's own normals (MVR_E_ARG when it has none)                          */
+  float  viewpoint[3];
+  int    fma_dist;
+} mvr_mls_params;
+int  mvr_cloud_mls(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_mls_params *p, size_t *n_out,
+                   uint32_t *kept_index, float *curvature);
+
 /* CorrespondenceEstimation::determineReciprocalCorrespondences(corrs, max_d)
  * (registrator.cpp:496-502, 644-649); reciprocal = 0 gives
  * determineCorrespondences.  Outputs are host arrays of capacity `cap`

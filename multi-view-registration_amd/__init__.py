@@ -122,6 +122,12 @@ class RorParams(C.Structure):
     _fields_ = [("radius", C.c_double), ("min_neighbors", C.c_int), ("negative", C.c_int), ("fma_dist", C.c_int)]
 
 
+class MlsParams(C.Structure):
+    """mvr_mls_params"""
+    _fields_ = [("radius", C.c_double), ("order", C.c_int), ("sqr_gauss_param", C.c_double), ("compute_normals", C.c_int),
+                ("orient", C.c_int), ("viewpoint", C.c_float * 3), ("fma_dist", C.c_int)]
+
+
 _fp, _dp, _u32p, _i32p = (C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                           C.POINTER(C.c_int32))
 _vp, _sz = C.c_void_p, C.c_size_t
@@ -146,6 +152,7 @@ SIGNATURES = {
     "mvr_cloud_statistical_outlier_removal": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(SorParams), C.POINTER(_sz), _u32p, _fp,
                                                         C.POINTER(SorStats)]),
     "mvr_cloud_radius_outlier_removal": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RorParams), C.POINTER(_sz), _u32p, _u32p]),
+    "mvr_cloud_mls": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(MlsParams), C.POINTER(_sz), _u32p, _fp]),
     "mvr_cloud_set_global_base": (C.c_int, [_vp, C.c_int, _sz]),
     "mvr_cloud_append_range": (C.c_int, [_vp, C.c_int, C.c_int, _sz, _sz, _sz]),
     "mvr_nn_forward_keys": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp]),
@@ -607,6 +614,33 @@ class Context:
             out.append(idx[:n_out.value].copy())
         if return_counts:
             out.append(cnt[:n])
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def mls(self, dst, src, radius, order=2, sqr_gauss_param=0.0, compute_normals=False, orient="viewpoint",
+            viewpoint=(0.0, 0.0, 0.0), fma=False, return_index=False, return_curvature=False):
+        """pcl::MovingLeastSquares::process of slot src into slot dst (may be src): every point with at least 3 neighbours
+        within radius, projected onto the plane through them and -- order 2, at least 6 neighbours -- onto the weighted
+        quadratic fitted over that plane, in their original order (rules: mvr_cloud_mls in mvr_hip.h).  sqr_gauss_param 0
+        selects radius * radius.  compute_normals replaces the slot's normals by those of the fit, oriented towards
+        `viewpoint` (orient="viewpoint") or along the source slot's own normals (orient="normals"); without it the source's
+        normals follow their points.  Returns n_out, or (n_out[, kept_index][, curvature]): kept_index = original indices
+        of the output points, curvature = one f32 per OUTPUT point."""
+        if orient not in ("viewpoint", "normals"):
+            raise ValueError("orient must be 'viewpoint' or 'normals'")
+        n = self.size(src)
+        p = MlsParams(float(radius), int(order), float(sqr_gauss_param), int(bool(compute_normals)), int(orient == "normals"),
+                      (C.c_float * 3)(*[float(v) for v in viewpoint]), int(bool(fma)))
+        idx = np.empty(max(n, 1), np.uint32) if return_index else None
+        curv = np.empty(max(n, 1), np.float32) if return_curvature else None
+        n_out = _sz()
+        _chk(_lib.mvr_cloud_mls(self._h, int(dst), int(src), C.byref(p), C.byref(n_out),
+                                _p(idx, C.c_uint32) if return_index else None,
+                                _p(curv, C.c_float) if return_curvature else None), self._h)
+        out = [n_out.value]
+        if return_index:
+            out.append(idx[:n_out.value].copy())
+        if return_curvature:
+            out.append(curv[:n_out.value].copy())
         return out[0] if len(out) == 1 else tuple(out)
 
     # ---- target sharding over ranks (sequential mode): see seq.py

@@ -31,6 +31,7 @@
 
 #include "mvr_internal.h"
 #include "mvr_knn_walk.h"
+#include "mvr_plane.h"
 
 namespace mvr {
 namespace {
@@ -111,40 +112,6 @@ __device__ __forceinline__ void knn_walk(const KnnSlot &S, const float4 q, const
   }
 }
 
-// ---- the 3 x 3 symmetric eigenproblem in f64: cyclic Jacobi (A is destroyed, V = eigenvectors in columns)
-template <int P, int Q, int R>
-__device__ __forceinline__ void jacobi_rot(double (&A)[3][3], double (&V)[3][3])
-{
-  const double apq = A[P][Q];
-  if (apq == 0.0) return;
-  const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
-  const double t = fabs(theta) > 1.0e150 ? 0.5 / theta : copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-  A[P][P] -= t * apq;
-  A[Q][Q] += t * apq;
-  A[P][Q] = A[Q][P] = 0.0;
-  const double arp = A[R][P], arq = A[R][Q];
-  A[R][P] = A[P][R] = c * arp - s * arq;
-  A[R][Q] = A[Q][R] = s * arp + c * arq;
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const double vp = V[r][P], vq = V[r][Q];
-    V[r][P] = c * vp - s * vq;
-    V[r][Q] = s * vp + c * vq;
-  }
-}
-
-// f64 moments of the neighbours about the query point
-struct Moments {
-  double cnt = 0.0, sx = 0.0, sy = 0.0, sz = 0.0, xx = 0.0, xy = 0.0, xz = 0.0, yy = 0.0, yz = 0.0, zz = 0.0;
-  __device__ __forceinline__ void add(const float4 p, const float4 q)
-  {
-    const double dx = (double)p.x - (double)q.x, dy = (double)p.y - (double)q.y, dz = (double)p.z - (double)q.z;
-    cnt += 1.0; sx += dx; sy += dy; sz += dz;
-    xx += dx * dx; xy += dx * dy; xz += dx * dz; yy += dy * dy; yz += dy * dz; zz += dz * dz;
-  }
-};
-
 // moments about the query point -> unit normal (f32, oriented) and curvature; fewer than 3 neighbours: NaN
 __device__ __forceinline__ void plane_from_moments(const KnnSlot &S, const KnnBatch &b, const float4 q, const uint32_t qi, const Moments &M)
 {
@@ -153,29 +120,9 @@ __device__ __forceinline__ void plane_from_moments(const KnnSlot &S, const KnnBa
     out = make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), 0.f);
     curv = __builtin_nanf("");
   } else {
-    const double inv = 1.0 / M.cnt, m0 = M.sx * inv, m1 = M.sy * inv, m2 = M.sz * inv;
-    double A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    A[0][0] = M.xx * inv - m0 * m0; A[0][1] = A[1][0] = M.xy * inv - m0 * m1; A[0][2] = A[2][0] = M.xz * inv - m0 * m2;
-    A[1][1] = M.yy * inv - m1 * m1; A[1][2] = A[2][1] = M.yz * inv - m1 * m2; A[2][2] = M.zz * inv - m2 * m2;
-    for (int sweep = 0; sweep < 12; ++sweep) {
-      const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-      const double dia = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
-      if (!(off > 1.0e-40 * dia)) break;                      // (an all-zero matrix ends here too)
-      jacobi_rot<0, 1, 2>(A, V);
-      jacobi_rot<0, 2, 1>(A, V);
-      jacobi_rot<1, 2, 0>(A, V);
-    }
-    const double l0 = A[0][0], l1 = A[1][1], l2 = A[2][2];
-    // the column of the smallest eigenvalue, picked by 0 / 1 weights (a select between array elements becomes a select between
-    // their ADDRESSES, which sends A and V to scratch memory)
-    const double w0 = (l0 <= l1 && l0 <= l2) ? 1.0 : 0.0, w1 = (w0 == 0.0 && l1 <= l2) ? 1.0 : 0.0, w2 = 1.0 - w0 - w1;
-    const double lmin = w0 * l0 + w1 * l1 + w2 * l2;
-    const double nx = w0 * V[0][0] + w1 * V[0][1] + w2 * V[0][2], ny = w0 * V[1][0] + w1 * V[1][1] + w2 * V[1][2],
-                 nz = w0 * V[2][0] + w1 * V[2][1] + w2 * V[2][2];
-    const double nn = 1.0 / sqrt(nx * nx + ny * ny + nz * nz);
-    const double sum = l0 + l1 + l2;
-    curv = sum != 0.0 ? (float)(fabs(lmin) / sum) : 0.f;
-    float fx = (float)(nx * nn), fy = (float)(ny * nn), fz = (float)(nz * nn);
+    const PlaneFit f = plane_fit(M);      // (mvr_plane.h: f64 covariance, cyclic Jacobi, the smallest eigenvalue's eigenvector)
+    curv = f.sum != 0.0 ? (float)(fabs(f.lmin) / f.sum) : 0.f;
+    float fx = (float)f.nx, fy = (float)f.ny, fz = (float)f.nz;
     // flipNormalTowardsViewpoint: f32, the normal already rounded
     const float vx = b.vp[0] - q.x, vy = b.vp[1] - q.y, vz = b.vp[2] - q.z;
     float cs = vx * fx;

@@ -1,5 +1,5 @@
 // csrc/mvr_knn_walk.h -- what the kernels that walk a cloud's model grid around a query share (mvr_knn.hip: k-NN lists and
-// normals; mvr_outlier.hip: mean neighbour distances and neighbour counts): the search side of a slot, the cell lookup of the
+// normals; mvr_outlier.hip: mean neighbour distances and neighbour counts; mvr_mls.hip: moving least squares): the search side of a slot, the cell lookup of the
 // compact table, the row ranges, the library's f32 distance and the f64 bound at which a shell walk may stop.  Not installed.
 #pragma once
 
