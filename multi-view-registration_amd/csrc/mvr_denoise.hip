@@ -189,12 +189,52 @@ __global__ void gather_kernel(const float4 *__restrict__ in, const unsigned long
 
 }  // namespace
 
+// ---- the tail of a filter that keeps a subset (declared in mvr_internal.h)
+int select_flagged(Ctx *c, void *tmp, size_t &tmp_bytes, const uint8_t *flags, size_t n, unsigned long long *list, uint32_t *count)
+{
+  size_t b = tmp_bytes;
+  MVR_HIP_TRY(c, hipcub::DeviceSelect::Flagged(tmp, b, hipcub::CountingInputIterator<unsigned long long>(0), flags, list, count, (int)n, c->stream));
+  if (!tmp) tmp_bytes = b;
+  return MVR_OK;
+}
+
 int launch_gather(Ctx *c, const float4 *in, const unsigned long long *okey, size_t kept, float4 *out, uint32_t *index_out)
 {
   if (!kept) return MVR_OK;
-  hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((kept + 255) / 256)), dim3(256), 0, c->stream, in, okey, kept, out, index_out);
+  hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(kept, 256)), dim3(256), 0, c->stream, in, okey, kept, out, index_out);
   MVR_HIP_TRY(c, hipGetLastError());
   return MVR_OK;
+}
+
+// out[k] = in[list[k]]; in place (in == out) through `stage`
+static int gather_into(Ctx *c, const float4 *in, const unsigned long long *list, size_t kept, float4 *out, float4 *stage, uint32_t *index_out)
+{
+  if (!kept) return MVR_OK;
+  if (int rc = launch_gather(c, in, list, kept, in == out ? stage : out, index_out)) return rc;
+  if (in == out) MVR_HIP_TRY(c, hipMemcpyAsync(out, stage, kept * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  return MVR_OK;
+}
+
+int gather_kept(Ctx *c, Cloud &dst, const float4 *pts, const float4 *nrm, const unsigned long long *list, size_t kept, float4 *stage,
+                uint32_t *index_out)
+{
+  if (pts != dst.pts) {
+    dst.n = 0;
+    if (int rc = cloud_reserve(c, dst, kept, false)) return rc;
+  }
+  if (int rc = gather_into(c, pts, list, kept, dst.pts, stage, index_out)) return rc;
+  if (!nrm || !kept) return MVR_OK;
+  if (nrm != dst.nrm)
+    if (int rc = ensure(c, dst.nrm, dst.nrm_cap, kept)) return rc;
+  return gather_into(c, nrm, list, kept, dst.nrm, stage, nullptr);
+}
+
+void finish_dst(Ctx *c, Cloud &dst, size_t n, bool normals)
+{
+  dst.n = n;
+  dst.has_normals = normals && n > 0;
+  dst.segs.clear();
+  new_point_set(c, dst);
 }
 
 int denoise_cloud(Ctx *c, Cloud &cl, int segment_threshold, double triangle_length, size_t *n_kept, size_t *n_components,
@@ -254,17 +294,11 @@ int denoise_cloud(Ctx *c, Cloud &cl, int segment_threshold, double triangle_leng
   MVR_HIP_TRY(c, hipMemcpyAsync(hc, counters, sizeof hc, hipMemcpyDeviceToHost, c->stream));
   MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
   const size_t kept = hc[1];
-  if (kept) {
-    if (int rc = launch_gather(c, cl.pts, okey_b, kept, out, d_index)) return rc;
-    MVR_HIP_TRY(c, hipMemcpyAsync(cl.pts, out, kept * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-    if (cl.has_normals) {
-      if (int rc = launch_gather(c, cl.nrm, okey_b, kept, out, nullptr)) return rc;
-      MVR_HIP_TRY(c, hipMemcpyAsync(cl.nrm, out, kept * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-    }
-    if (host_index) MVR_HIP_TRY(c, hipMemcpyAsync(host_index, d_index, kept * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  }
+  if (int rc = gather_kept(c, cl, cl.pts, cl.has_normals ? cl.nrm : nullptr, okey_b, kept, out, d_index)) return rc;
+  if (host_index && kept) MVR_HIP_TRY(c, hipMemcpyAsync(host_index, d_index, kept * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   MVR_HIP_TRY(c, hipGetLastError());
   MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));          // host_index is complete on return
+  // (not finish_dst: a denoise leaves has_normals as it is, also when nothing is kept)
   cl.n = kept;
   cl.segs.clear();
   new_point_set(c, cl);

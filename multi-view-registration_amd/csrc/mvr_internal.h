@@ -466,6 +466,9 @@ int ensure(Ctx *c, T *&p, size_t &cap, size_t want)
   return MVR_OK;
 }
 
+inline unsigned blocks_for(size_t n, int threads) { return (unsigned)((n + (size_t)threads - 1) / (size_t)threads); }
+__device__ __forceinline__ bool finite3(const float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
+
 // several clouds per launch (kernel arguments by value)
 constexpr int kBatchClouds = 16;
 // (Tp[k], when set, overrides T[k]: the pose is read from device memory -- see PoseRec)
@@ -800,9 +803,19 @@ int cloud_reserve(Ctx *c, Cloud &cl, size_t cap, bool keep);
 // PointCloud::denoise (mvr_denoise.hip): the cloud is replaced by its kept points, in the reference's output order
 int denoise_cloud(Ctx *c, Cloud &cl, int segment_threshold, double triangle_length, size_t *n_kept, size_t *n_components,
                   uint32_t *host_index);
-// the tail of a filter that keeps a subset (mvr_denoise.hip: gather_kernel): out[k] = in[low word of okey[k]] for k < kept, and
-// index_out[k] (optional) = that index -- points and normals alike
+// ---- the tail of a filter that keeps a subset (mvr_denoise.hip), in the order its callers run it
+// flags -> list[] = the indices of the set flags, ascending, and *count (a device word) = how many: hipCUB's
+// DeviceSelect::Flagged.  tmp null: only tmp_bytes = the temporary storage a call over n flags needs
+int select_flagged(Ctx *c, void *tmp, size_t &tmp_bytes, const uint8_t *flags, size_t n, unsigned long long *list, uint32_t *count);
+// gather_kernel: out[k] = in[low word of okey[k]] for k < kept, and index_out[k] (optional) = that index -- points and normals alike
 int launch_gather(Ctx *c, const float4 *in, const unsigned long long *okey, size_t kept, float4 *out, uint32_t *index_out);
+// dst's points become pts[list[k]], k < kept, and (nrm set) its normals nrm[list[k]]; index_out as launch_gather.  pts / nrm
+// may be dst's own arrays (a filter in place: gathered through `stage`, kept elements, and copied back) or any others (dst's
+// arrays are grown to `kept`).  All of it queued on the context's stream.
+int gather_kept(Ctx *c, Cloud &dst, const float4 *pts, const float4 *nrm, const unsigned long long *list, size_t kept, float4 *stage,
+                uint32_t *index_out);
+// the output replaces dst's points: a new point set of n points (as after an upload)
+void finish_dst(Ctx *c, Cloud &dst, size_t n, bool normals);
 // pcl::VoxelGrid::filter (mvr_voxel.hip; rules at mvr_cloud_voxel_grid in mvr_hip.h): dst (which may be src) gets the voxel
 // centroids as a new point set
 int voxel_grid_cloud(Ctx *c, Cloud &dst, Cloud &src, const float leaf[3], unsigned min_points, size_t *n_out, uint32_t *voxel_of,

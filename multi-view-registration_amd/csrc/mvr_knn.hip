@@ -7,7 +7,7 @@
 //     starts, points in grid order with w = bits of the point's index).  The queries are taken in that grid order too, so
 //     the 64 lanes of a wave are neighbours on the surface and walk the same cells; results are scattered back by index.
 //     A cloud too small for a grid (n < 4) or without one (a shard) is searched as ONE cell over its points in index order.
-//   * k-NN walk: shells of cells outward from the query's cell (Chebyshev shell s = the cells at distance s).  The walk
+//   * k-NN walk (knn_shell_walk, mvr_knn_walk.h): shells of cells outward from the query's cell (Chebyshev shell s = the cells at distance s).  The walk
 //     stops when the list is full and every unvisited cell lies beyond the current k-th distance -- the gap between the
 //     query and the visited box, taken in f64 in cell units of the grid's own f32 inverse edge, minus a margin that covers
 //     every rounding of the cell assignment and of the f32 distance.  A cell at exactly that distance is
@@ -26,7 +26,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <limits>
 #include <vector>
 
 #include "mvr_internal.h"
@@ -36,7 +35,6 @@
 namespace mvr {
 namespace {
 
-constexpr int kKnnThreads = 256;
 constexpr int kKnnSlots = 16;      // slots per launch (kernel argument by value)
 
 struct KnnBatch {
@@ -65,51 +63,31 @@ __device__ __forceinline__ void knn_insert(nnkey_t (&L)[KMAX], const nnkey_t key
   L[0] = key < L[0] ? key : L[0];
 }
 
-// the exact k-best list of query q: KMAX - k leading zero keys, then the k best (kKnnKeyEmpty where the target has fewer
-// FINITE points within a finite f32 d2; a non-finite query has none: it returns at once and walks nothing)
+// the visitor of the shell walk that keeps the exact k-best list of query q: KMAX - k leading zero keys, then the k best
+// (kKnnKeyEmpty where the target has fewer FINITE points within a finite f32 d2; a non-finite query has none)
+template <int KMAX, bool FMA>
+struct KnnList {
+  nnkey_t (&L)[KMAX];
+  const KnnSlot &S;
+  const float4 q;
+  __device__ __forceinline__ void visit(const float4 p, const uint32_t j)
+  {
+    const nnkey_t key = ((nnkey_t)__float_as_uint(knn_dist2<FMA>(p, q)) << 32) | knn_index_of(S, p, j);
+    if (key < L[KMAX - 1]) knn_insert<KMAX>(L, key);
+  }
+  __device__ __forceinline__ bool full() const { return L[KMAX - 1] != kKnnKeyEmpty; }
+  // strictly beyond the k-th distance: a cell AT it is still visited, since a candidate that ties the k-th d2 with a lower
+  // index must get in
+  __device__ __forceinline__ bool beyond(const double b2) const { return b2 > (double)__uint_as_float((uint32_t)(L[KMAX - 1] >> 32)); }
+};
+
 template <int KMAX, bool FMA>
 __device__ __forceinline__ void knn_walk(const KnnSlot &S, const float4 q, const int k, nnkey_t (&L)[KMAX])
 {
 #pragma unroll
   for (int i = 0; i < KMAX; ++i) L[i] = i < KMAX - k ? 0ull : kKnnKeyEmpty;
-  if (S.nt == 0 || !knn_finite3(q)) return;
-  const bool by_pos = !S.dir;
-  const int cx = knn_cell_of(q.x, S.lo[0], S.inv_h, S.dim[0]), cy = knn_cell_of(q.y, S.lo[1], S.inv_h, S.dim[1]),
-            cz = knn_cell_of(q.z, S.lo[2], S.inv_h, S.dim[2]);
-  for (int s = 0;; ++s) {
-    const int x0 = cx - s, x1 = cx + s, y0 = cy - s, y1 = cy + s, z0 = cz - s, z1 = cz + s;
-    const int ya = max(y0, 0), yb = min(y1, S.dim[1] - 1), za = max(z0, 0), zb = min(z1, S.dim[2] - 1);
-    // the shell's rows one after the other: on a face of the shell the whole row [x0, x1], inside it the row's two end cells
-    // (ONE loop and one candidate loop: every copy of the unrolled insertion costs registers and code)
-    for (int r = 0, nr = (yb - ya + 1) * (zb - za + 1) * 2; r < nr; ++r) {
-      const int part = r & 1, y = ya + (r >> 1) % (yb - ya + 1), z = za + (r >> 1) / (yb - ya + 1);
-      const bool face = z == z0 || z == z1 || y == y0 || y == y1;
-      int a, b;
-      if (face) {
-        if (part) continue;
-        a = max(x0, 0); b = min(x1, S.dim[0] - 1);
-      } else {
-        a = b = part ? x1 : x0;
-        if (a < 0 || a >= S.dim[0]) continue;
-      }
-      uint32_t j, e;
-      knn_row_range(S, a, b, y, z, &j, &e);
-      for (; j < e; ++j) {
-        const float4 p = S.gt[j];
-        const nnkey_t key = ((nnkey_t)__float_as_uint(knn_dist2<FMA>(p, q)) << 32) | (by_pos ? j : __float_as_uint(p.w));
-        if (key < L[KMAX - 1]) knn_insert<KMAX>(L, key);
-      }
-    }
-    if (!S.dir) return;                                               // one cell: all of it seen
-    const bool lo_x = x0 > 0, hi_x = x1 < S.dim[0] - 1, lo_y = y0 > 0, hi_y = y1 < S.dim[1] - 1, lo_z = z0 > 0, hi_z = z1 < S.dim[2] - 1;
-    if (!(lo_x || hi_x || lo_y || hi_y || lo_z || hi_z)) return;      // the whole grid seen
-    const nnkey_t kth = L[KMAX - 1];
-    if (kth == kKnnKeyEmpty) continue;                                // the list is not full yet
-    // the nearest an unvisited cell can be (knn_unvisited_bound, mvr_knn_walk.h)
-    const double b = knn_unvisited_bound(S, q, x0, x1, y0, y1, z0, z1, lo_x, hi_x, lo_y, hi_y, lo_z, hi_z);
-    const double kd2 = (double)__uint_as_float((uint32_t)(kth >> 32));
-    if (b > 0.0 && b * b * (1.0 - 1.0e-5) > kd2) return;              // strictly beyond the k-th distance (NaN: never)
-  }
+  KnnList<KMAX, FMA> v{L, S, q};
+  knn_shell_walk(S, q, v);
 }
 
 // moments about the query point -> unit normal (f32, oriented) and curvature; fewer than 3 neighbours: NaN
@@ -121,27 +99,11 @@ __device__ __forceinline__ void plane_from_moments(const KnnSlot &S, const KnnBa
     curv = __builtin_nanf("");
   } else {
     const PlaneFit f = plane_fit(M);      // (mvr_plane.h: f64 covariance, cyclic Jacobi, the smallest eigenvalue's eigenvector)
-    curv = f.sum != 0.0 ? (float)(fabs(f.lmin) / f.sum) : 0.f;
-    float fx = (float)f.nx, fy = (float)f.ny, fz = (float)f.nz;
-    // flipNormalTowardsViewpoint: f32, the normal already rounded
-    const float vx = b.vp[0] - q.x, vy = b.vp[1] - q.y, vz = b.vp[2] - q.z;
-    float cs = vx * fx;
-    cs = cs + vy * fy;
-    cs = cs + vz * fz;
-    if (cs < 0.f) { fx = -fx; fy = -fy; fz = -fz; }
-    out = make_float4(fx, fy, fz, 0.f);
+    curv = plane_curvature(f);
+    out = plane_normal_towards((float)f.nx, (float)f.ny, (float)f.nz, b.vp[0] - q.x, b.vp[1] - q.y, b.vp[2] - q.z);
   }
   S.nrm[qi] = out;
   if (S.curv) S.curv[qi] = curv;
-}
-
-__device__ __forceinline__ bool knn_query(const KnnSlot &S, float4 *q, uint32_t *qi)
-{
-  const uint32_t pos = (blockIdx.x - S.blk0) * kKnnThreads + threadIdx.x;
-  if (pos >= S.nq) return false;
-  *q = S.qs[pos];
-  *qi = S.q_by_pos ? pos : __float_as_uint(q->w);
-  return true;
 }
 
 // k-NN lists out to memory
@@ -189,21 +151,8 @@ __global__ void __launch_bounds__(kKnnThreads) normals_radius_kernel(KnnBatch b)
   const KnnSlot &S = b.s[knn_slot_of(b)];
   float4 q; uint32_t qi;
   if (!knn_query(S, &q, &qi)) return;
-  Moments M;
-  int x0 = 0, x1 = -1, y0 = 0, y1 = -1, z0 = 0, z1 = -1;      // (a non-finite query walks nothing: no neighbours, a NaN normal)
-  if (knn_finite3(q) && S.nt) {
-    x1 = y1 = z1 = 0;
-    if (S.dir) knn_ball_cells(S, q, b.r2, &x0, &x1, &y0, &y1, &z0, &z1);
-  }
-  for (int z = z0; z <= z1; ++z)
-    for (int y = y0; y <= y1; ++y) {
-      uint32_t j, e;
-      knn_row_range(S, x0, x1, y, z, &j, &e);
-      for (; j < e; ++j) {
-        const float4 p = S.gt[j];
-        if (knn_dist2<FMA>(p, q) <= b.r2) M.add(p, q);      // (r2 is finite: a non-finite p, with d2 = +inf or NaN, fails)
-      }
-    }
+  Moments M;      // (a non-finite query walks nothing: no neighbours, a NaN normal)
+  knn_ball_walk<FMA>(S, q, b.r2, [&](const float4 p, uint32_t) { M.add(p, q); });
   plane_from_moments(S, b, q, qi, M);
 }
 
@@ -247,8 +196,6 @@ using namespace mvr;
 #define API __attribute__((visibility("default")))
 #define CTX(p) reinterpret_cast<Ctx *>(p)
 
-static bool knn_slot_ok(int s) { return s >= 0 && s < MVR_MAX_SLOTS; }
-
 API int mvr_knn(mvr_ctx *ctx, int qs, int ts, int k, int fma, uint32_t *idx, float *d2)
 {
   if (!ctx || !knn_slot_ok(qs) || !knn_slot_ok(ts) || k < 1 || k > MVR_MAX_KNN) return MVR_E_ARG;
@@ -256,14 +203,14 @@ API int mvr_knn(mvr_ctx *ctx, int qs, int ts, int k, int fma, uint32_t *idx, flo
   MVR_HIP_TRY(c, hipSetDevice(c->device));
   Cloud &q = c->slots[qs], &t = c->slots[ts];
   if (q.n == 0) return MVR_OK;
-  if (q.n > 0x7FFFFFF0ull || t.n > 0x7FFFFFF0ull) return set_error(c, MVR_E_ARG, "mvr_knn: cloud too large");
+  if (int rc = knn_cloud_ok(c, q, "mvr_knn")) return rc;
+  if (int rc = knn_cloud_ok(c, t, "mvr_knn")) return rc;
   KnnSlot S{};
   if (int rc = fill_target(c, t, S)) return rc;
-  if (qs != ts && q.n >= 4 && !q.pts_stale) {      // the queries' own grid gives them their walking order
+  if (qs != ts && q.n >= 4) {      // the queries' own grid gives them their walking order
     bool ok = false;
     if (int rc = ensure_model_grid(c, q, 0.0, &ok)) return rc;
   }
-  if (q.pts_stale) return set_error(c, MVR_E_ARG, "mvr_knn: the query cloud's points are not current (pipelined run)");
   fill_queries(q, S);
   const size_t m = q.n * (size_t)k;
   uint32_t *didx = nullptr; float *dd2 = nullptr;
@@ -303,7 +250,7 @@ API int mvr_cloud_estimate_normals(mvr_ctx *ctx, int count, const int *slots, co
   for (int i = 0; i < count; ++i) {
     Cloud &cl = c->slots[slots[i]];
     if (cl.n == 0) continue;
-    if (cl.n > 0x7FFFFFF0ull) return set_error(c, MVR_E_ARG, "mvr_cloud_estimate_normals: cloud too large");
+    if (int rc = knn_cloud_ok(c, cl, "mvr_cloud_estimate_normals")) return rc;
     KnnSlot S{};
     if (int rc = fill_target(c, cl, S)) return rc;
     fill_queries(cl, S);
@@ -325,8 +272,7 @@ API int mvr_cloud_estimate_normals(mvr_ctx *ctx, int count, const int *slots, co
     if (curvature && curvature[used[j]]) { all[j].curv = dcurv + off; off += all[j].nq; }
   KnnBatch proto{};
   proto.k = p->k;
-  // (float)(radius * radius), kept finite: a d2 of +inf -- a non-finite neighbour, or an f32 overflow -- is never <= r2
-  proto.r2 = (float)std::min(p->radius * p->radius, (double)std::numeric_limits<float>::max());
+  proto.r2 = clamp_r2(p->radius);
   for (int j = 0; j < 3; ++j) proto.vp[j] = p->viewpoint[j];
   int rc = run_batches(c, all, proto, kmode ? kmax_bucket(p->k) : 8, kmode ? 1 : 2, p->fma_dist != 0);
   hipError_t e = hipSuccess;

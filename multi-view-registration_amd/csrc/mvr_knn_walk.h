@@ -1,7 +1,15 @@
-// csrc/mvr_knn_walk.h -- what the kernels that walk a cloud's model grid around a query share (mvr_knn.hip: k-NN lists and
-// normals; mvr_outlier.hip: mean neighbour distances and neighbour counts; mvr_mls.hip: moving least squares): the search side of a slot, the cell lookup of the
-// compact table, the row ranges, the library's f32 distance and the f64 bound at which a shell walk may stop.  Not installed.
+// csrc/mvr_knn_walk.h -- the walks of a cloud's model grid around a query, each written once, for the kernels that search a
+// neighbourhood (mvr_knn.hip: k-NN lists and normals; mvr_outlier.hip: mean neighbour distances and neighbour counts;
+// mvr_mls.hip: moving least squares):
+//   * knn_shell_walk: shells of cells outward from the query's cell until a visitor's k-best list is full and every unvisited
+//     cell lies beyond it (the f64 bound of knn_unvisited_bound);
+//   * knn_ball_walk: every point within a radius of the query, in grid order.
+// Around them the search side of a slot, the query of a thread, the cell lookup of the compact table, the row ranges, the
+// library's f32 distance, and the host-side checks every caller makes.  Not installed.
 #pragma once
+
+#include <limits>
+#include <string>
 
 #include "mvr_internal.h"
 
@@ -20,12 +28,21 @@ struct KnnSlot {
   uint32_t nq, nt, q_by_pos, blk0;
 };
 
+constexpr int kKnnThreads = 256;   // the block of every kernel that takes its query with knn_query
 constexpr uint32_t kSegOcc = 0x80000000u;
 // the empty entry of a k-best list of (d2 bits << 32 | index) keys: d2 = +inf, index 0.  Every key with a FINITE d2 is below
 // it, every key with d2 = +inf or NaN (either sign: the bits of a NaN are above those of +inf) is not -- so the one test
 // `key < L[KMAX - 1]` of the candidate loop also keeps the non-finite target points out (mvr_hip.h: the non-finite rule).
 constexpr nnkey_t kKnnKeyEmpty = 0x7F80000000000000ull;
-__device__ __forceinline__ bool knn_finite3(const float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
+// the query of this thread: by position in the slot's block range, its index from w in grid order; false: past the end
+__device__ __forceinline__ bool knn_query(const KnnSlot &S, float4 *q, uint32_t *qi)
+{
+  const uint32_t pos = (blockIdx.x - S.blk0) * kKnnThreads + threadIdx.x;
+  if (pos >= S.nq) return false;
+  *q = S.qs[pos];
+  *qi = S.q_by_pos ? pos : __float_as_uint(q->w);
+  return true;
+}
 // the cell-start lookup of the compact table (the same encoding as cell_start_of in mvr_grid.hip)
 __device__ __forceinline__ uint32_t knn_cell_start(const KnnSlot &S, uint32_t c)
 {
@@ -94,12 +111,94 @@ __device__ __forceinline__ void knn_ball_cells(const KnnSlot &S, const float4 q,
   *z0 = knn_cell_of(q.z - rad, S.lo[2], S.inv_h, S.dim[2]); *z1 = knn_cell_of(q.z + rad, S.lo[2], S.inv_h, S.dim[2]);
 }
 
+// the index of the target point p at grid position j (no grid: the points lie in index order)
+__device__ __forceinline__ uint32_t knn_index_of(const KnnSlot &S, const float4 p, const uint32_t j) { return S.dir ? __float_as_uint(p.w) : j; }
+
+// The shell walk: Chebyshev shells of cells outward from the query's cell (shell s = the cells at distance s), every point of
+// a shell handed to the visitor as v.visit(p, j), j = the point's grid position (knn_index_of gives its index).  After a shell
+// the walk ends when the whole grid is seen, or when the visitor's list is full -- v.full() -- and every unvisited cell lies
+// beyond it: v.beyond(b2), b2 = the square of knn_unvisited_bound less 1e-5 of itself, in f64.  Whether "beyond" includes "at"
+// is the visitor's rule (a tie that can still change the result must be visited).  A non-finite query or an empty target
+// walks nothing.
+template <class V>
+__device__ __forceinline__ void knn_shell_walk(const KnnSlot &S, const float4 q, V &v)
+{
+  if (S.nt == 0 || !finite3(q)) return;
+  const int cx = knn_cell_of(q.x, S.lo[0], S.inv_h, S.dim[0]), cy = knn_cell_of(q.y, S.lo[1], S.inv_h, S.dim[1]),
+            cz = knn_cell_of(q.z, S.lo[2], S.inv_h, S.dim[2]);
+  for (int s = 0;; ++s) {
+    const int x0 = cx - s, x1 = cx + s, y0 = cy - s, y1 = cy + s, z0 = cz - s, z1 = cz + s;
+    const int ya = max(y0, 0), yb = min(y1, S.dim[1] - 1), za = max(z0, 0), zb = min(z1, S.dim[2] - 1);
+    // the shell's rows one after the other: on a face of the shell the whole row [x0, x1], inside it the row's two end cells
+    // (ONE loop and one candidate loop: every copy of a visitor's unrolled insertion costs registers and code)
+    for (int r = 0, nr = (yb - ya + 1) * (zb - za + 1) * 2; r < nr; ++r) {
+      const int part = r & 1, y = ya + (r >> 1) % (yb - ya + 1), z = za + (r >> 1) / (yb - ya + 1);
+      const bool face = z == z0 || z == z1 || y == y0 || y == y1;
+      int a, b;
+      if (face) {
+        if (part) continue;
+        a = max(x0, 0); b = min(x1, S.dim[0] - 1);
+      } else {
+        a = b = part ? x1 : x0;
+        if (a < 0 || a >= S.dim[0]) continue;
+      }
+      uint32_t j, e;
+      knn_row_range(S, a, b, y, z, &j, &e);
+      for (; j < e; ++j) {
+        v.visit(S.gt[j], j);
+      }
+    }
+    if (!S.dir) return;                                               // one cell: all of it seen
+    const bool lo_x = x0 > 0, hi_x = x1 < S.dim[0] - 1, lo_y = y0 > 0, hi_y = y1 < S.dim[1] - 1, lo_z = z0 > 0, hi_z = z1 < S.dim[2] - 1;
+    if (!(lo_x || hi_x || lo_y || hi_y || lo_z || hi_z)) return;      // the whole grid seen
+    if (!v.full()) continue;
+    const double b = knn_unvisited_bound(S, q, x0, x1, y0, y1, z0, z1, lo_x, hi_x, lo_y, hi_y, lo_z, hi_z);
+    if (b > 0.0 && v.beyond(b * b * (1.0 - 1.0e-5))) return;          // (a NaN on either side: never)
+  }
+}
+
+// The ball walk: f(p, j) for every target point p (j = its grid position) with d2 <= r2 in the library's f32 distance, cell rows in
+// z, y order and grid order within a row -- the same points in the same order every time it is called with the same
+// arguments.  Against a finite r2 (clamp_r2) a non-finite p, with d2 = +inf or NaN, fails the test.  A non-finite query or
+// an empty target walks nothing.
+template <bool FMA, class F>
+__device__ __forceinline__ void knn_ball_walk(const KnnSlot &S, const float4 q, const float r2, F &&f)
+{
+  if (S.nt == 0 || !finite3(q)) return;
+  int x0, x1, y0, y1, z0, z1;
+  knn_ball_cells(S, q, r2, &x0, &x1, &y0, &y1, &z0, &z1);
+  for (int z = z0; z <= z1; ++z)
+    for (int y = y0; y <= y1; ++y) {
+      uint32_t j, e;
+      knn_row_range(S, x0, x1, y, z, &j, &e);
+      for (; j < e; ++j) {
+        const float4 p = S.gt[j];
+        if (knn_dist2<FMA>(p, q) <= r2) f(p, j);
+      }
+    }
+}
+
+// ---- the host side
+inline bool knn_slot_ok(int s) { return s >= 0 && s < MVR_MAX_SLOTS; }
+
+// (float)(radius * radius), kept finite: a d2 of +inf -- a non-finite neighbour, or an f32 overflow -- is never <= r2
+inline float clamp_r2(double radius) { return (float)std::min(radius * radius, (double)std::numeric_limits<float>::max()); }
+
+// what every entry point checks of a cloud before it walks it (`fn`: its name for the error text): indices fit the 31 bits the
+// walks and their callers leave them, and pts[] are what the cloud holds (a pipelined run leaves them out: Cloud::pts_stale)
+inline int knn_cloud_ok(Ctx *c, const Cloud &cl, const char *fn)
+{
+  if (cl.n > 0x7FFFFFF0ull) return set_error(c, MVR_E_ARG, (std::string(fn) + ": cloud too large").c_str());
+  if (cl.pts_stale) return set_error(c, MVR_E_ARG, (std::string(fn) + ": the cloud's points are not current (pipelined run)").c_str());
+  return MVR_OK;
+}
+
 inline int kmax_bucket(int k) { return k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64; }
 
-// the search side of a slot: its grid over the current coordinates when it can have one, else one cell over the points
+// the search side of a slot (a cloud that passed knn_cloud_ok): its grid over the current coordinates when it can have one,
+// else one cell over the points
 inline int fill_target(Ctx *c, Cloud &t, KnnSlot &S)
 {
-  if (t.pts_stale) return set_error(c, MVR_E_ARG, "k-NN / normals: the cloud's points are not current (pipelined run)");
   S.gt = t.pts; S.tpts = t.pts; S.dir = nullptr; S.recs = nullptr; S.nt = (uint32_t)t.n;
   for (int j = 0; j < 3; ++j) { S.lo[j] = 0.f; S.dim[j] = 1; }
   S.inv_h = 0.f;

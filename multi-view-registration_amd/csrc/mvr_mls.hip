@@ -3,20 +3,18 @@
 //
 // One thread per query, in the order of the cloud's model grid (ensure_model_grid; the helpers of mvr_knn_walk.h), so the 64
 // lanes of a wave are neighbours on the surface and walk the same cells:
-//   1. the radius walk of normals_radius_kernel accumulates the f64 moments of the neighbours about the query point; cyclic
+//   1. the ball walk (knn_ball_walk) accumulates the f64 moments of the neighbours about the query point; cyclic
 //      Jacobi gives the plane (mvr_plane.h).  Fewer than 3 neighbours: the point is dropped.
-//   2. order 2 and at least 6 neighbours: a SECOND walk over the same cells (their lines are in L1 / L2 from the first)
+//   2. order 2 and at least 6 neighbours: the SAME walk a second time (the cells' lines are in L1 / L2 from the first)
 //      accumulates, in f64, the 15 monomial sums and the 6 right-hand sums of the weighted bivariate fit about the projected
 //      query.  Everything is taken relative to the query point: the projected query is q + t n with t = (mean - q) . n, a
 //      neighbour's offset from it (p - q) - t n, so no sum ever sees the magnitude of the coordinates.
 //   3. the 6 x 6 normal equations are solved by Cholesky in registers: the loops are fully unrolled, every index a compile-time
 //      constant (a runtime-indexed private array lives in scratch memory: mvr_knn.hip).  A pivot that is not finite and
 //      positive, or a coefficient that is not finite, abandons the fit; the plane result stands.
-//   4. the results are written by SOURCE index into arrays of the context's arena (Ctx::dn_arena), with a keep flag; hipCUB's
-//      DeviceSelect::Flagged over a counting iterator gives the kept indices, ascending; launch_gather moves points and normals.
+//   4. the results are written by SOURCE index into arrays of the context's arena (Ctx::dn_arena), with a keep flag;
+//      select_flagged gives the kept indices, ascending; gather_kept moves points and normals.
 // No atomics and a fixed walk order: bit-identical from run to run on one grid.  Compiled with -ffp-contract=off.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -29,7 +27,7 @@
 namespace mvr {
 namespace {
 
-constexpr int kMlsThreads = 256;
+constexpr int kMlsThreads = kKnnThreads;
 
 struct MlsArgs {
   KnnSlot S;                       // the cloud searched against itself (nrm / curv / oidx / od2 unused)
@@ -110,25 +108,13 @@ template <bool FMA, bool POLY>
 __global__ void __launch_bounds__(kMlsThreads) mls_kernel(MlsArgs a)
 {
   const KnnSlot &S = a.S;
+  // (knn_query, written out: through the helper the order-2 kernel takes two more registers than this)
   const uint32_t pos = blockIdx.x * kMlsThreads + threadIdx.x;
   if (pos >= S.nq) return;
   const float4 q = S.qs[pos];
   const uint32_t qi = S.q_by_pos ? pos : __float_as_uint(q.w);
-  int x0 = 0, x1 = -1, y0 = 0, y1 = -1, z0 = 0, z1 = -1;      // (a non-finite query walks nothing: no neighbours, dropped)
-  if (knn_finite3(q) && S.nt) {
-    x1 = y1 = z1 = 0;
-    if (S.dir) knn_ball_cells(S, q, a.r2, &x0, &x1, &y0, &y1, &z0, &z1);
-  }
-  Moments M;
-  for (int z = z0; z <= z1; ++z)
-    for (int y = y0; y <= y1; ++y) {
-      uint32_t j, e;
-      knn_row_range(S, x0, x1, y, z, &j, &e);
-      for (; j < e; ++j) {
-        const float4 p = S.gt[j];
-        if (knn_dist2<FMA>(p, q) <= a.r2) M.add(p, q);      // (r2 is finite: a non-finite p, with d2 = +inf or NaN, fails)
-      }
-    }
+  Moments M;      // (a non-finite query walks nothing: no neighbours, dropped)
+  knn_ball_walk<FMA>(S, q, a.r2, [&](const float4 p, uint32_t) { M.add(p, q); });
   if (M.cnt < 3.0) { a.keep[qi] = 0; return; }
   const PlaneFit f = plane_fit(M);
   const double t = f.m0 * f.nx + f.m1 * f.ny + f.m2 * f.nz;      // the projected query is q + t n
@@ -143,18 +129,11 @@ __global__ void __launch_bounds__(kMlsThreads) mls_kernel(MlsArgs a)
     const double vx = f.ny * uz - f.nz * uy, vy = f.nz * ux - f.nx * uz, vz = f.nx * uy - f.ny * ux;
     const double tx = t * f.nx, ty = t * f.ny, tz = t * f.nz, ig = -1.0 / a.sqr_gauss;
     MlsSums m;
-    for (int z = z0; z <= z1; ++z)
-      for (int y = y0; y <= y1; ++y) {
-        uint32_t j, e;
-        knn_row_range(S, x0, x1, y, z, &j, &e);
-        for (; j < e; ++j) {
-          const float4 p = S.gt[j];
-          if (!(knn_dist2<FMA>(p, q) <= a.r2)) continue;
-          const double dx = ((double)p.x - (double)q.x) - tx, dy = ((double)p.y - (double)q.y) - ty, dz = ((double)p.z - (double)q.z) - tz;
-          const double w = exp((dx * dx + dy * dy + dz * dz) * ig);
-          m.add(w, dx * ux + dy * uy + dz * uz, dx * vx + dy * vy + dz * vz, dx * f.nx + dy * f.ny + dz * f.nz);
-        }
-      }
+    knn_ball_walk<FMA>(S, q, a.r2, [&](const float4 p, uint32_t) {
+      const double dx = ((double)p.x - (double)q.x) - tx, dy = ((double)p.y - (double)q.y) - ty, dz = ((double)p.z - (double)q.z) - tz;
+      const double w = exp((dx * dx + dy * dy + dz * dz) * ig);
+      m.add(w, dx * ux + dy * uy + dz * uz, dx * vx + dy * vy + dz * vz, dx * f.nx + dy * f.ny + dz * f.nz);
+    });
     double c[6];
     if (mls_solve(m, c)) {
       h = t + c[0];
@@ -166,19 +145,14 @@ __global__ void __launch_bounds__(kMlsThreads) mls_kernel(MlsArgs a)
     }
   }
   a.out_pts[qi] = make_float4((float)((double)q.x + h * f.nx), (float)((double)q.y + h * f.ny), (float)((double)q.z + h * f.nz), 1.f);
-  a.curv[qi] = f.sum != 0.0 ? (float)(fabs(f.lmin) / f.sum) : 0.f;
+  a.curv[qi] = plane_curvature(f);
   a.keep[qi] = 1;
   if (a.normals) {
-    float fx = (float)nx, fy = (float)ny, fz = (float)nz;
     // the f32 flip of mvr_cloud_estimate_normals, against the viewpoint seen from the source point or against its normal
     float rx, ry, rz;
     if (a.orient) { const float4 s = a.src_nrm[qi]; rx = s.x; ry = s.y; rz = s.z; }
     else { rx = a.vp[0] - q.x; ry = a.vp[1] - q.y; rz = a.vp[2] - q.z; }
-    float cs = rx * fx;
-    cs = cs + ry * fy;
-    cs = cs + rz * fz;
-    if (cs < 0.f) { fx = -fx; fy = -fy; fz = -fz; }
-    a.out_nrm[qi] = make_float4(fx, fy, fz, 0.f);
+    a.out_nrm[qi] = plane_normal_towards((float)nx, (float)ny, (float)nz, rx, ry, rz);
   }
 }
 
@@ -189,23 +163,17 @@ __global__ void __launch_bounds__(kMlsThreads) mls_gather_curv_kernel(const floa
   if (k < kept) out[k] = in[(uint32_t)list[k]];
 }
 
-inline unsigned mls_blocks(size_t n) { return (unsigned)((n + kMlsThreads - 1) / kMlsThreads); }
-
-using CountIt = hipcub::CountingInputIterator<unsigned long long>;
-
 int mls_cloud(Ctx *c, Cloud &dst, Cloud &src, const mvr_mls_params &p, size_t *n_out, uint32_t *kept_index, float *curvature)
 {
   const size_t n = src.n;
-  const bool same = &dst == &src, computed = p.compute_normals != 0, normals = computed || src.has_normals;
+  const bool computed = p.compute_normals != 0, normals = computed || src.has_normals;
   size_t kept = 0;
   if (p.orient == 1 && !src.has_normals) return set_error(c, MVR_E_ARG, "mls: orient 1 needs the source slot's normals");
-  if (n > 0x7FFFFFF0ull) return set_error(c, MVR_E_ARG, "mls: cloud too large");
-  if (src.pts_stale) return set_error(c, MVR_E_ARG, "mls: the source's points are not current (pipelined run)");
+  if (int rc = knn_cloud_ok(c, src, "mls")) return rc;
   if (n > 0) {
     MVR_MAY_BLOCK(c, "mls reads back");
     size_t sel_bytes = 0;
-    MVR_HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, sel_bytes, CountIt(0), (uint8_t *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr,
-                                                 (int)n, c->stream));
+    if (int rc = select_flagged(c, nullptr, sel_bytes, nullptr, n, nullptr, nullptr)) return rc;
     MlsArgs a{};
     if (int rc = fill_target(c, src, a.S)) return rc;      // (before the arena is carved: the grid build uses the context's buffers)
     fill_queries(src, a.S);
@@ -226,51 +194,32 @@ int mls_cloud(Ctx *c, Cloud &dst, Cloud &src, const mvr_mls_params &p, size_t *n
     // 1. the fit, by source index
     a.src_nrm = src.nrm; a.out_pts = o_pts; a.out_nrm = o_nrm; a.curv = o_curv; a.keep = keep;
     a.sqr_gauss = p.sqr_gauss_param != 0.0 ? p.sqr_gauss_param : p.radius * p.radius;
-    // (float)(radius * radius), kept finite: a d2 of +inf -- a non-finite neighbour, or an f32 overflow -- is never <= r2
-    a.r2 = (float)std::min(p.radius * p.radius, (double)std::numeric_limits<float>::max());
+    a.r2 = clamp_r2(p.radius);
     for (int j = 0; j < 3; ++j) a.vp[j] = p.viewpoint[j];
     a.normals = computed ? 1 : 0; a.orient = p.orient;
-    const dim3 grid(mls_blocks(n)), block(kMlsThreads);
+    const dim3 grid(blocks_for(n, kMlsThreads)), block(kMlsThreads);
     const bool fma = p.fma_dist != 0, poly = p.order == 2;
     if (fma) { if (poly) hipLaunchKernelGGL((mls_kernel<true, true>), grid, block, 0, c->stream, a); else hipLaunchKernelGGL((mls_kernel<true, false>), grid, block, 0, c->stream, a); }
     else { if (poly) hipLaunchKernelGGL((mls_kernel<false, true>), grid, block, 0, c->stream, a); else hipLaunchKernelGGL((mls_kernel<false, false>), grid, block, 0, c->stream, a); }
     MVR_HIP_TRY(c, hipGetLastError());
     // 2. the kept indices, ascending; the one read-back
     uint32_t hc[4] = {0, 0, 0, 0};
-    size_t b = sel_bytes;
-    MVR_HIP_TRY(c, hipcub::DeviceSelect::Flagged(tmp, b, CountIt(0), keep, list, counters, (int)n, c->stream));
+    if (int rc = select_flagged(c, tmp, sel_bytes, keep, n, list, counters)) return rc;
     MVR_HIP_TRY(c, hipMemcpyAsync(hc, counters, sizeof hc, hipMemcpyDeviceToHost, c->stream));
     MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
     kept = hc[0];
     // 3. the output.  Every result lies in the arena, so an in-place call gathers straight into the slot -- except the source's
     // own normals, which follow their points through a copy as in the outlier filters
-    if (!same) {
-      dst.n = 0;
-      if (int rc = cloud_reserve(c, dst, kept, false)) return rc;
-    }
-    if (int rc = launch_gather(c, o_pts, list, kept, dst.pts, d_index)) return rc;
-    if (normals && kept) {
-      if (computed || !same) {
-        if (int rc = ensure(c, dst.nrm, dst.nrm_cap, kept)) return rc;
-        if (int rc = launch_gather(c, computed ? o_nrm : src.nrm, list, kept, dst.nrm, nullptr)) return rc;
-      } else {
-        if (int rc = launch_gather(c, src.nrm, list, kept, out, nullptr)) return rc;
-        MVR_HIP_TRY(c, hipMemcpyAsync(src.nrm, out, kept * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-      }
-    }
+    if (int rc = gather_kept(c, dst, o_pts, computed ? o_nrm : normals ? src.nrm : nullptr, list, kept, out, d_index)) return rc;
     if (curvature && kept) {
-      hipLaunchKernelGGL(mls_gather_curv_kernel, dim3(mls_blocks(kept)), dim3(kMlsThreads), 0, c->stream, o_curv, list, kept, curv_out);
+      hipLaunchKernelGGL(mls_gather_curv_kernel, dim3(blocks_for(kept, kMlsThreads)), dim3(kMlsThreads), 0, c->stream, o_curv, list, kept, curv_out);
       MVR_HIP_TRY(c, hipGetLastError());
       MVR_HIP_TRY(c, hipMemcpyAsync(curvature, curv_out, kept * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     }
     if (kept_index && kept) MVR_HIP_TRY(c, hipMemcpyAsync(kept_index, d_index, kept * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));      // the host arrays are complete on return, and the arena is free again
   }
-  // the output replaces dst's points: a new point set (as after an upload)
-  dst.n = kept;
-  dst.has_normals = normals && kept > 0;
-  dst.segs.clear();
-  new_point_set(c, dst);
+  finish_dst(c, dst, kept, normals);
   if (n_out) *n_out = kept;
   return MVR_OK;
 }
@@ -282,11 +231,9 @@ using namespace mvr;
 
 #define API __attribute__((visibility("default")))
 
-static bool mls_slot_ok(int s) { return s >= 0 && s < MVR_MAX_SLOTS; }
-
 API int mvr_cloud_mls(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_mls_params *p, size_t *n_out, uint32_t *kept_index, float *curvature)
 {
-  if (!ctx || !p || !mls_slot_ok(dst_slot) || !mls_slot_ok(src_slot)) return MVR_E_ARG;
+  if (!ctx || !p || !knn_slot_ok(dst_slot) || !knn_slot_ok(src_slot)) return MVR_E_ARG;
   if (!(std::isfinite(p->radius) && p->radius > 0.0) || !(std::isfinite(p->sqr_gauss_param) && p->sqr_gauss_param >= 0.0)) return MVR_E_ARG;
   if (p->order < 0 || p->order > 2 || p->orient < 0 || p->orient > 1) return MVR_E_ARG;
   for (int j = 0; j < 3; ++j) if (!std::isfinite(p->viewpoint[j])) return MVR_E_ARG;

@@ -6,7 +6,7 @@
 //      bounding box or a cell computation of the grid build); results are written back by original index.
 //   2. the search, one thread per query in the order of the cloud's model grid (ensure_model_grid; the helpers of
 //      mvr_knn_walk.h), the query itself skipped by index:
-//      * mean distance: the shell walk of knn_kernel with its f64 stopping bound, but the k-best list is KMAX 32-bit keys --
+//      * mean distance: the shell walk (knn_shell_walk) with its f64 stopping bound, but the k-best list is KMAX 32-bit keys --
 //        the bits of the non-negative f32 d2, which order as unsigned integers.  No index: the result does not depend on how
 //        ties are broken, so the walk stops as soon as every unvisited cell is AT or beyond the k-th d2.  An insertion is
 //        L[i] = max(L[i - 1], min(key, L[i])) with compile-time indices: two 32-bit operations per entry where the 64-bit
@@ -14,16 +14,13 @@
 //        of 0 (an exact duplicate of the query) lands behind them because min / max keep the earlier entry on a tie, and
 //        only the last k entries are summed.  The thread sums sqrtf(d2) of its own list in f64, ascending, and writes one
 //        f32: no list goes to memory.
-//      * neighbour count: the radius walk of normals_radius_kernel with a counter instead of the moments.
+//      * neighbour count: the ball walk (knn_ball_walk) with a counter.
 //   3. statistics (mean distances only): two f64 reductions in a FIXED order -- a block sums a contiguous chunk of the
 //      points (strided per thread, then an LDS tree), one block sums the partials -- first the mean, then the squared
 //      deviations from it; the threshold is formed on the device.  No float atomics: bit-identical from run to run.
-//   4. a flag per point from the threshold or the count, hipCUB's DeviceSelect::Flagged over a counting iterator (the
-//      selected indices, ascending), one small read-back (count and statistics), then the gather of points and normals
-//      mvr_cloud_denoise ends with (launch_gather).
+//   4. a flag per point from the threshold or the count, the selected indices, ascending (select_flagged), one small
+//      read-back (count and statistics), then the gather of points and normals (gather_kept).
 // Scratch arrays come out of the context's arena (Ctx::dn_arena), as in mvr_voxel.hip.  Compiled with -ffp-contract=off.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -35,7 +32,7 @@
 namespace mvr {
 namespace {
 
-constexpr int kOutlThreads = 256;
+constexpr int kOutlThreads = kKnnThreads;
 constexpr unsigned kOutlSumBlocks = 1024;     // most partial sums of a reduction (a function of n alone: the summation order is fixed)
 constexpr uint32_t kListInit = 0xFFFFFFFFu;   // above the bits of every d2 (+inf is 0x7F800000; finite points give no NaN)
 
@@ -48,8 +45,6 @@ struct OutlArgs {
   float r2;
 };
 
-__device__ __forceinline__ bool outl_finite3(const float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
-
 // fin[i], the per-point result preset to what a non-finite point gets (NaN bits / 0), counters[0] += finite points
 __global__ void __launch_bounds__(kOutlThreads) outl_finite_kernel(const float4 *__restrict__ p, size_t n, uint8_t *__restrict__ fin,
                                                                    uint32_t *__restrict__ val, uint32_t preset, uint32_t *__restrict__ counters)
@@ -60,7 +55,7 @@ __global__ void __launch_bounds__(kOutlThreads) outl_finite_kernel(const float4 
   const size_t i = (size_t)blockIdx.x * kOutlThreads + threadIdx.x;
   bool f = false;
   if (i < n) {
-    f = outl_finite3(p[i]);
+    f = finite3(p[i]);
     fin[i] = f ? 1 : 0;
     val[i] = preset;
   }
@@ -68,15 +63,6 @@ __global__ void __launch_bounds__(kOutlThreads) outl_finite_kernel(const float4 
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(&s_cnt, (uint32_t)__popcll(m));
   __syncthreads();
   if (threadIdx.x == 0 && s_cnt) atomicAdd(&counters[0], s_cnt);
-}
-
-__device__ __forceinline__ bool outl_query(const OutlArgs &a, float4 *q, uint32_t *qi)
-{
-  const uint32_t pos = blockIdx.x * kOutlThreads + threadIdx.x;
-  if (pos >= a.S.nq) return false;
-  *q = a.S.qs[pos];
-  *qi = a.S.q_by_pos ? pos : __float_as_uint(q->w);
-  return true;
 }
 
 // the ordered list: insert `key` (which is below L[KMAX - 1]); every index is a compile-time constant
@@ -88,55 +74,36 @@ __device__ __forceinline__ void outl_insert(uint32_t (&L)[KMAX], const uint32_t 
   L[0] = min(key, L[0]);
 }
 
-// mean distance to the k nearest other points: the shell walk of knn_walk (mvr_knn.hip) over a distance-only list
+// the visitor of the shell walk that keeps the k smallest d2 to OTHER points
+template <int KMAX, bool FMA>
+struct OutlList {
+  uint32_t (&L)[KMAX];
+  const KnnSlot &S;
+  const float4 q;
+  const uint32_t qi;
+  __device__ __forceinline__ void visit(const float4 p, const uint32_t j)
+  {
+    const uint32_t key = knn_index_of(S, p, j) == qi ? kListInit : __float_as_uint(knn_dist2<FMA>(p, q));      // the query itself: never below the k-th
+    if (key < L[KMAX - 1]) outl_insert<KMAX>(L, key);
+  }
+  __device__ __forceinline__ bool full() const { return L[KMAX - 1] != kListInit; }
+  // at or beyond the k-th distance: a tie could only replace an equal value
+  __device__ __forceinline__ bool beyond(const double b2) const { return b2 >= (double)__uint_as_float(L[KMAX - 1]); }
+};
+
+// mean distance to the k nearest other points
 template <int KMAX, bool FMA>
 __global__ void __launch_bounds__(kOutlThreads) outl_mean_dist_kernel(OutlArgs a)
 {
-  const KnnSlot &S = a.S;
   float4 q; uint32_t qi;
-  if (!outl_query(a, &q, &qi)) return;
+  if (!knn_query(a.S, &q, &qi)) return;
   const int k = a.k;
   uint32_t L[KMAX];
 #pragma unroll
   for (int i = 0; i < KMAX; ++i) L[i] = i < KMAX - k ? 0u : kListInit;
-  const bool by_pos = !S.dir;
-  const int cx = knn_cell_of(q.x, S.lo[0], S.inv_h, S.dim[0]), cy = knn_cell_of(q.y, S.lo[1], S.inv_h, S.dim[1]),
-            cz = knn_cell_of(q.z, S.lo[2], S.inv_h, S.dim[2]);
-  for (int s = 0;; ++s) {
-    const int x0 = cx - s, x1 = cx + s, y0 = cy - s, y1 = cy + s, z0 = cz - s, z1 = cz + s;
-    const int ya = max(y0, 0), yb = min(y1, S.dim[1] - 1), za = max(z0, 0), zb = min(z1, S.dim[2] - 1);
-    // the shell's rows one after the other: on a face of the shell the whole row [x0, x1], inside it the row's two end cells
-    // (ONE loop and one candidate loop: every copy of the unrolled insertion costs registers and code)
-    for (int r = 0, nr = (yb - ya + 1) * (zb - za + 1) * 2; r < nr; ++r) {
-      const int part = r & 1, y = ya + (r >> 1) % (yb - ya + 1), z = za + (r >> 1) / (yb - ya + 1);
-      const bool face = z == z0 || z == z1 || y == y0 || y == y1;
-      int c0, c1;
-      if (face) {
-        if (part) continue;
-        c0 = max(x0, 0); c1 = min(x1, S.dim[0] - 1);
-      } else {
-        c0 = c1 = part ? x1 : x0;
-        if (c0 < 0 || c0 >= S.dim[0]) continue;
-      }
-      uint32_t j, e;
-      knn_row_range(S, c0, c1, y, z, &j, &e);
-      for (; j < e; ++j) {
-        const float4 p = S.gt[j];
-        const uint32_t pi = by_pos ? j : __float_as_uint(p.w);
-        const uint32_t key = pi == qi ? kListInit : __float_as_uint(knn_dist2<FMA>(p, q));      // the query itself: never below the k-th
-        if (key < L[KMAX - 1]) outl_insert<KMAX>(L, key);
-      }
-    }
-    if (!S.dir) break;                                                // one cell: all of it seen
-    const bool lo_x = x0 > 0, hi_x = x1 < S.dim[0] - 1, lo_y = y0 > 0, hi_y = y1 < S.dim[1] - 1, lo_z = z0 > 0, hi_z = z1 < S.dim[2] - 1;
-    if (!(lo_x || hi_x || lo_y || hi_y || lo_z || hi_z)) break;       // the whole grid seen
-    const uint32_t kth = L[KMAX - 1];
-    if (kth == kListInit) continue;                                   // the list is not full yet
-    const double b = knn_unvisited_bound(S, q, x0, x1, y0, y1, z0, z1, lo_x, hi_x, lo_y, hi_y, lo_z, hi_z);
-    // at or beyond the k-th distance: a tie could only replace an equal value (NaN: never)
-    if (b > 0.0 && b * b * (1.0 - 1.0e-5) >= (double)__uint_as_float(kth)) break;
-  }
-  // the caller runs this kernel only when the cloud holds at least k other points: the list is full
+  OutlList<KMAX, FMA> v{L, a.S, q, qi};
+  knn_shell_walk(a.S, q, v);
+  // the caller runs this kernel only when the cloud holds at least k other points, and every query is finite: the list is full
   double sum = 0.0;
 #pragma unroll
   for (int i = 0; i < KMAX; ++i)
@@ -144,27 +111,14 @@ __global__ void __launch_bounds__(kOutlThreads) outl_mean_dist_kernel(OutlArgs a
   a.mean_dist[a.remap ? a.remap[qi] : qi] = (float)(sum / (double)k);
 }
 
-// the number of other points with d2 <= r2: the radius walk of normals_radius_kernel
+// the number of other points with d2 <= r2
 template <bool FMA>
 __global__ void __launch_bounds__(kOutlThreads) outl_count_kernel(OutlArgs a)
 {
-  const KnnSlot &S = a.S;
   float4 q; uint32_t qi;
-  if (!outl_query(a, &q, &qi)) return;
-  const bool by_pos = !S.dir;
-  int x0 = 0, x1 = 0, y0 = 0, y1 = 0, z0 = 0, z1 = 0;
-  if (S.dir) knn_ball_cells(S, q, a.r2, &x0, &x1, &y0, &y1, &z0, &z1);
+  if (!knn_query(a.S, &q, &qi)) return;
   uint32_t cnt = 0;
-  for (int z = z0; z <= z1; ++z)
-    for (int y = y0; y <= y1; ++y) {
-      uint32_t j, e;
-      knn_row_range(S, x0, x1, y, z, &j, &e);
-      for (; j < e; ++j) {
-        const float4 p = S.gt[j];
-        const uint32_t pi = by_pos ? j : __float_as_uint(p.w);
-        if (pi != qi && knn_dist2<FMA>(p, q) <= a.r2) ++cnt;
-      }
-    }
+  knn_ball_walk<FMA>(a.S, q, a.r2, [&](const float4 p, const uint32_t j) { if (knn_index_of(a.S, p, j) != qi) ++cnt; });
   a.count[a.remap ? a.remap[qi] : qi] = cnt;
 }
 
@@ -235,12 +189,10 @@ __global__ void __launch_bounds__(kOutlThreads) outl_flag_count_kernel(const uin
   sel[i] = (in != (negative != 0)) ? 1 : 0;
 }
 
-inline unsigned blocks_for(size_t n) { return (unsigned)((n + kOutlThreads - 1) / kOutlThreads); }
-
 template <bool FMA>
 void launch_search(int kmax, const OutlArgs &a, hipStream_t st)
 {
-  const dim3 grid(blocks_for(a.S.nq)), block(kOutlThreads);
+  const dim3 grid(blocks_for(a.S.nq, kOutlThreads)), block(kOutlThreads);
   switch (kmax) {
     case 0:  hipLaunchKernelGGL(outl_count_kernel<FMA>, grid, block, 0, st, a); break;
     case 8:  hipLaunchKernelGGL((outl_mean_dist_kernel<8, FMA>), grid, block, 0, st, a); break;
@@ -257,25 +209,21 @@ struct WorkCloud {
   ~WorkCloud() { if (cl.pts) { (void)hipStreamSynchronize(stream); (void)hipFree(cl.pts); } }
 };
 
-using CountIt = hipcub::CountingInputIterator<unsigned long long>;
-
 // both filters: k > 0 = mean distances over the k nearest, k == 0 = neighbour counts within sqrt(r2)
 int outlier_filter(Ctx *c, Cloud &dst, Cloud &src, int k, double stddev_mul, float r2, uint32_t min_neighbors, bool negative, bool fma,
                    size_t *n_out, uint32_t *kept_index, void *per_point, mvr_sor_stats *stats)
 {
   const size_t n = src.n;
-  const bool same = &dst == &src, normals = src.has_normals, dist = k > 0;
+  const bool normals = src.has_normals, dist = k > 0;
   const double nan = std::numeric_limits<double>::quiet_NaN();
   double hs[4] = {nan, nan, nan, 0.0};
   size_t n_valid = 0, kept = 0;
-  if (n > 0x7FFFFFF0ull) return set_error(c, MVR_E_ARG, "outlier removal: cloud too large");
-  if (src.pts_stale) return set_error(c, MVR_E_ARG, "outlier removal: the source's points are not current (pipelined run)");
+  if (int rc = knn_cloud_ok(c, src, "outlier removal")) return rc;
   if (n > 0) {
     MVR_MAY_BLOCK(c, "outlier removal reads back");
     size_t sel_bytes = 0;
-    MVR_HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, sel_bytes, CountIt(0), (uint8_t *)nullptr, (unsigned long long *)nullptr, (uint32_t *)nullptr,
-                                                 (int)n, c->stream));
-    const unsigned nb = std::min(kOutlSumBlocks, blocks_for(n));
+    if (int rc = select_flagged(c, nullptr, sel_bytes, nullptr, n, nullptr, nullptr)) return rc;
+    const unsigned nb = std::min(kOutlSumBlocks, blocks_for(n, kOutlThreads));
     const size_t chunk = (n + nb - 1) / nb;
     Carver plan;
     plan.plan<uint8_t>(n); plan.plan<uint8_t>(n); plan.plan<uint32_t>(n); plan.plan<unsigned long long>(n); plan.plan<uint32_t>(n);
@@ -295,7 +243,7 @@ int outlier_filter(Ctx *c, Cloud &dst, Cloud &src, int k, double stddev_mul, flo
     uint32_t preset = 0, hc[4] = {0, 0, 0, 0};
     if (dist) std::memcpy(&preset, &fnan, 4);
     MVR_HIP_TRY(c, hipMemsetAsync(counters, 0, 4 * sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(outl_finite_kernel, dim3(blocks_for(n)), dim3(kOutlThreads), 0, c->stream, src.pts, n, fin, val, preset, counters);
+    hipLaunchKernelGGL(outl_finite_kernel, dim3(blocks_for(n, kOutlThreads)), dim3(kOutlThreads), 0, c->stream, src.pts, n, fin, val, preset, counters);
     MVR_HIP_TRY(c, hipGetLastError());
     MVR_HIP_TRY(c, hipMemcpyAsync(hc, counters, sizeof hc, hipMemcpyDeviceToHost, c->stream));
     MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -306,8 +254,7 @@ int outlier_filter(Ctx *c, Cloud &dst, Cloud &src, int k, double stddev_mul, flo
     // 2. the search, when there is anything to find: a mean distance needs k OTHER finite points
     const bool run = dist ? nf >= (size_t)k + 1 : nf > 0;
     if (run && nf < n) {
-      size_t b = sel_bytes;
-      MVR_HIP_TRY(c, hipcub::DeviceSelect::Flagged(tmp, b, CountIt(0), fin, list, counters + 1, (int)n, c->stream));
+      if (int rc = select_flagged(c, tmp, sel_bytes, fin, n, list, counters + 1)) return rc;
       if (int rc = cloud_reserve(c, wc.cl, nf, false)) return rc;
       if (int rc = launch_gather(c, src.pts, list, nf, wc.cl.pts, remap)) return rc;
       wc.cl.n = nf;
@@ -331,43 +278,23 @@ int outlier_filter(Ctx *c, Cloud &dst, Cloud &src, int k, double stddev_mul, flo
       hipLaunchKernelGGL(outl_sum_kernel<1>, dim3(nb), dim3(kOutlThreads), 0, c->stream, md, fin, n, chunk, dstats, partial);
       hipLaunchKernelGGL(outl_final_kernel<1>, dim3(1), dim3(kOutlThreads), 0, c->stream, partial, nb, (double)nf, stddev_mul, dstats);
     }
-    if (dist) hipLaunchKernelGGL(outl_flag_dist_kernel, dim3(blocks_for(n)), dim3(kOutlThreads), 0, c->stream, md, fin, n,
+    if (dist) hipLaunchKernelGGL(outl_flag_dist_kernel, dim3(blocks_for(n, kOutlThreads)), dim3(kOutlThreads), 0, c->stream, md, fin, n,
                                  run ? dstats : (const double *)nullptr, negative ? 1 : 0, sel);
-    else hipLaunchKernelGGL(outl_flag_count_kernel, dim3(blocks_for(n)), dim3(kOutlThreads), 0, c->stream, val, fin, n, min_neighbors, negative ? 1 : 0, sel);
+    else hipLaunchKernelGGL(outl_flag_count_kernel, dim3(blocks_for(n, kOutlThreads)), dim3(kOutlThreads), 0, c->stream, val, fin, n, min_neighbors, negative ? 1 : 0, sel);
     MVR_HIP_TRY(c, hipGetLastError());
     // 4. the selected indices, ascending; the one read-back of the chain
-    size_t b = sel_bytes;
-    MVR_HIP_TRY(c, hipcub::DeviceSelect::Flagged(tmp, b, CountIt(0), sel, list, counters + 2, (int)n, c->stream));
+    if (int rc = select_flagged(c, tmp, sel_bytes, sel, n, list, counters + 2)) return rc;
     MVR_HIP_TRY(c, hipMemcpyAsync(hc, counters, sizeof hc, hipMemcpyDeviceToHost, c->stream));
     if (dist && run) MVR_HIP_TRY(c, hipMemcpyAsync(hs, dstats, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (per_point) MVR_HIP_TRY(c, hipMemcpyAsync(per_point, val, n * 4, hipMemcpyDeviceToHost, c->stream));
     MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
     kept = hc[2];
-    // 5. the output: the gather mvr_cloud_denoise ends with
-    if (same) {
-      if (int rc = launch_gather(c, src.pts, list, kept, out, d_index)) return rc;
-      if (kept) MVR_HIP_TRY(c, hipMemcpyAsync(src.pts, out, kept * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-      if (normals && kept) {
-        if (int rc = launch_gather(c, src.nrm, list, kept, out, nullptr)) return rc;
-        MVR_HIP_TRY(c, hipMemcpyAsync(src.nrm, out, kept * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-      }
-    } else {
-      dst.n = 0;
-      if (int rc = cloud_reserve(c, dst, kept, false)) return rc;
-      if (int rc = launch_gather(c, src.pts, list, kept, dst.pts, d_index)) return rc;
-      if (normals && kept) {
-        if (int rc = ensure(c, dst.nrm, dst.nrm_cap, kept)) return rc;
-        if (int rc = launch_gather(c, src.nrm, list, kept, dst.nrm, nullptr)) return rc;
-      }
-    }
+    // 5. the output
+    if (int rc = gather_kept(c, dst, src.pts, normals ? src.nrm : nullptr, list, kept, out, d_index)) return rc;
     if (kept_index && kept) MVR_HIP_TRY(c, hipMemcpyAsync(kept_index, d_index, kept * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));      // kept_index is complete on return, and the arena is free again
   }
-  // the output replaces dst's points: a new point set (as after an upload)
-  dst.n = kept;
-  dst.has_normals = normals && kept > 0;
-  dst.segs.clear();
-  new_point_set(c, dst);
+  finish_dst(c, dst, kept, normals);
   if (n_out) *n_out = kept;
   if (stats) { stats->mean = hs[0]; stats->stddev = hs[1]; stats->threshold = hs[2]; stats->n_valid = n_valid; }
   return MVR_OK;
@@ -381,12 +308,10 @@ using namespace mvr;
 
 #define API __attribute__((visibility("default")))
 
-static bool outl_slot_ok(int s) { return s >= 0 && s < MVR_MAX_SLOTS; }
-
 API int mvr_cloud_statistical_outlier_removal(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_sor_params *p, size_t *n_out,
                                               uint32_t *kept_index, float *mean_dist, mvr_sor_stats *stats)
 {
-  if (!ctx || !p || !outl_slot_ok(dst_slot) || !outl_slot_ok(src_slot)) return MVR_E_ARG;
+  if (!ctx || !p || !knn_slot_ok(dst_slot) || !knn_slot_ok(src_slot)) return MVR_E_ARG;
   if (p->mean_k < 1 || p->mean_k > MVR_MAX_KNN || !std::isfinite(p->stddev_mul)) return MVR_E_ARG;
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   MVR_HIP_TRY(c, hipSetDevice(c->device));
@@ -397,7 +322,7 @@ API int mvr_cloud_statistical_outlier_removal(mvr_ctx *ctx, int dst_slot, int sr
 API int mvr_cloud_radius_outlier_removal(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_ror_params *p, size_t *n_out,
                                          uint32_t *kept_index, uint32_t *neighbor_count)
 {
-  if (!ctx || !p || !outl_slot_ok(dst_slot) || !outl_slot_ok(src_slot)) return MVR_E_ARG;
+  if (!ctx || !p || !knn_slot_ok(dst_slot) || !knn_slot_ok(src_slot)) return MVR_E_ARG;
   if (!(std::isfinite(p->radius) && p->radius > 0.0) || p->min_neighbors < 0) return MVR_E_ARG;
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   MVR_HIP_TRY(c, hipSetDevice(c->device));

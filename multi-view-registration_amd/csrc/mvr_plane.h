@@ -1,6 +1,6 @@
 // csrc/mvr_plane.h -- the plane through a neighbourhood, shared by the kernels that fit one (mvr_knn.hip: normals; mvr_mls.hip:
 // moving least squares): f64 moments of the neighbours about the query point, the 3 x 3 symmetric eigenproblem by cyclic Jacobi,
-// and the pick of the smallest eigenvalue's eigenvector.  Every index is a compile-time constant: the matrices stay in
+// the pick of the smallest eigenvalue's eigenvector, the curvature and the f32 orientation of the normal.  Every index is a compile-time constant: the matrices stay in
 // registers.  Not installed.
 #pragma once
 
@@ -75,6 +75,20 @@ __device__ __forceinline__ PlaneFit plane_fit(const Moments &M)
   f.sum = l0 + l1 + l2;
   f.m0 = m0; f.m1 = m1; f.m2 = m2;
   return f;
+}
+
+// PCL's curvature of a fitted plane: the smallest eigenvalue's share of the three
+__device__ __forceinline__ float plane_curvature(const PlaneFit &f) { return f.sum != 0.0 ? (float)(fabs(f.lmin) / f.sum) : 0.f; }
+
+// flipNormalTowardsViewpoint: the normal, already rounded to f32, turned to the side of the direction r (towards the viewpoint,
+// or along a reference normal) with PCL's f32 test, cos < 0 strictly
+__device__ __forceinline__ float4 plane_normal_towards(float fx, float fy, float fz, const float rx, const float ry, const float rz)
+{
+  float cs = rx * fx;
+  cs = cs + ry * fy;
+  cs = cs + rz * fz;
+  if (cs < 0.f) { fx = -fx; fy = -fy; fz = -fz; }
+  return make_float4(fx, fy, fz, 0.f);
 }
 
 }  // namespace mvr

@@ -34,8 +34,6 @@ constexpr unsigned kPieceGrid = 2048; // blocks of the piece launch (grid-stride
 
 static_assert(kBoxBlocks <= kVoxThreads, "the final box reduction takes one partial record per thread");
 
-__device__ __forceinline__ bool finite3(const float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
-
 __device__ __forceinline__ void box_reduce(const float lo[3], const float hi[3], uint32_t cnt, float *__restrict__ rec);
 
 // part[block][8]: lo xyz, hi xyz of the finite points, their count (bits), unused
@@ -269,17 +267,6 @@ __global__ __launch_bounds__(kVoxThreads) void vox_map_kernel(const uint32_t *__
   voxel_of[sidx[j]] = j < nf ? vmap[vid[j] - 1u] : kNone;
 }
 
-inline unsigned blocks_for(size_t n) { return (unsigned)((n + kVoxThreads - 1) / kVoxThreads); }
-
-// the output replaces dst's points: a new point set (as after an upload)
-void finish_dst(Ctx *c, Cloud &dst, size_t n, bool normals)
-{
-  dst.n = n;
-  dst.has_normals = normals && n > 0;
-  dst.segs.clear();
-  new_point_set(c, dst);
-}
-
 template <class K, bool NRM>
 int voxel_pass(Ctx *c, const Cloud &src, size_t nf, const VoxGeom &g, int bits, unsigned min_points, Carver &s, size_t sort_bytes,
                size_t scan_bytes, uint32_t *counters, float4 **out, float4 **onrm, uint32_t **d_voxel_of, bool want_map)
@@ -298,22 +285,22 @@ int voxel_pass(Ctx *c, const Cloud &src, size_t nf, const VoxGeom &g, int bits, 
   double *partial = s.take<double>(max_pieces * 8);
   *d_voxel_of = want_map ? s.take<uint32_t>(n) : nullptr;
   char *tmp = s.take<char>(std::max(sort_bytes, scan_bytes));
-  hipLaunchKernelGGL(vox_key_kernel<K>, dim3(blocks_for(n)), dim3(kVoxThreads), 0, c->stream, src.pts, n, g, key_a, idx_a);
+  hipLaunchKernelGGL(vox_key_kernel<K>, dim3(blocks_for(n, kVoxThreads)), dim3(kVoxThreads), 0, c->stream, src.pts, n, g, key_a, idx_a);
   MVR_HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, key_a, key_b, idx_a, idx_b, n, 0, bits, c->stream));
-  hipLaunchKernelGGL(vox_head_kernel<K>, dim3(blocks_for(nf)), dim3(kVoxThreads), 0, c->stream, key_b, nf, head);
+  hipLaunchKernelGGL(vox_head_kernel<K>, dim3(blocks_for(nf, kVoxThreads)), dim3(kVoxThreads), 0, c->stream, key_b, nf, head);
   size_t b = scan_bytes;
   MVR_HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(tmp, b, head, vid, nf, c->stream));
-  hipLaunchKernelGGL((vox_voxel_kernel<K, NRM>), dim3(blocks_for(nf)), dim3(kVoxThreads), 0, c->stream, key_b, idx_b, nf, src.pts,
+  hipLaunchKernelGGL((vox_voxel_kernel<K, NRM>), dim3(blocks_for(nf, kVoxThreads)), dim3(kVoxThreads), 0, c->stream, key_b, idx_b, nf, src.pts,
                      (const float4 *)src.nrm, (uint32_t)min_points, keep, cent, cnrm, longs, pieces, counters);
   hipLaunchKernelGGL(vox_piece_kernel<NRM>, dim3((unsigned)std::min<size_t>(max_pieces, kPieceGrid)), dim3(kVoxThreads), 0, c->stream,
                      pieces, counters, idx_b, src.pts, (const float4 *)src.nrm, partial);
-  hipLaunchKernelGGL(vox_long_kernel<NRM>, dim3(blocks_for(max_long)), dim3(kVoxThreads), 0, c->stream, longs, counters, partial, cent, cnrm);
+  hipLaunchKernelGGL(vox_long_kernel<NRM>, dim3(blocks_for(max_long, kVoxThreads)), dim3(kVoxThreads), 0, c->stream, longs, counters, partial, cent, cnrm);
   b = scan_bytes;
   MVR_HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(tmp, b, keep, kpos, nf, c->stream));
-  hipLaunchKernelGGL(vox_out_kernel<NRM>, dim3(blocks_for(nf)), dim3(kVoxThreads), 0, c->stream, head, vid, keep, kpos, nf, cent, cnrm,
+  hipLaunchKernelGGL(vox_out_kernel<NRM>, dim3(blocks_for(nf, kVoxThreads)), dim3(kVoxThreads), 0, c->stream, head, vid, keep, kpos, nf, cent, cnrm,
                      *out, *onrm, vmap, counters);
   if (want_map)
-    hipLaunchKernelGGL(vox_map_kernel, dim3(blocks_for(n)), dim3(kVoxThreads), 0, c->stream, idx_b, vid, vmap, n, nf, *d_voxel_of);
+    hipLaunchKernelGGL(vox_map_kernel, dim3(blocks_for(n, kVoxThreads)), dim3(kVoxThreads), 0, c->stream, idx_b, vid, vmap, n, nf, *d_voxel_of);
   MVR_HIP_TRY(c, hipGetLastError());
   return MVR_OK;
 }
@@ -365,7 +352,7 @@ int voxel_grid_cloud(Ctx *c, Cloud &dst, Cloud &src, const float leaf[3], unsign
   float *part = s.take<float>(8 * kBoxBlocks), *box = s.take<float>(8);
   uint32_t *counters = s.take<uint32_t>(4);
   // 1. finite box + count
-  const int bb = (int)std::min<size_t>(kBoxBlocks, blocks_for(n));
+  const int bb = (int)std::min<size_t>(kBoxBlocks, blocks_for(n, kVoxThreads));
   MVR_HIP_TRY(c, hipMemsetAsync(counters, 0, 4 * sizeof(uint32_t), c->stream));
   hipLaunchKernelGGL(vox_box_partial_kernel, dim3(bb), dim3(kVoxThreads), 0, c->stream, src.pts, n, part);
   hipLaunchKernelGGL(vox_box_final_kernel, dim3(1), dim3(kVoxThreads), 0, c->stream, part, bb, box);
