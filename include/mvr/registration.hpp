@@ -17,6 +17,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -496,6 +497,79 @@ class MovingLeastSquares {
   int order_ = 2;
   bool gauss_set_ = false, compute_normals_ = false;
   PointIndicesPtr corresponding_ = std::make_shared<PointIndices>();
+};
+
+// ---------------------------------------------------------------- fast point feature histograms
+// pcl::FPFHEstimation<PointInT, PointNT, PointOutT> (features/fpfh.h) in radius mode, the input cloud its own search surface:
+// setInputCloud, setInputNormals, setSearchMethod, setRadiusSearch, compute.  Semantics: mvr_cloud_fpfh (mvr_hip.h) -- one call
+// on the GPU per compute().  PointInT: any point whose first three floats are x, y, z; PointNT: any point with normal_x / y / z
+// (Normal, PointNormal).  A point with a non-finite coordinate or normal gets a NaN signature (PCL does the same) and
+// is_dense is cleared.  As PCL's Feature::compute, a missing input, missing normals, a normal cloud of another size or a
+// radius that is not finite and > 0 prints an error and leaves `output` empty.  What this class cannot do it refuses with an
+// exception, not silently: the k-neighbour mode (setKSearch with a non-zero k), setSearchSurface and setIndices.
+template <typename PointInT, typename PointNT, typename PointOutT = FPFHSignature33>
+class FPFHEstimation {
+ public:
+  typedef PointCloud<PointInT> PointCloudIn;
+  typedef typename PointCloudIn::ConstPtr PointCloudConstPtr;
+  typedef PointCloud<PointNT> PointCloudN;
+  typedef typename PointCloudN::ConstPtr PointCloudNConstPtr;
+  typedef PointCloud<PointOutT> PointCloudOut;
+  typedef search::KdTree<PointInT> KdTree;
+  typedef typename KdTree::Ptr KdTreePtr;
+  typedef std::shared_ptr<const std::vector<int> > IndicesConstPtr;
+
+  void setInputCloud(const PointCloudConstPtr &c) { input_ = c; }
+  PointCloudConstPtr getInputCloud() const { return input_; }
+  void setInputNormals(const PointCloudNConstPtr &n) { normals_ = n; }
+  PointCloudNConstPtr getInputNormals() const { return normals_; }
+  void setSearchMethod(const KdTreePtr &tree) { tree_ = tree; }
+  KdTreePtr getSearchMethod() const { return tree_; }
+  void setRadiusSearch(double r) { radius_ = r; }
+  double getRadiusSearch() const { return radius_; }
+  void setKSearch(int k) { if (k != 0) throw std::invalid_argument("[pcl::FPFHEstimation::setKSearch] the k-neighbour mode is not offered: use setRadiusSearch"); }
+  int getKSearch() const { return 0; }
+  void setSearchSurface(const PointCloudConstPtr &) { throw std::invalid_argument("[pcl::FPFHEstimation::setSearchSurface] a separate search surface is not offered: the input cloud is its own surface"); }
+  void setIndices(const IndicesConstPtr &) { throw std::invalid_argument("[pcl::FPFHEstimation::setIndices] index subsets are not offered: every point gets a signature"); }
+
+  void compute(PointCloudOut &output)
+  {
+    static_assert(sizeof(PointInT) % 4 == 0 && sizeof(PointInT) >= 12, "points that begin with x, y, z expected");
+    static_assert(sizeof(PointOutT) == sizeof(float) * 3 * MVR_FPFH_BINS, "a 33-float signature expected");
+    output.clear();
+    if (!input_) { std::fprintf(stderr, "[pcl::FPFHEstimation::compute] No input dataset was given!\n"); return; }
+    if (!normals_ || normals_->size() != input_->size()) {
+      std::fprintf(stderr, "[pcl::FPFHEstimation::compute] The number of points in the input dataset differs from the number of points in the dataset containing the normals!\n");
+      return;
+    }
+    if (!(std::isfinite(radius_) && radius_ > 0.0)) {
+      std::fprintf(stderr, "[pcl::FPFHEstimation::compute] The search radius (%f) must be finite and > 0 (setRadiusSearch).\n", radius_);
+      return;
+    }
+    const size_t n = input_->size();
+    output.resize(n);
+    if (!n) return;
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.check(mvr_cloud_upload(d.ctx(), s.s, input_->points[0].data, n, sizeof(PointInT)), "mvr_cloud_upload");
+    std::vector<float> nrm(4 * n);
+    for (size_t i = 0; i < n; ++i) {
+      const PointNT &q = normals_->points[i];
+      nrm[4 * i] = q.normal_x; nrm[4 * i + 1] = q.normal_y; nrm[4 * i + 2] = q.normal_z; nrm[4 * i + 3] = 0.f;
+    }
+    d.check(mvr_cloud_upload_normals(d.ctx(), s.s, nrm.data(), n, 16), "mvr_cloud_upload_normals");
+    mvr_fpfh_params p;
+    p.radius = radius_; p.fma_dist = 0;
+    d.check(mvr_cloud_fpfh(d.ctx(), s.s, &p, output.points[0].histogram, nullptr, nullptr), "mvr_cloud_fpfh");
+    for (size_t i = 0; i < n && output.is_dense; ++i)
+      if (std::isnan(output.points[i].histogram[0])) output.is_dense = false;
+  }
+
+ private:
+  PointCloudConstPtr input_;
+  PointCloudNConstPtr normals_;
+  KdTreePtr tree_;
+  double radius_ = 0.0;
 };
 
 namespace registration {

@@ -281,6 +281,36 @@ class ScanCloud {
     return before - kept;
   }
 
+  // EXTENSION (pcl::FPFHEstimation on the raw points, on the GPU; rules: mvr_cloud_fpfh in mvr_hip.h): one 33-bin signature per
+  // point from every neighbour within `radius`, with the normals of `rich` (estimateNormals, smooth with compute_normals, or
+  // a file that carries them).  Without one rich record per point, or with a radius that is not finite and > 0, it prints an
+  // error, leaves `out` empty and returns false.  `points`, `rich` and the pose stay as they are.
+  bool computeFPFH(double radius, std::vector<FPFHSignature33> &out) const
+  {
+    out.clear();
+    const size_t n = points.size();
+    if (rich.size() != n) {
+      std::fprintf(stderr, "[ScanCloud::computeFPFH] The cloud has no normals (%zu points, %zu records): call estimateNormals first.\n", n, rich.size());
+      return false;
+    }
+    if (!(std::isfinite(radius) && radius > 0.0)) {
+      std::fprintf(stderr, "[ScanCloud::computeFPFH] The radius (%f) must be finite and > 0.\n", radius);
+      return false;
+    }
+    out.resize(n);
+    if (!n) return true;
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.upload(s.s, points);
+    std::vector<float> nrm(4 * n);
+    for (size_t i = 0; i < n; ++i) { nrm[4 * i] = rich[i].normal_x; nrm[4 * i + 1] = rich[i].normal_y; nrm[4 * i + 2] = rich[i].normal_z; nrm[4 * i + 3] = 0.f; }
+    d.check(mvr_cloud_upload_normals(d.ctx(), s.s, nrm.data(), n, 16), "mvr_cloud_upload_normals");
+    mvr_fpfh_params p;
+    p.radius = radius; p.fma_dist = 0;
+    d.check(mvr_cloud_fpfh(d.ctx(), s.s, &p, out[0].histogram, nullptr, nullptr), "mvr_cloud_fpfh");
+    return true;
+  }
+
   // point_cloud.cpp:305-326 / :328-347 -- `transformation.txt`: the column-vector
   // 4x4 printed row by row (matrix(j,i), i outer), "%lf " per element, one row per
   // line.  6 decimals: poses round-trip to 1e-6 only.

@@ -63,6 +63,14 @@ struct alignas(16) PointNormal {
 };
 static_assert(sizeof(PointNormal) == 48, "PointNormal must match pcl::PointNormal");
 
+// pcl::FPFHSignature33: the 3 x 11 bins of a fast point feature histogram (mvr_cloud_fpfh in mvr_hip.h)
+struct FPFHSignature33 {
+  float histogram[33];
+  static int descriptorSize() { return 33; }
+  FPFHSignature33() { for (float &h : histogram) h = 0.f; }
+};
+static_assert(sizeof(FPFHSignature33) == 132, "FPFHSignature33 must match pcl::FPFHSignature33");
+
 // pcl::PointIndices (the member MovingLeastSquares::getCorrespondingIndices hands out)
 struct PointIndices {
   typedef std::shared_ptr<PointIndices> Ptr;

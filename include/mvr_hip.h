@@ -364,6 +364,50 @@ typedef struct {
 int  mvr_cloud_mls(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_mls_params *p, size_t *n_out,
                    uint32_t *kept_index, float *curvature);
 
+/* ---- fast point feature histograms (EXTENSION: pcl::FPFHEstimation) ----------------------------------------------------
+ * The 33-bin signatures a feature matcher or a sample-consensus aligner starts from when no pose prior is at hand.  The
+ * reference pins no PCL version; the model is pcl/features/impl/fpfh.hpp (computePointSPFHSignature,
+ * weightPointSPFHSignature) and pcl::computePairFeatures in radius mode; deviations are marked.
+ *  F1. Input: the cloud in `slot` and its normals; the cloud is search surface and input at once (PCL: setSearchSurface
+ *      unset, all indices).  A point is VALID when its three coordinates and its three normal components are finite.  An
+ *      invalid point is nobody's neighbour and enters no count and no sum; its own signature and its SPFH row are 33 NaN and
+ *      its neighbor_count is 0; no query walks the grid because of one (rules N2 and N5 above).
+ *  F2. Neighbourhood: N(i) = every valid j with d2(i, j) <= (float)(radius * radius) under the f32 distance of mvr_nn /
+ *      mvr_knn, i itself included -- exactly the radius mode of mvr_cloud_estimate_normals; fma_dist = 1 selects the fma
+ *      chain.  n_i = |N(i)|.
+ *  F3. Pair features of (i, j), j in N(i), j != i, all in f32, every operation rounded, none contracted.  A dot product is
+ *      (ax*bx + ay*by) + az*bz, a norm sqrtf of that.  dp = p_j - p_i, f4 = |dp|; f4 == 0: no features (PCL returns false).
+ *      a1 = (n_i . dp) / f4, a2 = (n_j . dp) / f4.  Swap iff fabsf(a1) < fabsf(a2): the roles of n_i and n_j exchange,
+ *      dp = -dp and f3 = -a2; otherwise f3 = a1.  (PCL tests acos(|a1|) > acos(|a2|): the same wherever f32 acos is
+ *      injective, without the libm call.)  With n1 / n2 the normals after the swap: v = dp x n1; |v| == 0: no features;
+ *      v /= |v|; w = n1 x v; f2 = v . n2; f1 = atan2f(w . n2, n1 . n2).
+ *  F4. Bins, PCL's expressions in f64 from the f32 feature: b1 = floor(11 * ((f1 + M_PI) * (double)d_pi)) with
+ *      d_pi = (float)(1 / (2 pi)); b2 = floor(11 * ((f2 + 1.0) * 0.5)), b3 the same from f3; each clamped to 0..10.
+ *  F5. SPFH: c_i[f][b] = the number of pairs of i that F3 gives features and F4 puts in bin b of feature f, an exact integer;
+ *      SPFH_i[f][b] = (float)c * (100.0f / (float)(n_i - 1)) in f32; n_i = 1: 33 zeros.  Pairs without features still count
+ *      in n_i - 1, as in PCL.  (PCL adds the increment 100 / (n_i - 1) c times in f32: a difference of rounding only.)
+ *  F6. FPFH: for every j in N(i) with d2 != 0 and w = 1.0f / d2 finite, val = SPFH_j[f][b] * w in f32 (PCL's arithmetic: the
+ *      weight is one over the SQUARED distance) is added in f64 to the bin and to the sum of its feature, in walk order; the
+ *      query's own SPFH is not added, as in PCL.  Output (float)(bin * (100.0 / sum_f)) when sum_f != 0, else 0: each of the
+ *      three 11-bin blocks of a point with a contributing neighbour sums to 100.  (PCL accumulates the bins in f32 in the
+ *      order FLANN returns the neighbours; here the order is the grid walk's and the sums are f64.)
+ *  F7. MVR_E_ARG, before any GPU work and with nothing written, for a NULL ctx / params, a bad slot, a radius that is
+ *      non-finite or <= 0, a slot without normals, a cloud above 0x7FFFFFF0 points, or a cloud whose points are stale
+ *      because a pipelined run is in flight.  An empty cloud is MVR_OK.  All three outputs NULL: MVR_OK after the work.
+ *  F8. Bit-identical from run to run on one grid: one thread per query, one fixed walk order, no floating-point atomics.
+ * The slot is not modified and no descriptor stays on the device after the call.
+ * Out of scope: the k-neighbour mode (setKSearch), setSearchSurface / setIndices, PFH, and the matching and
+ * sample-consensus alignment that consume the signatures. */
+#define MVR_FPFH_BINS 11            /* per feature; a signature is 3 * 11 = 33 floats (pcl::FPFHSignature33) */
+typedef struct {
+  double radius;        /* setRadiusSearch: finite, > 0 */
+  int    fma_dist;
+} mvr_fpfh_params;
+int  mvr_cloud_fpfh(mvr_ctx *ctx, int slot, const mvr_fpfh_params *p,
+                    float *fpfh,              /* host, n * 33, row = point index; may be NULL   */
+                    float *spfh,              /* optional host, n * 33: the intermediate SPFH   */
+                    uint32_t *neighbor_count  /* optional host, n: n_i of rule F2               */);
+
 /* CorrespondenceEstimation::determineReciprocalCorrespondences(corrs, max_d)
  * (registrator.cpp:496-502, 644-649); reciprocal = 0 gives
  * determineCorrespondences.  Outputs are host arrays of capacity `cap`

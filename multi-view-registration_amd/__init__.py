@@ -128,6 +128,13 @@ class MlsParams(C.Structure):
                 ("orient", C.c_int), ("viewpoint", C.c_float * 3), ("fma_dist", C.c_int)]
 
 
+class FpfhParams(C.Structure):
+    """mvr_fpfh_params"""
+    _fields_ = [("radius", C.c_double), ("fma_dist", C.c_int)]
+
+
+FPFH_BINS = 11          # MVR_FPFH_BINS: a signature is 3 * 11 = 33 floats
+
 _fp, _dp, _u32p, _i32p = (C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                           C.POINTER(C.c_int32))
 _vp, _sz = C.c_void_p, C.c_size_t
@@ -153,6 +160,7 @@ SIGNATURES = {
                                                         C.POINTER(SorStats)]),
     "mvr_cloud_radius_outlier_removal": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RorParams), C.POINTER(_sz), _u32p, _u32p]),
     "mvr_cloud_mls": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(MlsParams), C.POINTER(_sz), _u32p, _fp]),
+    "mvr_cloud_fpfh": (C.c_int, [_vp, C.c_int, C.POINTER(FpfhParams), _fp, _fp, _u32p]),
     "mvr_cloud_set_global_base": (C.c_int, [_vp, C.c_int, _sz]),
     "mvr_cloud_append_range": (C.c_int, [_vp, C.c_int, C.c_int, _sz, _sz, _sz]),
     "mvr_nn_forward_keys": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp]),
@@ -642,6 +650,26 @@ class Context:
         if return_curvature:
             out.append(curv[:n_out.value].copy())
         return out[0] if len(out) == 1 else tuple(out)
+
+    def fpfh(self, slot, radius, fma=False, return_spfh=False, return_counts=False):
+        """pcl::FPFHEstimation::compute of slot against itself, radius mode, with the slot's own normals (estimate_normals or
+        upload_normals first): the (n, 33) float32 signatures, row = point index (rules: mvr_cloud_fpfh in mvr_hip.h).  A point
+        with a non-finite coordinate or normal gets a NaN row.  Returns the signatures, or (fpfh[, spfh][, neighbor_count])
+        with the return_* options: spfh = the intermediate (n, 33) simplified histograms, neighbor_count = one uint32 per
+        point, the point itself included."""
+        n = self.size(slot)
+        p = FpfhParams(float(radius), int(bool(fma)))
+        out = np.empty((n, 3 * FPFH_BINS), np.float32)
+        sp = np.empty((n, 3 * FPFH_BINS), np.float32) if return_spfh else None
+        cnt = np.empty(n, np.uint32) if return_counts else None
+        _chk(_lib.mvr_cloud_fpfh(self._h, int(slot), C.byref(p), _p(out, C.c_float), _p(sp, C.c_float) if return_spfh else None,
+                                 _p(cnt, C.c_uint32) if return_counts else None), self._h)
+        res = [out]
+        if return_spfh:
+            res.append(sp)
+        if return_counts:
+            res.append(cnt)
+        return res[0] if len(res) == 1 else tuple(res)
 
     # ---- target sharding over ranks (sequential mode): see seq.py
     def set_global_base(self, slot, global_begin):

@@ -1,0 +1,223 @@
+// csrc/mvr_fpfh.hip -- pcl::FPFHEstimation (radius search, the cloud its own search surface) on the GPU (gfx950); the rules F1-F8
+// are written next to mvr_cloud_fpfh in mvr_hip.h.
+//
+// One thread per query, in the order of the cloud's model grid (ensure_model_grid; the helpers of mvr_knn_walk.h), so the 64
+// lanes of a wave are neighbours on the surface and walk the same cells.  Every table a walk reads lies in GRID order, so a
+// neighbour found at grid position j has its normal and its SPFH row at j and the neighbours of one cell are consecutive rows:
+//   1. fpfh_normals_kernel copies the slot's normals from index order to grid order; w = 1 marks a valid point (finite
+//      coordinates and a finite normal), w = 0 an invalid one, which every later walk skips.
+//   2. fpfh_spfh_kernel: the ball walk (knn_ball_walk) computes the three f32 pair features of every neighbour and counts them
+//      into 3 x 11 bins.  The bin index is a runtime value, and a runtime-indexed private array lives in scratch memory
+//      (mvr_knn.hip), so the 33 u32 counters of a thread lie in LDS as hist[bin][thread]: lane t reads and writes the address
+//      bin * 256 + t, which is bank t mod 32 whatever its bin -- no two lanes of a 32-lane group share a bank -- and the
+//      counters are private, so plain read-modify-write is enough.  33 KiB per block of 256.  The row, scaled by
+//      100 / (n_i - 1), is written at the query's grid position.
+//   3. fpfh_weight_kernel: the same walk; per neighbour the 33 floats of its SPFH row times 1 / d2 (f32), added in f64 to
+//      33 bin and 3 block sums that are registers (compile-time indices).  The signature is written by source index.
+//   4. fpfh_rows_kernel moves the SPFH table from grid order to index order when the caller asked for it.
+// No atomics and a fixed walk order: bit-identical from run to run on one grid.  Compiled with -ffp-contract=off (every f32
+// operation of the pair features is rounded as written).
+#include <cmath>
+#include <cstring>
+
+#include "mvr_internal.h"
+#include "mvr_knn_walk.h"
+
+namespace mvr {
+namespace {
+
+constexpr int kFpfhThreads = kKnnThreads;
+constexpr int kBins = MVR_FPFH_BINS, kRow = 3 * MVR_FPFH_BINS;
+
+struct FpfhArgs {
+  KnnSlot S;                       // the cloud searched against itself (nrm / curv / oidx / od2 unused)
+  const float4 *src_nrm;           // the slot's normals, by index
+  float4 *gn;                      // normals by grid position, w = 1 for a valid point, else 0
+  float *spfh;                     // [n][33] by grid position
+  float *out;                      // [n][33] by index: the signature
+  uint32_t *count;                 // n_i by index
+  float r2;
+};
+
+__device__ __forceinline__ float dot3(const float ax, const float ay, const float az, const float bx, const float by, const float bz)
+{
+  return (ax * bx + ay * by) + az * bz;
+}
+
+// F4: the bin of a scaled coordinate, clamped to 0..10 (a NaN goes to 0)
+__device__ __forceinline__ int fpfh_bin(const double x) { return (int)fmin(fmax(floor((double)kBins * x), 0.0), (double)(kBins - 1)); }
+
+__global__ void __launch_bounds__(kFpfhThreads) fpfh_normals_kernel(FpfhArgs a)
+{
+  const KnnSlot &S = a.S;
+  const uint32_t pos = blockIdx.x * kFpfhThreads + threadIdx.x;
+  if (pos >= S.nq) return;
+  const float4 p = S.qs[pos];
+  const float4 n = a.src_nrm[S.q_by_pos ? pos : __float_as_uint(p.w)];
+  const bool ok = finite3(p) && finite3(n);
+  a.gn[pos] = make_float4(n.x, n.y, n.z, ok ? 1.f : 0.f);
+}
+
+template <bool FMA>
+__global__ void __launch_bounds__(kFpfhThreads) fpfh_spfh_kernel(FpfhArgs a)
+{
+  __shared__ uint32_t hist[kRow * kFpfhThreads];      // [bin][thread]: private counters, every lane on its own bank
+  const KnnSlot &S = a.S;
+  const uint32_t tid = threadIdx.x, pos = blockIdx.x * kFpfhThreads + tid;
+  if (pos >= S.nq) return;
+  const float4 q = S.qs[pos];
+  const uint32_t qi = S.q_by_pos ? pos : __float_as_uint(q.w);
+  const float4 ni = a.gn[pos];
+  float *row = a.spfh + (size_t)pos * kRow;
+  if (ni.w == 0.f) {                                  // F1 (an invalid query walks nothing)
+#pragma unroll
+    for (int k = 0; k < kRow; ++k) row[k] = __builtin_nanf("");
+    a.count[qi] = 0u;
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < kRow; ++k) hist[k * kFpfhThreads + tid] = 0u;
+  uint32_t n = 0;
+  const float d_pi = (float)(1.0 / (2.0 * M_PI));
+  knn_ball_walk<FMA>(S, q, a.r2, [&](const float4 p, const uint32_t j) {
+    const float4 nj = a.gn[j];
+    if (nj.w == 0.f) return;
+    ++n;
+    if (j == pos) return;
+    // F3
+    float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+    const float f4 = sqrtf(dot3(dx, dy, dz, dx, dy, dz));
+    if (f4 == 0.f) return;
+    const float a1 = dot3(ni.x, ni.y, ni.z, dx, dy, dz) / f4, a2 = dot3(nj.x, nj.y, nj.z, dx, dy, dz) / f4;
+    const bool swap = fabsf(a1) < fabsf(a2);
+    const float n1x = swap ? nj.x : ni.x, n1y = swap ? nj.y : ni.y, n1z = swap ? nj.z : ni.z;
+    const float n2x = swap ? ni.x : nj.x, n2y = swap ? ni.y : nj.y, n2z = swap ? ni.z : nj.z;
+    const float f3 = swap ? -a2 : a1;
+    if (swap) { dx = -dx; dy = -dy; dz = -dz; }
+    float vx = dy * n1z - dz * n1y, vy = dz * n1x - dx * n1z, vz = dx * n1y - dy * n1x;
+    const float vn = sqrtf(dot3(vx, vy, vz, vx, vy, vz));
+    if (vn == 0.f) return;
+    vx /= vn; vy /= vn; vz /= vn;
+    const float wx = n1y * vz - n1z * vy, wy = n1z * vx - n1x * vz, wz = n1x * vy - n1y * vx;
+    const float f2 = dot3(vx, vy, vz, n2x, n2y, n2z);
+    const float f1 = atan2f(dot3(wx, wy, wz, n2x, n2y, n2z), dot3(n1x, n1y, n1z, n2x, n2y, n2z));
+    // F4, F5
+    const int b1 = fpfh_bin(((double)f1 + M_PI) * (double)d_pi);
+    const int b2 = fpfh_bin(((double)f2 + 1.0) * 0.5);
+    const int b3 = fpfh_bin(((double)f3 + 1.0) * 0.5);
+    hist[b1 * kFpfhThreads + tid] += 1u;
+    hist[(kBins + b2) * kFpfhThreads + tid] += 1u;
+    hist[(2 * kBins + b3) * kFpfhThreads + tid] += 1u;
+  });
+  const float scale = n > 1u ? 100.0f / (float)(n - 1u) : 0.f;
+#pragma unroll
+  for (int k = 0; k < kRow; ++k) row[k] = (float)hist[k * kFpfhThreads + tid] * scale;
+  a.count[qi] = n;
+}
+
+template <bool FMA>
+__global__ void __launch_bounds__(kFpfhThreads) fpfh_weight_kernel(FpfhArgs a)
+{
+  const KnnSlot &S = a.S;
+  const uint32_t pos = blockIdx.x * kFpfhThreads + threadIdx.x;
+  if (pos >= S.nq) return;
+  const float4 q = S.qs[pos];
+  const uint32_t qi = S.q_by_pos ? pos : __float_as_uint(q.w);
+  float *out = a.out + (size_t)qi * kRow;
+  if (a.gn[pos].w == 0.f) {
+#pragma unroll
+    for (int k = 0; k < kRow; ++k) out[k] = __builtin_nanf("");
+    return;
+  }
+  double acc[kRow], sum[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int k = 0; k < kRow; ++k) acc[k] = 0.0;
+  knn_ball_walk<FMA>(S, q, a.r2, [&](const float4 p, const uint32_t j) {
+    if (a.gn[j].w == 0.f) return;
+    const float d2 = knn_dist2<FMA>(p, q);
+    if (d2 == 0.f) return;                            // (the query itself among them)
+    const float w = 1.0f / d2;
+    if (!isfinite(w)) return;
+    const float *r = a.spfh + (size_t)j * kRow;
+#pragma unroll
+    for (int k = 0; k < kRow; ++k) {
+      const double val = (double)(r[k] * w);
+      acc[k] += val;
+      sum[k / kBins] += val;
+    }
+  });
+#pragma unroll
+  for (int k = 0; k < kRow; ++k) {
+    const double s = sum[k / kBins];
+    out[k] = s != 0.0 ? (float)(acc[k] * (100.0 / s)) : 0.f;
+  }
+}
+
+// the SPFH table from grid order to index order: one thread per float
+__global__ void __launch_bounds__(kFpfhThreads) fpfh_rows_kernel(FpfhArgs a, float *__restrict__ by_index)
+{
+  const KnnSlot &S = a.S;
+  const size_t e = (size_t)blockIdx.x * kFpfhThreads + threadIdx.x;
+  if (e >= (size_t)S.nq * kRow) return;
+  const uint32_t pos = (uint32_t)(e / kRow), k = (uint32_t)(e % kRow);
+  const uint32_t qi = S.q_by_pos ? pos : __float_as_uint(S.qs[pos].w);
+  by_index[(size_t)qi * kRow + k] = a.spfh[e];
+}
+
+int fpfh_cloud(Ctx *c, Cloud &cl, const mvr_fpfh_params &p, float *fpfh, float *spfh, uint32_t *neighbor_count)
+{
+  const size_t n = cl.n;
+  if (!cl.has_normals && n > 0) return set_error(c, MVR_E_ARG, "fpfh: the slot has no normals");
+  if (int rc = knn_cloud_ok(c, cl, "fpfh")) return rc;
+  if (n == 0) return MVR_OK;
+  MVR_MAY_BLOCK(c, "fpfh reads back");
+  FpfhArgs a{};
+  if (int rc = fill_target(c, cl, a.S)) return rc;      // (before the arena is carved: the grid build uses the context's buffers)
+  fill_queries(cl, a.S);
+  const size_t m = n * (size_t)kRow;
+  Carver plan;
+  plan.plan<float4>(n); plan.plan<float>(m); plan.plan<float>(m); plan.plan<uint32_t>(n); plan.plan<float>(spfh ? m : 1);
+  if (int rc = ensure(c, c->dn_arena, c->dn_arena_cap, plan.off + 256)) return rc;
+  Carver s; s.base = c->dn_arena;
+  a.src_nrm = cl.nrm;
+  a.gn = s.take<float4>(n);
+  a.spfh = s.take<float>(m);
+  a.out = s.take<float>(m);
+  a.count = s.take<uint32_t>(n);
+  float *rows = s.take<float>(spfh ? m : 1);
+  a.r2 = clamp_r2(p.radius);
+  const dim3 grid(blocks_for(n, kFpfhThreads)), block(kFpfhThreads);
+  hipLaunchKernelGGL(fpfh_normals_kernel, grid, block, 0, c->stream, a);
+  MVR_HIP_TRY(c, hipGetLastError());
+  if (p.fma_dist) hipLaunchKernelGGL(fpfh_spfh_kernel<true>, grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL(fpfh_spfh_kernel<false>, grid, block, 0, c->stream, a);
+  MVR_HIP_TRY(c, hipGetLastError());
+  if (p.fma_dist) hipLaunchKernelGGL(fpfh_weight_kernel<true>, grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL(fpfh_weight_kernel<false>, grid, block, 0, c->stream, a);
+  MVR_HIP_TRY(c, hipGetLastError());
+  if (spfh) {
+    hipLaunchKernelGGL(fpfh_rows_kernel, dim3(blocks_for(m, kFpfhThreads)), block, 0, c->stream, a, rows);
+    MVR_HIP_TRY(c, hipGetLastError());
+    MVR_HIP_TRY(c, hipMemcpyAsync(spfh, rows, m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (fpfh) MVR_HIP_TRY(c, hipMemcpyAsync(fpfh, a.out, m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (neighbor_count) MVR_HIP_TRY(c, hipMemcpyAsync(neighbor_count, a.count, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));      // the host arrays are complete on return, and the arena is free again
+  return MVR_OK;
+}
+
+}  // namespace
+}  // namespace mvr
+
+using namespace mvr;
+
+#define API __attribute__((visibility("default")))
+
+API int mvr_cloud_fpfh(mvr_ctx *ctx, int slot, const mvr_fpfh_params *p, float *fpfh, float *spfh, uint32_t *neighbor_count)
+{
+  if (!ctx || !p || !knn_slot_ok(slot)) return MVR_E_ARG;
+  if (!(std::isfinite(p->radius) && p->radius > 0.0)) return MVR_E_ARG;
+  Ctx *c = reinterpret_cast<Ctx *>(ctx);
+  MVR_HIP_TRY(c, hipSetDevice(c->device));
+  return fpfh_cloud(c, c->slots[slot], *p, fpfh, spfh, neighbor_count);
+}

@@ -1,6 +1,6 @@
 // csrc/mvr_knn_walk.h -- the walks of a cloud's model grid around a query, each written once, for the kernels that search a
 // neighbourhood (mvr_knn.hip: k-NN lists and normals; mvr_outlier.hip: mean neighbour distances and neighbour counts;
-// mvr_mls.hip: moving least squares):
+// mvr_mls.hip: moving least squares; mvr_fpfh.hip: FPFH descriptors):
 //   * knn_shell_walk: shells of cells outward from the query's cell until a visitor's k-best list is full and every unvisited
 //     cell lies beyond it (the f64 bound of knn_unvisited_bound);
 //   * knn_ball_walk: every point within a radius of the query, in grid order.
