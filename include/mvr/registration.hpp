@@ -572,6 +572,102 @@ class FPFHEstimation {
   double radius_ = 0.0;
 };
 
+// ---------------------------------------------------------------- sample-consensus alignment
+// pcl::SampleConsensusPrerejective<PointSource, PointTarget, FeatureT> (registration/sample_consensus_prerejective.h):
+// setInputSource, setInputTarget, setSourceFeatures, setTargetFeatures, setMaximumIterations, setNumberOfSamples,
+// setCorrespondenceRandomness, setSimilarityThreshold, setMaxCorrespondenceDistance, setInlierFraction, align, hasConverged,
+// getFinalTransformation, getFitnessScore, getInliers.  Semantics: mvr_align_prerejective (mvr_hip.h) -- one call per align().
+// PCL draws with rand(); here the result is a pure function of the inputs and of setSeed (ours).  Defaults are PCL's (3
+// samples, randomness 2, similarity 0.9, inlier fraction 0); an inlier fraction of 0 -- which the C-ABI refuses -- is sent as
+// the smallest positive double, the same test.  As PCL, a missing cloud or feature set, or a feature set of another size than
+// its cloud, prints an error and leaves `output` empty and hasConverged() false.  getInliers() lists, ascending, the source
+// points within the correspondence distance of the target under the final pose (one call of mvr_nn).
+template <typename PointSource, typename PointTarget, typename FeatureT = FPFHSignature33>
+class SampleConsensusPrerejective {
+ public:
+  typedef PointCloud<PointSource> PointCloudSource;
+  typedef PointCloud<PointTarget> PointCloudTarget;
+  typedef typename PointCloudSource::Ptr PointCloudSourcePtr;
+  typedef typename PointCloudTarget::Ptr PointCloudTargetPtr;
+  typedef PointCloud<FeatureT> FeatureCloud;
+  typedef typename FeatureCloud::ConstPtr FeatureCloudConstPtr;
+  typedef Matrix4f Matrix4;
+
+  SampleConsensusPrerejective()
+  {
+    p_ = mvr_prerej_params();
+    p_.max_iterations = 10; p_.nr_samples = 3; p_.k = 2; p_.similarity = 0.9; p_.max_dist = std::sqrt(DBL_MAX); p_.inlier_fraction = 0.0;
+  }
+  void setInputSource(const PointCloudSourcePtr &c) { input_ = c; }
+  void setInputTarget(const PointCloudTargetPtr &c) { target_ = c; }
+  void setSourceFeatures(const FeatureCloudConstPtr &f) { sfeat_ = f; }
+  void setTargetFeatures(const FeatureCloudConstPtr &f) { tfeat_ = f; }
+  void setMaximumIterations(int n) { p_.max_iterations = n; }
+  int getMaximumIterations() const { return p_.max_iterations; }
+  void setNumberOfSamples(int n) { p_.nr_samples = n; }
+  int getNumberOfSamples() const { return p_.nr_samples; }
+  void setCorrespondenceRandomness(int k) { p_.k = k; }
+  int getCorrespondenceRandomness() const { return p_.k; }
+  void setSimilarityThreshold(float s) { p_.similarity = s; }
+  float getSimilarityThreshold() const { return (float)p_.similarity; }
+  void setMaxCorrespondenceDistance(double d) { p_.max_dist = d; }
+  double getMaxCorrespondenceDistance() const { return p_.max_dist; }
+  void setInlierFraction(float f) { p_.inlier_fraction = f; }
+  float getInlierFraction() const { return (float)p_.inlier_fraction; }
+  void setSeed(uint64_t seed) { p_.seed = seed; }
+  uint64_t getSeed() const { return p_.seed; }
+
+  void align(PointCloudSource &output) { align(output, Matrix4::Identity(), false); }
+  void align(PointCloudSource &output, const Matrix4 &guess) { align(output, guess, true); }
+
+  bool hasConverged() const { return result_.converged != 0; }
+  Matrix4 getFinalTransformation() const { return final_; }
+  const mvr_prerej_result &getResult() const { return result_; }
+  // the mean squared distance of the inliers of the final pose (PCL's getFitness; DBL_MAX without a pose)
+  double getFitnessScore() const { return result_.error; }
+  const std::vector<int> &getInliers() const { return inliers_; }
+
+ private:
+  void align(PointCloudSource &output, const Matrix4 &guess, bool with_guess)
+  {
+    static_assert(sizeof(FeatureT) == sizeof(float) * 3 * MVR_FPFH_BINS, "a 33-float signature expected");
+    output.clear(); inliers_.clear();
+    result_ = mvr_prerej_result(); result_.best_iteration = -1; result_.error = DBL_MAX;
+    final_ = with_guess ? guess : Matrix4::Identity();
+    if (!input_ || !target_) { std::fprintf(stderr, "[pcl::SampleConsensusPrerejective::align] No input source or target was given!\n"); return; }
+    if (!sfeat_ || !tfeat_ || sfeat_->size() != input_->size() || tfeat_->size() != target_->size()) {
+      std::fprintf(stderr, "[pcl::SampleConsensusPrerejective::align] The source and target features must be set, one per point of their cloud!\n");
+      return;
+    }
+    Device &d = Device::instance();
+    d.upload(src_.s, *input_);
+    d.upload(tgt_.s, *target_);
+    mvr_prerej_params p = p_;
+    if (p.inlier_fraction == 0.0) p.inlier_fraction = DBL_MIN;
+    static const float none[33] = {0};
+    d.check(mvr_align_prerejective(d.ctx(), src_.s, tgt_.s, sfeat_->empty() ? none : sfeat_->points[0].histogram,
+                                   tfeat_->empty() ? none : tfeat_->points[0].histogram, &p, with_guess ? guess.data() : nullptr, &result_, nullptr),
+            "mvr_align_prerejective");
+    final_ = Matrix4(result_.T);
+    d.check(mvr_cloud_transform_f32(d.ctx(), out_.s, src_.s, result_.T), "mvr_cloud_transform_f32");
+    d.download(out_.s, output);
+    if (result_.converged && !input_->empty()) {
+      std::vector<float> d2(input_->size());
+      d.check(mvr_nn(d.ctx(), out_.s, tgt_.s, p.fma_dist, nullptr, d2.data()), "mvr_nn");
+      for (size_t i = 0; i < d2.size(); ++i) if ((double)d2[i] < p.max_dist * p.max_dist) inliers_.push_back((int)i);
+    }
+  }
+
+  mvr_prerej_params p_;
+  mvr_prerej_result result_ = mvr_prerej_result();
+  PointCloudSourcePtr input_;
+  PointCloudTargetPtr target_;
+  FeatureCloudConstPtr sfeat_, tfeat_;
+  Matrix4 final_;
+  std::vector<int> inliers_;
+  SlotGuard src_, tgt_, out_;
+};
+
 namespace registration {
 
 // ------------------------------------------------- CorrespondenceEstimation

@@ -311,6 +311,35 @@ class ScanCloud {
     return true;
   }
 
+  // EXTENSION (pcl::SampleConsensusPrerejective on the raw points, on the GPU; rules: mvr_align_prerejective in mvr_hip.h): the
+  // coarse pose of THIS scan onto `target` for a pair without a turntable prior -- computeFPFH of both scans (both need their
+  // normals in `rich`) at feature_radius, then the aligner.  On success `pose` is the scan's pose in the scene's own type:
+  // setMatrix(pose * target.getMatrix()) puts the scan where registrationICPDevice can take over.  false (pose untouched): no
+  // normals, a bad radius, or the aligner found no pose that reaches inlier_fraction; `result` (optional) says which.
+  struct PrerejectiveParams {
+    double feature_radius = 0.0;
+    mvr_prerej_params align;
+    PrerejectiveParams() { align = mvr_prerej_params(); align.max_iterations = 10; align.nr_samples = 3; align.k = 2; align.similarity = 0.9; align.inlier_fraction = 0.25; }
+  };
+  bool alignPrerejective(const ScanCloud &target, const PrerejectiveParams &params, RowMatrixd &pose, mvr_prerej_result *result = nullptr) const
+  {
+    std::vector<FPFHSignature33> sf, tf;
+    if (result) { *result = mvr_prerej_result(); result->best_iteration = -1; result->error = DBL_MAX; }
+    if (!computeFPFH(params.feature_radius, sf) || !target.computeFPFH(params.feature_radius, tf)) return false;
+    Device &d = Device::instance();
+    SlotGuard s, t;
+    d.upload(s.s, points);
+    d.upload(t.s, target.points);
+    static const float none[33] = {0};
+    mvr_prerej_result res;
+    d.check(mvr_align_prerejective(d.ctx(), s.s, t.s, sf.empty() ? none : sf[0].histogram, tf.empty() ? none : tf[0].histogram, &params.align,
+                                   nullptr, &res, nullptr), "mvr_align_prerejective");
+    if (result) *result = res;
+    if (!res.converged) return false;
+    pose = PclMatrixCaster<RowMatrixd>(Matrix4f(res.T));
+    return true;
+  }
+
   // point_cloud.cpp:305-326 / :328-347 -- `transformation.txt`: the column-vector
   // 4x4 printed row by row (matrix(j,i), i outer), "%lf " per element, one row per
   // line.  6 decimals: poses round-trip to 1e-6 only.

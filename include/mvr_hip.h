@@ -396,8 +396,8 @@ int  mvr_cloud_mls(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_mls_param
  *      because a pipelined run is in flight.  An empty cloud is MVR_OK.  All three outputs NULL: MVR_OK after the work.
  *  F8. Bit-identical from run to run on one grid: one thread per query, one fixed walk order, no floating-point atomics.
  * The slot is not modified and no descriptor stays on the device after the call.
- * Out of scope: the k-neighbour mode (setKSearch), setSearchSurface / setIndices, PFH, and the matching and
- * sample-consensus alignment that consume the signatures. */
+ * Out of scope: the k-neighbour mode (setKSearch), setSearchSurface / setIndices and PFH.  The matching and the
+ * sample-consensus alignment that consume the signatures follow below (mvr_feature_knn, mvr_align_prerejective). */
 #define MVR_FPFH_BINS 11            /* per feature; a signature is 3 * 11 = 33 floats (pcl::FPFHSignature33) */
 typedef struct {
   double radius;        /* setRadiusSearch: finite, > 0 */
@@ -407,6 +407,94 @@ int  mvr_cloud_fpfh(mvr_ctx *ctx, int slot, const mvr_fpfh_params *p,
                     float *fpfh,              /* host, n * 33, row = point index; may be NULL   */
                     float *spfh,              /* optional host, n * 33: the intermediate SPFH   */
                     uint32_t *neighbor_count  /* optional host, n: n_i of rule F2               */);
+
+/* ---- feature matching and coarse alignment (EXTENSION: pcl::SampleConsensusPrerejective) -------------------------------
+ * What brings a scan without a pose prior within the capture range of mvr_icp_align.  The reference pins no PCL version and
+ * PCL was not at hand: the models are pcl/registration/impl/sample_consensus_prerejective.hpp,
+ * correspondence_rejection_poly.hpp (thresholdPolygon) and pcl::KdTreeFLANN<FPFHSignature33> with flann::L2_Simple<float>, as
+ * published; deviations are marked.
+ *
+ * mvr_feature_knn: exact k nearest neighbours in feature space.  q / t: host arrays, row = point, `dim` floats per row.
+ * dim must be 33 (3 * MVR_FPFH_BINS; the field is there for later descriptors), 1 <= k <= MVR_MAX_KNN, else MVR_E_ARG
+ * before any GPU work.  idx / d2: host, nq * k, row-major (either may be NULL).
+ *  M1. Distance, FLANN's L2_Simple: acc = 0; for b = 0..32 { diff = q[b] - t[b]; acc = acc + diff * diff; } -- all f32,
+ *      every operation rounded, in this order, never contracted.  There is no fma variant.
+ *  M2. Order: the k smallest under the key (d2 bits, index), ascending; ties go to the lower index -- the key of mvr_knn.
+ *  M3. Non-finite rows: a target row with a non-finite component is never listed, and neither is a pair whose d2 is not
+ *      finite; a non-finite query row gets UINT32_MAX / +inf in all k entries, and so does the tail of a list beyond the
+ *      listable targets (rules N1-N3 carried over).
+ *  The target is split over blocks as well as the queries (tune key "feat_split", 0 = by the launch size); the partial
+ *  lists are merged under the same total order, so the result does not depend on the split.
+ *
+ * mvr_pose_scores: inliers and error of `count` poses of src_slot against tgt_slot in one call.  T: count * 16 floats, each
+ * a column-major 4 x 4.  inliers / error: host, `count` entries (either may be NULL).
+ *  S1. For pose h and source point i: p' = mvr_cloud_transform_f32's arithmetic on p_i; its exact nearest target point under
+ *      the library's f32 distance (fma_dist as everywhere); i is an inlier iff (double)d2 < max_dist * max_dist -- strictly, as
+ *      in PCL's getFitness.  A non-finite p', a non-finite target point and an empty target give no inlier.
+ *  S2. inliers[h] is the exact count; error[h] = (sum of the inliers' (double)d2) / count, DBL_MAX when the count is 0.  The
+ *      sum is f64 in a fixed order: one partial per block of 256 source points in the source's grid order (a fixed tree inside
+ *      the block), the partials added in ascending order.  No tune key changes it ("score_chunk": poses per launch).
+ *  Neither slot is modified and no posed copy is materialised.  MVR_E_ARG for a NULL ctx, a bad slot, a NULL T with count > 0,
+ *  or a max_dist that is not finite and > 0.
+ *
+ * mvr_align_prerejective: pcl::SampleConsensusPrerejective::computeTransformation.  src_feat / tgt_feat: host, 33 floats per
+ * point of the slot.  DEVIATION: PCL draws with rand(); this is a pure function of its arguments (seed included), bit for bit.
+ *  A1. Eligible source points: finite coordinates and 33 finite features, in ascending index; ne of them.  ne < nr_samples:
+ *      MVR_OK with converged = 0 and nothing scored (every traced iteration has status 2).
+ *  A2. Draws, arithmetic mod 2^64, G = 0x9E3779B97F4A7C15:  mix(x): z = x; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *      z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31.   draw(i, j, m) = ((mix(seed + G * (16 i + j + 1)) >> 32) * m) >> 32.
+ *      Sample j of iteration i: r = draw(i, j, ne - j); for every earlier sample POSITION c of this iteration, in ascending
+ *      order of c: if (r >= c) ++r -- distinct samples without rejection; the source point is eligible[r].
+ *  A3. Matches: the table of rule M, k entries, from the eligible source rows into tgt_feat.  kk = the non-empty entries of
+ *      sample j's list; the match is entry draw(i, 8 + j, kk).  kk = 0 for any sample: status 2 (its tgt entry UINT32_MAX).
+ *  A4. Polygon (thresholdPolygon) over the edges (j, (j + 1) % nr_samples): ds / dt = the library's f32 d2 between the two
+ *      source points / the two matches (fma_dist); sim = ds < dt ? ds / dt : dt / ds in f32; the edge passes iff
+ *      sim >= (float)(similarity * similarity) (a NaN, 0 / 0 included, fails).  A failing edge: status 0, counted in `rejected`.
+ *  A5. Pose: the estimator of mvr_icp_align -- f64 means and covariance of the nr_samples pairs in sample order, the host
+ *      SVD (Eigen::umeyama without scaling), cast to f32.
+ *  A6. Score: rule S over ALL points of the source slot; fraction = inliers / (double)n_src (the slot's size, as PCL).  A
+ *      pose is taken iff fraction >= inlier_fraction && error < lowest, poses visited in iteration order, lowest = DBL_MAX
+ *      at the start.  A non-NULL guess is scored first by the same test and recorded as best_iteration = -1.
+ *  Result: converged = a pose was taken; T = that pose (none: the guess, else the identity, with inliers = 0 and
+ *  error = DBL_MAX, best_iteration = -1); rejected / scored = iterations with status 0 / 1.  trace (optional, max_iterations
+ *  entries): per iteration its status, samples, matches and -- status 1 -- inliers, error and T (otherwise zeros).
+ *  MVR_E_ARG, before any GPU work, for a NULL ctx / params / result / feature table, a bad slot, max_iterations < 0,
+ *  nr_samples outside 3..8, k outside 1..MVR_MAX_KNN, similarity outside [0, 1), max_dist not finite and > 0, or
+ *  inlier_fraction outside (0, 1].  The draws, matches and polygon tests of all iterations are one launch; the surviving poses
+ *  are solved on the host and scored through the kernel of mvr_pose_scores.
+ * Out of scope: SampleConsensusInitialAlignment, CorrespondenceRejectorSampleConsensus, descriptors of other lengths. */
+int  mvr_feature_knn(mvr_ctx *ctx, const float *q, size_t nq, const float *t, size_t nt, int dim, int k,
+                     uint32_t *idx /* nq * k */, float *d2 /* nq * k */);
+int  mvr_pose_scores(mvr_ctx *ctx, int src_slot, int tgt_slot, const float *T /* count * 16, column-major */, size_t count,
+                     double max_dist, int fma_dist, uint32_t *inliers /* count */, double *error /* count */);
+#define MVR_PREREJ_MAX_SAMPLES 8
+typedef struct {
+  int      max_iterations;   /* setMaximumIterations: >= 0                                  */
+  int      nr_samples;       /* setNumberOfSamples: 3..8                                    */
+  int      k;                /* setCorrespondenceRandomness: 1..MVR_MAX_KNN                 */
+  double   similarity;       /* setSimilarityThreshold: [0, 1)                              */
+  double   max_dist;         /* setMaxCorrespondenceDistance: finite, > 0                   */
+  double   inlier_fraction;  /* setInlierFraction: (0, 1]                                   */
+  uint64_t seed;             /* ours: PCL draws with rand()                                 */
+  int      fma_dist;
+} mvr_prerej_params;
+typedef struct {
+  int      converged;
+  int      best_iteration;   /* -1: the guess (or, without converged, nothing)              */
+  uint32_t inliers;
+  double   error;
+  uint32_t rejected, scored;
+  float    T[16];
+} mvr_prerej_result;
+typedef struct {
+  int      status;           /* 0 polygon-rejected, 1 scored, 2 no match                    */
+  uint32_t src[MVR_PREREJ_MAX_SAMPLES], tgt[MVR_PREREJ_MAX_SAMPLES], inliers;
+  double   error;
+  float    T[16];
+} mvr_prerej_trace;
+int  mvr_align_prerejective(mvr_ctx *ctx, int src_slot, int tgt_slot, const float *src_feat, const float *tgt_feat,
+                            const mvr_prerej_params *params, const float *guess /* optional, 16 */,
+                            mvr_prerej_result *result, mvr_prerej_trace *trace /* optional, max_iterations */);
 
 /* CorrespondenceEstimation::determineReciprocalCorrespondences(corrs, max_d)
  * (registrator.cpp:496-502, 644-649); reciprocal = 0 gives
@@ -741,7 +829,9 @@ enum { MVR_K_NN = 0, MVR_K_REDUCE = 1, MVR_K_XFORM = 2, MVR_K_GLUE = 3,
  * same permutations), "seed_delta_um" (forward start bounds from the previous distance + the clouds' motion while that is below
  * this many micrometres; 0, default: from the old match's coordinates), "rim_cert_um" (rim certificates with this margin; 0,
  * default: off), "pipeline_multi_rank" (1: passes with a collective over more than one rank may be queued ahead of their poses
- * too; 0, default, until a recorded two-GPU run).
+ * too; 0, default, until a recorded two-GPU run);
+ * feature matching and pose scoring: "feat_split" (blocks the target of mvr_feature_knn is split over, 1..64; 0, default: by the
+ * launch size), "score_chunk" (poses per launch of mvr_pose_scores, default 256).
  * Results never depend on them. */
 int  mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value);
 /* wall milliseconds of every pass of the LAST mvr_ring_run / mvr_ring_run_sharded on this context (from the end of the
@@ -750,7 +840,8 @@ int  mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value);
 int  mvr_ctx_pass_log(mvr_ctx *ctx, double *ms, int cap, int *n);
 /* counters of the context, by name: "piped_passes" (passes of mvr_ring_run / mvr_ring_run_sharded whose launch chain was
  * enqueued ahead of their poses, see "pipeline"), "fused_passes" (fused pair batches run so far), "blocking_events"
- * (times the library waited for its stream or re-allocated a buffer: a pass without any is in steady state) */
+ * (times the library waited for its stream or re-allocated a buffer: a pass without any is in steady state),
+ * "prerej_match_ms" / "prerej_hypotheses_ms" / "prerej_score_ms" (wall milliseconds of the last mvr_align_prerejective by phase) */
 int  mvr_ctx_stat(mvr_ctx *ctx, const char *key, double *value);
 /* diagnostics: the ordering of the cloud in `slot` (sorted position -> original index); *n = its length (0: none yet) */
 int  mvr_debug_order(mvr_ctx *ctx, int slot, uint32_t *perm, size_t cap, size_t *n);

@@ -134,6 +134,26 @@ class FpfhParams(C.Structure):
 
 
 FPFH_BINS = 11          # MVR_FPFH_BINS: a signature is 3 * 11 = 33 floats
+PREREJ_MAX_SAMPLES = 8  # MVR_PREREJ_MAX_SAMPLES
+
+
+class PrerejParams(C.Structure):
+    """mvr_prerej_params"""
+    _fields_ = [("max_iterations", C.c_int), ("nr_samples", C.c_int), ("k", C.c_int), ("similarity", C.c_double),
+                ("max_dist", C.c_double), ("inlier_fraction", C.c_double), ("seed", C.c_uint64), ("fma_dist", C.c_int)]
+
+
+class PrerejResult(C.Structure):
+    """mvr_prerej_result"""
+    _fields_ = [("converged", C.c_int), ("best_iteration", C.c_int), ("inliers", C.c_uint32), ("error", C.c_double),
+                ("rejected", C.c_uint32), ("scored", C.c_uint32), ("T", C.c_float * 16)]
+
+
+class PrerejTrace(C.Structure):
+    """mvr_prerej_trace"""
+    _fields_ = [("status", C.c_int), ("src", C.c_uint32 * PREREJ_MAX_SAMPLES), ("tgt", C.c_uint32 * PREREJ_MAX_SAMPLES),
+                ("inliers", C.c_uint32), ("error", C.c_double), ("T", C.c_float * 16)]
+
 
 _fp, _dp, _u32p, _i32p = (C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                           C.POINTER(C.c_int32))
@@ -161,6 +181,10 @@ SIGNATURES = {
     "mvr_cloud_radius_outlier_removal": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RorParams), C.POINTER(_sz), _u32p, _u32p]),
     "mvr_cloud_mls": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(MlsParams), C.POINTER(_sz), _u32p, _fp]),
     "mvr_cloud_fpfh": (C.c_int, [_vp, C.c_int, C.POINTER(FpfhParams), _fp, _fp, _u32p]),
+    "mvr_feature_knn": (C.c_int, [_vp, _fp, _sz, _fp, _sz, C.c_int, C.c_int, _u32p, _fp]),
+    "mvr_pose_scores": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _sz, C.c_double, C.c_int, _u32p, _dp]),
+    "mvr_align_prerejective": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, C.POINTER(PrerejParams), _fp, C.POINTER(PrerejResult),
+                                         C.POINTER(PrerejTrace)]),
     "mvr_cloud_set_global_base": (C.c_int, [_vp, C.c_int, _sz]),
     "mvr_cloud_append_range": (C.c_int, [_vp, C.c_int, C.c_int, _sz, _sz, _sz]),
     "mvr_nn_forward_keys": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp]),
@@ -670,6 +694,57 @@ class Context:
         if return_counts:
             res.append(cnt)
         return res[0] if len(res) == 1 else tuple(res)
+
+    def feature_knn(self, q, t, k):
+        """exact k nearest neighbours of every row of q among the rows of t in feature space (33 floats per row, FLANN's
+        L2_Simple in f32; rules M1-M3: mvr_feature_knn in mvr_hip.h): (idx[nq, k] uint32, d2[nq, k] float32), each row ascending
+        by (d2, index); UINT32_MAX / +inf for a non-finite query row and beyond the listable targets"""
+        q, t = np.ascontiguousarray(q, np.float32), np.ascontiguousarray(t, np.float32)
+        if q.ndim != 2 or t.ndim != 2 or q.shape[1] != t.shape[1]:
+            raise ValueError("q and t must be (n, dim) float32 tables of one dim")
+        idx, d2 = np.empty((len(q), k), np.uint32), np.empty((len(q), k), np.float32)
+        _chk(_lib.mvr_feature_knn(self._h, _p(q, C.c_float), len(q), _p(t, C.c_float), len(t), q.shape[1], int(k),
+                                  _p(idx, C.c_uint32), _p(d2, C.c_float)), self._h)
+        return idx, d2
+
+    def pose_scores(self, src, tgt, T, max_dist, fma=False):
+        """inliers and error of every pose in T ((count, 4, 4), math layout) of slot src against slot tgt (rules S1-S2:
+        mvr_pose_scores in mvr_hip.h): (inliers[count] uint32, error[count] float64; DBL_MAX where no point is an inlier)"""
+        T = np.asarray(T, np.float32).reshape(-1, 4, 4)
+        cm = np.ascontiguousarray(T.transpose(0, 2, 1)).reshape(-1, 16)
+        inl, err = np.empty(len(cm), np.uint32), np.empty(len(cm), np.float64)
+        _chk(_lib.mvr_pose_scores(self._h, int(src), int(tgt), _p(cm, C.c_float), len(cm), float(max_dist), int(bool(fma)),
+                                  _p(inl, C.c_uint32), _p(err, C.c_double)), self._h)
+        return inl, err
+
+    def align_prerejective(self, src, tgt, src_feat, tgt_feat, max_iterations=1000, nr_samples=3, k=2, similarity=0.9,
+                           max_dist=4.0, inlier_fraction=0.25, seed=0, fma=False, guess=None, return_trace=False):
+        """pcl::SampleConsensusPrerejective::align of slot src onto slot tgt from their (n, 33) descriptors (rules A1-A6:
+        mvr_align_prerejective in mvr_hip.h; k = setCorrespondenceRandomness).  A pure function of its arguments.  Returns a
+        dict(converged, best_iteration, inliers, error, rejected, scored, T (4, 4) float32), or (that, trace) with return_trace:
+        trace = dict(status[it], src[it, nr_samples], tgt[it, nr_samples], inliers[it], error[it], T[it, 4, 4])."""
+        sf, tf = np.ascontiguousarray(src_feat, np.float32), np.ascontiguousarray(tgt_feat, np.float32)
+        if sf.shape != (self.size(src), 3 * FPFH_BINS) or tf.shape != (self.size(tgt), 3 * FPFH_BINS):
+            raise ValueError("descriptors must be (n, 33) float32 tables, one row per point of the slot")
+        p = PrerejParams(int(max_iterations), int(nr_samples), int(k), float(similarity), float(max_dist), float(inlier_fraction),
+                         int(seed), int(bool(fma)))
+        g = to_cm(guess, np.float32) if guess is not None else None
+        res = PrerejResult()
+        tr = (PrerejTrace * max(int(max_iterations), 1))() if return_trace else None
+        _chk(_lib.mvr_align_prerejective(self._h, int(src), int(tgt), _p(sf, C.c_float), _p(tf, C.c_float), C.byref(p),
+                                         _p(g, C.c_float) if g is not None else None, C.byref(res), tr), self._h)
+        out = dict(converged=bool(res.converged), best_iteration=res.best_iteration, inliers=int(res.inliers), error=res.error,
+                   rejected=int(res.rejected), scored=int(res.scored), T=from_cm(np.array(res.T, np.float32)))
+        if not return_trace:
+            return out
+        dt = np.dtype([("status", np.int32), ("src", np.uint32, PREREJ_MAX_SAMPLES), ("tgt", np.uint32, PREREJ_MAX_SAMPLES),
+                       ("inliers", np.uint32), ("error", np.float64), ("T", np.float32, 16)], align=True)
+        assert dt.itemsize == C.sizeof(PrerejTrace)
+        a = np.frombuffer(tr, dtype=dt, count=max(int(max_iterations), 0)).copy()
+        trace = {k: np.ascontiguousarray(v) for k, v in dict(
+            status=a["status"], src=a["src"][:, :nr_samples], tgt=a["tgt"][:, :nr_samples], inliers=a["inliers"], error=a["error"],
+            T=a["T"].reshape(-1, 4, 4).transpose(0, 2, 1)).items()}
+        return out, trace
 
     # ---- target sharding over ranks (sequential mode): see seq.py
     def set_global_base(self, slot, global_begin):

@@ -2752,6 +2752,8 @@ API int mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value)
   else if (!std::strcmp(key, "inject_fail_pass")) { c->inject_fail_at = value; c->dist_pass = 0; }
   else if (!std::strcmp(key, "inject_stall_pass")) { c->inject_stall_at = value; c->dist_pass = 0; }
   else if (!std::strcmp(key, "pair_fused")) c->pair_fused = value != 0;
+  else if (!std::strcmp(key, "feat_split")) { if (value < 0 || value > 64) return MVR_E_ARG; c->feat_split = value; }
+  else if (!std::strcmp(key, "score_chunk")) { if (value < 1 || value > 65535) return MVR_E_ARG; c->score_chunk = value; }
   else if (!std::strcmp(key, "posed_refresh")) c->posed_refresh = value != 0;
   else if (!std::strcmp(key, "pair_groups")) { if (value < 1 || value > 8) return MVR_E_ARG; c->pair_groups = value; }
   else if (!std::strcmp(key, "inplace_ratio")) c->inplace_ratio = value;
@@ -2791,6 +2793,9 @@ API int mvr_ctx_stat(mvr_ctx *ctx, const char *key, double *value)
   else if (!std::strcmp(key, "lean_passes")) *value = (double)c->lean_passes;
   else if (!std::strcmp(key, "blocking_events")) *value = (double)c->blocking_events;
   else if (!std::strcmp(key, "pipeline")) *value = (double)c->pipeline;
+  else if (!std::strcmp(key, "prerej_match_ms")) *value = c->prerej_ms[0];
+  else if (!std::strcmp(key, "prerej_hypotheses_ms")) *value = c->prerej_ms[1];
+  else if (!std::strcmp(key, "prerej_score_ms")) *value = c->prerej_ms[2];
   else if (!std::strncmp(key, "stage_", 6) && c->stage_stat) {      // staged walk diagnostics: waves by outcome since grid_stage_stat was set
     unsigned long long h[64] = {0};
     std::vector<unsigned long long> raw(64 * 64);

@@ -313,6 +313,10 @@ struct Ctx {
   Ctx *parent = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   double *batch_table = nullptr; size_t batch_cap = 0;   // [pairs][32] staging of mvr_pair_moments2_batch
+  // feature matching and pose scoring (mvr_feature.hip): blocks a target is split over (0: by the launch size) and poses per
+  // scoring launch -- results never depend on either; wall milliseconds of the last mvr_align_prerejective by phase
+  int feat_split = 0, score_chunk = 256;
+  double prerej_ms[3] = {0.0, 0.0, 0.0};                 // matching, hypothesis generation, scoring
   char *dn_arena = nullptr; size_t dn_arena_cap = 0;     // scratch of mvr_cloud_denoise and mvr_cloud_voxel_grid (one buffer, carved per call)
   double *h_table = nullptr; size_t h_table_cap = 0;     // pinned host memory the final kernels of mvr_ring_step write straight into (zero-copy)
   // workspace of the fused batch (culled mode): forward keys of all pairs, reverse keys + flags, per-pair partial rows

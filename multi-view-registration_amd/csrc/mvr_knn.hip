@@ -54,15 +54,6 @@ __device__ __forceinline__ int knn_slot_of(const KnnBatch &b)
   return si;
 }
 
-// the ordered list: insert `key` (which is below L[KMAX - 1]); every index is a compile-time constant
-template <int KMAX>
-__device__ __forceinline__ void knn_insert(nnkey_t (&L)[KMAX], const nnkey_t key)
-{
-#pragma unroll
-  for (int i = KMAX - 1; i > 0; --i) L[i] = key < L[i - 1] ? L[i - 1] : (key < L[i] ? key : L[i]);
-  L[0] = key < L[0] ? key : L[0];
-}
-
 // the visitor of the shell walk that keeps the exact k-best list of query q: KMAX - k leading zero keys, then the k best
 // (kKnnKeyEmpty where the target has fewer FINITE points within a finite f32 d2; a non-finite query has none)
 template <int KMAX, bool FMA>

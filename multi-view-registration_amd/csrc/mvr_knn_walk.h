@@ -1,6 +1,6 @@
 // csrc/mvr_knn_walk.h -- the walks of a cloud's model grid around a query, each written once, for the kernels that search a
 // neighbourhood (mvr_knn.hip: k-NN lists and normals; mvr_outlier.hip: mean neighbour distances and neighbour counts;
-// mvr_mls.hip: moving least squares; mvr_fpfh.hip: FPFH descriptors):
+// mvr_mls.hip: moving least squares; mvr_fpfh.hip: FPFH descriptors; mvr_feature.hip: the scores of posed copies):
 //   * knn_shell_walk: shells of cells outward from the query's cell until a visitor's k-best list is full and every unvisited
 //     cell lies beyond it (the f64 bound of knn_unvisited_bound);
 //   * knn_ball_walk: every point within a radius of the query, in grid order.
@@ -34,6 +34,15 @@ constexpr uint32_t kSegOcc = 0x80000000u;
 // it, every key with d2 = +inf or NaN (either sign: the bits of a NaN are above those of +inf) is not -- so the one test
 // `key < L[KMAX - 1]` of the candidate loop also keeps the non-finite target points out (mvr_hip.h: the non-finite rule).
 constexpr nnkey_t kKnnKeyEmpty = 0x7F80000000000000ull;
+// the ordered k-best list of such keys (ascending, the k-th entry last): insert `key` (which is below L[KMAX - 1]); every index is a compile-time constant
+template <int KMAX>
+__device__ __forceinline__ void knn_insert(nnkey_t (&L)[KMAX], const nnkey_t key)
+{
+#pragma unroll
+  for (int i = KMAX - 1; i > 0; --i) L[i] = key < L[i - 1] ? L[i - 1] : (key < L[i] ? key : L[i]);
+  L[0] = key < L[0] ? key : L[0];
+}
+
 // the query of this thread: by position in the slot's block range, its index from w in grid order; false: past the end
 __device__ __forceinline__ bool knn_query(const KnnSlot &S, float4 *q, uint32_t *qi)
 {

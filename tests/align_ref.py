@@ -1,0 +1,158 @@
+"""numpy reference of the feature matching and of the sample-consensus alignment (include/mvr_hip.h: mvr_feature_knn rules
+M1-M3, mvr_align_prerejective rules A1-A4 and A6): FLANN's L2_Simple as a 33-step f32 loop vectorised over pairs, the
+(d2 bits, index) selection of normals_ref.knn_brute, the draws in np.uint64, the polygon test in f32 and the selection of the
+best pose.  The pose estimate (A5) and the scores (rule S) have anchors of their own in the GPU tests: numpy's Kabsch here,
+ctx.transform_f32 + ctx.nn there."""
+import numpy as np
+
+from outlier_ref import d2_f32, finite_mask
+
+F32, F64, U64 = np.float32, np.float64, np.uint64
+NONE = np.uint32(0xFFFFFFFF)
+DIM = 33
+G = U64(0x9E3779B97F4A7C15)
+DBL_MAX = np.finfo(F64).max
+
+
+# ------------------------------------------------------------------ rule M
+
+def feat_d2(q, t):
+    """M1 for every pair: acc = 0; for b: diff = q[b] - t[b]; acc = acc + diff * diff -- numpy rounds every f32 operation
+    (the three operations of a step are written into preallocated arrays: the same roundings, less memory traffic)"""
+    q, t = np.asarray(q, F32), np.asarray(t, F32)
+    qT, tT = np.ascontiguousarray(q.T), np.ascontiguousarray(t.T)
+    acc = np.zeros((len(q), len(t)), F32)
+    diff = np.empty_like(acc)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for b in range(q.shape[1]):
+            np.subtract(qT[b][:, None], tT[b][None, :], out=diff)
+            np.multiply(diff, diff, out=diff)
+            np.add(acc, diff, out=acc)
+    return acc
+
+
+def feature_knn(q, t, k, chunk=None):
+    """(idx[nq, k] uint32, d2[nq, k] float32): the k smallest (d2 bits, index) keys per query, ascending; a pair whose d2 is not
+    finite is not listed (M3: that is every pair of a non-finite row); UINT32_MAX / +inf fill the rest"""
+    q, t = np.asarray(q, F32).reshape(-1, DIM), np.asarray(t, F32).reshape(-1, DIM)
+    n, m = len(q), len(t)
+    idx = np.full((n, k), NONE, np.uint32)
+    d2 = np.full((n, k), np.inf, F32)
+    if n == 0 or m == 0:
+        return idx, d2
+    kk = min(k, m)
+    step = chunk or max(1, int(1e6) // m)      # (a chunk's arrays stay in the cache)
+    ti = np.arange(m, dtype=U64)[None, :]
+    for c0 in range(0, n, step):
+        D = feat_d2(q[c0:c0 + step], t)
+        with np.errstate(invalid="ignore"):
+            D = np.where(np.isfinite(D), D, F32(np.inf))
+        key = (D.view(np.uint32).astype(U64) << U64(32)) | ti
+        if kk < m:
+            key = np.partition(key, kk - 1, axis=1)[:, :kk]
+        key.sort(axis=1)
+        d = (key >> U64(32)).astype(np.uint32).view(F32)
+        none = np.isinf(d)
+        idx[c0:c0 + step, :kk] = np.where(none, NONE, (key & U64(0xFFFFFFFF)).astype(np.uint32))
+        d2[c0:c0 + step, :kk] = np.where(none, F32(np.inf), d)
+    return idx, d2
+
+
+# ------------------------------------------------------------------ rule A2
+
+def mix(x):
+    """splitmix64's finaliser on np.uint64 arrays (arithmetic mod 2^64)"""
+    with np.errstate(over="ignore"):
+        z = np.asarray(x, U64).copy()
+        z = (z ^ (z >> U64(30))) * U64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> U64(27))) * U64(0x94D049BB133111EB)
+        return z ^ (z >> U64(31))
+
+
+def draw(seed, i, j, m):
+    """draw(i, j, m) = ((mix(seed + G * (16 i + j + 1)) >> 32) * m) >> 32, vectorised over i (j, m scalars or arrays)"""
+    with np.errstate(over="ignore"):
+        i, j, m = np.asarray(i, U64), np.asarray(j, U64), np.asarray(m, U64)
+        x = U64(seed) + G * (U64(16) * i + j + U64(1))
+        return (((mix(x) >> U64(32)) * m) >> U64(32)).astype(np.int64)
+
+
+def sample_positions(seed, i, ne, nr):
+    """the nr distinct positions in 0..ne-1 of iteration i, in sample order"""
+    pos = []
+    for j in range(nr):
+        r = int(draw(seed, i, j, ne - j))
+        for c in sorted(pos):
+            if r >= c:
+                r += 1
+        pos.append(r)
+    return pos
+
+
+# ------------------------------------------------------------------ rules A1, A3, A4
+
+def eligible(points, feat):
+    """A1: indices of the points with finite coordinates and 33 finite features, ascending"""
+    return np.nonzero(finite_mask(points) & np.isfinite(np.asarray(feat, F32).reshape(len(points), DIM)).all(1))[0].astype(np.uint32)
+
+
+def polygon_ok(ps, pt, similarity, fma=False):
+    """A4 on one polygon: ps / pt are the [nr, >=3] sampled points and their matches"""
+    nr = len(ps)
+    thr = F32(F64(similarity) * F64(similarity))
+    ok = True
+    for j in range(nr):
+        n = (j + 1) % nr
+        ds, dt = F32(d2_f32(ps[j, :3], ps[n, :3], fma)), F32(d2_f32(pt[j, :3], pt[n, :3], fma))
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            sim = ds / dt if ds < dt else dt / ds
+        ok = ok and bool(sim >= thr)
+    return ok
+
+
+def replay(src_pts, tgt_pts, elig, knn_idx, iters, nr, seed, similarity, fma=False):
+    """A2-A4 for every iteration from a k-NN table of the eligible rows: (status[iters], src[iters, nr], tgt[iters, nr]);
+    status 0 polygon-rejected, 1 to be scored, 2 no match"""
+    ne = len(elig)
+    status = np.full(iters, 2, np.int32)
+    src = np.full((iters, nr), NONE, np.uint32)
+    tgt = np.full((iters, nr), NONE, np.uint32)
+    if ne < nr:
+        return status, src, tgt
+    kk_all = (knn_idx != NONE).sum(1)
+    for i in range(iters):
+        pos = sample_positions(seed, i, ne, nr)
+        src[i] = elig[pos]
+        matched = True
+        for j, r in enumerate(pos):
+            kk = int(kk_all[r])
+            if kk == 0:
+                matched = False
+                continue
+            tgt[i, j] = knn_idx[r, int(draw(seed, i, 8 + j, kk))]
+        if matched:
+            status[i] = 1 if polygon_ok(src_pts[src[i]], tgt_pts[tgt[i]], similarity, fma) else 0
+    return status, src, tgt
+
+
+# ------------------------------------------------------------------ rule A6
+
+def select(status, inliers, error, n_src, inlier_fraction, guess=None):
+    """the pose A6 takes: (converged, best_iteration); guess = (inliers, error) of the guess, scored first (-1)"""
+    lowest, best, conv = DBL_MAX, -1, False
+    order = ([(-1,) + tuple(guess)] if guess is not None else []) + [(i, inliers[i], error[i]) for i in np.nonzero(status == 1)[0]]
+    for i, n, e in order:
+        if n_src and F64(n) / F64(n_src) >= inlier_fraction and e < lowest:
+            lowest, best, conv = e, int(i), True
+    return conv, best
+
+
+def kabsch(p, q):
+    """the rigid motion of least squares from p to q ([n, 3] f64): R = U diag(1, 1, det) V^T of E[(q - mq)(p - mp)^T]"""
+    p, q = np.asarray(p, F64), np.asarray(q, F64)
+    pm, qm = p.mean(0), q.mean(0)
+    U, S, Vt = np.linalg.svd((q - qm).T @ (p - pm) / len(p))
+    R = U @ np.diag([1.0, 1.0, np.sign(np.linalg.det(U) * np.linalg.det(Vt))]) @ Vt
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, qm - R @ pm
+    return T, S
