@@ -164,7 +164,7 @@ double pose_motion_bound(const double *Told, const double *Tnew, const float bbo
 
 void note_pose(Cloud &dst, const Cloud &src, bool src_canonical, const double T[16])
 {
-  dst.canonical = false; dst.pose_known = false; dst.fin_known = false; dst.parts.clear();
+  dst.canonical = false; dst.pose_known = false;
   // how far the copy moves with this pose (seed_delta): from the pose it had last, if that was a pose of the same point set
   const bool chain = src_canonical && &dst != &src && dst.last_pose_set == src.set_id && dst.last_pose_set != 0 && dst.moved >= 0.0 && src.bbox_set == src.set_id;
   const double step = chain ? pose_motion_bound(dst.last_pose, T, src.bbox) : -1.0;
@@ -402,12 +402,10 @@ static int ctx_create_impl(mvr_ctx **out, int device_id, void *hip_stream, bool 
   if (const char *m = std::getenv("MVR_CULL_W")) c->cull_w = std::atoi(m);     // waves per query set: 1, 2, 4 (default)
   if (const char *m = std::getenv("MVR_CULL_SLICES")) c->cull_slices = std::atoi(m);   // XCD dealing of a pair's query sets: 1, 2, 4, 8 (0 = auto)
   if (const char *m = std::getenv("MVR_SEED_FORWARD")) c->seed_forward = std::atoi(m) != 0;
-  if (const char *m = std::getenv("MVR_PARTS_LANES")) c->parts_lanes = std::atoi(m);
-  if (const char *m = std::getenv("MVR_PARTS_MAX_ROWS")) c->parts_max_rows = std::max(1, std::atoi(m));
   if (const char *m = std::getenv("MVR_GRID_DEBUG")) c->grid_debug = std::atoi(m) != 0;
   if (const char *m = std::getenv("MVR_SEQ_SEED")) c->seq_seed = std::atoi(m) != 0;
   if (const char *m = std::getenv("MVR_ALIGN_SPIN")) c->align_spin = std::atoi(m) != 0;      // 0: an align's iteration row by copy + synchronise
-  if (const char *m = std::getenv("MVR_SEQ_SEARCH")) c->seq_search = std::max(0, std::min(3, std::atoi(m)));    // align against a target made of posed scans: 1 = through the scans' grids, 0 = culled kernel
+  if (const char *m = std::getenv("MVR_SEQ_SEARCH")) c->seq_search = std::max(0, std::min(1, std::atoi(m)));    // align of a posed scan: the reverse searches 1 = walk the source scan's grid, 0 = culled kernel
   if (const char *m = std::getenv("MVR_RING_SEARCH")) c->ring_search = std::atoi(m);   // fused pass: 1 = grid search for bounded queries, 0 = culled kernel only
   if (const char *m = std::getenv("MVR_INPLACE_RATIO")) c->inplace_ratio = std::atoi(m);
   if (const char *m = std::getenv("MVR_PAIR_FUSED")) c->pair_fused = std::atoi(m) != 0;
@@ -472,8 +470,6 @@ API int mvr_ctx_destroy(mvr_ctx *ctx)
   if (c->stage_stat) (void)hipFree(c->stage_stat);
   if (c->proj_rows) (void)hipFree(c->proj_rows);
   if (c->oscratch) (void)hipFree(c->oscratch);
-  if (c->d_parts) (void)hipFree(c->d_parts);
-  if (c->h_parts) (void)hipHostFree(c->h_parts);
   if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
   if (c->side_after) (void)hipEventDestroy(c->side_after);
   if (c->scratch_event) (void)hipEventDestroy(c->scratch_event);
@@ -690,9 +686,6 @@ API int mvr_cloud_copy(mvr_ctx *ctx, int dst, int src)
   d.n = s.n;
   inherit_point_set(d, s);
   d.canonical = s.canonical; d.pose_known = s.pose_known; d.pose_stretch = s.pose_stretch; std::memcpy(d.pose, s.pose, sizeof d.pose); d.grid = s.grid;
-  d.fin_known = s.fin_known; std::memcpy(d.fin, s.fin, sizeof d.fin);
-  d.parts = s.parts;
-  for (GridPart &gp : d.parts) gp.gs_filled = false;          // (the grid-ordered coordinates are not copied: written again at the first search)
   d.segs = s.segs;
   d.has_normals = false;
   if (s.has_normals && s.n) {
@@ -710,25 +703,6 @@ API int mvr_cloud_append(mvr_ctx *ctx, int dst, int src)
   MVR_HIP_TRY(c, hipSetDevice(c->device));
   Cloud &d = c->slots[dst];
   const size_t add = c->slots[src].n;         // read before a self-append grows it
-  // What the grown cloud is made of, when both sides are posed copies of scans (the sequential mode's model: view 0 posed,
-  // then one aligned view after the other): recorded so that mvr_icp_align can search it through the scans' grids.
-  auto provenance = [](const Cloud &x, size_t base, GridPart *gp) {
-    if (!(x.pose_known || x.fin_known) || x.n == 0 || !x.segs.empty()) return false;
-    gp->set_id = x.set_id; gp->n = x.n; gp->base = base; gp->kind = x.fin_known ? 2 : 1;
-    std::memcpy(gp->pose, x.pose, sizeof gp->pose); std::memcpy(gp->fin, x.fin, sizeof gp->fin);
-    gp->grid = x.grid; gp->gs_filled = false;
-    return true;
-  };
-  std::vector<GridPart> parts_after;
-  {
-    bool ok = dst != src && d.segs.empty() && add > 0;
-    if (ok) {
-      if (!d.parts.empty()) parts_after = d.parts;
-      else if (d.n > 0) { GridPart p0; ok = provenance(d, 0, &p0); if (ok) parts_after.push_back(p0); }
-    }
-    GridPart pn;
-    if (ok && provenance(c->slots[src], d.n, &pn)) parts_after.push_back(pn); else parts_after.clear();
-  }
   if (!d.segs.empty()) {                       // a shard: the appended points continue its global numbering
     uint32_t gend = 0;
     for (const Seg &sg : d.segs) gend = std::max(gend, sg.global_begin + sg.count);
@@ -746,12 +720,8 @@ API int mvr_cloud_append(mvr_ctx *ctx, int dst, int src)
     if (dst != src && d.segs.empty() && extend_point_set(c, d, d.n, s)) {
       // a different point set all the same: what it is now DEFINES it (as new_point_set says for the other branch); a pose
       // or a grid of the set it grew from is not its own
-      // (for a cloud made of parts gcoords_valid says "the parts' gs_filled flags can be trusted": the stretches of
-      // gsorted[] already written stay valid here -- those points did not move)
-      const bool keep_gs = d.gcoords_valid && !parts_after.empty() && !d.parts.empty();
-      d.forget_pose(); d.canonical = true; d.gcoords_valid = keep_gs;
+      d.forget_pose(); d.canonical = true; d.gcoords_valid = false;
     } else new_point_set(c, d);
-    if (!parts_after.empty()) d.parts.swap(parts_after);
     // normals survive only if both parts carry them
     const bool keep = s.has_normals && (d.has_normals || d.n == 0);
     if (keep) {
@@ -2035,17 +2005,13 @@ API int mvr_pair_moments2_from_corr(mvr_ctx *ctx, int ss, int ts, const int32_t 
   return MVR_OK;
 }
 
-// ---- mvr_icp_align against a target MADE OF POSED SCANS (the growing model of the sequential mode) --------------------
-// Everything the part-by-part search needs, or false when the align has to take the culled kernel: every part's scan and
-// the source's scan must be resident in canonical form (their grids are found or built here, batched), the target's
-// grid-ordered coordinates are written for the parts that do not have them yet, the current source gets the pose and the
-// grid of the posed source it is a copy of, and the part table goes to the device.
+// ---- mvr_icp_align of a POSED SCAN (the sequential mode aligns every scan, under its pose so far, against the growing model)
 // the current source of an align is an exact copy of a posed scan: give it that scan's pose, grid and grid-ordered
 // coordinates, so that the REVERSE searches (matched targets looking for their nearest source point, each with the bound
 // its forward match gives) can walk the source's grid instead of the culled kernel's box hierarchy
 static bool prepare_source_grid(Ctx *c, const Cloud &posed_src, Cloud &cur, double max_dist)
 {
-  if (!c->seq_search || c->nn_mode == 0 || !posed_src.pose_known || posed_src.fin_known || posed_src.n == 0 || posed_src.n != cur.n) return false;
+  if (!c->seq_search || c->nn_mode == 0 || !posed_src.pose_known || posed_src.n == 0 || posed_src.n != cur.n) return false;
   if (!(max_dist * max_dist < (double)FLT_MAX)) return false;
   Cloud *src_canon = nullptr;
   for (Cloud &o : c->slots) if (o.set_id == posed_src.set_id && o.canonical && o.n == posed_src.n) { src_canon = &o; break; }
@@ -2062,102 +2028,10 @@ static bool prepare_source_grid(Ctx *c, const Cloud &posed_src, Cloud &cur, doub
   return refresh_grid_coords_batch(c, &one, 1) == MVR_OK && cur.gcoords_valid;
 }
 
-static bool prepare_parts_search(Ctx *c, const Cloud &posed_src, Cloud &cur, Cloud &tgt, double max_dist)
-{
-  if (c->seq_search < 2 || c->nn_mode == 0 || !posed_src.pose_known || posed_src.fin_known || posed_src.n == 0) return false;
-  if (!(max_dist * max_dist < (double)FLT_MAX)) return false;
-  if (tgt.parts.empty() && (tgt.pose_known || tgt.fin_known) && tgt.segs.empty() && tgt.n > 0) {
-    // a single posed scan (the model before its first append: view 0 under its pose) is a composite of one part
-    GridPart gp;
-    gp.set_id = tgt.set_id; gp.n = tgt.n; gp.base = 0; gp.kind = tgt.fin_known ? 2 : 1;
-    std::memcpy(gp.pose, tgt.pose, sizeof gp.pose); std::memcpy(gp.fin, tgt.fin, sizeof gp.fin);
-    gp.grid = nullptr; gp.gs_filled = false;
-    tgt.parts.push_back(gp);
-    tgt.gcoords_valid = false;              // (a posed scan's gsorted[] carries original indices without a base: same thing for base 0, but written by another kernel)
-  }
-  if (tgt.parts.empty()) return false;
-  size_t total = 0;
-  for (const GridPart &gp : tgt.parts) { if (gp.base != total || gp.n == 0 || (gp.kind != 1 && gp.kind != 2)) return false; total += gp.n; }
-  if (total != tgt.n || tgt.n > 0xFFFFFFF0ull) return false;
-  auto canon_of = [&](unsigned long long set_id, size_t n) -> Cloud * {
-    for (Cloud &o : c->slots) if (o.set_id == set_id && o.canonical && o.n == n) return &o;
-    return nullptr;
-  };
-  std::vector<Cloud *> canon;
-  for (const GridPart &gp : tgt.parts) { Cloud *o = canon_of(gp.set_id, gp.n); if (!o) return false; canon.push_back(o); }
-  Cloud *src_canon = canon_of(posed_src.set_id, posed_src.n);
-  if (!src_canon) return false;
-  canon.push_back(src_canon);
-  if (ensure_grids(c, canon.data(), (int)canon.size(), max_dist + 0.5, c->stream, nullptr) != MVR_OK) return false;
-  for (Cloud *o : canon) if (!o->grid || o->grid->n != o->n) return false;
-  // the target's coordinates in grid order, part after part
-  const float4 *before = tgt.gsorted;
-  if (ensure(c, tgt.gsorted, tgt.gsorted_cap, std::max(tgt.cap, tgt.n)) != MVR_OK) return false;
-  if (tgt.gsorted != before || !tgt.gcoords_valid) for (GridPart &gp : tgt.parts) gp.gs_filled = false;
-  for (size_t k = 0; k < tgt.parts.size(); ++k) {
-    GridPart &gp = tgt.parts[k];
-    gp.grid = canon[k]->grid;
-    if (gp.grid->ready && !gp.grid->ready_waited) { if (hipStreamWaitEvent(c->stream, gp.grid->ready, 0) != hipSuccess) return false; gp.grid->ready_waited = true; }
-    if (!gp.gs_filled && fill_part_coords(c, tgt, gp) != MVR_OK) return false;
-  }
-  tgt.gcoords_valid = true;
-  // the current source: an exact copy of the posed source, so its pose and its scan's grid
-  cur.pose_known = true; cur.pose_stretch = posed_src.pose_stretch; std::memcpy(cur.pose, posed_src.pose, sizeof cur.pose);
-  cur.grid = src_canon->grid; cur.gcoords_valid = false;
-  Cloud *one = &cur;
-  if (refresh_grid_coords_batch(c, &one, 1) != MVR_OK || !cur.gcoords_valid) return false;
-  // the part table
-  const size_t K = tgt.parts.size();
-  if (c->parts_cap < K) {
-    if (may_block(c, "not in steady state: the part table has to grow") != MVR_OK) return false;
-    (void)hipStreamSynchronize(c->stream);
-    if (c->d_parts) (void)hipFree(c->d_parts);
-    if (c->h_parts) (void)hipHostFree(c->h_parts);
-    c->d_parts = nullptr; c->h_parts = nullptr; c->parts_cap = 0;
-    const size_t cap = std::max<size_t>(64, 2 * K);
-    if (hipMalloc(&c->d_parts, cap * sizeof(PartDesc)) != hipSuccess || hipHostMalloc(reinterpret_cast<void **>(&c->h_parts), cap * sizeof(PartDesc)) != hipSuccess) return false;
-    c->parts_cap = cap;
-  }
-  for (size_t k = 0; k < K; ++k) {
-    const GridPart &gp = tgt.parts[k];
-    const CellGrid &g = *gp.grid;
-    PartDesc &d = c->h_parts[k];
-    d.gts = tgt.gsorted + gp.base; d.start = g.start; d.dir = g.dir; d.recs = g.recs; d.dt_shift = g.dt_shift; for (int k3 = 0; k3 < 3; ++k3) d.dtdim[k3] = g.dtdim[k3]; d.dt = g.dt;
-    for (int j = 0; j < 3; ++j) { d.lo[j] = g.lo[j]; d.dim[j] = g.dim[j]; }
-    d.inv_h = g.inv_h; d.h = g.h; d.dt_max = g.dt_steps; d.base = (uint32_t)gp.base; d.n = (uint32_t)gp.n;
-    // canonical -> posed: the f64 pose, then (kind 2) the align's f32 matrix
-    double M[16];
-    std::memcpy(M, gp.pose, sizeof M);
-    if (gp.kind == 2) { double F[16]; for (int j = 0; j < 16; ++j) F[j] = (double)gp.fin[j]; mvr_mat4d_mul(F, gp.pose, M); }
-    if (M[3] != 0.0 || M[7] != 0.0 || M[11] != 0.0 || M[15] != 1.0) return false;
-    double e2 = 0.0;
-    for (int a = 0; a < 3; ++a)
-      for (int b = 0; b < 3; ++b) {
-        const double dd = M[4 * a] * M[4 * b] + M[4 * a + 1] * M[4 * b + 1] + M[4 * a + 2] * M[4 * b + 2], x = dd - (a == b ? 1.0 : 0.0);
-        e2 += x * x;
-      }
-    const double e = std::sqrt(e2);
-    if (!(e <= 1e-3)) return false;                        // (note_pose's bar: beyond it a ball is no ball any more)
-    d.stretch = std::nextafterf((float)((1.0 / std::sqrt(1.0 - e)) * (1.0 + 1e-6)), INFINITY);
-    const double A[3][3] = {{M[0], M[4], M[8]}, {M[1], M[5], M[9]}, {M[2], M[6], M[10]}};
-    const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) + A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
-    const double id = 1.0 / det;
-    const double I[3][3] = {{(A[1][1] * A[2][2] - A[1][2] * A[2][1]) * id, (A[0][2] * A[2][1] - A[0][1] * A[2][2]) * id, (A[0][1] * A[1][2] - A[0][2] * A[1][1]) * id},
-                            {(A[1][2] * A[2][0] - A[1][0] * A[2][2]) * id, (A[0][0] * A[2][2] - A[0][2] * A[2][0]) * id, (A[0][2] * A[1][0] - A[0][0] * A[1][2]) * id},
-                            {(A[1][0] * A[2][1] - A[1][1] * A[2][0]) * id, (A[0][1] * A[2][0] - A[0][0] * A[2][1]) * id, (A[0][0] * A[1][1] - A[0][1] * A[1][0]) * id}};
-    for (int r = 0; r < 3; ++r) {
-      for (int j = 0; j < 3; ++j) d.minv[4 * r + j] = I[r][j];
-      d.minv[4 * r + 3] = -(I[r][0] * M[12] + I[r][1] * M[13] + I[r][2] * M[14]);
-    }
-  }
-  if (hipMemcpyAsync(c->d_parts, c->h_parts, K * sizeof(PartDesc), hipMemcpyHostToDevice, c->stream) != hipSuccess) return false;
-  return true;
-}
-
-// the search of one iteration through the parts: forward = nn_parts_kernel (+ the culled kernel for the queries it
-// flags), reverse = the grid walk over the CURRENT SOURCE's grid for the matched targets, compacted by the kernels of
-// the fused pass (no hipCUB).  Leaves keys / slot / rkeys as run_search does.
-static int run_search_parts(Ctx *c, Cloud &cur, Cloud &tgt, double max_dist, bool reciprocal, bool fma, SearchPlan *plan, bool parts_forward)
+// the search of an align's first iteration when the source has its scan's grid (prepare_source_grid): forward = the culled
+// kernel over the target's index, every query starting from its seed; reverse = the grid walk over the CURRENT SOURCE's grid
+// for the matched targets, compacted by the kernels of the fused pass (no hipCUB).  Leaves keys / slot / rkeys as run_search does.
+static int run_search_source_grid(Ctx *c, Cloud &cur, Cloud &tgt, double max_dist, bool reciprocal, bool fma, SearchPlan *plan)
 {
   const size_t ns = cur.n, nt = tgt.n;
   const double max2 = max_dist * max_dist;
@@ -2166,7 +2040,6 @@ static int run_search_parts(Ctx *c, Cloud &cur, Cloud &tgt, double max_dist, boo
   if (int rc = ensure(c, c->keys, c->keys_cap, ns)) return rc;
   if (int rc = ensure(c, c->match, c->match_cap, ns)) return rc;
   if (int rc = ensure(c, c->rkeys, c->rkeys_cap, std::max(ns, std::min(ns, nt)))) return rc;
-  if (int rc = ensure(c, c->bheavy, c->bheavy_cap, ns)) return rc;
   if (int rc = ensure_index(c, cur)) return rc;
   if (int rc = ensure_index(c, tgt)) return rc;
   plan->qperm = cur.order->perm; plan->tinv = tgt.order->inv;
@@ -2181,87 +2054,10 @@ static int run_search_parts(Ctx *c, Cloud &cur, Cloud &tgt, double max_dist, boo
       qb = c->seed_bound;
     }
   }
-  // seq_search 2: forward through the parts' grids (measured slower)
-  const bool through_parts = parts_forward && c->seq_search == 2;
-  // seq_search 3: forward through ONE grid over the model's own coordinates (Cloud::mgrid): the thread-per-query walk, then the
-  // wide bounded queries a wave each and the flagged 64-query sets a block each, as a fused pass's forward searches
-  bool model_ok = false;
-  if (c->seq_search == 3 && !through_parts) { if (int rc = ensure_model_grid(c, tgt, max_dist + 0.5, &model_ok)) return rc; }
-  if (model_ok) {
-    if (!c->bwide_count) {
-      MVR_MAY_BLOCK(c, "the wide-query counters are not allocated yet");
-      MVR_HIP_TRY(c, hipMalloc(&c->bwide_count, 3 * kWideCounters * sizeof(uint32_t)));
-      MVR_HIP_TRY(c, hipMemsetAsync(c->bwide_count, 0, 3 * kWideCounters * sizeof(uint32_t), c->stream));
-    }
-    if (int rc = ensure(c, c->bwide, c->bwide_cap, std::max(ns, std::min(ns, nt)))) return rc;
-    if (int rc = ensure(c, c->bcull_sets, c->bcull_sets_cap, ns / 64 + 2)) return rc;
-    GridPair f = make_model_pair(cur, tgt, c->keys);
-    f.qbound = qb;
-    f.heavy = c->bheavy;
-    f.wide_list = c->bwide; f.wide_count = c->bwide_count + kWideCounters - 2;
-    f.cull_sets = c->bcull_sets; f.cull_count = c->bwide_count + 2 * kWideCounters + kWideCounters - 1;
-    MVR_HIP_TRY(c, hipMemsetAsync(f.wide_count, 0, sizeof(uint32_t), c->stream));
-    MVR_HIP_TRY(c, hipMemsetAsync(f.cull_count, 0, sizeof(uint32_t), c->stream));
-    if (int rc = launch_nn_grid_batch(c, &f, 1, cap2, fma)) return rc;
-    if (c->grid_debug) {           // diagnostics: how many queries left the thread-per-query walk
-      std::vector<uint8_t> hv(ns); uint32_t wc = 0, sc = 0;
-      MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
-      MVR_HIP_TRY(c, hipMemcpy(hv.data(), c->bheavy, ns, hipMemcpyDeviceToHost));
-      MVR_HIP_TRY(c, hipMemcpy(&wc, f.wide_count, 4, hipMemcpyDeviceToHost));
-      MVR_HIP_TRY(c, hipMemcpy(&sc, f.cull_count, 4, hipMemcpyDeviceToHost));
-      size_t fl = 0;
-      for (size_t i = 0; i < ns; ++i) fl += hv[i];
-      if (qb) {
-        std::vector<uint32_t> sbv(ns);
-        MVR_HIP_TRY(c, hipMemcpy(sbv.data(), qb, ns * 4, hipMemcpyDeviceToHost));
-        size_t z = 0, in = 0, out = 0, none = 0, fz = 0, fin = 0, fout = 0, fnone = 0;
-        uint32_t capb; std::memcpy(&capb, &cap2, 4);
-        for (size_t i = 0; i < ns; ++i) {
-          const uint32_t v = sbv[i];
-          if (v == 0) { ++z; fz += hv[i]; } else if (v == 0xFFFFFFFFu) { ++none; fnone += hv[i]; } else if (v <= capb) { ++in; fin += hv[i]; } else { ++out; fout += hv[i]; }
-        }
-        std::fprintf(stderr, "[model]   start bounds: %zu zero (%zu flagged), %zu within the cap (%zu), %zu beyond (%zu), %zu none (%zu)\n", z, fz, in, fin, out, fout, none, fnone);
-      }
-      std::fprintf(stderr, "[model] nt %zu, h %.3f, dim %d x %d x %d, %zu queries (%s): %u to a wave each, %zu flagged in %u sets\n", nt, tgt.mgrid->h, tgt.mgrid->dim[0], tgt.mgrid->dim[1],
-                   tgt.mgrid->dim[2], ns, qb ? "seeded" : "no seeds", wc, fl, sc);
-    }
-    if (c->seq_model_tail == 0) { if (int rc = launch_nn_grid_tail_batch(c, &f, 1, cap2, fma)) return rc; }
-    else {
-      // the wide bounded queries a wave each; the flagged sets through the culled kernel over the model's composite ordering
-      // (its box hierarchy throws out the sets that have nothing within the cap at once), keys by sorted position, then merged
-      if (int rc = launch_nn_grid_wide_batch(c, &f, 1, cap2, fma)) return rc;
-      CullPair p = make_cull_pair(cur, 0, ns, c->bheavy, tgt, c->rkeys);
-      p.qbound = qb; p.setlist = f.cull_sets; p.setcount = f.cull_count;
-      // (several lanes per query -- grid_lanes 2 / 4 / 8 -- write no set list: the culled kernel then starts a block per set and the
-      // blocks without a flagged query leave at once)
-      if (c->grid_lanes == 2 || c->grid_lanes == 4 || c->grid_lanes == 8) { p.setlist = nullptr; p.setcount = nullptr; if (int rc = launch_nn_cull_batch(c, &p, 1, cap2, fma)) return rc; }
-      else
-      if (int rc = launch_nn_cull_list_batch(c, &p, 1, cap2, fma)) return rc;
-      if (int rc = launch_merge_flagged_keys(c, cur.sorted, c->bheavy, c->rkeys, ns, c->keys)) return rc;
-    }
-  } else
-  if (!through_parts) {
-    // forward: the culled kernel over the target's composite index (keys are written by exactly one wave per query)
-    CullPair fp = make_cull_pair(cur, 0, ns, nullptr, tgt, c->keys);
-    fp.qbound = qb;
-    if (int rc = launch_nn_cull_batch(c, &fp, 1, cap2, fma)) return rc;
-  } else {
-  if (int rc = launch_nn_parts(c, cur, (int)tgt.parts.size(), cap2, fma, c->keys, c->bheavy, qb)) return rc;
-  if (c->grid_debug) {           // diagnostics: how many queries the parts could not answer
-    std::vector<uint8_t> hv(ns);
-    MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    MVR_HIP_TRY(c, hipMemcpy(hv.data(), c->bheavy, ns, hipMemcpyDeviceToHost));
-    size_t f = 0, sets = 0;
-    for (size_t i = 0; i < ns; i += 64) { size_t g = 0; for (size_t j = i; j < std::min(ns, i + 64); ++j) g += hv[j]; f += g; sets += g != 0; }
-    std::fprintf(stderr, "[parts] %zu parts, %zu queries: %zu left to the culled kernel in %zu of %zu sets\n", tgt.parts.size(), ns, f, sets, (ns + 63) / 64);
-  }
-  {   // the flagged queries: the culled kernel over the composite index, keys by SORTED position into rkeys[], then merged
-    CullPair p = make_cull_pair(cur, 0, ns, c->bheavy, tgt, c->rkeys);
-    p.qbound = qb;
-    if (int rc = launch_nn_cull_batch(c, &p, 1, cap2, fma)) return rc;
-    if (int rc = launch_merge_flagged_keys(c, cur.sorted, c->bheavy, c->rkeys, ns, c->keys)) return rc;
-  }
-  }
+  // forward: the culled kernel over the target's index (keys are written by exactly one wave per query)
+  CullPair fp = make_cull_pair(cur, 0, ns, nullptr, tgt, c->keys);
+  fp.qbound = qb;
+  if (int rc = launch_nn_cull_batch(c, &fp, 1, cap2, fma)) return rc;
   uint32_t *seed_out = nullptr;
   if (c->seq_seed) {
     if (c->seq_seeds.size() >= 256 && !c->seq_seeds.count(cur.set_id)) {      // (scans that are gone: start over rather than grow without bound)
@@ -2352,20 +2148,17 @@ API int mvr_icp_align(mvr_ctx *ctx, int ss, int ts, int os, const mvr_icp_params
   double cur_mse = 0.0, evals = 0.0, fwdq = 0.0, evals_total = 0.0;
   int iters = 0, converged = 0, state = MVR_CONV_NOT, ncorr = 0, status = MVR_OK;
   Cloud &tgt = c->slots[ts];
-  // a target made of posed scans (the sequential mode's model) is searched through the scans' grids -- in the first
-  // iteration, while the current source still IS the posed source (later iterations, which the reference's settings never
-  // reach, take the culled kernel: the moved source's coordinates are no longer a known pose of its scan)
-  // (seq_search 2: forward through the parts as well; measured on the 12 x 200k sweep it does NOT pay -- DESIGN.md 4.5 -- so
-  // the default, 1, keeps the culled kernel for the forward search and takes the grid for the reverse one)
-  const bool parts_ok = ns > 0 && tgt.n > 0 && ts != ss && prepare_parts_search(c, c->slots[ss], *curp, tgt, p->max_corr_dist);
-  const bool rev_grid_ok = parts_ok || (ns > 0 && tgt.n > 0 && ts != ss && p->use_reciprocal && tgt.n <= 0xFFFFFFF0ull &&
-                                        prepare_source_grid(c, c->slots[ss], *curp, p->max_corr_dist));
+  // a posed scan's reverse searches walk its scan's grid -- in the first iteration, while the current source still IS the posed
+  // source (later iterations, which the reference's settings never reach, take the culled kernel: the moved source's
+  // coordinates are no longer a known pose of its scan)
+  const bool rev_grid_ok = ns > 0 && tgt.n > 0 && ts != ss && p->use_reciprocal && tgt.n <= 0xFFFFFFF0ull &&
+                           prepare_source_grid(c, c->slots[ss], *curp, p->max_corr_dist);
   // (point-to-point: the iteration's row comes to the host from the last sums launch itself, no copy, no synchronise)
   const bool spin = c->align_spin && !p->point_to_plane && ensure_align_row(c) == MVR_OK;
   do {
     double ev = 0.0;
     SearchPlan plan;
-    if (rev_grid_ok && iters == 0) { if (int rc = run_search_parts(c, *curp, tgt, p->max_corr_dist, p->use_reciprocal != 0, p->fma_dist != 0, &plan, parts_ok)) return rc; }
+    if (rev_grid_ok && iters == 0) { if (int rc = run_search_source_grid(c, *curp, tgt, p->max_corr_dist, p->use_reciprocal != 0, p->fma_dist != 0, &plan)) return rc; }
     else
     if (int rc = run_search(c, *curp, tgt, 0, ns, p->max_corr_dist, p->use_reciprocal != 0, p->fma_dist != 0, &ev, &plan)) return rc;
     if (int rc = launch_pass1(c, curp->pts, tgt.pts, c->keys, c->rkeys, plan.slot, plan.count, plan.qperm, plan.tinv, 0, ns,
@@ -2406,7 +2199,7 @@ API int mvr_icp_align(mvr_ctx *ctx, int ss, int ts, int os, const mvr_icp_params
         curp = &scratch;
       } else if (int rc = launch_transform_f32(c, curp->pts, curp->pts, ns, tr)) return rc;
       curp->stale_coords();
-      curp->pose_known = false; curp->fin_known = false; curp->grid.reset(); curp->parts.clear();
+      curp->pose_known = false; curp->grid.reset();
     }
   } while (!converged);
   // output = final * (*input), from the ORIGINAL input: alias-safe (registrator.cpp:920)
@@ -2414,16 +2207,8 @@ API int mvr_icp_align(mvr_ctx *ctx, int ss, int ts, int os, const mvr_icp_params
     if (os != ss) { c->slots[os].n = 0; if (int rc = cloud_reserve(c, c->slots[os], ns, false)) return rc; }
     if (int rc = launch_transform_f32(c, c->slots[ss].pts, c->slots[os].pts, ns, fin)) return rc;
     c->slots[os].n = ns;
-    if (os != ss) {
-      inherit_point_set(c->slots[os], c->slots[ss]);
-      // the output is the f32 matrix `fin` applied to a cloud with a known f64 pose: a posed copy still, by known arithmetic
-      // (what the sequential mode appends to its model, registrator.cpp:576 -- see GridPart)
-      const Cloud &in = c->slots[ss];
-      if (in.pose_known && !in.fin_known) {
-        Cloud &o = c->slots[os];
-        o.fin_known = true; std::memcpy(o.fin, fin, sizeof fin); std::memcpy(o.pose, in.pose, sizeof o.pose); o.pose_stretch = in.pose_stretch; o.grid = in.grid;
-      }
-    } else {
+    if (os != ss) inherit_point_set(c->slots[os], c->slots[ss]);      // (the output keeps the set's ordering, not its pose or grid)
+    else {
       // the aliased align(*source_) of registrator.cpp:920: the slot's points moved in place by a FLOAT matrix -- they are
       // neither the set's upload coordinates nor a known f64 pose of them any more, and a grid built in the old frame
       // must not be walked with them (the other in-place paths: mvr_cloud_transform, _f32, _batch)
@@ -2702,9 +2487,8 @@ API int mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value)
   else if (!std::strcmp(key, "lazy_super")) { if (value < 0 || value > 1) return MVR_E_ARG; c->lazy_super = value; }
   else if (!std::strcmp(key, "fused_mark")) { if (value < 0 || value > 2) return MVR_E_ARG; c->fused_mark = value; }
   else if (!std::strcmp(key, "ring_search")) c->ring_search = value;
-  else if (!std::strcmp(key, "seq_search")) { if (value < 0 || value > 3) return MVR_E_ARG; c->seq_search = value; }
+  else if (!std::strcmp(key, "seq_search")) { if (value < 0 || value > 1) return MVR_E_ARG; c->seq_search = value; }
   else if (!std::strcmp(key, "unseeded_grid")) { if (value < 0 || value > 1) return MVR_E_ARG; c->unseeded_grid = value; }
-  else if (!std::strcmp(key, "seq_model_tail")) { if (value < 0 || value > 1) return MVR_E_ARG; c->seq_model_tail = value; }
   else if (!std::strcmp(key, "seq_cell_points")) { if (value < 1) return MVR_E_ARG; c->seq_cell_points = value; }
   else if (!std::strcmp(key, "seq_seed")) {          // 0 also forgets what the aligns so far have left behind
     c->seq_seed = value != 0;
@@ -2714,8 +2498,6 @@ API int mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value)
       c->seq_seeds.clear();
     }
   }
-  else if (!std::strcmp(key, "parts_lanes")) { if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return MVR_E_ARG; c->parts_lanes = value; }
-  else if (!std::strcmp(key, "parts_max_rows")) { if (value < 1) return MVR_E_ARG; c->parts_max_rows = value; }
   else if (!std::strcmp(key, "grid_light_rows")) { if (value < 1) return MVR_E_ARG; c->grid_light_rows = value; }
   else if (!std::strcmp(key, "grid_light_rows_lone")) { if (value < 1) return MVR_E_ARG; c->grid_light_rows_lone = value; }
   else if (!std::strcmp(key, "align_spin")) c->align_spin = value != 0;

@@ -237,7 +237,7 @@ int pose_scores_device(Ctx *c, Cloud &src, Cloud &tgt, const float *dT, size_t c
   if (int rc = fill_target(c, tgt, a.S)) return rc;
   if (&src != &tgt && src.n >= 4) {      // the source's own grid gives its points their walking order
     bool ok = false;
-    if (int rc = ensure_model_grid(c, src, 0.0, &ok)) return rc;
+    if (int rc = ensure_model_grid(c, src, &ok)) return rc;
   }
   fill_queries(src, a.S);
   a.T = dT;

@@ -115,19 +115,6 @@ struct PoseRec {
   float stretch, delta;     // bound of how much the inverse lengthens a distance (1 for a rigid pose); how far (mm, upper bound) any point of the cloud has moved since the pass before (1e30: unknown)
 };
 
-// One merged scan inside a cloud that is a CONCATENATION of posed copies of scans -- the growing target of the sequential
-// mode (`*target += transformed_source`, registrator.cpp:576).  Its points never move once appended, so the raw scan's
-// pose-invariant cell grid serves it: the part records which point set it is a copy of and by which arithmetic its
-// coordinates were made (kind 1: p = f32(pose * canonical) as mvr_cloud_transform; kind 2: that, then the f32 matrix of an
-// align's result as mvr_icp_align's output) -- enough to write its coordinates in GRID order bit for bit and to map a
-// query into the scan's canonical frame.
-struct GridPart {
-  unsigned long long set_id = 0; size_t n = 0, base = 0; int kind = 0;
-  double pose[16]; float fin[16];
-  std::shared_ptr<CellGrid> grid;      // found (or built) when the part is first searched
-  bool gs_filled = false;              // its stretch of the cloud's gsorted[] is written
-};
-
 struct Cloud {
   float4 *pts = nullptr;
   size_t n = 0;
@@ -154,17 +141,13 @@ struct Cloud {
   std::shared_ptr<CellGrid> grid;          // the set's grid (shared)
   float4 *gsorted = nullptr; size_t gsorted_cap = 0;      // posed coordinates in grid order, w = bits(original index)
   bool gcoords_valid = false;          // gsorted matches pts
-  std::shared_ptr<CellGrid> mgrid;     // a grid over THESE coordinates (the sequential mode's model searched as one point set: ensure_model_grid), valid while mgrid_ok
+  std::shared_ptr<CellGrid> mgrid;     // a grid over THESE coordinates (ensure_model_grid: what the k-NN, outlier, MLS, FPFH and pose-score walks search), valid while mgrid_ok
   bool mgrid_ok = false;
   // pipelined ring run (mvr_ctx.hip: ring_passes): where the kernels of a pass that is enqueued BEFORE its poses are known
   // find this posed copy's pose, inverse and stretch (device memory, filled by pose_prep_kernel once the host's solve has
   // released the pass); null outside such a run
   const struct PoseRec *pose_dev = nullptr;
-  // ... or a known f64 pose FOLLOWED by a known f32 matrix (the output cloud of an align whose source had a known pose):
-  // pts = xform_f32(fin, f32(pose * canonical)); the sequential mode's merged scans are made this way
-  bool fin_known = false; float fin[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  std::vector<GridPart> parts;         // non-empty: this cloud is exactly the concatenation of these posed scans (see GridPart)
-  void forget_pose() { canonical = false; pose_known = false; fin_known = false; pose_stretch = 1.0; grid.reset(); parts.clear(); }
+  void forget_pose() { canonical = false; pose_known = false; pose_stretch = 1.0; grid.reset(); }
   // how far this posed copy has moved since it was last searched (seed_delta, mvr_grid.hip): `moved` (mm, an upper bound over the
   // cloud's points; < 0: unknown) accumulates over the poses note_pose() records, from `last_pose`; a fused pass that searches the
   // cloud puts it back to 0.  Valid while last_pose_set == set_id.
@@ -241,10 +224,8 @@ struct Ctx {
   struct G2HJob { std::shared_ptr<CellGrid> grid; std::shared_ptr<Order> order; size_t n; };
   std::vector<G2HJob> g2h_todo;                       // grid_coords_prepare -> flush_g2h
   int unseeded_grid = 0;                              // 1: the forward searches of a fused pass WITHOUT seeds (a registration's first) walk the grid as well (probe, then the listed sets) instead of the culled kernel
-  int seq_model_tail = 1;                             // seq_search 3: the flagged query sets go 1 = to the culled kernel (listed sets), 0 = to the grid's set kernel
-  int seq_cell_points = 4;                            // points per occupied cell the MODEL's grid aims at (seq_search 3)
-  int seq_search = 1;                                 // mvr_icp_align of a posed scan: 1 (default) = the REVERSE searches walk the source scan's cell grid (compaction by the fused pass's kernels, no hipCUB), the forward search stays with the culled kernel; 2 = the forward search too, through the grids of the posed scans the target is made of (nn_parts_kernel: exact, measured slower -- DESIGN.md 4.5); 0 = the culled kernel for both
-  int parts_lanes = 0, parts_max_rows = 25;           // nn_parts_kernel: lanes per query (1, 2, 4, 8; 0 = by the number of parts) and the widest ball (rows of cells) a lane walks itself
+  int seq_cell_points = 4;                            // points per occupied cell the grid of a cloud over its own coordinates aims at (every ensure_model_grid)
+  int seq_search = 1;                                 // mvr_icp_align of a posed scan: the forward search is the culled kernel's; the REVERSE searches 1 (default) = walk the source scan's cell grid (compaction by the fused pass's kernels, no hipCUB), 0 = take the culled kernel too
   int ring_search = 1;                                // fused pass: 1 = seeded searches walk the uniform grid (thread per query), 0 = always the culled kernel
   std::shared_ptr<OrderPool> order_pool = std::make_shared<OrderPool>();
   // per-pair work buffers (grown on demand)
@@ -269,7 +250,6 @@ struct Ctx {
   // index-build scratch
   uint32_t *codes_a = nullptr, *codes_b = nullptr, *idx_a = nullptr; size_t sort_cap = 0;
   void *cub_tmp = nullptr; size_t cub_cap = 0;
-  struct PartDesc *d_parts = nullptr, *h_parts = nullptr; size_t parts_cap = 0;      // the part table of a composite target: device copy and pinned staging
   char *scratch = nullptr; size_t scratch_cap = 0;    // temporaries of the grid builds (grows, never shrinks)
   char *oscratch = nullptr; size_t oscratch_cap = 0;  // temporaries of a batched ordering build (its own buffer: the grid builds use `scratch` on the side stream meanwhile)
   int order_batch = 1;                                // 1 (default): the orderings a call needs for several point sets are built together (one sort); 0: one set after the other
@@ -693,8 +673,7 @@ int launch_nn_grid_sets_batch(Ctx *c, const GridPair *pairs, int n_pairs, float 
 // coordinates; false = not available (the caller uses the culled kernel)
 int cloud_bbox(Ctx *c, const float4 *pts, size_t n, float out[6], bool finite_only = false);      // {lo xyz, hi xyz} on the host (synchronises the stream); finite_only: over the points without a NaN or an infinity (none: lo > hi)
 bool ensure_grid(Ctx *c, Cloud &canon, double reach);
-int ensure_model_grid(Ctx *c, Cloud &t, double reach, bool *ok, bool *no_finite = nullptr);      // the grid of a cloud over its own coordinates (Cloud::mgrid); *no_finite: refused because no point of the cloud is finite
-GridPair make_model_pair(const Cloud &q, const Cloud &t, nnkey_t *keys);
+int ensure_model_grid(Ctx *c, Cloud &t, bool *ok, bool *no_finite = nullptr);      // the grid of a cloud over its own coordinates (Cloud::mgrid); *no_finite: refused because no point of the cloud is finite
 int ensure_grids(Ctx *c, Cloud *const *canon, int count, double reach, hipStream_t on, hipEvent_t after);      // the same for many sets at once, enqueued on `on` (no wait afterwards)      // reach: the search radius the distance map should be able to rule out (mm)
 int refresh_grid_coords_batch(Ctx *c, Cloud *const *posed, int count);
 int ensure_pose_table(Ctx *c);      // (mvr_ctx.hip) fills the device pose records of the chain being enqueued if nobody has yet
@@ -722,21 +701,6 @@ bool drain_bounded(Ctx *c, int ms);           // hipStreamSynchronize -- bounded
 int comm_abort(Ctx *c, const char *why);      // ncclCommAbort + release of anything that could hold the stream; returns MVR_E_RCCL
 int stream_wait(Ctx *c);                      // hipStreamSynchronize; with a communicator: bounded by wait_timeout_ms and watching comm_poll, a timeout aborts
 GridPair make_grid_pair(const Cloud &q, size_t q_begin, size_t q_count, const Cloud &t, nnkey_t *keys);
-// ---- a composite target searched part by part (mvr_grid.hip: nn_parts_kernel)
-struct PartDesc {
-  const float4 *gts; const uint32_t *start; const uint8_t *dt;
-  const uint32_t *dir, *recs; int dt_shift, dtdim[3];
-  float lo[3], inv_h, h, stretch; int dim[3], dt_max;
-  double minv[12];
-  uint32_t base, n;
-};
-// forward search of the queries q.sorted[0, nq) in the `count` parts described at c->d_parts: keys[original query index] =
-// (d2 bits, COMPOSITE original target index), kKeyInit = nothing within cap2; heavy[sorted position] = 1 for the queries
-// that were NOT answered here (an unbounded ball too wide to walk): the culled kernel takes those
-int launch_nn_parts(Ctx *c, const Cloud &q, int count, float cap2, bool fma, nnkey_t *keys, uint8_t *heavy, const uint32_t *qbound = nullptr);
-int fill_part_coords(Ctx *c, Cloud &target, GridPart &part);
-// keys[original index of sorted[pos]] = by_pos[pos] for the flagged positions (the culled kernel answers flagged queries by sorted position)
-int launch_merge_flagged_keys(Ctx *c, const float4 *sorted, const uint8_t *flags, const nnkey_t *by_pos, size_t n, nnkey_t *keys);      // target.gsorted[part.base ...] <- the part's coordinates in its grid's order
 int launch_nn_cull(Ctx *c, const Cloud &q, size_t q_begin, size_t q_count, const uint8_t *qflags, const Cloud &t, float cap2,
                    bool fma, nnkey_t *keys);
 // one scan pair of a batched global pass (mvr_pair_moments2_batch, culled mode): everything the glue and the

@@ -200,7 +200,7 @@ API int mvr_knn(mvr_ctx *ctx, int qs, int ts, int k, int fma, uint32_t *idx, flo
   if (int rc = fill_target(c, t, S)) return rc;
   if (qs != ts && q.n >= 4) {      // the queries' own grid gives them their walking order
     bool ok = false;
-    if (int rc = ensure_model_grid(c, q, 0.0, &ok)) return rc;
+    if (int rc = ensure_model_grid(c, q, &ok)) return rc;
   }
   fill_queries(q, S);
   const size_t m = q.n * (size_t)k;

@@ -214,7 +214,7 @@ inline int fill_target(Ctx *c, Cloud &t, KnnSlot &S)
   if (t.n == 0) return MVR_OK;
   bool ok = false;
   bool no_finite = false;
-  if (int rc = ensure_model_grid(c, t, 0.0, &ok, &no_finite)) return rc;
+  if (int rc = ensure_model_grid(c, t, &ok, &no_finite)) return rc;
   if (no_finite) S.nt = 0;            // nobody's neighbour, all of them: an empty target (no query scans it)
   if (!ok) return MVR_OK;
   const CellGrid &g = *t.mgrid;

@@ -169,13 +169,15 @@ def _sequential(mvr, ctx, scans, poses0, params, repeat, V, hook=None):
 
 
 @pytest.mark.parametrize("case", ["reference_settings", "two_sweeps", "three_iterations", "ragged_sizes", "wide_radius"])
-def test_sequential_align_through_the_parts_equals_the_culled_search(mvr, orc, case):
-    """mvr_icp_align of a posed scan against the growing model of the sequential mode: the reverse searches walk the
-    source scan's cell grid (seq_search 1, the default) and, with seq_search 2, the forward search goes through the merged
-    scans' pose-invariant grids as well (nn_parts_kernel): the same transformations, counts, residuals and merged cloud,
-    bit for bit, as the culled kernel both ways (seq_search 0) -- with the reference's settings, over two sweeps (the grids are reused, the model is rebuilt),
-    with aligns that iterate (only their first iteration can use the parts), with scans of different sizes and with a
-    radius so wide that most queries go to the fallback.  The first align's correspondences equal the oracle's."""
+def test_sequential_align_over_the_source_grid_equals_the_culled_search(mvr, orc, case):
+    """mvr_icp_align of a posed scan against the growing model of the sequential mode: with the reverse searches walking the
+    source scan's cell grid (seq_search 1, the default) the same transformations, counts, residuals and merged cloud, bit for
+    bit, as with the culled kernel both ways (seq_search 0) -- with the reference's settings, over two sweeps (the grids are
+    reused, the model is rebuilt), with aligns that iterate (only their first iteration can use the grid), with scans of
+    different sizes and with a radius ten times as wide (wide balls leave the thread-per-query walk).  The forward
+    searches' seeds, the iteration row's two ways to the host and the native driver change nothing either.  The tune keys of
+    the forward searches that were removed (seq_search 2 and 3 and their knobs) are refused.  The first align's
+    correspondences equal the oracle's."""
     V, N, max_d = 8, 9000, 4.0
     sp = mvr.synth_params(V, 3)
     sizes = [N] * V if case != "ragged_sizes" else [N - 613 * v for v in range(V)]
@@ -189,9 +191,9 @@ def test_sequential_align_through_the_parts_equals_the_culled_search(mvr, orc, c
         kw = dict(max_dist=40.0, max_iter=1000)
     params = mvr.icp_params(**kw)
     runs = []
-    for mode in (0, 1, 2, 3, 4, 5):  # culled both ways; reverse over the source's grid (default); forward through the parts as well; forward through ONE grid over the model -- its flagged query sets through the culled kernel's listed-set launch (3), the grid's set kernel (4 here: seq_model_tail 0), or, with four lanes per query (no set list), the culled kernel over the flags (5)
+    for mode in (0, 1):  # culled both ways; reverse over the source's grid (default)
         with mvr.Context(0) as ctx:
-            ctx.tune(seq_search=min(mode, 3), seq_model_tail=0 if mode == 4 else 1, grid_lanes=4 if mode == 5 else 1)
+            ctx.tune(seq_search=mode)
             for v in range(V):
                 ctx.upload(16 + v, scans[v])
             ctx.prof_reset(); ctx.prof_enable(1)
@@ -206,7 +208,7 @@ def test_sequential_align_through_the_parts_equals_the_culled_search(mvr, orc, c
     # the matches of the sweep before) -- three sweeps, so that seeds left by seeded searches are used as well
     seeded = []
     # (last arm: the iteration's row fetched by a copy and a synchronise instead of stored to the host by the sums launch itself, align_spin 0)
-    for seed, mode, spin in ((1, 1, 1), (0, 1, 1), (1, 2, 1), (1, 0, 1), (1, 1, 0), (1, 3, 1), (0, 3, 1)):      # (the seeds serve the culled kernel and the walk through the parts' grids alike)
+    for seed, mode, spin in ((1, 1, 1), (0, 1, 1), (1, 0, 1), (1, 1, 0)):
         with mvr.Context(0) as ctx:
             ctx.tune(seq_seed=seed, seq_search=mode, align_spin=spin, lazy_super=spin)
             for v in range(V):
@@ -230,6 +232,10 @@ def test_sequential_align_through_the_parts_equals_the_culled_search(mvr, orc, c
            [(l[0], l[1], l[2], l[3], l[4], l[5]) for l in seeded[0][1]], case
     # ... and against the oracle: the first align's correspondences, one by one
     with mvr.Context(0) as ctx:
+        for gone in (dict(seq_search=2), dict(seq_search=3), dict(seq_model_tail=0), dict(parts_lanes=4), dict(parts_max_rows=8)):
+            with pytest.raises(mvr.MvrError) as refused:
+                ctx.tune(**gone)
+            assert refused.value.status == mvr.E_ARG, gone
         for v in range(V):
             ctx.upload(16 + v, scans[v])
         ctx.transform(0, 16, poses0[0]); ctx.transform(1, 17, poses0[1])

@@ -40,7 +40,7 @@ def test_grid_sizing_is_clean_under_asan_and_ubsan(tmp_path):
 def test_the_library_source_sizes_its_grid_through_the_shared_function():
     """ensure_model_grid holds no sizing arithmetic of its own"""
     src = open(os.path.join(ROOT, "multi-view-registration_amd", "csrc", "mvr_grid.hip")).read()
-    body = src[src.index("int ensure_model_grid("):src.index("GridPair make_model_pair(")]
+    body = src[src.index("int ensure_model_grid("):src.index("int grid_coords_prepare(")]
     assert "model_grid_size(" in body and "std::floor" not in body and "cloud_bbox(c, t.pts, t.n, bb, true)" in body
 
 

@@ -96,7 +96,7 @@ while time.time() < t_end:
     if 4 <= V <= 12:
         params = mvr.icp_params(max_dist=max_d, max_iter=int(rng.choice([1000, 3])), teps=float(rng.choice([1e-6, 0.0])), feps=float(rng.choice([64.0, -1e300])), fma=fma)
         seq = []
-        for knobs in (dict(seq_seed=1), dict(seq_seed=0), dict(seq_search=0, seq_seed=0), dict(seq_search=3), dict(seq_search=3, seq_model_tail=0, seq_cell_points=16)):      # (round 4: one grid over the model)
+        for knobs in (dict(seq_seed=1), dict(seq_seed=0), dict(seq_search=0, seq_seed=0)):
             with mvr.Context(0) as ctx:
                 ctx.tune(**knobs)
                 for v in range(V):
