@@ -792,7 +792,7 @@ enum { MVR_K_NN = 0, MVR_K_REDUCE = 1, MVR_K_XFORM = 2, MVR_K_GLUE = 3,
  * rows of cells; 2: always; 0: by the culled kernel over the set list), "grid_tail" (1, default: that launch and the
  * wave-per-query launch of a forward pass are one launch), "cull_list" (1, default: the culled kernel
  * visits only the query sets the walk listed; 0: a block per set), "cull_list_w" (waves per listed set: 1, 2, 4),
- * "grid_lanes" (lanes sharing a query: 1 (default), 2, 4, 8), "grid_wide_waves" (waves per CU of the wave-per-query
+ * "grid_wide_waves" (waves per CU of the wave-per-query
  * launch), "fused_mark" (1, default: the forward searches record the start bounds of the reverse searches themselves when
  * they are the grid walk; 2: always; 0: never -- a separate launch re-reads the keys), "grid_debug" (1: every pass prints how its queries split; synchronises);
  * "pipeline" (1, default: mvr_ring_run / mvr_ring_run_sharded enqueue pass k+1's whole launch chain while pass k runs,
@@ -825,9 +825,7 @@ enum { MVR_K_NN = 0, MVR_K_REDUCE = 1, MVR_K_XFORM = 2, MVR_K_GLUE = 3,
  * built from then on: 2, default = dense, built through the compact form and expanded; 1 = compact: a directory of 32-cell segments
  * + records of the occupied ones, a tenth of the bytes, walks 8-11 % slower; 0 = the round-3 dense build; also MVR_GRID_INDEX),
  * "order_batch" (1, default: the orderings several point sets need are built in one composite sort; 0: one after the other -- the
- * same permutations), "seed_delta_um" (forward start bounds from the previous distance + the clouds' motion while that is below
- * this many micrometres; 0, default: from the old match's coordinates), "rim_cert_um" (rim certificates with this margin; 0,
- * default: off), "pipeline_multi_rank" (1: passes with a collective over more than one rank may be queued ahead of their poses
+ * same permutations), "pipeline_multi_rank" (1: passes with a collective over more than one rank may be queued ahead of their poses
  * too; 0, default, until a recorded two-GPU run);
  * feature matching and pose scoring: "feat_split" (blocks the target of mvr_feature_knn is split over, 1..64; 0, default: by the
  * launch size), "score_chunk" (poses per launch of mvr_pose_scores, default 256).

@@ -200,7 +200,7 @@ __device__ __forceinline__ Ball grid_ball(const GridPair &a, const float4 q, con
 #ifndef MVR_GRID_THREADS
 #define MVR_GRID_THREADS 128
 #endif
-constexpr int kGridThreads = MVR_GRID_THREADS;      // (threads per block of the walk: 128 and 256 measured equal -- 281 against 282.5 us of kernels per pass --, 512 slower -- 297; 128 it is since the two waves of a block stage ONE region together, MVR_STAGE_BLOCK; tools/ab_variant_kernels.sh)
+constexpr int kGridThreads = MVR_GRID_THREADS;      // (threads per block of the walk: 128 and 256 measured equal -- 281 against 282.5 us of kernels per pass --, 512 slower -- 297; 128 it is since the two waves of a block stage ONE region together; tools/ab_variant_kernels.sh)
 #ifndef MVR_GRID_ROW4
 #define MVR_GRID_ROW4 1
 #endif
@@ -308,7 +308,7 @@ __device__ __forceinline__ uint32_t wave_scan_incl_u32(uint32_t x, uint32_t *tot
 // (the dealt rounds took 4 k cycles per wave instead of 12 k -- making the list cost 13 k, slot allocation by LDS atomics or by a
 // prefix sum alike); more points per wave at fewer waves per SIMD (256 / 320 / 448 points: 98 / 122 / 141 us); a per-cell table
 // in LDS instead of the lanes' own range loads (a box of up to 7 cells along x: 20 % of the waves are wider); the probe as part
-// of the staged step (97 -> 113 us); start bounds without the seed's two gathers (seed_delta: exact, equal).  The REVERSE
+// of the staged step (97 -> 113 us); start bounds without the seed's two gathers (exact, equal).  The REVERSE
 // launch's queries are 2.4 x sparser (the matched targets): its waves want ~350 points, 14 % of them fit, and it stays with the
 // plain walk (70 us against 72 staged).  Memory-side traffic is unchanged (286 MB per forward launch): a wave's lines were
 // shared through the L1 / L2 before, they are fetched once per wave now -- the misses are the same lines.
@@ -321,20 +321,10 @@ __device__ __forceinline__ uint32_t wave_scan_incl_u32(uint32_t x, uint32_t *tot
 #ifndef MVR_STAGE_BURST
 #define MVR_STAGE_BURST 4
 #endif
-#ifndef MVR_STAGE_PROBE
-#define MVR_STAGE_PROBE 0
-#endif
-#ifndef MVR_STAGE_BLOCK
-#define MVR_STAGE_BLOCK (MVR_GRID_THREADS == 128)
-#endif
 constexpr int kStageRows = MVR_STAGE_ROWS;     // rows of cells of a wave's box: one or two per lane
 constexpr int kStagePts = MVR_STAGE_PTS;       // points a wave stages at most (16 bytes each; + the table: ~7.5 KB of LDS per wave at 384)
 
-// G lanes share a query: lane `sub` of the group walks rows sub, sub + G, ... of the ball's rows of cells, the group's
-// answers meet in log2(G) shuffles.  (One lane per query leaves a wave waiting for its widest ball -- rows times points
-// of dependent round trips; dealing the rows to G lanes cuts that chain G-fold and the spread between lanes with it.
-// The query, its seed and its cell range are loaded by all G lanes from the same addresses: one request.)
-// (at least seven waves per SIMD: what the staged walk's LDS admits -- it sits at 74 registers without the hint, one too many; the plain
+// One lane per query.  (at least seven waves per SIMD: what the staged walk's LDS admits -- it sits at 74 registers without the hint, one too many; the plain
 // instantiations need fewer than 64 and keep their eighth wave)
 #ifndef MVR_STAGE_WAVES
 #define MVR_STAGE_WAVES 7
@@ -344,18 +334,15 @@ constexpr int kStagePts = MVR_STAGE_PTS;       // points a wave stages at most (
 #else
 #define MVR_GRID_OCC
 #endif
-template <bool FMA, int G, bool STAGE>
+template <bool FMA, bool STAGE>
 __global__ void __launch_bounds__(kGridThreads) MVR_GRID_OCC nn_grid_kernel(GridBatch batch, XcdMap map, unsigned long long *__restrict__ evals, unsigned long long *__restrict__ stage_stat)
 {
-  static_assert(!STAGE || G == 1, "the staged walk is the one-lane-per-query walk");
-  constexpr uint32_t kPerBlock = kGridThreads / G;
   uint32_t pair = 0, set = 0;
   if (!xcd_map_block(map, blockIdx.x, &pair, &set)) return;
   const GridPair &a = batch.p[pair];
   const float cap2 = batch.cap2;
   const uint32_t nq = a.qlist ? min(*a.qcount, a.q_count) : a.q_count;
-  const uint32_t sub = threadIdx.x % G;
-  const uint32_t pos = set * kPerBlock + threadIdx.x / G;
+  const uint32_t pos = set * kGridThreads + threadIdx.x;
   unsigned long long n_eval = 0;
   bool went_wide = false, went_cull = false;
 #ifdef MVR_STAGE_CLOCK
@@ -405,32 +392,21 @@ __global__ void __launch_bounds__(kGridThreads) MVR_GRID_OCC nn_grid_kernel(Grid
         if (++yy == ny) { yy = 0; row += z_step; }
         row_range(row, s2, e2);
       }
-      if (sub == 0) n_eval += e - s;
-      if (G == 1) {
-        // one lane per query: four CONSECUTIVE points per round from one address (the loads differ by their immediate offsets).
-        // A short row runs on into the points behind it -- points of the target all the same: looking at one more changes
-        // nothing (whatever lies within the bound lies in the ball's cells and is looked at anyway); only the array's end is
-        // kept clear of (the last round starts four points before it at the latest).
-        for (uint32_t k = s; k < e; k += 4) {
-          const uint32_t kb = min(k, nt4);
-          const float4 *__restrict__ p4 = a.gts + kb;
-          const float4 t0 = p4[0], t1 = p4[1], t2 = p4[2], t3 = p4[3];
-          take(t0); take(t1); take(t2); take(t3);
-        }
-      } else {
-        // G lanes per query: they take CONSECUTIVE points of the row -- one instruction, one cache line per query
-        // (what a gather costs in the L1 is the number of distinct lines its lanes touch, not the bytes per lane:
-        // tools/exp_ta.hip), two rounds in flight
-        for (uint32_t k = s + sub; k < e; k += 2 * G) {
-          const uint32_t k1 = k + G < e ? k + G : k;
-          const float4 t0 = a.gts[k], t1 = a.gts[k1];
-          take(t0); take(t1);
-        }
+      n_eval += e - s;
+      // four CONSECUTIVE points per round from one address (the loads differ by their immediate offsets).
+      // A short row runs on into the points behind it -- points of the target all the same: looking at one more changes
+      // nothing (whatever lies within the bound lies in the ball's cells and is looked at anyway); only the array's end is
+      // kept clear of (the last round starts four points before it at the latest).
+      for (uint32_t k = s; k < e; k += 4) {
+        const uint32_t kb = min(k, nt4);
+        const float4 *__restrict__ p4 = a.gts + kb;
+        const float4 t0 = p4[0], t1 = p4[1], t2 = p4[2], t3 = p4[3];
+        take(t0); take(t1); take(t2); take(t3);
       }
       s = s2; e = e2;
     }
   };
-  // (prologue state that outlives it: with STAGE the probe of a wide ball is itself a staged walk, so the prologue is cut in two)
+  // (prologue state that outlives it: route(), its second half, runs once the probe has been walked)
   float rx = 0.f, ry = 0.f, rz = 0.f;
   bool worth = false, seeded = false, wants_probe = false, wide = false;
   int px0 = 0, px1 = -1, py0 = 0, py1 = -1, pz0 = 0, pz1 = -1;      // the probe's 2 x 2 x 2 cells
@@ -442,28 +418,14 @@ __global__ void __launch_bounds__(kGridThreads) MVR_GRID_OCC nn_grid_kernel(Grid
     if (a.qraw) q = pose_query_f64(load_pose_uniform(a.qpose_dev), a.qraw, qpos);
     else q = a.qs[qpos];
     const uint32_t start_bits = a.qbound ? a.qbound[qpos] : 0xFFFFFFFFu;
-    const unsigned long long pkey = a.seed_from_keys ? a.keys[qpos] : kKeyInit;
-    const uint32_t prev = (uint32_t)pkey;
+    const uint32_t prev = (uint32_t)(a.seed_from_keys ? a.keys[qpos] : kKeyInit);
     // the bound: the cap, or a distance within which a point is KNOWN to exist (inclusive)
     float bound = cap2;
     if (start_bits <= __float_as_uint(bound)) { bound = __uint_as_float(start_bits); seeded = true; }
-    const float pdelta = (a.seed_from_keys || a.cert) ? (a.pose_dev ? a.pose_dev->delta + (a.qpose_dev ? a.qpose_dev->delta : 1.0e30f) : a.delta) : -1.f;
     if (prev < a.nt) {
-      // the query's match of the pass before is still a point of the target: its distance NOW bounds the nearest point's.
-      // seed_delta: while the two clouds have moved by little since (delta: an upper bound from the poses, through the device
-      // records or by value) that distance is at most the old one + delta -- no need to gather the point's coordinates (two
-      // dependent gathers at the head of every wave).  What the slack covers: the float roundings of the four posed points
-      // involved (half an ulp per coordinate at their magnitude: the 4e-6 |q|_1 term, as in grid_ball), of the two distance
-      // formulas and of the square root (the 1.000001 factors); the old and the new distance are compared as real numbers.
-      const float delta = pdelta;
-      if (delta >= 0.f && delta <= batch.delta_max) {
-        const float b = __builtin_amdgcn_sqrtf(__uint_as_float((uint32_t)(pkey >> 32))) * 1.000001f + delta + (1.0e-3f + 4.0e-6f * (fabsf(q.x) + fabsf(q.y) + fabsf(q.z)));
-        const float b2 = b * b * 1.000001f;
-        if (b2 <= bound) { bound = b2; seeded = true; }
-      } else {
-        const float d = gdist2<FMA>(a.gts[a.h2g[prev]], q.x, q.y, q.z);      // (the same point, read from the array the walk is about to read)
-        if (d <= bound) { bound = d; seeded = true; }
-      }
+      // the query's match of the pass before is still a point of the target: its distance NOW bounds the nearest point's
+      const float d = gdist2<FMA>(a.gts[a.h2g[prev]], q.x, q.y, q.z);      // (the same point, read from the array the walk is about to read)
+      if (d <= bound) { bound = d; seeded = true; }
     }
     // the ball in the target's canonical frame (the mapping itself is done in double)
     const Ball ball = grid_ball(a, q, bound);
@@ -480,21 +442,10 @@ __global__ void __launch_bounds__(kGridThreads) MVR_GRID_OCC nn_grid_kernel(Grid
       const int cx = cell_of(rx, a.lo[0], a.inv_h, a.dim[0]), cy = cell_of(ry, a.lo[1], a.inv_h, a.dim[1]), cz = cell_of(rz, a.lo[2], a.inv_h, a.dim[2]);
       worth = !(dt_least_of(a, dt_of(a, cx, cy, cz)) > rad);
     }
-    if (a.cert) {
-      // a rim certificate: an earlier pass proved that NO target point lies within the cap + a margin of this query, and the two
-      // clouds have moved by less than what is left of that margin since: there is still none within the cap -- no distance map,
-      // no probe, no listed set.  (What is left must stay above what the float roundings of the posed points can amount to.)
-      const float cm = a.cert[qpos];
-      if (cm > 0.f) {
-        float rem = (!seeded && pdelta >= 0.f) ? cm - pdelta : 0.f;
-        if (rem > 2.0e-3f + 4.0e-6f * (fabsf(q.x) + fabsf(q.y) + fabsf(q.z))) worth = false; else rem = 0.f;
-        a.cert[qpos] = rem;
-      }
-    }
     best = ((unsigned long long)__float_as_uint(bound) << 32) | kNone;
     const int nrows = (y1 - y0 + 1) * (z1 - z0 + 1);
     wide = worth && nrows > batch.light_rows;
-    wants_probe = G == 1 && worth && batch.probe && nrows > batch.probe_rows;
+    wants_probe = worth && batch.probe && nrows > batch.probe_rows;
     if (wants_probe) {
       // A wide ball is a LOOSE bound more often than a far neighbour: the seed of a pass after a large motion (the first passes
       // of a registration, a restart) is the old match, a millimetre or two off, while the nearest point is where it always
@@ -525,80 +476,58 @@ __global__ void __launch_bounds__(kGridThreads) MVR_GRID_OCC nn_grid_kernel(Grid
     // wide balls are not walked here: without a bound they come in clusters (the rim of the overlap) and go to the culled
     // kernel, which answers 64 neighbouring queries at once; with a bound they are scattered and get a wave each
     bool to_cull = wide && a.heavy != nullptr && (!seeded || a.wide_list == nullptr);
-    if (G == 1 && a.heavy != nullptr && a.wide_list != nullptr) {
+    if (a.heavy != nullptr && a.wide_list != nullptr) {
       // ... unless the wave is full of them (a stretch of rim whose matches lie far: the same 64 queries are one set of the culled kernel)
       if (__popcll(__ballot(wide)) >= batch.cluster) to_cull = wide;
     }
     const bool to_wave = wide && !to_cull && a.wide_list != nullptr;
-    if (a.heavy && sub == 0) a.heavy[a.qlist ? pos : qpos] = to_cull ? 1 : 0;
-    went_wide = to_wave && sub == 0;
+    if (a.heavy) a.heavy[a.qlist ? pos : qpos] = to_cull ? 1 : 0;
+    went_wide = to_wave;
     went_cull = to_cull;
     // (a wide query that goes on with a bound from the probe: the launch that answers it starts from the start bound or the
     // seed again -- it finds the probe's point itself; what the probe saves there is nothing, what it costs is four short rows)
     answers = !to_cull && !to_wave;
     walks = answers && worth;
   };
-  // (the probe as part of the STAGED step -- its four rows from LDS too -- was built and measured: the forward launch of a settled
-  // pass 97 -> 113 us, the pass that restarts from the prior 0.58 -> 0.63 ms: a wave with one probing lane stages the hull of the
-  // probe boxes AND walks the refined balls the plain way afterwards, at 72 registers instead of 65.  -DMVR_STAGE_PROBE=1 builds it.)
-  constexpr bool kStageProbe = STAGE && MVR_STAGE_PROBE;
-  if constexpr (!kStageProbe) {
-    if (live) {
-      if (wants_probe) walk_box(px0, px1, py0, py1, pz0, pz1);
-      route();
-    }
+  if (live) {
+    if (wants_probe) walk_box(px0, px1, py0, py1, pz0, pz1);
+    route();
   }
   bool staged = false;
   MVR_CK();
   if constexpr (STAGE) {
     static_assert(kStageRows == 64, "one row of the box per lane");
-    // (MVR_STAGE_BLOCK, the default with blocks of 128 threads: the two waves of a block stage ONE region for their 128 queries -- the
-    // hull of both, a row of it per THREAD, twice the points -- instead of one each.  Settled passes equal (the hull of 128 Hilbert
-    // neighbours holds 1.4 x the points of 64, the waves wait for each other at five barriers); the passes after a large motion, whose
-    // balls are wide, fit the shared 384 points where they overflowed 192: pass 1 of a window from the prior 0.58 -> 0.54 ms, its first
-    // ten passes 0.372 -> 0.364 ms.  -DMVR_GRID_THREADS=256 -DMVR_STAGE_BLOCK=0 builds the per-wave form.)
-    constexpr bool kBlk = MVR_STAGE_BLOCK != 0;
-    static_assert(!kBlk || kGridThreads == 128 || kGridThreads == 256, "block-wide staging: two or four waves per block");
-    constexpr int kWaves = kGridThreads / 64, kSets = kBlk ? 1 : kWaves;
-    constexpr int kRowsT = kBlk ? kWaves * kStageRows : kStageRows, kPtsT = kBlk ? kWaves * kStagePts : kStagePts, kClear = kBlk ? 4 * kGridThreads : 256;
+    // (The waves of a block stage ONE region for all its queries -- the hull of them, a row of it per THREAD, kStagePts points per
+    // wave -- instead of one each.  Settled passes equal (the hull of 128 Hilbert neighbours holds 1.4 x the points of 64, the waves
+    // wait for each other at five barriers); the passes after a large motion, whose balls are wide, fit the shared 384 points where
+    // they overflowed 192: pass 1 of a window from the prior 0.58 -> 0.54 ms, its first ten passes 0.372 -> 0.364 ms.)
+    static_assert(kGridThreads == 128 || kGridThreads == 256, "block-wide staging: two or four waves per block");
+    constexpr int kWaves = kGridThreads / 64;
+    constexpr int kRowsT = kWaves * kStageRows, kPtsT = kWaves * kStagePts, kClear = 4 * kGridThreads;
     typedef typename std::conditional<(kRowsT > 255), uint16_t, uint8_t>::type mark_t;      // (row + 1 per staged position: 256 rows need nine bits)
     constexpr int kMarkBytesRaw = (kPtsT + 3 + 63) / 64 * 64 * (int)sizeof(mark_t);
     constexpr int kMarkBytes = kMarkBytesRaw < kClear ? kClear : (kMarkBytesRaw + kClear - 1) / kClear * kClear;      // (a multiple of what the threads clear with one store each)
-    __shared__ float4 s_pts[kSets][kPtsT + 4];
-    __shared__ uint2 s_rows[kSets][kRowsT];          // per row of the box: {grid position of its first staged point, staged position of that point} ({~0, ~0}: not staged)
-    __shared__ uint32_t s_mask[kSets][kRowsT];       // per row of the box: the cells (bit c = cell X0 + c) some lane's ball overlaps
-    __shared__ uint32_t s_mark[kSets][kMarkBytes / 4];   // per staged position (a byte each): row + 1 where a row's points begin, else 0
-    __shared__ int s_red[kBlk ? kWaves : 1][8];       // (block-wide staging: the waves' partial results meet here)
-    __shared__ uint32_t s_ends[kBlk ? kRowsT : 1], s_cmax[kBlk ? (kPtsT + 3 + 63) / 64 + 1 : 1];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int sw = kBlk ? 0 : wv, tid = kBlk ? (int)threadIdx.x : lane;
-    float4 *const pts = s_pts[sw];
-    uint2 *const rowtab = s_rows[sw];
-    uint32_t *const rmask = s_mask[sw];
-    mark_t *const mark = reinterpret_cast<mark_t *>(s_mark[sw]);
-    auto sync = [&]() {
-      if constexpr (kBlk) __syncthreads();
-      else { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
-    };
-    // what a lane walks in the staged step: the box of its ball -- or, for a ball that is to be probed first, the probe's
-    // 2 x 2 x 2 cells (the probe IS a walk: in the passes after a large motion nearly every lane probes, and four rows from
-    // global memory per lane was what those passes' launches were made of)
-    const bool pb = kStageProbe && wants_probe;
-    const bool swalk = kStageProbe ? (live && worth && (wants_probe || !wide)) : walks;
-    const int bx0 = pb ? px0 : x0, bx1 = pb ? px1 : x1, by0 = pb ? py0 : y0, by1 = pb ? py1 : y1, bz0 = pb ? pz0 : z0, bz1 = pb ? pz1 : z1;
+    __shared__ float4 s_pts[kPtsT + 4];
+    __shared__ uint2 s_rows[kRowsT];          // per row of the box: {grid position of its first staged point, staged position of that point} ({~0, ~0}: not staged)
+    __shared__ uint32_t s_mask[kRowsT];        // per row of the box: the cells (bit c = cell X0 + c) some lane's ball overlaps
+    __shared__ uint32_t s_mark[kMarkBytes / 4];   // per staged position (a byte each): row + 1 where a row's points begin, else 0
+    __shared__ int s_red[kWaves][8];          // (the waves' partial results meet here)
+    __shared__ uint32_t s_ends[kRowsT], s_cmax[(kPtsT + 3 + 63) / 64 + 1];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, tid = (int)threadIdx.x;
+    mark_t *const mark = reinterpret_cast<mark_t *>(s_mark);
     // ---- 0. every walking lane asks for the ranges of its first rows of cells NOW (they depend on its own ball only): the
     // answers travel while the wave stages.  Rows in y-major order, as the plain walk takes them.
-    const int ny = by1 - by0 + 1, nrows = ny * (bz1 - bz0 + 1);
-    const uint32_t nxm = (uint32_t)(bx1 - bx0);
-    auto row_range = [&](uint32_t row, uint32_t &rs_, uint32_t &re_) { cell_range_of(a, row + (uint32_t)bx0, nxm, rs_, re_); };
-    uint32_t row_g = (uint32_t)((bz0 * a.dim[1] + by0) * a.dim[0]);
+    const int ny = y1 - y0 + 1, nrows = ny * (z1 - z0 + 1);
+    const uint32_t nxm = (uint32_t)(x1 - x0);
+    auto row_range = [&](uint32_t row, uint32_t &rs_, uint32_t &re_) { cell_range_of(a, row + (uint32_t)x0, nxm, rs_, re_); };
+    uint32_t row_g = (uint32_t)((z0 * a.dim[1] + y0) * a.dim[0]);
     const uint32_t row_step = (uint32_t)a.dim[0], z_step_g = (uint32_t)((a.dim[1] - ny) * a.dim[0]);
     int yy = 0;
     constexpr int kBurst = MVR_STAGE_BURST;
     uint32_t bs[kBurst], be[kBurst];
 #pragma unroll
     for (int u = 0; u < kBurst; ++u) { bs[u] = 0; be[u] = 0; }
-    if (swalk) {
+    if (walks) {
 #pragma unroll
       for (int u = 0; u < kBurst; ++u)
         if (u < nrows) {
@@ -608,51 +537,44 @@ __global__ void __launch_bounds__(kGridThreads) MVR_GRID_OCC nn_grid_kernel(Grid
         }
     }
     // ---- 1. the box of the walking lanes' cells
-    int X0 = wave_min_i32(swalk ? bx0 : 0x7FFFFFFF), X1 = wave_max_i32(swalk ? bx1 : -1);
-    int Y0 = 0, Y1 = -1, Z0 = 0, Z1 = -1;
-    if constexpr (kBlk) {
-      Y0 = wave_min_i32(swalk ? by0 : 0x7FFFFFFF); Y1 = wave_max_i32(swalk ? by1 : -1);
-      Z0 = wave_min_i32(swalk ? bz0 : 0x7FFFFFFF); Z1 = wave_max_i32(swalk ? bz1 : -1);
-      if (lane == 0) { s_red[wv][0] = X0; s_red[wv][1] = X1; s_red[wv][2] = Y0; s_red[wv][3] = Y1; s_red[wv][4] = Z0; s_red[wv][5] = Z1; }
-      __syncthreads();
+    int X0 = wave_min_i32(walks ? x0 : 0x7FFFFFFF), X1 = wave_max_i32(walks ? x1 : -1);
+    int Y0 = wave_min_i32(walks ? y0 : 0x7FFFFFFF), Y1 = wave_max_i32(walks ? y1 : -1);
+    int Z0 = wave_min_i32(walks ? z0 : 0x7FFFFFFF), Z1 = wave_max_i32(walks ? z1 : -1);
+    if (lane == 0) { s_red[wv][0] = X0; s_red[wv][1] = X1; s_red[wv][2] = Y0; s_red[wv][3] = Y1; s_red[wv][4] = Z0; s_red[wv][5] = Z1; }
+    __syncthreads();
 #pragma unroll
-      for (int w = 0; w < kWaves; ++w) {
-        if (w == 0) { X0 = s_red[0][0]; X1 = s_red[0][1]; Y0 = s_red[0][2]; Y1 = s_red[0][3]; Z0 = s_red[0][4]; Z1 = s_red[0][5]; }
-        else { X0 = min(X0, s_red[w][0]); X1 = max(X1, s_red[w][1]); Y0 = min(Y0, s_red[w][2]); Y1 = max(Y1, s_red[w][3]); Z0 = min(Z0, s_red[w][4]); Z1 = max(Z1, s_red[w][5]); }
-      }
+    for (int w = 0; w < kWaves; ++w) {
+      if (w == 0) { X0 = s_red[0][0]; X1 = s_red[0][1]; Y0 = s_red[0][2]; Y1 = s_red[0][3]; Z0 = s_red[0][4]; Z1 = s_red[0][5]; }
+      else { X0 = min(X0, s_red[w][0]); X1 = max(X1, s_red[w][1]); Y0 = min(Y0, s_red[w][2]); Y1 = max(Y1, s_red[w][3]); Z0 = min(Z0, s_red[w][4]); Z1 = max(Z1, s_red[w][5]); }
     }
     uint32_t why = 0;      // diagnostics: 1 staged in full, 2 more rows than the table holds (the rows behind it from global memory), 3 too wide, 4 more points than fit (the rows behind from global memory)
     if (X1 >= X0) {
-      if constexpr (!kBlk) {
-        Y0 = wave_min_i32(swalk ? by0 : 0x7FFFFFFF); Y1 = wave_max_i32(swalk ? by1 : -1);
-        Z0 = wave_min_i32(swalk ? bz0 : 0x7FFFFFFF); Z1 = wave_max_i32(swalk ? bz1 : -1);
-      }
       const int NY = Y1 - Y0 + 1, R = NY * (Z1 - Z0 + 1), W = X1 - X0 + 1;
       if (W > 32) why = 3u;
       else {
         const int Rs = min(R, kRowsT);          // rows of the box that get a table entry: the first Rs in y-major order
         // ---- 2a. which cells of which rows are wanted at all: every lane ORs the x-range of its ball into the masks of its rows
         // (the box is the hull of the balls -- a surface runs through it at an angle, most of its cells are nobody's)
-        rmask[tid] = 0u;
+        s_mask[tid] = 0u;
         reinterpret_cast<uint32_t *>(mark)[tid] = 0u;
-        if (kMarkBytes > kClear) { for (int i = kClear / 4 + tid; i < kMarkBytes / 4; i += kClear / 4) reinterpret_cast<uint32_t *>(mark)[i] = 0u; }      // (kClear / 4 = the threads that clear: 64 per wave form, all of the block)
-        sync();
+        if (kMarkBytes > kClear) { for (int i = kClear / 4 + tid; i < kMarkBytes / 4; i += kClear / 4) reinterpret_cast<uint32_t *>(mark)[i] = 0u; }      // (kClear / 4 = the threads that clear: all of the block)
+        __syncthreads();
         const uint32_t z_step_r = (uint32_t)(NY - ny);
-        if (swalk) {
-          const uint32_t bits = ((nxm >= 31u ? 0xFFFFFFFFu : ((2u << nxm) - 1u))) << (uint32_t)(bx0 - X0);
-          uint32_t ridx = (uint32_t)((bz0 - Z0) * NY + (by0 - Y0));
+        if (walks) {
+          const uint32_t bits = ((nxm >= 31u ? 0xFFFFFFFFu : ((2u << nxm) - 1u))) << (uint32_t)(x0 - X0);
+          uint32_t ridx = (uint32_t)((z0 - Z0) * NY + (y0 - Y0));
           int ryi = 0;
           for (int k = 0; k < nrows; ++k) {
-            if (ridx < (uint32_t)kRowsT) __hip_atomic_fetch_or(&rmask[ridx], bits, __ATOMIC_RELAXED, kBlk ? __HIP_MEMORY_SCOPE_WORKGROUP : __HIP_MEMORY_SCOPE_WAVEFRONT);
+            if (ridx < (uint32_t)kRowsT) __hip_atomic_fetch_or(&s_mask[ridx], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             ridx += 1u;
             if (++ryi == ny) { ryi = 0; ridx += z_step_r; }
           }
         }
-        sync();
+        __syncthreads();
         // ---- 2b. the rows of the box, a lane each (row `lane` = (Y0 + lane % NY, Z0 + lane / NY)): where its wanted cells
         // [first, last] begin and end in the grid-ordered array
         uint32_t sA = 0, len = 0, P = 0;
-        const uint32_t m = tid < Rs ? rmask[tid] : 0u;
+        const uint32_t m = tid < Rs ? s_mask[tid] : 0u;
         if (m) {
           const int zq = (int)(((float)tid + 0.5f) * (1.0f / (float)NY)), yq = tid - zq * NY;      // (tid / NY: the float quotient is off by 1e-5 at most, the true one sits 1 / (2 NY) from an integer)
           const uint32_t base = (uint32_t)(((Z0 + zq) * a.dim[1] + (Y0 + yq)) * a.dim[0] + X0);
@@ -661,37 +583,30 @@ __global__ void __launch_bounds__(kGridThreads) MVR_GRID_OCC nn_grid_kernel(Grid
           len = cell_start_of(a, base + last + 1u) - sA;
         }
         uint32_t off = wave_scan_incl_u32(len, &P) - len;
-        if constexpr (kBlk) {      // (the second wave's rows begin behind the first wave's)
-          if (lane == 0) s_red[wv][6] = (int)P;
-          __syncthreads();
-          P = 0u;
+        if (lane == 0) s_red[wv][6] = (int)P;      // (the second wave's rows begin behind the first wave's)
+        __syncthreads();
+        P = 0u;
 #pragma unroll
-          for (int w = 0; w < kWaves; ++w) { if (w < wv) off += (uint32_t)s_red[w][6]; P += (uint32_t)s_red[w][6]; }
-        }
+        for (int w = 0; w < kWaves; ++w) { if (w < wv) off += (uint32_t)s_red[w][6]; P += (uint32_t)s_red[w][6]; }
         // rows are staged in order while they fit: a row that does not fit any more (and every row behind it) is walked from
         // global memory by the lanes that want it -- the staging degrades row by row instead of failing for the wave
         staged = true;
         const bool fits = off + len <= (uint32_t)kPtsT;
         why = P > (uint32_t)kPtsT ? 4u : R > kRowsT ? 2u : 1u;
-        rowtab[tid] = fits ? make_uint2(sA, off) : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+        s_rows[tid] = fits ? make_uint2(sA, off) : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
         if (fits && len) mark[off] = (mark_t)(tid + 1);
         uint32_t Ps = P;
         if (P > (uint32_t)kPtsT) {      // (what is staged: the rows before the first that does not fit -- `fits` is monotone)
-          if constexpr (kBlk) {
-            s_ends[tid] = off + len;
-            const int nf = __popcll(__ballot(fits));
-            if (lane == 0) s_red[wv][7] = nf;
-            __syncthreads();
-            int nfit = 0;
+          s_ends[tid] = off + len;
+          const int nf = __popcll(__ballot(fits));
+          if (lane == 0) s_red[wv][7] = nf;
+          __syncthreads();
+          int nfit = 0;
 #pragma unroll
-            for (int w = 0; w < kWaves; ++w) nfit += s_red[w][7];
-            Ps = nfit ? s_ends[nfit - 1] : 0u;
-          } else {
-            const int nfit = __popcll(__ballot(fits));
-            Ps = nfit ? (uint32_t)__builtin_amdgcn_readlane((int)(off + len), nfit - 1) : 0u;
-          }
+          for (int w = 0; w < kWaves; ++w) nfit += s_red[w][7];
+          Ps = nfit ? s_ends[nfit - 1] : 0u;
         }
-        sync();
+        __syncthreads();
         MVR_CK();
         // ---- 3. the points: staged position j <- the row whose range holds it: the last row that begins at or before j -- a
         // running maximum over the positions' marks (row + 1 where a row begins), 64 positions at a time; three more positions
@@ -699,73 +614,49 @@ __global__ void __launch_bounds__(kGridThreads) MVR_GRID_OCC nn_grid_kernel(Grid
         // instruction, and the instruction is an LDS-DMA load (global_load_lds_dwordx4: per-lane source address, destination
         // = a wave-uniform LDS address + 16 x lane): no registers for the data, no ds_write, ALL of a wave's point loads in
         // flight at once.
-        if constexpr (kBlk) {
-          // (chunks of 64 staged positions alternate between the two waves; the running maximum of the marks is taken inside a
-          // chunk first, the chunks' maxima meet in LDS, then every chunk adds what lies before it)
-          constexpr int kChunks = (kPtsT + 3 + 63) / 64, kOwn = (kChunks + kWaves - 1) / kWaves;
-          const uint32_t Pm1 = Ps ? Ps - 1u : 0u, n_stage = Ps ? Ps + 3u : 0u;
-          int vv[kOwn];
+        // (chunks of 64 staged positions alternate between the two waves; the running maximum of the marks is taken inside a
+        // chunk first, the chunks' maxima meet in LDS, then every chunk adds what lies before it)
+        constexpr int kChunks = (kPtsT + 3 + 63) / 64, kOwn = (kChunks + kWaves - 1) / kWaves;
+        const uint32_t Pm1 = Ps ? Ps - 1u : 0u, n_stage = Ps ? Ps + 3u : 0u;
+        int vv[kOwn];
 #pragma unroll
-          for (int k = 0; k < kOwn; ++k) {
-            const int c = kWaves * k + wv;
-            vv[k] = 0;
-            if (c < kChunks && (uint32_t)(c * 64) < n_stage) {
-              const uint32_t j = (uint32_t)(c * 64 + lane);
-              int v = j <= Pm1 ? (int)mark[j] : 0;
-              v = max(v, dpp_keep<0x111>(v)); v = max(v, dpp_keep<0x112>(v)); v = max(v, dpp_keep<0x114>(v)); v = max(v, dpp_keep<0x118>(v));
-              const int r0 = __builtin_amdgcn_readlane(v, 15), r1 = __builtin_amdgcn_readlane(v, 31), r2 = __builtin_amdgcn_readlane(v, 47), r3 = __builtin_amdgcn_readlane(v, 63);
-              const int q4 = lane >> 4;
-              const int before = q4 == 0 ? 0 : q4 == 1 ? r0 : q4 == 2 ? max(r0, r1) : max(max(r0, r1), r2);
-              vv[k] = max(v, before);
-              if (lane == 0) s_cmax[c] = (uint32_t)max(max(r0, r1), max(r2, r3));
-            }
+        for (int k = 0; k < kOwn; ++k) {
+          const int c = kWaves * k + wv;
+          vv[k] = 0;
+          if (c < kChunks && (uint32_t)(c * 64) < n_stage) {
+            const uint32_t j = (uint32_t)(c * 64 + lane);
+            int v = j <= Pm1 ? (int)mark[j] : 0;
+            v = max(v, dpp_keep<0x111>(v)); v = max(v, dpp_keep<0x112>(v)); v = max(v, dpp_keep<0x114>(v)); v = max(v, dpp_keep<0x118>(v));
+            const int r0 = __builtin_amdgcn_readlane(v, 15), r1 = __builtin_amdgcn_readlane(v, 31), r2 = __builtin_amdgcn_readlane(v, 47), r3 = __builtin_amdgcn_readlane(v, 63);
+            const int q4 = lane >> 4;
+            const int before = q4 == 0 ? 0 : q4 == 1 ? r0 : q4 == 2 ? max(r0, r1) : max(max(r0, r1), r2);
+            vv[k] = max(v, before);
+            if (lane == 0) s_cmax[c] = (uint32_t)max(max(r0, r1), max(r2, r3));
           }
-          __syncthreads();
-#pragma unroll
-          for (int k = 0; k < kOwn; ++k) {
-            const int c = kWaves * k + wv;
-            if (c < kChunks && (uint32_t)(c * 64) < n_stage) {
-              int carry = 0;
-              for (int cc = 0; cc < c; ++cc) carry = max(carry, (int)s_cmax[cc]);
-              const uint32_t j = (uint32_t)(c * 64 + lane), jj = min(j, Pm1);
-              const int v = max(vv[k], carry);
-              const uint2 t = rowtab[v - 1];          // (v >= 1: position 0 is the beginning of the first row with points)
-              if (j < n_stage)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(a.gts + (t.x + (jj - t.y))),
-                                                 (__attribute__((address_space(3))) void *)(pts + c * 64), 16, 0, 0);
-            }
-          }
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else
-        if (Ps) {
-          const uint32_t Pm1 = Ps - 1u, n_stage = Ps + 3u;
-          int carry = 0;
-#pragma unroll
-          for (int c = 0; c < (kStagePts + 3 + 63) / 64; ++c) {
-            if ((uint32_t)(c * 64) < n_stage) {          // (uniform)
-              const uint32_t j = (uint32_t)(c * 64 + lane), jj = min(j, Pm1);
-              int v = j <= Pm1 ? (int)mark[j] : 0;
-              v = max(v, dpp_keep<0x111>(v)); v = max(v, dpp_keep<0x112>(v)); v = max(v, dpp_keep<0x114>(v)); v = max(v, dpp_keep<0x118>(v));      // running maximum inside the rows of 16 lanes
-              const int r0 = __builtin_amdgcn_readlane(v, 15), r1 = __builtin_amdgcn_readlane(v, 31), r2 = __builtin_amdgcn_readlane(v, 47), r3 = __builtin_amdgcn_readlane(v, 63);
-              const int q4 = lane >> 4;
-              const int before = q4 == 0 ? carry : q4 == 1 ? max(carry, r0) : q4 == 2 ? max(carry, max(r0, r1)) : max(carry, max(max(r0, r1), r2));
-              v = max(v, before);
-              carry = max(max(carry, max(r0, r1)), max(r2, r3));
-              const uint2 t = rowtab[v - 1];          // (v >= 1: position 0 is the beginning of the first row with points)
-              if (j < n_stage)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(a.gts + (t.x + (jj - t.y))),
-                                                 (__attribute__((address_space(3))) void *)(pts + c * 64), 16, 0, 0);
-            }
-          }
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the DMA writes count as vector memory operations of this wave
         }
-        sync();
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kOwn; ++k) {
+          const int c = kWaves * k + wv;
+          if (c < kChunks && (uint32_t)(c * 64) < n_stage) {
+            int carry = 0;
+            for (int cc = 0; cc < c; ++cc) carry = max(carry, (int)s_cmax[cc]);
+            const uint32_t j = (uint32_t)(c * 64 + lane), jj = min(j, Pm1);
+            const int v = max(vv[k], carry);
+            const uint2 t = s_rows[v - 1];          // (v >= 1: position 0 is the beginning of the first row with points)
+            if (j < n_stage)
+              __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(a.gts + (t.x + (jj - t.y))),
+                                               (__attribute__((address_space(3))) void *)(s_pts + c * 64), 16, 0, 0);
+          }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the DMA writes count as vector memory operations of this wave
+        __syncthreads();
         MVR_CK();
         // ---- 4. every lane walks its own cells: a row's range in the grid-ordered array (asked for above, kBurst rows at a
         // time) becomes a range of staged positions through the row's table entry -- or stays what it is for a row that was
         // not staged
-        if (swalk) {
-          uint32_t ridx = (uint32_t)((bz0 - Z0) * NY + (by0 - Y0));
+        if (walks) {
+          uint32_t ridx = (uint32_t)((z0 - Z0) * NY + (y0 - Y0));
           int ryi = 0;
           for (int k0 = 0; k0 < nrows; k0 += kBurst) {
             if (k0) {
@@ -781,14 +672,14 @@ __global__ void __launch_bounds__(kGridThreads) MVR_GRID_OCC nn_grid_kernel(Grid
             for (int u = 0; u < kBurst; ++u)
               if (k0 + u < nrows) {
                 uint2 t = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
-                if (ridx < (uint32_t)kRowsT) t = rowtab[ridx];
+                if (ridx < (uint32_t)kRowsT) t = s_rows[ridx];
                 ridx += 1u;
                 if (++ryi == ny) { ryi = 0; ridx += z_step_r; }
                 n_eval += be[u] - bs[u];
                 if (t.y != 0xFFFFFFFFu) {
                   const uint32_t ka = t.y + (bs[u] - t.x), kb = t.y + (be[u] - t.x);
                   for (uint32_t k = ka; k < kb; k += 4) {
-                    const float4 *p4 = pts + k;
+                    const float4 *p4 = s_pts + k;
                     const float4 t0 = p4[0], t1 = p4[1], t2 = p4[2], t3 = p4[3];
                     take(t0); take(t1); take(t2); take(t3);
                   }
@@ -805,17 +696,7 @@ __global__ void __launch_bounds__(kGridThreads) MVR_GRID_OCC nn_grid_kernel(Grid
       }
     }
     if (stage_stat && lane == 0 && why) atomicAdd(stage_stat + (size_t)((blockIdx.x * 4u + (uint32_t)wv) & 63u) * 64u + why + (a.qlist ? 8u : 0u), 1ull);      // (64 shards of 64 counters; + 8: a launch over a compacted query list, i.e. the reverse searches)
-    // ---- 5. the rest of the prologue: what the probe found, where the query goes; a lane whose probe did not settle it (its new
-    // ball reaches beyond the probed cells, or the probe found nothing) walks that ball the plain way
-    if constexpr (kStageProbe) {
-      if (staged) {
-        if (live) route();
-        if (walks && !wants_probe) walks = false;          // (walked above, from LDS)
-      } else if (live) {
-        if (wants_probe) walk_box(px0, px1, py0, py1, pz0, pz1);
-        route();
-      }
-    } else if (staged) walks = false;                      // (walked above, from LDS)
+    if (staged) walks = false;                      // (walked above, from LDS)
   }
 #ifdef MVR_STAGE_CLOCK
   if (!staged) { while (ckn < 4) { ck[ckn] = (long long)__builtin_readcyclecounter(); ++ckn; } }      // (a wave that was not staged: phases 1 / 2 hold whatever the attempt cost)
@@ -823,28 +704,20 @@ __global__ void __launch_bounds__(kGridThreads) MVR_GRID_OCC nn_grid_kernel(Grid
   if (walks) walk_box(x0, x1, y0, y1, z0, z1);      // (the plain walk: every walking lane without STAGE; with it, the lanes the staged step left over)
   MVR_CK();
   if (answers) {
-    // the group's answer: the smallest (d2, index) of its lanes
-#pragma unroll
-    for (int o = 1; o < G; o <<= 1) {
-      const unsigned long long ob = __shfl_xor(best, o, 64);
-      if (ob < best) best = ob;
-    }
     const float bd = __uint_as_float((uint32_t)(best >> 32));
     const uint32_t bi = (uint32_t)best;
-    if (sub == 0) {
-      const bool found = bi != kNone && bd <= cap2;
-      const uint32_t ord = a.qlist ? pos : (a.key_by_pos ? qpos : __float_as_uint(q.w));
-      uint32_t low = bi;
-      if (found && (a.key_by_pos || a.mark)) {
-        const uint32_t hp = a.tinv[bi];              // the match's position in its set's Hilbert order
-        if (a.key_by_pos) low = hp;
-        if (a.mark) __hip_atomic_store(&a.mark[hp], __float_as_uint(bd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      a.keys[ord] = found ? (((nnkey_t)__float_as_uint(bd) << 32) | low) : kKeyInit;
+    const bool found = bi != kNone && bd <= cap2;
+    const uint32_t ord = a.qlist ? pos : (a.key_by_pos ? qpos : __float_as_uint(q.w));
+    uint32_t low = bi;
+    if (found && (a.key_by_pos || a.mark)) {
+      const uint32_t hp = a.tinv[bi];              // the match's position in its set's Hilbert order
+      if (a.key_by_pos) low = hp;
+      if (a.mark) __hip_atomic_store(&a.mark[hp], __float_as_uint(bd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    a.keys[ord] = found ? (((nnkey_t)__float_as_uint(bd) << 32) | low) : kKeyInit;
   }
-  if (G == 1 && a.cull_sets) {   // a wave = one 64-query set of the culled kernel: listed if any of its queries was flagged
-    if (__ballot(went_cull) != 0ull && (threadIdx.x & 63) == 0) a.cull_sets[atomicAdd(a.cull_count, 1u)] = (set * kPerBlock + threadIdx.x) >> 6;
+  if (a.cull_sets) {   // a wave = one 64-query set of the culled kernel: listed if any of its queries was flagged
+    if (__ballot(went_cull) != 0ull && (threadIdx.x & 63) == 0) a.cull_sets[atomicAdd(a.cull_count, 1u)] = (set * kGridThreads + threadIdx.x) >> 6;
   }
   {   // the wave's wide queries: one counter bump per wave, ordinals in lane order
     const unsigned long long m = __ballot(went_wide);
@@ -1560,8 +1433,7 @@ int launch_nn_grid_batch(Ctx *c, const GridPair *pairs, int n_pairs, float cap2,
     GridBatch batch;
     XcdMap map;
     const int m = std::min(kGridBatchPairs, n_pairs - base);
-    const int lanes = (c->grid_lanes == 1 || c->grid_lanes == 2 || c->grid_lanes == 8) ? c->grid_lanes : 4;
-    const size_t per_block = (size_t)(kGridThreads / lanes);
+    const size_t per_block = (size_t)kGridThreads;
     size_t total = 0;
     for (int k = 0; k < kBatchPairs; ++k) map.sets[k] = 0;
     for (int k = 0; k < kGridBatchPairs; ++k) {
@@ -1580,7 +1452,6 @@ int launch_nn_grid_batch(Ctx *c, const GridPair *pairs, int n_pairs, float cap2,
     batch.cluster = c->grid_cluster;
     batch.probe = c->grid_probe;
     batch.probe_rows = std::min(c->grid_probe_rows, batch.light_rows);
-    batch.delta_max = 1.0e-3f * (float)c->seed_delta_um;
     if (total == 0) continue;
     map.n_pairs = (uint32_t)m;
     unsigned grid_blocks = 0;
@@ -1588,8 +1459,8 @@ int launch_nn_grid_batch(Ctx *c, const GridPair *pairs, int n_pairs, float cap2,
     const bool per_launch = c->prof && !c->prof_totals;
     if (per_launch) MVR_HIP_TRY(c, hipMemsetAsync(c->evals, 0, kEvalRegion * sizeof(unsigned long long), c->stream));
     ProfScope ps(c, MVR_K_NN_GRID, per_launch ? c->evals : nullptr, (int)(kEvalRegion * sizeof(unsigned long long)), 1.0, 0.0, per_launch ? kEvalShards : 0);
-#define MVR_GRID_LAUNCH(F, GG) hipLaunchKernelGGL((nn_grid_kernel<F, GG, false>), dim3(grid_blocks), dim3(kGridThreads), 0, c->stream, batch, map, c->evals, (unsigned long long *)nullptr)
-#define MVR_GRID_LAUNCH_STAGED(F) hipLaunchKernelGGL((nn_grid_kernel<F, 1, true>), dim3(grid_blocks), dim3(kGridThreads), 0, c->stream, batch, map, c->evals, c->stage_stat)
+#define MVR_GRID_LAUNCH(F) hipLaunchKernelGGL((nn_grid_kernel<F, false>), dim3(grid_blocks), dim3(kGridThreads), 0, c->stream, batch, map, c->evals, (unsigned long long *)nullptr)
+#define MVR_GRID_LAUNCH_STAGED(F) hipLaunchKernelGGL((nn_grid_kernel<F, true>), dim3(grid_blocks), dim3(kGridThreads), 0, c->stream, batch, map, c->evals, c->stage_stat)
     // (grid_stage 1: the staged walk for launches over a scan's OWN query order only -- the forward searches; a launch over a compacted
     // list, the reverse searches, has queries 2.4 x sparser: with a region per WAVE its boxes did not fit, measured equal or slower.
     // grid_stage 2, the default since a block's two waves stage one region of 448 points together: both -- the step -1.4 %)
@@ -1597,15 +1468,9 @@ int launch_nn_grid_batch(Ctx *c, const GridPair *pairs, int n_pairs, float cap2,
     for (int k = 0; k < m; ++k) listed = listed || (batch.p[k].q_count != 0 && batch.p[k].qlist != nullptr);
     // (a LONE pair's launch over a list -- the reverse search of a sequential align, 3 waves per SIMD -- stays plain: staged it measured
     // 1.5 % of an align slower; grid_stage_lone = 2 stages it all the same)
-    const bool stage = lanes == 1 && c->grid_stage && (c->grid_stage == 2 || !listed) && (n_pairs > 1 || (c->grid_stage_lone && (!listed || c->grid_stage_lone == 2)));
+    const bool stage = c->grid_stage && (c->grid_stage == 2 || !listed) && (n_pairs > 1 || (c->grid_stage_lone && (!listed || c->grid_stage_lone == 2)));
     if (stage) { if (fma) MVR_GRID_LAUNCH_STAGED(true); else MVR_GRID_LAUNCH_STAGED(false); }
-    else
-    switch (lanes) {
-      case 1: if (fma) MVR_GRID_LAUNCH(true, 1); else MVR_GRID_LAUNCH(false, 1); break;
-      case 2: if (fma) MVR_GRID_LAUNCH(true, 2); else MVR_GRID_LAUNCH(false, 2); break;
-      case 8: if (fma) MVR_GRID_LAUNCH(true, 8); else MVR_GRID_LAUNCH(false, 8); break;
-      default: if (fma) MVR_GRID_LAUNCH(true, 4); else MVR_GRID_LAUNCH(false, 4); break;
-    }
+    else { if (fma) MVR_GRID_LAUNCH(true); else MVR_GRID_LAUNCH(false); }
 #undef MVR_GRID_LAUNCH
 #undef MVR_GRID_LAUNCH_STAGED
     MVR_HIP_TRY(c, hipGetLastError());
@@ -1649,7 +1514,7 @@ __device__ __forceinline__ void nn_grid_set_body(const GridBatch &batch, unsigne
   for (uint32_t si = bx; si < n_sets; si += nbx) {
     const uint32_t set = a.cull_sets[si];
     // ---- the set's queries (wave 0): bound, ball in cells, union of the flagged ones
-    bool valid = false, grant = false;
+    bool valid = false;
     uint32_t qpos = 0;
     float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
     if (wv == 0) {
@@ -1663,17 +1528,11 @@ __device__ __forceinline__ void nn_grid_set_body(const GridBatch &batch, unsigne
       if (valid) {
         if (a.qraw) q = pose_query_f64(a.qpose_dev->T, a.qraw, qpos);      // (posed lean: as in nn_grid_wide_body)
         else q = a.qs[qpos];
-        bool bounded = false;
-        if (a.qbound) { const uint32_t v = a.qbound[qpos]; if (v <= __float_as_uint(bound)) { bound = __uint_as_float(v); bounded = true; } }
+        if (a.qbound) { const uint32_t v = a.qbound[qpos]; if (v <= __float_as_uint(bound)) bound = __uint_as_float(v); }
         if (a.seed_from_keys) {
           const uint32_t prev = (uint32_t)a.keys[qpos];
-          if (prev < a.nt) { const float d = gdist2<FMA>(a.gts[a.h2g[prev]], q.x, q.y, q.z); if (d <= bound) { bound = d; bounded = true; } }
+          if (prev < a.nt) { const float d = gdist2<FMA>(a.gts[a.h2g[prev]], q.x, q.y, q.z); if (d <= bound) bound = d; }
         }
-        // rim certificates: a query without any bound is searched a margin BEYOND the cap -- nothing within that earns it a
-        // certificate (the walk then leaves it alone while the clouds move by less); what it finds between the cap and the margin
-        // is no match (the key below takes matches within the cap only) and no certificate
-        grant = a.cert != nullptr && !bounded && batch.cert_margin > 0.f;
-        if (grant) { const float cm = __builtin_amdgcn_sqrtf(cap2) * 1.000001f + batch.cert_margin; bound = cm * cm * 1.000001f; }
         const Ball ball = grid_ball(a, q, bound);
         const float rad = ball.rad, rx = ball.rx, ry = ball.ry, rz = ball.rz;
         c0[0] = cell_of(rx - rad, a.lo[0], a.inv_h, a.dim[0]); c1[0] = cell_of(rx + rad, a.lo[0], a.inv_h, a.dim[0]);
@@ -1767,7 +1626,6 @@ __device__ __forceinline__ void nn_grid_set_body(const GridBatch &batch, unsigne
         if (a.mark) __hip_atomic_store(&a.mark[hp], (uint32_t)(m >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       a.keys[ord] = found ? ((m & 0xFFFFFFFF00000000ull) | low) : kKeyInit;
-      if (a.cert) a.cert[qpos] = (grant && bi == kNone) ? batch.cert_margin : 0.f;
     }
     __syncthreads();                                // lq / ubox / lbest are reused by the next set
   }
@@ -1812,7 +1670,6 @@ int launch_nn_grid_tail_batch(Ctx *c, const GridPair *pairs, int n_pairs, float 
     if (!any) continue;
     batch.cap2 = cap2;
     batch.light_rows = c->grid_light_rows;
-    batch.cert_margin = 1.0e-3f * (float)c->rim_cert_um;
     const unsigned wide_blocks = (unsigned)std::max(1, c->n_cu * c->grid_wide_waves / (std::max(1, m) * kWideWaves * 4));
     const unsigned set_blocks = (unsigned)std::max(1, c->n_cu * (2048 / (64 * kWideWaves)) / std::max(1, m));
     const bool per_launch = c->prof && !c->prof_totals;
@@ -1840,7 +1697,6 @@ int launch_nn_grid_sets_batch(Ctx *c, const GridPair *pairs, int n_pairs, float 
     if (!any) continue;
     batch.cap2 = cap2;
     batch.light_rows = c->grid_light_rows;
-    batch.cert_margin = 1.0e-3f * (float)c->rim_cert_um;
     const unsigned blocks_x = (unsigned)std::max(1, c->n_cu * (2048 / (64 * kWideWaves)) / std::max(1, m));      // listed sets are strided over (every block's loop ends at the count)
     const bool per_launch = c->prof && !c->prof_totals;
     if (per_launch) MVR_HIP_TRY(c, hipMemsetAsync(c->evals, 0, kEvalRegion * sizeof(unsigned long long), c->stream));

@@ -112,7 +112,7 @@ struct Mat44d { double m[16]; };
 struct PoseRec {
   Mat44d T;                 // the pose (column-major 4 x 4)
   double minv[12];          // its inverse affine map, row-major 3 x 4: posed frame -> canonical frame
-  float stretch, delta;     // bound of how much the inverse lengthens a distance (1 for a rigid pose); how far (mm, upper bound) any point of the cloud has moved since the pass before (1e30: unknown)
+  float stretch;            // bound of how much the inverse lengthens a distance (1 for a rigid pose)
 };
 
 struct Cloud {
@@ -148,10 +148,6 @@ struct Cloud {
   // released the pass); null outside such a run
   const struct PoseRec *pose_dev = nullptr;
   void forget_pose() { canonical = false; pose_known = false; pose_stretch = 1.0; grid.reset(); }
-  // how far this posed copy has moved since it was last searched (seed_delta, mvr_grid.hip): `moved` (mm, an upper bound over the
-  // cloud's points; < 0: unknown) accumulates over the poses note_pose() records, from `last_pose`; a fused pass that searches the
-  // cloud puts it back to 0.  Valid while last_pose_set == set_id.
-  double last_pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, moved = -1.0; uint64_t last_pose_set = 0;
   float bbox[6] = {0, 0, 0, 0, 0, 0}; uint64_t bbox_set = 0;      // with bbox_set == set_id (and canonical): the bounding box of pts[], taken when the cloud was uploaded (the grid build then needs no round trip for it)
   bool pts_stale = false;              // pts[] were left out by the last (pipelined) pose of this cloud: sorted[] / gsorted[] are current, pts[] are written when the run leaves the pipe
   bool posed_by_table = false;         // ... and the last transform of this cloud did read it (its host-side pose is filled in when the run leaves the pipe)
@@ -263,23 +259,6 @@ struct Ctx {
   int cull_q = 0;                                     // culled kernel: queries per lane (0 = auto)
   int cull_w = 0;                                     // culled kernel: waves sharing one query set (1, 2, 4; 0 = by launch size)
   int cull_slices = 0;                                // culled kernel: interleaved slices a pair's query sets are dealt to the XCDs in (1, 2, 4, 8; 0 = 8 / gcd(pairs, 8))
-  // seed_delta (round 4): a forward search of the grid walk that has the previous pass's key at hand takes its start bound from THAT
-  // distance plus how far the two clouds have moved since (an upper bound from the poses and the scan's bounding box) instead of
-  // gathering the old match's coordinates (two dependent gathers at the head of every wave) -- while the motion is below
-  // seed_delta_um micrometres (0: never, the default).  Any bound within which a point is known to exist is a valid start: results do
-  // not change (tests/test_gpu_ring.py) -- and, measured, neither does the time: 0.339 / 0.329 ms per settled pass with it against
-  // 0.336 / 0.330 without (same box, 50 um): the two gathers it removes are latency other waves cover.  Kept as a knob; the
-  // per-view motion bound it rests on (PoseRec::delta, Cloud::moved) is what a certificate for the rim queries would need too.
-  int seed_delta_um = 0;
-  // rim certificates: a forward query without any target point within the cap + rim_cert_um micrometres (found so by the listed-sets
-  // search) is not searched again -- no distance-map read, no probe, no place in a listed set -- while the pair has moved by less
-  // than that since (the same per-view motion bounds; 0: off, the default).  Results do not change (knob tests) -- and neither does
-  // the time: of the ~30 k rim queries per 1.2 M of a settled pass, 50 / 200 / 500 / 1000 um of margin take 0 / 2 / 8 / 9 k out and the
-  // listed SETS (a block each: what the tail launch costs) go from 950 to 800 at best -- a rim query is not a query with nothing
-  // near, it is one whose nearest target point lies just beyond the cap, and a registration that still moves 0.02 mm per view and
-  // pass spends a small margin at once.  The tail launch stays at 22-24 us either way (profiles/r04_c_rim_cert.txt).
-  int rim_cert_um = 0;
-  float *bcert = nullptr; size_t bcert_cap = 0; bool bcert_zero = false; float bcert_cap2 = -1.f;      // (the cap the certificates in bcert[] were granted for)
   int seed_forward = 1;                               // fused pass: forward searches start from the previous pass's matches when the same pairs are searched again
   int fused_mark = 1;                                 // fused pass: the forward launches themselves record the matched targets' start bounds -- 1: when they are the grid walk, 2: always, 0: never (a separate launch re-reads the keys)
   bool marked_in_search = false;                      // ... what this pass does (decided with its forward launches)
@@ -311,7 +290,6 @@ struct Ctx {
   // launch, compacted query lists too (measured equal or slower there).  A lone pair's launch has its own switch.
   int grid_stage = 2, grid_stage_lone = 1;      // (2 since the two waves of a block stage one region together: the reverse launches' sparser queries fit it too)
   unsigned long long *stage_stat = nullptr;              // diagnostics (tune key grid_stage_stat = 1): device counters [64 shards][64] of the staged walk's waves: [1] staged, [2] too many rows, [3] too wide, [4] too many points
-  int grid_lanes = 1;                                    // lanes that share one query of the grid search (1, 2, 4 or 8): they deal the ball's rows of cells among them
   int grid_cluster = 8;                                  // a wave of the grid search with at least this many wide queries hands them ALL to the culled kernel (65: never)
   int grid_wide_waves = 32;                              // waves per CU of the wave-per-query launch
   int grid_tail = 1;                                     // 1: the wave-per-query launch and the listed-sets launch of a forward pass are one launch
@@ -492,7 +470,7 @@ __device__ __forceinline__ float4 pose_query_f64(const Mat44d &T, const float4 *
 }
 // the device record of a pose (PoseRec) from its 16 doubles: inverse of x -> A x + t by cofactors, in double, as make_grid_pair
 // does on the host; the stretch for ANY invertible matrix (the host has checked e <= 1e-3 before it released the pass: note_pose's bar)
-__device__ __forceinline__ void make_pose_rec(const double *T, float delta, PoseRec *out)
+__device__ __forceinline__ void make_pose_rec(const double *T, PoseRec *out)
 {
   PoseRec r;
   for (int j = 0; j < 16; ++j) r.T.m[j] = T[j];
@@ -516,7 +494,6 @@ __device__ __forceinline__ void make_pose_rec(const double *T, float delta, Pose
     }
   const double e = fmin(sqrt(e2), 0.5);
   r.stretch = __double2float_ru((1.0 / sqrt(1.0 - e)) * (1.0 + 1e-6));
-  r.delta = delta;
   *out = r;
 }
 struct RefreshBatch {
@@ -646,12 +623,7 @@ struct GridPair {
   uint32_t *mark = nullptr;                   // optional: start bounds of the reverse searches, by the match's Hilbert position
   uint32_t key_by_pos = 0, seed_from_keys = 0;
   const PoseRec *pose_dev = nullptr;     // optional: minv / stretch are read from here (device-visible) instead of the two by-value members
-  const PoseRec *qpose_dev = nullptr;    // ... and the QUERY cloud's record (for its `delta`)
-  // rim certificates (round 4): per plain forward query (by position), how much more (mm) the pair may move before the finding "no
-  // target point within the cap" of an earlier pass has to be proved again; 0 = none.  Granted by the listed-sets search (which then
-  // looks cert_margin beyond the cap), spent by the walk (GridBatch::cert_margin; delta as for seed_delta)
-  float *cert = nullptr;
-  float delta = -1.f;                    // without records: how far the two clouds have moved against each other since the searches that left keys[] (mm, upper bound; < 0: unknown)
+  const PoseRec *qpose_dev = nullptr;    // ... and the QUERY cloud's record (with qraw: the pose its queries are posed with)
   float stretch = 1.f;                   // distances in the searched cloud's canonical frame are at most this times the posed ones (Cloud::pose_stretch, rounded up)
   int dt_max = 12;                       // what dt == 255 stands for (the grid's dt_steps)
   // a BOUNDED query whose ball is wide (scattered among the others: a match that moved far, a long correspondence) is
@@ -664,7 +636,7 @@ constexpr int kGridBatchPairs = 12;
 constexpr int kWideCounters = 64;          // pairs of one fused pass that can have wide lists (more: the pass takes the culled kernel)
 constexpr int kGridDtMax = 12;        // most dilation steps of the distance map (a grid is built with as many as the first search radius it serves needs)
 constexpr int kGridLightRows = 24;    // default number of rows of cells (x-runs) a thread walks by itself (with the probe at its own threshold of 12 rows: 24 takes 0.19 ms off the first four passes of a window that restarts from the prior, settled passes equal; 32 and 48 within 2 % of it; before the probe had a threshold of its own, on the 12 x 200k ring: 9..16 equal, 4 and 27 slower)
-struct GridBatch { GridPair p[kGridBatchPairs]; float cap2; int light_rows; int cluster = 65; int probe = 0; int probe_rows = 1 << 30; float delta_max = 0.f; float cert_margin = 0.f; };
+struct GridBatch { GridPair p[kGridBatchPairs]; float cap2; int light_rows; int cluster = 65; int probe = 0; int probe_rows = 1 << 30; };
 int launch_nn_grid_batch(Ctx *c, const GridPair *pairs, int n_pairs, float cap2, bool fma);
 int launch_nn_grid_wide_batch(Ctx *c, const GridPair *pairs, int n_pairs, float cap2, bool fma);
 int launch_nn_grid_tail_batch(Ctx *c, const GridPair *pairs, int n_pairs, float cap2, bool fma);     // the two launches below in one

@@ -176,7 +176,8 @@ def test_sequential_align_over_the_source_grid_equals_the_culled_search(mvr, orc
     reused, the model is rebuilt), with aligns that iterate (only their first iteration can use the grid), with scans of
     different sizes and with a radius ten times as wide (wide balls leave the thread-per-query walk).  The forward
     searches' seeds, the iteration row's two ways to the host and the native driver change nothing either.  The tune keys of
-    the forward searches that were removed (seq_search 2 and 3 and their knobs) are refused.  The first align's
+    the forward searches that were removed (seq_search 2 and 3 and their knobs; the ring walk's grid_lanes, seed_delta_um and
+    rim_cert_um) are refused.  The first align's
     correspondences equal the oracle's."""
     V, N, max_d = 8, 9000, 4.0
     sp = mvr.synth_params(V, 3)
@@ -232,7 +233,8 @@ def test_sequential_align_over_the_source_grid_equals_the_culled_search(mvr, orc
            [(l[0], l[1], l[2], l[3], l[4], l[5]) for l in seeded[0][1]], case
     # ... and against the oracle: the first align's correspondences, one by one
     with mvr.Context(0) as ctx:
-        for gone in (dict(seq_search=2), dict(seq_search=3), dict(seq_model_tail=0), dict(parts_lanes=4), dict(parts_max_rows=8)):
+        for gone in (dict(seq_search=2), dict(seq_search=3), dict(seq_model_tail=0), dict(parts_lanes=4), dict(parts_max_rows=8),
+                     dict(grid_lanes=4), dict(seed_delta_um=50), dict(rim_cert_um=200)):
             with pytest.raises(mvr.MvrError) as refused:
                 ctx.tune(**gone)
             assert refused.value.status == mvr.E_ARG, gone

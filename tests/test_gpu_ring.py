@@ -229,10 +229,10 @@ def test_grid_search_equals_culled_search_over_passes(mvr, orc):
 
 
 @pytest.mark.parametrize("knobs", [
-    dict(grid_lanes=2), dict(grid_lanes=4), dict(grid_lanes=8, grid_cell_points=20),
+    dict(grid_cell_points=20),
     dict(grid_wide=0), dict(grid_wide=0, grid_light_rows=1), dict(grid_light_rows=1), dict(grid_light_rows=64),
     dict(cull_list=0), dict(cull_list_w=1), dict(cull_list_w=4, grid_cluster=1), dict(grid_cluster=65),
-    dict(grid_cell_points=1), dict(grid_cell_points=40, grid_light_rows=3), dict(fused_mark=0), dict(fused_mark=2), dict(grid_sets=0), dict(grid_tail=0), dict(grid_sets=2, grid_light_rows=1, grid_cluster=1), dict(grid_sets=2, grid_cell_points=1, grid_light_rows=2, grid_cluster=2), dict(fused_mark=0, grid_lanes=4, pair_groups=1),
+    dict(grid_cell_points=1), dict(grid_cell_points=40, grid_light_rows=3), dict(fused_mark=0), dict(fused_mark=2), dict(grid_sets=0), dict(grid_tail=0), dict(grid_sets=2, grid_light_rows=1, grid_cluster=1), dict(grid_sets=2, grid_cell_points=1, grid_light_rows=2, grid_cluster=2), dict(fused_mark=0, pair_groups=1),
     dict(grid_wide_waves=1), dict(pair_groups=3, cull_slices=8),
     dict(grid_probe_rows=1), dict(grid_probe_rows=4, grid_cell_points=1), dict(grid_probe_rows=3, grid_light_rows=64, grid_cell_points=40),
     dict(grid_probe=0), dict(grid_probe=0, grid_light_rows=2), dict(grid_probe=1, grid_light_rows=1, grid_cluster=1), dict(setup_first=0), dict(cull_w=4), dict(cull_w=2),
@@ -241,17 +241,15 @@ def test_grid_search_equals_culled_search_over_passes(mvr, orc):
     # with huge cells and wide balls walked in-thread (more points than a wave's LDS holds: the rows behind are walked from global memory)
     dict(grid_stage=0), dict(grid_stage=2), dict(grid_stage=2, grid_cell_points=1), dict(grid_stage=2, grid_cell_points=40, grid_light_rows=64),
     dict(order_batch=0), dict(order_batch=0, grid_stage=0),
-    # rim certificates (round 4): off, with a margin of 1 mm, with the compact index and the staged walk everywhere
-    dict(rim_cert_um=50), dict(rim_cert_um=1000), dict(rim_cert_um=1000, seed_delta_um=1000, grid_stage=2, grid_index=1), dict(rim_cert_um=200, pipeline=0),
-    # seed_delta (round 4): start bounds from the previous distance + the clouds' motion instead of the old match's coordinates: off, always on
-    dict(seed_delta_um=50), dict(seed_delta_um=100000), dict(seed_delta_um=100000, grid_stage=0), dict(seed_delta_um=100000, pipeline=0, grid_index=1),
+    # pass by pass instead of queued ahead, with the compact index too
+    dict(pipeline=0), dict(pipeline=0, grid_index=1),
     # the compact cell-start tables (round 4): forced for these small grids, with the staged walk everywhere, with tiny / huge cells, dense forced
     dict(grid_index=1), dict(grid_index=1, grid_stage=2), dict(grid_index=1, grid_cell_points=1), dict(grid_index=1, grid_cell_points=40, grid_light_rows=64, grid_probe=0),
-    dict(grid_index=1, grid_stage=0, grid_lanes=4), dict(grid_index=1, grid_sets=2, grid_light_rows=1, grid_cluster=1), dict(grid_index=0),
+    dict(grid_index=1, grid_stage=0), dict(grid_index=1, grid_sets=2, grid_light_rows=1, grid_cluster=1), dict(grid_index=0),
     dict(grid_stage=2, grid_light_rows=64, grid_probe=0), dict(grid_stage=1, grid_cell_points=2, grid_light_rows=64, grid_probe=0), dict(grid_stage=2, grid_cell_points=12, grid_wide=0),
 ], ids=lambda k: ",".join("%s=%s" % kv for kv in k.items()))
 def test_grid_search_knobs_never_show_in_a_result(mvr, knobs):
-    """Every routing knob of the grid search (lanes per query, cell size, what counts as a wide ball, where the wide ones
+    """Every routing knob of the grid search (cell size, what counts as a wide ball, where the wide ones
     go, set lists, marking) only moves queries between three exact searches: six passes of the 12 x 20k ring from the
     prior give the same poses and edge tables, bit for bit, as the default settings (so do the probe for wide balls, the order of
     the set-up of a plain pass, the waves per query set of the culled kernel, and who refreshes the super boxes)."""

@@ -36,8 +36,8 @@ def _one(usage, pattern):
 
 # waves/SIMD of the hot kernels before they posed their own queries: none may drop
 @pytest.mark.parametrize("pattern,waves,vgprs,lds", [
-    (r"nn_grid_kernel<false, 1, true>", 8, 64, 10240),
-    (r"nn_grid_kernel<false, 1, false>", 8, 64, None),
+    (r"nn_grid_kernel<false, true>", 8, 64, 10240),
+    (r"nn_grid_kernel<false, false>", 8, 64, None),
     (r"nn_grid_tail_kernel<false>", 5, None, None),
     (r"nn_grid_wide_kernel<false>", 7, None, None),
     (r"accept_moments2_batch_kernel", 4, 128, None),
