@@ -572,6 +572,85 @@ class FPFHEstimation {
   double radius_ = 0.0;
 };
 
+// ---------------------------------------------------------------- intrinsic shape signature keypoints
+// pcl::ISSKeypoint3D<PointInT, PointOutT> (keypoints/iss_3d.h) without border estimation: setInputCloud, setSearchMethod,
+// setSalientRadius, setNonMaxRadius, setThreshold21, setThreshold32, setMinNeighbors, setNumberOfThreads, compute,
+// getKeypointsIndices, PCL's defaults (both thresholds 0.975, 5 neighbours; the radii must be set).  Semantics:
+// mvr_cloud_iss_keypoints (mvr_hip.h) -- one call on the GPU per compute().  PointInT / PointOutT: any point whose first three
+// floats are x, y, z.  `output` may be the input cloud itself.  A missing input, a radius that is not finite and > 0, a
+// non-finite threshold or a negative neighbour count prints an error and leaves the output empty (untouched when it is the
+// input), and so does a non-zero setBorderRadius / setNormalRadius: the border estimation is not offered, and computing
+// something else in silence would be worse than computing nothing.
+template <typename PointInT, typename PointOutT = PointInT>
+class ISSKeypoint3D {
+ public:
+  typedef PointCloud<PointInT> PointCloudIn;
+  typedef typename PointCloudIn::ConstPtr PointCloudInConstPtr;
+  typedef PointCloud<PointOutT> PointCloudOut;
+  typedef search::KdTree<PointInT> KdTree;
+  typedef typename KdTree::Ptr KdTreePtr;
+
+  void setInputCloud(const PointCloudInConstPtr &c) { input_ = c; }
+  PointCloudInConstPtr getInputCloud() const { return input_; }
+  void setSearchMethod(const KdTreePtr &tree) { tree_ = tree; }
+  KdTreePtr getSearchMethod() const { return tree_; }
+  void setSalientRadius(double r) { p_.salient_radius = r; }
+  void setNonMaxRadius(double r) { p_.non_max_radius = r; }
+  void setThreshold21(double g) { p_.gamma_21 = g; }
+  void setThreshold32(double g) { p_.gamma_32 = g; }
+  void setMinNeighbors(int m) { p_.min_neighbors = m; }
+  void setNumberOfThreads(unsigned int = 0) {}
+  void setBorderRadius(double r) { border_radius_ = r; }
+  void setNormalRadius(double r) { normal_radius_ = r; }
+  PointIndices::ConstPtr getKeypointsIndices() const { return indices_; }
+
+  void compute(PointCloudOut &output)
+  {
+    static_assert(sizeof(PointInT) % 4 == 0 && sizeof(PointInT) >= 12 && sizeof(PointOutT) >= 12, "points that begin with x, y, z expected");
+    indices_->indices.clear();
+    const bool alias = (const void *)&output == (const void *)input_.get();
+    if (!input_) { std::fprintf(stderr, "[pcl::ISSKeypoint3D::compute] No input dataset given!\n"); output.clear(); return; }
+    if (border_radius_ != 0.0 || normal_radius_ != 0.0) {
+      std::fprintf(stderr, "[pcl::ISSKeypoint3D::compute] The border estimation (setBorderRadius %f, setNormalRadius %f) is not offered.\n",
+                   border_radius_, normal_radius_);
+      if (!alias) output.clear();
+      return;
+    }
+    if (!(std::isfinite(p_.salient_radius) && p_.salient_radius > 0.0) || !(std::isfinite(p_.non_max_radius) && p_.non_max_radius > 0.0) ||
+        !std::isfinite(p_.gamma_21) || !std::isfinite(p_.gamma_32) || p_.min_neighbors < 0) {
+      std::fprintf(stderr, "[pcl::ISSKeypoint3D::compute] The salient radius (%f) and the non maxima radius (%f) must be finite and > 0, the thresholds (%f, %f) finite, the minimum number of neighbors (%d) >= 0.\n",
+                   p_.salient_radius, p_.non_max_radius, p_.gamma_21, p_.gamma_32, p_.min_neighbors);
+      if (!alias) output.clear();
+      return;
+    }
+    Device &d = Device::instance();
+    SlotGuard s;
+    const size_t n = input_->size();
+    // first: `output` may alias the input
+    d.check(mvr_cloud_upload(d.ctx(), s.s, n ? input_->points[0].data : nullptr, n, sizeof(PointInT)), "mvr_cloud_upload");
+    std::vector<uint32_t> kept(n ? n : 1);
+    size_t m = 0;
+    d.check(mvr_cloud_iss_keypoints(d.ctx(), s.s, s.s, &p_, &m, kept.data(), nullptr, nullptr, nullptr), "mvr_cloud_iss_keypoints");
+    std::vector<float> xyz(4 * (m ? m : 1));
+    size_t got = 0;
+    if (m) d.check(mvr_cloud_download(d.ctx(), s.s, xyz.data(), m, 16, &got), "mvr_cloud_download");
+    output.clear();
+    output.resize(m);
+    for (size_t i = 0; i < m; ++i) {
+      PointOutT &o = output.points[i];
+      o.x = xyz[4 * i]; o.y = xyz[4 * i + 1]; o.z = xyz[4 * i + 2];
+    }
+    indices_->indices.assign(kept.begin(), kept.begin() + (std::ptrdiff_t)m);
+  }
+
+ private:
+  PointCloudInConstPtr input_;
+  KdTreePtr tree_;
+  mvr_iss_params p_ = {0.0, 0.0, 0.975, 0.975, 5, 0};
+  double border_radius_ = 0.0, normal_radius_ = 0.0;
+  PointIndicesPtr indices_ = std::make_shared<PointIndices>();
+};
+
 // ---------------------------------------------------------------- sample-consensus alignment
 // pcl::SampleConsensusPrerejective<PointSource, PointTarget, FeatureT> (registration/sample_consensus_prerejective.h):
 // setInputSource, setInputTarget, setSourceFeatures, setTargetFeatures, setMaximumIterations, setNumberOfSamples,

@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstring>
 #include <iostream>
+#include <limits>
 #include <utility>
 #include <vector>
 
@@ -311,21 +312,56 @@ class ScanCloud {
     return true;
   }
 
+  // EXTENSION (pcl::ISSKeypoint3D on the raw points, on the GPU; rules: mvr_cloud_iss_keypoints in mvr_hip.h): the indices,
+  // ascending, of the points whose scatter over salient_radius passes both eigenvalue ratio tests and whose smallest eigenvalue
+  // no neighbour within non_max_radius exceeds.  A parameter outside its range prints an error, leaves `indices` empty and
+  // returns false.  `points`, `rich` and the pose stay as they are.
+  bool detectKeypoints(const mvr_iss_params &p, std::vector<uint32_t> &indices) const
+  {
+    indices.clear();
+    if (!(std::isfinite(p.salient_radius) && p.salient_radius > 0.0) || !(std::isfinite(p.non_max_radius) && p.non_max_radius > 0.0) ||
+        !std::isfinite(p.gamma_21) || !std::isfinite(p.gamma_32) || p.min_neighbors < 0) {
+      std::fprintf(stderr, "[ScanCloud::detectKeypoints] The radii (%f, %f) must be finite and > 0, the thresholds (%f, %f) finite, min_neighbors (%d) >= 0.\n",
+                   p.salient_radius, p.non_max_radius, p.gamma_21, p.gamma_32, p.min_neighbors);
+      return false;
+    }
+    const size_t n = points.size();
+    if (!n) return true;
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.upload(s.s, points);
+    indices.resize(n);
+    size_t kept = 0;
+    d.check(mvr_cloud_iss_keypoints(d.ctx(), -1, s.s, &p, &kept, indices.data(), nullptr, nullptr, nullptr), "mvr_cloud_iss_keypoints");
+    indices.resize(kept);
+    return true;
+  }
+
   // EXTENSION (pcl::SampleConsensusPrerejective on the raw points, on the GPU; rules: mvr_align_prerejective in mvr_hip.h): the
   // coarse pose of THIS scan onto `target` for a pair without a turntable prior -- computeFPFH of both scans (both need their
   // normals in `rich`) at feature_radius, then the aligner.  On success `pose` is the scan's pose in the scene's own type:
   // setMatrix(pose * target.getMatrix()) puts the scan where registrationICPDevice can take over.  false (pose untouched): no
   // normals, a bad radius, or the aligner found no pose that reaches inlier_fraction; `result` (optional) says which.
+  // With use_keypoints, detectKeypoints(keypoints) runs on both scans first and the descriptor rows of the other points are
+  // overwritten with NaN: such a row is never sampled (A1) and never matched (M3), so the matcher's work drops from
+  // n_source x n_target pairs to keypoints x n_target while every pose is still scored over all points of the source.
   struct PrerejectiveParams {
     double feature_radius = 0.0;
     mvr_prerej_params align;
-    PrerejectiveParams() { align = mvr_prerej_params(); align.max_iterations = 10; align.nr_samples = 3; align.k = 2; align.similarity = 0.9; align.inlier_fraction = 0.25; }
+    mvr_iss_params keypoints;            // salient_radius / non_max_radius must be set when use_keypoints is
+    bool use_keypoints = false;
+    PrerejectiveParams()
+    {
+      align = mvr_prerej_params(); align.max_iterations = 10; align.nr_samples = 3; align.k = 2; align.similarity = 0.9; align.inlier_fraction = 0.25;
+      keypoints = mvr_iss_params(); keypoints.gamma_21 = keypoints.gamma_32 = 0.975; keypoints.min_neighbors = 5;
+    }
   };
   bool alignPrerejective(const ScanCloud &target, const PrerejectiveParams &params, RowMatrixd &pose, mvr_prerej_result *result = nullptr) const
   {
     std::vector<FPFHSignature33> sf, tf;
     if (result) { *result = mvr_prerej_result(); result->best_iteration = -1; result->error = DBL_MAX; }
     if (!computeFPFH(params.feature_radius, sf) || !target.computeFPFH(params.feature_radius, tf)) return false;
+    if (params.use_keypoints && (!keepKeypointRows(params.keypoints, sf) || !target.keepKeypointRows(params.keypoints, tf))) return false;
     Device &d = Device::instance();
     SlotGuard s, t;
     d.upload(s.s, points);
@@ -337,6 +373,18 @@ class ScanCloud {
     if (result) *result = res;
     if (!res.converged) return false;
     pose = PclMatrixCaster<RowMatrixd>(Matrix4f(res.T));
+    return true;
+  }
+  // the descriptor rows of the points detectKeypoints does not list become NaN (false: the detector refused its parameters)
+  bool keepKeypointRows(const mvr_iss_params &p, std::vector<FPFHSignature33> &feat) const
+  {
+    std::vector<uint32_t> key;
+    if (!detectKeypoints(p, key)) return false;
+    std::vector<char> keep(feat.size(), 0);
+    for (uint32_t i : key) keep[i] = 1;
+    for (size_t i = 0; i < feat.size(); ++i)
+      if (!keep[i])
+        for (float &v : feat[i].histogram) v = std::numeric_limits<float>::quiet_NaN();
     return true;
   }
 

@@ -496,6 +496,47 @@ int  mvr_align_prerejective(mvr_ctx *ctx, int src_slot, int tgt_slot, const floa
                             const mvr_prerej_params *params, const float *guess /* optional, 16 */,
                             mvr_prerej_result *result, mvr_prerej_trace *trace /* optional, max_iterations */);
 
+/* ---- intrinsic shape signature keypoints (EXTENSION: pcl::ISSKeypoint3D) -----------------------------------------------
+ * What chooses the points that carry a descriptor into the matcher: a row of a feature table that is overwritten with NaN is
+ * ineligible as a sample (A1) and never listed as a match (M3), so a non-keypoint is a NaN row.  The reference pins no PCL
+ * version and PCL was not at hand; the model is pcl/keypoints/impl/iss_3d.hpp (getScatterMatrix, detectKeypoints) with
+ * border_radius == 0, as published; deviations are marked.
+ *  K1. A point is VALID when its three coordinates are finite.  An invalid point is nobody's neighbour and never a keypoint;
+ *      its saliency is 0 and both its counts are 0; no query walks the grid because of one (rules N2 and N5 above).
+ *  K2. Neighbourhood of radius r: every valid j with d2(i, j) <= (float)(r * r) under the f32 distance of mvr_nn / mvr_knn,
+ *      i itself included -- exactly the radius mode of mvr_cloud_estimate_normals; fma_dist = 1 selects the fma chain.
+ *  K3. Scatter: the sum over the neighbourhood of salient_radius of (p_j - p_i)(p_j - p_i)^T in f64, in walk order; the
+ *      differences are taken in f64 from the f32 coordinates; the sum is NOT divided by the count (as PCL).  salient_count[i]
+ *      is the size of that neighbourhood; below min_neighbors the saliency is 0.  (PCL accumulates the f32 differences
+ *      into a double matrix.)
+ *  K4. Eigenvalues e1 >= e2 >= e3 of the scatter by the library's cyclic Jacobi in f64 (PCL: Eigen's SelfAdjointEigenSolver).
+ *      Point i is SALIENT iff all of: the three are finite, e3 >= 0, e2 / e1 < gamma_21, e3 / e2 < gamma_32, e3 > 0.  The
+ *      divisions are IEEE: a NaN ratio fails.  saliency[i] = e3 for a salient point, else 0.
+ *  K5. Non-maximum suppression: a salient i is a keypoint iff nms_count[i] >= min_neighbors, with nms_count[i] the size of
+ *      its neighbourhood of non_max_radius, and no j of that neighbourhood has saliency[i] < saliency[j].  The comparison is
+ *      strict: equal saliencies are both kept, as in PCL.  nms_count is 0 for a point that is not salient.
+ *  K6. Output: the keypoints go to dst_slot in ascending original index, w = 1; the source's normals follow their points, as
+ *      in the outlier filters.  The output is a NEW point set: orderings, grids and pose bookkeeping are dropped.  dst_slot
+ *      may equal src_slot.  dst_slot == -1 fills the host arrays only and leaves every slot untouched.  kept_index (optional,
+ *      host, capacity = source size) receives the keypoints' original indices, ascending; n_out (optional) their number;
+ *      saliency / salient_count / nms_count (optional, host) one entry per SOURCE point.
+ *  K7. MVR_E_ARG, before any GPU work and with nothing written, for a NULL ctx / params, a bad slot, a radius that is
+ *      non-finite or <= 0, a non-finite gamma, min_neighbors < 0, a cloud above 0x7FFFFFF0 points, or a cloud whose points are
+ *      stale because a pipelined run is in flight.  An empty cloud is MVR_OK with an empty output.
+ *  K8. Bit-identical from run to run on one grid: one thread per query, sums in walk order, no floating-point atomics.
+ * Out of scope: the border estimation (setBorderRadius, setNormalRadius, setAngleThreshold -- border_radius is 0 throughout),
+ * setSearchSurface, and the other keypoint detectors (Harris3D, SIFT, NARF, ...). */
+typedef struct {
+  double salient_radius;     /* setSalientRadius: finite, > 0 */
+  double non_max_radius;     /* setNonMaxRadius:  finite, > 0 */
+  double gamma_21, gamma_32; /* setThreshold21 / setThreshold32 (PCL default 0.975 each): finite */
+  int    min_neighbors;      /* setMinNeighbors (PCL default 5): >= 0 */
+  int    fma_dist;
+} mvr_iss_params;
+int  mvr_cloud_iss_keypoints(mvr_ctx *ctx, int dst_slot /* -1: none */, int src_slot, const mvr_iss_params *p,
+                             size_t *n_out, uint32_t *kept_index, double *saliency /* n */,
+                             uint32_t *salient_count /* n */, uint32_t *nms_count /* n */);
+
 /* CorrespondenceEstimation::determineReciprocalCorrespondences(corrs, max_d)
  * (registrator.cpp:496-502, 644-649); reciprocal = 0 gives
  * determineCorrespondences.  Outputs are host arrays of capacity `cap`

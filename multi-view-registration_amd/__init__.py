@@ -133,6 +133,12 @@ class FpfhParams(C.Structure):
     _fields_ = [("radius", C.c_double), ("fma_dist", C.c_int)]
 
 
+class IssParams(C.Structure):
+    """mvr_iss_params"""
+    _fields_ = [("salient_radius", C.c_double), ("non_max_radius", C.c_double), ("gamma_21", C.c_double), ("gamma_32", C.c_double),
+                ("min_neighbors", C.c_int), ("fma_dist", C.c_int)]
+
+
 FPFH_BINS = 11          # MVR_FPFH_BINS: a signature is 3 * 11 = 33 floats
 PREREJ_MAX_SAMPLES = 8  # MVR_PREREJ_MAX_SAMPLES
 
@@ -181,6 +187,7 @@ SIGNATURES = {
     "mvr_cloud_radius_outlier_removal": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RorParams), C.POINTER(_sz), _u32p, _u32p]),
     "mvr_cloud_mls": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(MlsParams), C.POINTER(_sz), _u32p, _fp]),
     "mvr_cloud_fpfh": (C.c_int, [_vp, C.c_int, C.POINTER(FpfhParams), _fp, _fp, _u32p]),
+    "mvr_cloud_iss_keypoints": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(IssParams), C.POINTER(_sz), _u32p, _dp, _u32p, _u32p]),
     "mvr_feature_knn": (C.c_int, [_vp, _fp, _sz, _fp, _sz, C.c_int, C.c_int, _u32p, _fp]),
     "mvr_pose_scores": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _sz, C.c_double, C.c_int, _u32p, _dp]),
     "mvr_align_prerejective": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, C.POINTER(PrerejParams), _fp, C.POINTER(PrerejResult),
@@ -694,6 +701,33 @@ class Context:
         if return_counts:
             res.append(cnt)
         return res[0] if len(res) == 1 else tuple(res)
+
+    def iss_keypoints(self, dst, src, salient_radius, non_max_radius, gamma_21=0.975, gamma_32=0.975, min_neighbors=5, fma=False,
+                      return_index=False, return_saliency=False, return_counts=False):
+        """pcl::ISSKeypoint3D::compute of slot src into slot dst (may be src; -1: no output slot, the host arrays only): the
+        points whose scatter over salient_radius passes both eigenvalue ratio tests and whose smallest eigenvalue no neighbour
+        within non_max_radius exceeds, in their original order; normals follow (rules K1-K8: mvr_cloud_iss_keypoints in
+        mvr_hip.h).  Returns n_out, or (n_out[, kept_index][, saliency][, salient_count, nms_count]) with the return_*
+        options: kept_index = original indices of the keypoints, saliency = one float64 per SOURCE point (0: not salient),
+        the counts one uint32 per SOURCE point."""
+        n = self.size(src)
+        p = IssParams(float(salient_radius), float(non_max_radius), float(gamma_21), float(gamma_32), int(min_neighbors), int(bool(fma)))
+        idx = np.empty(max(n, 1), np.uint32) if return_index else None
+        sal = np.empty(max(n, 1), np.float64) if return_saliency else None
+        sc = np.empty(max(n, 1), np.uint32) if return_counts else None
+        nc = np.empty(max(n, 1), np.uint32) if return_counts else None
+        n_out = _sz()
+        _chk(_lib.mvr_cloud_iss_keypoints(self._h, int(dst), int(src), C.byref(p), C.byref(n_out),
+                                          _p(idx, C.c_uint32) if return_index else None, _p(sal, C.c_double) if return_saliency else None,
+                                          _p(sc, C.c_uint32) if return_counts else None, _p(nc, C.c_uint32) if return_counts else None), self._h)
+        out = [n_out.value]
+        if return_index:
+            out.append(idx[:n_out.value].copy())
+        if return_saliency:
+            out.append(sal[:n])
+        if return_counts:
+            out += [sc[:n], nc[:n]]
+        return out[0] if len(out) == 1 else tuple(out)
 
     def feature_knn(self, q, t, k):
         """exact k nearest neighbours of every row of q among the rows of t in feature space (33 floats per row, FLANN's

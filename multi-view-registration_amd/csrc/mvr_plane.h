@@ -1,5 +1,5 @@
 // csrc/mvr_plane.h -- the plane through a neighbourhood, shared by the kernels that fit one (mvr_knn.hip: normals; mvr_mls.hip:
-// moving least squares): f64 moments of the neighbours about the query point, the 3 x 3 symmetric eigenproblem by cyclic Jacobi,
+// moving least squares; mvr_iss.hip: the eigenvalues of a scatter alone): f64 moments of the neighbours about the query point, the 3 x 3 symmetric eigenproblem by cyclic Jacobi,
 // the pick of the smallest eigenvalue's eigenvector, the curvature and the f32 orientation of the normal.  Every index is a compile-time constant: the matrices stay in
 // registers.  Not installed.
 #pragma once
@@ -75,6 +75,54 @@ __device__ __forceinline__ PlaneFit plane_fit(const Moments &M)
   f.sum = l0 + l1 + l2;
   f.m0 = m0; f.m1 = m1; f.m2 = m2;
   return f;
+}
+
+// ---- eigenvalues only (mvr_iss.hip): the rotation of jacobi_rot on the matrix alone, the same arithmetic
+template <int P, int Q, int R>
+__device__ __forceinline__ void jacobi_rot_values(double (&A)[3][3])
+{
+  const double apq = A[P][Q];
+  if (apq == 0.0) return;
+  const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
+  const double t = fabs(theta) > 1.0e150 ? 0.5 / theta : copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+  A[P][P] -= t * apq;
+  A[Q][Q] += t * apq;
+  A[P][Q] = A[Q][P] = 0.0;
+  const double arp = A[R][P], arq = A[R][Q];
+  A[R][P] = A[P][R] = c * arp - s * arq;
+  A[R][Q] = A[Q][R] = s * arp + c * arq;
+}
+
+// the eigenvalues e1 >= e2 >= e3 of the scatter matrix of the moments -- the second sums as they are, about the query point,
+// NOT divided by the count and not centred on the mean (pcl::ISSKeypoint3D::getScatterMatrix).  The order is taken with
+// fmin / fmax between values (no array element is selected by a runtime index).  fmin / fmax drop a NaN, so a non-finite
+// diagonal makes all three NaN: the caller's test that they are finite sees it.
+struct Eigenvalues3 {
+  double e1, e2, e3;
+};
+
+__device__ __forceinline__ Eigenvalues3 scatter_eigenvalues(const Moments &M)
+{
+  double A[3][3];
+  A[0][0] = M.xx; A[0][1] = A[1][0] = M.xy; A[0][2] = A[2][0] = M.xz;
+  A[1][1] = M.yy; A[1][2] = A[2][1] = M.yz; A[2][2] = M.zz;
+  for (int sweep = 0; sweep < 12; ++sweep) {
+    const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
+    const double dia = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
+    if (!(off > 1.0e-40 * dia)) break;                      // (an all-zero matrix ends here too)
+    jacobi_rot_values<0, 1, 2>(A);
+    jacobi_rot_values<0, 2, 1>(A);
+    jacobi_rot_values<1, 2, 0>(A);
+  }
+  const double l0 = A[0][0], l1 = A[1][1], l2 = A[2][2];
+  const double hi = fmax(l0, l1), lo = fmin(l0, l1);
+  Eigenvalues3 e;
+  if (!(isfinite(l0) && isfinite(l1) && isfinite(l2))) { e.e1 = e.e2 = e.e3 = __builtin_nan(""); return e; }
+  e.e1 = fmax(hi, l2);
+  e.e2 = fmax(lo, fmin(hi, l2));
+  e.e3 = fmin(lo, l2);
+  return e;
 }
 
 // PCL's curvature of a fitted plane: the smallest eigenvalue's share of the three
