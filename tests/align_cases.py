@@ -18,7 +18,7 @@ def features(rng, n, step=4.0):
 
 
 KNN_NQ, KNN_NT = 300, 700            # no multiple of the 256 queries of a block nor of the 64 rows of a tile
-KNN_KS = (1, 2, 10, 64)
+KNN_KS = (1, 2, 8, 9, 10, 16, 17, 32, 33, 63, 64)      # every list size (8 / 16 / 32 / 64) and both sides of every edge between two
 KNN_TAILS = (1, 5, 63, 65)           # targets for k = 64: the tails of the lists, one row short of and past a tile
 KNN_BIG = (5000, 20000)              # crosses the automatic split of the target and its merge
 KNN_SPLITS = (1, 2, 3, 7, 64)        # values of the tune key "feat_split" (0, the default, besides)
@@ -53,6 +53,129 @@ def knn_non_finite(seed=3, nq=KNN_NQ, nt=KNN_NT):
             if j % 4 == 0:
                 a[i, rng.integers(DIM)] = np.inf
         a[bad[0]] = np.nan
+    return q, t
+
+
+# ------------------------------------------------------------------ feature tables of real values
+# On the tables above every partial sum of M1 is an exact integer: any order and any rounding of the sum gives the same bits.
+# The tables below are the ones on which the order and the rounding show (tests/test_align_host.py asserts both statements).
+
+KNN_REAL = ("real", "fpfh_like", "twins", "signatures", "range", "key_zero")
+KNN_SPLIT_SHAPE = (257, 4161)        # one query past a block; 66 tiles of 64 rows and one row: feat_split 7 gives 7 x 640 rows
+KNN_EDGE_NQ, KNN_EDGE_NT = (1, 255, 256, 257), (1, 63, 64, 65, 255, 257)
+TWIN_STEP = 2.0 ** -10               # the lattice of the twins: q, d and q - d are multiples of it below 2^7, exact in f32
+FEAT_TILE = 64                       # kFeatTile of csrc/mvr_feature.hip: a split of the target is a whole number of tiles
+
+
+def knn_real(seed=21, nq=KNN_NQ, nt=KNN_NT):
+    """uniform in 0..100, left unrounded: every step of M1 rounds"""
+    rng = np.random.default_rng(seed)
+    return rng.uniform(0.0, 100.0, (nq, DIM)).astype(F32), rng.uniform(0.0, 100.0, (nt, DIM)).astype(F32)
+
+
+def fpfh_like(rng, n):
+    """three blocks of 11 non-negative values that sum to 100 each, most of them small: the shape of a signature"""
+    g = rng.gamma(0.3, 1.0, (n, 3, DIM // 3)) + 1e-12
+    return (100.0 * g / g.sum(2, keepdims=True)).reshape(n, DIM).astype(F32)
+
+
+def knn_fpfh_like(seed=22, nq=KNN_NQ, nt=KNN_NT):
+    rng = np.random.default_rng(seed)
+    return fpfh_like(rng, nq), fpfh_like(rng, nt)
+
+
+def twin_rows(nq, nt):
+    """the rows of the first twin of every query (the second is the next row): odd rows, so a pair never shares its first
+    row with another, and first of all the rows 64 m - 1 -- those pairs straddle a tile boundary, and a split of the target
+    ends at one"""
+    odd = np.arange(1, nt - 1, 2)
+    edge = odd[(odd + 1) % FEAT_TILE == 0][:nq]
+    return edge, np.setdiff1d(odd, edge)
+
+
+def _twins(seed, nq, nt):
+    rng = np.random.default_rng(seed)
+    assert nt >= 2 * nq + 1
+    q = (rng.integers(0, int(100 / TWIN_STEP) + 1, (nq, DIM)) * TWIN_STEP).astype(F32)
+    d = rng.integers(-int(8 / TWIN_STEP), int(8 / TWIN_STEP) + 1, (nq, DIM)) * TWIN_STEP
+    dp = np.stack([row[rng.permutation(DIM)] for row in d])
+    t = rng.uniform(0.0, 100.0, (nt, DIM)).astype(F32)
+    edge, rest = twin_rows(nq, nt)
+    first = np.r_[edge, rng.choice(rest, nq - len(edge), replace=False)][rng.permutation(nq)]
+    a, b = (q.astype(F64) - d).astype(F32), (q.astype(F64) - dp).astype(F32)
+    assert np.array_equal(a.astype(F64), q.astype(F64) - d) and np.array_equal(b.astype(F64), q.astype(F64) - dp)
+    assert np.array_equal((q - a).astype(F64), d) and np.array_equal((q - b).astype(F64), dp)      # the f32 differences are exact
+    t[first], t[first + 1] = a, b
+    return q, t, first
+
+
+def knn_twins(seed=23, nq=KNN_NQ, nt=KNN_NT):
+    """Every query q has two target rows q - d and q - perm(d), adjacent in the table: the 33 differences of the one are a
+    permutation of the other's, all exact in f32 (asserted), so the two d2 are equal in exact arithmetic and differ in f32
+    by the order of the roundings alone.  The other rows are uniform in 0..100 and far away (a twin lies 33 * 8^2 at most from
+    its query, any other row about 33 * 1 666): which twin leads the list of q is decided by M1's order and rounding alone."""
+    return _twins(seed, nq, nt)[:2]
+
+
+def twin_first_rows(seed=23, nq=KNN_NQ, nt=KNN_NT):
+    """the row of the first twin of every query of knn_twins (the second is the next row)"""
+    return _twins(seed, nq, nt)[2]
+
+
+def knn_signatures(nq=KNN_NQ):
+    """the reference's FPFH signatures of fpfh_cases.box(), the first 300 as queries and the other 2 700 as the target: rows the
+    project's own descriptor produces"""
+    import fpfh_cases as FC
+    import fpfh_ref
+    p, nrm, radius = FC.box()
+    f = np.ascontiguousarray(fpfh_ref.fpfh(p, nrm, radius)[0], dtype=F32)
+    assert f.shape == (FC.BOX_N, DIM) and np.isfinite(f).all()
+    return f[:nq].copy(), f[nq:].copy()
+
+
+RANGE_BIG, RANGE_SMALL = 3.0e19, 1.0e-30      # (3e19)^2 overflows f32; (1e-30)^2 underflows to 0
+
+
+def knn_range(seed=25, nq=KNN_NQ, nt=KNN_NT):
+    """finite rows at the two ends of f32's range, on the table of knn_real.
+    Overflow: the first 40 queries have an exact copy among the target rows but for one component, RANGE_BIG away:
+    diff * diff is +inf, d2 is not finite and the pair is not listed (M3), although every row is finite.  Query 40 holds
+    RANGE_BIG itself: it lists the ten target rows that hold it in the same component, and no other.
+    Underflow: queries 50..129 are 0 in one component and have two copies in the target, an exact one and one that holds
+    RANGE_SMALL there: diff * diff underflows to 0, both d2 are 0 and the lower index leads -- the near copy for the even
+    queries, the exact copy for the odd ones."""
+    rng = np.random.default_rng(seed)
+    q, t = knn_real(seed, nq, nt)
+    rows = rng.permutation(nt)
+    assert nq >= 130 and nt >= 300
+    n_over, n_under = 40, 80
+    take = iter(rows)
+    for i in range(n_over):
+        r, b = next(take), rng.integers(DIM)
+        t[r] = q[i]
+        t[r, b] = q[i, b] + F32(RANGE_BIG) * (1 if i % 2 else -1)
+    q[40, 7] = RANGE_BIG
+    for j in range(10):
+        t[next(take), 7] = F32(RANGE_BIG) * (1.0 + 2.0 ** -20 * j)
+    pairs = np.sort(np.array([next(take) for _ in range(2 * n_under)]).reshape(-1, 2), axis=1)
+    for j, (lo, hi) in enumerate(pairs):
+        i, b = 50 + j, rng.integers(DIM)
+        q[i, b] = 0.0
+        near, exact = (lo, hi) if i % 2 == 0 else (hi, lo)
+        t[near], t[exact] = q[i], q[i]
+        t[near, b] = RANGE_SMALL
+    assert np.isfinite(q).all() and np.isfinite(t).all()
+    return q, t
+
+
+def knn_key_zero(seed=26, nq=KNN_NQ, nt=KNN_NT):
+    """query 0 IS target row 0: its first key is (d2 = +0.0, index 0), the 64-bit integer 0 -- the value the kernels fill the
+    unused slots of a list with.  Every third query is an exact copy of some other row, and rows 1..5 are copies of row 0."""
+    rng = np.random.default_rng(seed)
+    q, t = knn_real(seed, nq, nt)
+    q[::3] = t[rng.choice(np.arange(6, nt), len(q[::3]), replace=False)]
+    t[1:6] = t[0]
+    q[0] = t[0]
     return q, t
 
 

@@ -31,6 +31,73 @@ def feat_d2(q, t):
     return acc
 
 
+def _steps(q, t):
+    """(diff, diff * diff) of every step of M1 as f32 arrays over the pairs, component by component"""
+    q, t = np.asarray(q, F32), np.asarray(t, F32)
+    qT, tT = np.ascontiguousarray(q.T), np.ascontiguousarray(t.T)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for b in range(q.shape[1]):
+            diff = np.subtract(qT[b][:, None], tT[b][None, :])
+            yield diff, np.multiply(diff, diff)
+
+
+def d2_fma_chain(q, t):
+    """WRONG: acc = fma(diff, diff, acc).  The product of two f32 is exact in f64; the f64 sum rounded to f32 is the fused
+    result but for a double rounding in a few cases out of a million -- near enough for a variant that is wrong anyway"""
+    acc = np.zeros((len(q), len(t)), F32)
+    for diff, _ in _steps(q, t):
+        d = diff.astype(F64)
+        acc = (acc.astype(F64) + d * d).astype(F32)
+    return acc
+
+
+def d2_four_accumulators(q, t):
+    """WRONG: component b goes to accumulator b % 4, the four added as (a0 + a1) + (a2 + a3)"""
+    acc = [np.zeros((len(q), len(t)), F32) for _ in range(4)]
+    for b, (_, sq) in enumerate(_steps(q, t)):
+        acc[b % 4] = acc[b % 4] + sq
+    return (acc[0] + acc[1]) + (acc[2] + acc[3])
+
+
+def d2_reverse_order(q, t):
+    """WRONG: the sum from component 32 down to 0"""
+    sq = [s for _, s in _steps(q, t)]
+    acc = np.zeros((len(q), len(t)), F32)
+    for s in reversed(sq):
+        acc = acc + s
+    return acc
+
+
+def d2_pairwise_tree(q, t):
+    """WRONG: neighbours added in pairs, level by level"""
+    level = [s for _, s in _steps(q, t)]
+    while len(level) > 1:
+        level = [level[i] + level[i + 1] if i + 1 < len(level) else level[i] for i in range(0, len(level), 2)]
+    return level[0]
+
+
+def d2_f64_rounded_once(q, t):
+    """WRONG: differences, squares and sum in f64, one rounding to f32 at the end"""
+    acc = np.zeros((len(q), len(t)), F64)
+    for diff, _ in _steps(q, t):
+        d = diff.astype(F64)
+        acc += d * d
+    return acc.astype(F32)
+
+
+# what an "optimised" distance loop would compute instead of M1: for tests/test_align_host.py only, which asserts on which inputs
+# the suite can tell them from feat_d2
+WRONG_D2 = {"fma chain": d2_fma_chain, "four accumulators": d2_four_accumulators, "reverse order": d2_reverse_order,
+            "pairwise tree": d2_pairwise_tree, "f64 rounded once": d2_f64_rounded_once}
+
+
+def knn_from_d2(D, k):
+    """the k smallest (d2 bits, index) keys per row of a finite d2 table: (idx, d2)"""
+    key = (np.asarray(D, F32).view(np.uint32).astype(U64) << U64(32)) | np.arange(D.shape[1], dtype=U64)[None, :]
+    key = np.sort(np.partition(key, k - 1, axis=1)[:, :k], axis=1)
+    return (key & U64(0xFFFFFFFF)).astype(np.uint32), (key >> U64(32)).astype(np.uint32).view(F32)
+
+
 def feature_knn(q, t, k, chunk=None):
     """(idx[nq, k] uint32, d2[nq, k] float32): the k smallest (d2 bits, index) keys per query, ascending; a pair whose d2 is not
     finite is not listed (M3: that is every pair of a non-finite row); UINT32_MAX / +inf fill the rest"""

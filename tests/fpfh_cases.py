@@ -1,7 +1,8 @@
 """The inputs the FPFH tests share (tests/test_gpu_fpfh.py compares the GPU on them, tests/test_fpfh_host.py checks on the
 reference alone that the share of queries with a slack pair stays under its cap).  Every case is (points [n, 4], normals
 [n, 4], radius).  The GPU tests replace the normals of the view by those mvr_cloud_estimate_normals gives for the same points;
-the host test takes them from tests/normals_ref.py, the reference of that call."""
+the host test takes them from tests/normals_ref.py, the reference of that call -- and so for the surface normals of the
+patches among the walk cases."""
 import numpy as np
 
 import mls_cases as K
@@ -77,6 +78,34 @@ def degenerate(name, mvr):
     t = W.get(name, mvr)[1]
     rng = np.random.default_rng(23)
     return t, unit_normals(rng, len(t)), float(W.radii(name, t)["several_cells"])
+
+
+# the walk cases (tests/walk_cases.py) the descriptor is run on: the target clouds
+WALK = ("patch_at_0", "patch_far_1e5", "patch_far_1e6", "lattice_3d", "clusters_and_a_far_point", "two_far_clusters", "duplicates_41",
+        "every_target_duplicated", "planar_sheet") + tuple("size_%d" % n for n in W.SIZES)
+WALK_SURFACE = tuple(n + "-surface" for n in WALK[:3])      # the patches a second time, with the normals of their surface
+WALK_NORMAL_CELLS = 2.5                                      # radius of those normals, in grid edges
+WALK_RADIUS_MM = {"clusters_and_a_far_point": 0.5, "two_far_clusters": 0.5}      # the grid edge spans the gap between the clusters:
+#                                                              a small ball in cells that hold thousands of points
+WALK_RADIUS_CELLS = {"lattice_3d": 2.0}                      # at one edge every lattice point is alone
+
+
+def walk_radius(name, t):
+    name = name.split("-")[0]
+    return float(WALK_RADIUS_MM[name]) if name in WALK_RADIUS_MM else float(WALK_RADIUS_CELLS.get(name, 1.0) * W.grid_edge(t))
+
+
+def walk(name, mvr):
+    """(g) the target of a walk case with random unit normals (those of degenerate()), at a radius of one grid edge but for the
+    exceptions above.  For a name of WALK_SURFACE the normals are None: the caller estimates them at walk_normal_radius() --
+    the GPU test with the library, the host test with ref_normals"""
+    t = W.get(name.split("-")[0], mvr)[1]
+    nrm = None if name.endswith("-surface") else unit_normals(np.random.default_rng(23), len(t))
+    return t, nrm, walk_radius(name, t)
+
+
+def walk_normal_radius(t):
+    return float(WALK_NORMAL_CELLS * W.grid_edge(t))
 
 
 def moved(p, nrm):

@@ -7,6 +7,7 @@ import numpy as np
 import fpfh_cases as FC
 import iss_ref as R
 import mls_cases as K
+import walk_cases as W
 
 VIEW_N, VIEW_SALIENT, VIEW_NON_MAX = 20000, 4.0, 2.5
 # a second parameter set on the view at which BOTH thresholds reject a visible share of the points (at PCL's defaults e3 / e2
@@ -16,7 +17,17 @@ VIEW_TIGHT = dict(gamma_21=0.8, gamma_32=0.015)
 DEFAULTS = dict(gamma_21=0.975, gamma_32=0.975, min_neighbors=5)
 
 EXACT = ("view", "view_tight", "box", "non_finite")
-NAMES = EXACT + tuple("tiny_%d" % n for n in FC.TINY_SIZES) + ("duplicates",) + FC.DEGENERATE
+# the targets of the walk cases (fpfh_cases.WALK): salient radius `several cells`, non-maximum radius 0.6 of it; the two cluster
+# cases 1.0 / 0.5 mm (their grid edge spans the gap between the clusters).  None is compared exactly: tests/test_iss_host.py
+# records what the reference decides on each
+WALK = FC.WALK
+WALK_NON_MAX = 0.6
+WALK_RADII_MM = {"clusters_and_a_far_point": (1.0, 0.5), "two_far_clusters": (1.0, 0.5)}
+# every_target_duplicated at `several cells` (3.5 edges) has 20 balls of 6 points that are 3 distinct ones twice: a scatter of
+# rank 2, whose e3 is rounding, and the reference calls 8 of them salient on that rounding alone.  At 5 edges the smallest ball
+# holds 10 points and every point is decided (tests/test_iss_host.py)
+WALK_RADII_CELLS = {"every_target_duplicated": 5.0}
+NAMES = EXACT + tuple("tiny_%d" % n for n in FC.TINY_SIZES) + ("duplicates",) + FC.DEGENERATE + WALK
 FMA_CASES = ("box", "non_finite", "duplicates")           # run a second time with the fma distance
 
 _cache = {}
@@ -42,6 +53,11 @@ def case(name, mvr):
     elif name in FC.DEGENERATE:
         p, _, r = FC.degenerate(name, mvr)
         c = dict(p=p, salient_radius=r, non_max_radius=r, **DEFAULTS)
+    elif name in WALK:
+        p = W.get(name, mvr)[1]
+        cells = float(WALK_RADII_CELLS[name] * W.grid_edge(p)) if name in WALK_RADII_CELLS else float(W.radii(name, p)["several_cells"])
+        r, m = WALK_RADII_MM.get(name) or (cells,) * 2
+        c = dict(p=p, salient_radius=r, non_max_radius=m if name in WALK_RADII_MM else WALK_NON_MAX * r, **DEFAULTS)
     else:
         raise KeyError(name)
     c["exact"] = name in EXACT

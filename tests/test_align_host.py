@@ -3,7 +3,15 @@
 (tests/align_cases.py), the exported symbols, their argument refusals, and the resources of the kernels of csrc/mvr_feature.hip.
 
 Measured here: 0.53 of the 200 iterations of the align case are polygon-rejected (similarity 0.5, k = 2, three samples), 94 are
-scored; chi-square of 40 000 draws over 50 bins 35.5 / 51.0 / 46.7 for the three samples (bound 86.7)."""
+scored; chi-square of 40 000 draws over 50 bins 35.5 / 51.0 / 46.7 for the three samples (bound 86.7).
+
+Which inputs see the order and the rounding of M1 (the five wrong accumulations of align_ref.WRONG_D2: fma chain, four
+accumulators, reverse order, pairwise tree, f64 rounded once): on knn_plain and knn_duplicates 0 of 210 000 pairs differ in a bit
+for any of the five.  On knn_real 0.33 / 0.66 / 0.73 / 0.63 / 0.63 of the pairs change their d2 bits and the k = 10 lists of
+297 / 300 / 300 / 300 / 300 of 300 queries; on knn_fpfh_like 0.32 / 0.65 / 0.72 / 0.63 / 0.63 and 294 / 300 / 300 / 300 / 300; on
+knn_signatures (810 000 pairs) 0.32 / 0.64 / 0.72 / 0.60 / 0.62 and 293 / 300 / 300 / 299 / 300 -- but an index of those lists
+changes for at most 1 query.  On knn_twins the two d2 differ in f32 for 201 of 300 queries and the nearest row changes for
+57 / 121 / 152 / 113 / 104 of 300 queries; 10 twin pairs straddle a tile boundary."""
 import ctypes as C
 import math
 import os
@@ -129,6 +137,105 @@ def test_reference_knn_order_and_non_finite_rows():
         diff = F32(q[~badq][0, b] - t[~badt][0, b])
         acc = F32(acc + F32(diff * diff))
     assert acc == x
+
+
+# ------------------------------------------------------------------ which inputs can see the order and the rounding of M1
+
+def bits(a):
+    return np.ascontiguousarray(a, F32).view(np.uint32)
+
+
+@pytest.fixture(scope="module")
+def real_tables():
+    return {name: getattr(AC, "knn_" + name)() for name in ("plain", "real", "fpfh_like", "signatures", "twins")}
+
+
+def test_feat_d2_is_the_scalar_loop_on_real_values(real_tables):
+    """M1 written out on np.float32 scalars, one rounded operation after the other, on 200 random pairs of every table"""
+    rng = np.random.default_rng(9)
+    for name, (q, t) in real_tables.items():
+        D = R.feat_d2(q, t)
+        for i, j in zip(rng.integers(0, len(q), 200), rng.integers(0, len(t), 200)):
+            acc = F32(0)
+            for b in range(AC.DIM):
+                diff = F32(q[i, b] - t[j, b])
+                acc = F32(acc + F32(diff * diff))
+            assert acc.view(np.uint32) == D[i, j].view(np.uint32), (name, i, j)
+
+
+def test_integer_valued_tables_cannot_tell_a_wrong_accumulation_from_m1(real_tables):
+    """the blind spot of knn_plain and of everything built from align_cases.features(): every partial sum is an exact integer
+    below 2^24, so the fma chain, four accumulators, the reverse order, a tree and an f64 sum all give the bits of M1"""
+    for q, t in (real_tables["plain"], AC.knn_duplicates()):
+        D = R.feat_d2(q, t)
+        assert D.max() < 2.0 ** 24 and (D == np.round(D)).all()
+        for what, wrong in R.WRONG_D2.items():
+            assert np.array_equal(bits(wrong(q, t)), bits(D)), what
+
+
+@pytest.mark.parametrize("name", ["real", "fpfh_like", "signatures"])
+def test_real_valued_tables_tell_every_wrong_accumulation_from_m1(name, real_tables):
+    """a condition on the inputs: where it fails the input changes, not the bar.  Every wrong accumulation changes the d2 bits
+    of at least a tenth of the pairs and the d2 bits of the k = 10 list of at least half of the queries"""
+    q, t = real_tables[name]
+    D = R.feat_d2(q, t)
+    assert np.isfinite(D).all()
+    want = R.knn_from_d2(D, 10)
+    ri, rd = R.feature_knn(q, t, 10)
+    assert np.array_equal(ri, want[0]) and np.array_equal(bits(rd), bits(want[1]))
+    for what, wrong in R.WRONG_D2.items():
+        W = wrong(q, t)
+        pairs = float((bits(W) != bits(D)).mean())
+        got = R.knn_from_d2(W, 10)
+        lists = int((bits(got[1]) != bits(want[1])).any(1).sum())
+        index = int((got[0] != want[0]).any(1).sum())
+        print("%s, %s: %.3f of %d pairs change their d2 bits; the k = 10 list of %d of %d queries changes in d2, of %d in an index"
+              % (name, what, pairs, D.size, lists, len(q), index))
+        assert pairs >= 0.10, (name, what)
+        assert lists >= len(q) // 2, (name, what)
+
+
+def test_twins_turn_a_wrong_accumulation_into_a_wrong_index(real_tables):
+    """a condition on the input: the two twins of a query have the same d2 in exact arithmetic, different bits under M1 for most
+    queries, and every wrong accumulation names the other twin first for at least 20 of the 300 queries"""
+    q, t = real_tables["twins"]
+    first = AC.twin_first_rows()
+    rows = np.arange(len(q))
+    exact = ((q.astype(F64)[:, None, :] - np.stack([t[first], t[first + 1]], 1).astype(F64)) ** 2).sum(2)
+    assert (exact[:, 0] == exact[:, 1]).all()                            # sums of 33 multiples of 2^-20 below 2^12: exact in f64
+    D = R.feat_d2(q, t)
+    differ = int((bits(D[rows, first]) != bits(D[rows, first + 1])).sum())
+    want = R.knn_from_d2(D, 2)[0]
+    assert np.array_equal(np.sort(want, axis=1), np.stack([first, first + 1], 1))      # the twins lead every list
+    edge = int(((first + 1) % AC.FEAT_TILE == 0).sum())
+    print("twins: the two d2 differ in f32 for %d of %d queries; %d pairs straddle a tile boundary" % (differ, len(q), edge))
+    assert differ >= len(q) // 2 and edge >= 10
+    for what, wrong in R.WRONG_D2.items():
+        got = R.knn_from_d2(wrong(q, t), 2)[0]
+        assert np.array_equal(np.sort(got, axis=1), np.sort(want, axis=1)), what
+        swapped = int((got[:, 0] != want[:, 0]).sum())
+        print("twins, %s: the nearest row changes for %d of %d queries" % (what, swapped, len(q)))
+        assert swapped >= 20, what
+
+
+def test_range_and_key_zero_cases_hold_what_they_say():
+    q, t = AC.knn_range()
+    idx, d2 = R.feature_knn(q, t, 10)
+    D = R.feat_d2(q, t)
+    assert np.isfinite(q).all() and np.isfinite(t).all() and np.isinf(D).sum() >= 40 + 10 * (len(q) - 1) + len(t) - 10
+    twin = np.array([np.nonzero((t[:, :] == q[i]).sum(1) == AC.DIM - 1)[0][0] for i in range(40)])      # the copy but for one component
+    assert np.isinf(D[np.arange(40), twin]).all() and not (idx[:40] == twin[:, None]).any()
+    assert (idx[40] != R.NONE).all()
+    assert (t[idx[40].astype(np.int64), 7] >= F32(AC.RANGE_BIG)).all()
+    assert (R.feature_knn(q, t, 64)[0][40] != R.NONE).sum() == 10
+    under = np.arange(50, 130)
+    assert (d2[under, :2] == 0).all() and (d2[under, 2] > 0).all() and (idx[under, 0] < idx[under, 1]).all()
+    near = (t[idx[under, 0].astype(np.int64)] != q[under]).any(1)        # the leading row is the near copy ...
+    assert np.array_equal(near, under % 2 == 0)                          # ... for the even queries, the exact one for the odd
+    q, t = AC.knn_key_zero()
+    idx, d2 = R.feature_knn(q, t, 10)
+    assert list(idx[0, :6]) == [0, 1, 2, 3, 4, 5] and (bits(d2[0, :6]) == 0).all() and d2[0, 6] > 0
+    assert (d2[::3, 0] == 0).all() and (d2[:, 0] == 0).sum() == len(q[::3])
 
 
 # ------------------------------------------------------------------ the C-ABI

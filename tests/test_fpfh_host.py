@@ -3,7 +3,11 @@ condition on the shared inputs (tests/fpfh_cases.py) that at most 0.30 of the qu
 its argument refusals, and the resources of the kernels of csrc/mvr_fpfh.hip (no scratch memory).
 
 Measured here: share of queries with a slack pair 0.221 on the view (44.7 neighbours, 894 168 pairs, 5 192 of them slack) and
-0.192 on the box (37.1 neighbours); the box fills all 33 bins, the view 28."""
+0.192 on the box (37.1 neighbours); the box fills all 33 bins, the view 28.  On the targets of the walk cases (fpfh_cases.WALK,
+random unit normals): the patches 0.111 / 0.105 / 0.111 at 0 / 1e5 / 1e6 mm (20 neighbours; 0.066 / 0.066 / 0.071 with the
+normals of their surface), lattice_3d 0.080, the two cluster cases 0.149 / 0.155 (29 and 30 neighbours in a ball of 0.5 mm),
+duplicates_41 0.102, every_target_duplicated 0.102, planar_sheet 0.079, the sizes 3 to 1 025 between 0.000 and 0.235 (size_1025,
+48 neighbours)."""
 import ctypes as C
 import math
 import os
@@ -77,6 +81,23 @@ def test_share_of_queries_with_a_slack_pair(case, box_ref, view_ref):
         b = np.abs((nrm[c["J"][o], :3].astype(F64) * (p[c["J"][o], :3].astype(F64) - p[c["I"][o], :3].astype(F64))).sum(1))
         assert 0.4 < (a < b).mean() < 0.6                                # the swap branch about half the time
         assert F["has_f64"].all()
+
+
+@pytest.mark.parametrize("name", FC.WALK + FC.WALK_SURFACE)
+def test_share_of_queries_with_a_slack_pair_on_the_walk_cases(name, mvr):
+    """the same condition on the targets of the walk cases: far frames, a lattice, clusters with thousands of points in a cell,
+    duplicates, an exact plane and the sizes around every launch edge"""
+    p, nrm, radius = FC.walk(name, mvr)
+    if nrm is None:
+        nrm = FC.ref_normals(p, FC.walk_normal_radius(p))
+    c = R.spfh_counts(p, nrm, radius)
+    share = float((c["slack"] > 0).mean())
+    print("%s: %d points, %d invalid, radius %.4g, %.1f neighbours, %d pairs, %d slack; share of queries with a slack pair %.3f"
+          % (name, len(p), int((~c["valid"]).sum()), radius, c["n"].mean(), len(c["I"]), int(c["slack"].sum()), share))
+    assert share <= FC.SLACK_CAP
+    assert c["valid"].mean() > 0.9
+    if len(p) >= 63:
+        assert c["n"].mean() > 2.0                                       # the radius reaches neighbours: there is something to compare
 
 
 def test_small_and_duplicate_clouds():

@@ -1,6 +1,6 @@
 """GPU tests of mvr_align_prerejective (rules A1-A6 in include/mvr_hip.h), every run with its trace:
- (a) status, samples and matches of every iteration equal align_ref's replay fed with the GPU's own k-NN table (itself compared
-     bit for bit in test_gpu_feature_knn.py);
+ (a) status, samples and matches of every iteration equal align_ref's replay fed with the GPU's own k-NN table, and that table
+     equals align_ref.feature_knn of the same rows bit for bit (as every table of test_gpu_feature_knn.py does);
  (b) inliers / error of every scored iteration equal the anchor of test_gpu_pose_scores.py applied to the traced pose;
  (c) every traced pose agrees with numpy's Kabsch on the traced pairs within the bar of the estimator's own test
      (tests/test_gpu_configs.py:22, used at :29-32: rotation entries 1e-5, translation 1e-4 mm);
@@ -60,13 +60,20 @@ def same_trace(a, b):
     return all(np.array_equal(np.ascontiguousarray(a[k]).view(np.uint8), np.ascontiguousarray(b[k]).view(np.uint8)) for k in b)
 
 
+def same_table(got, want):
+    """a k-NN table of the GPU against align_ref.feature_knn of the same rows: indices and d2 bits, nothing excluded"""
+    assert got[0].shape == want[0].shape and np.array_equal(got[0], want[0])
+    assert np.array_equal(np.ascontiguousarray(got[1]).view(np.uint32), np.ascontiguousarray(want[1]).view(np.uint32))
+
+
 def verify(ctx, pair, res, tr, a):
     """(a)-(d) on one traced run"""
     s, t, sf, tf = pair
     nr, iters = a["nr_samples"], a["max_iterations"]
     el = R.eligible(s, sf)
     if len(el) >= nr:
-        idx, _ = ctx.feature_knn(sf[el], tf, a["k"])
+        idx, d2 = ctx.feature_knn(sf[el], tf, a["k"])
+        same_table((idx, d2), R.feature_knn(sf[el], tf, a["k"]))     # the table the replay is fed is the reference's own
     else:
         idx = np.zeros((len(el), a["k"]), np.uint32)
     st, src, tgt = R.replay(s, t, el, idx, iters, nr, a["seed"], a["similarity"], a.get("fma", False))
@@ -220,7 +227,12 @@ def test_recovery_of_a_known_pose(ctx, mvr):
     assert worst <= AC.REC_MAX_DIST
     # the reference's replay of the first iterations of the same run, from the GPU's own table
     el = R.eligible(s, sf)
-    idx, _ = ctx.feature_knn(sf[el], tf, AC.REC_PARAMS["k"])
+    idx, d2 = ctx.feature_knn(sf[el], tf, AC.REC_PARAMS["k"])
+    # ... which is the reference's table of the same rows: the library's own FPFH signatures, real-valued, where the order and
+    # the rounding of M1's sum show in the bits
+    ri, rd = R.feature_knn(sf[el], tf, AC.REC_PARAMS["k"])
+    same_table((idx, d2), (ri, rd))
+    print("recovery: k-NN table of %d x %d signatures equals the reference's, %d entries" % (len(el), len(tf), idx.size))
     m = AC.REC_REPLAY
     st, src, tgt = R.replay(s, t, el, idx, m, 3, AC.REC_PARAMS["seed"], AC.REC_PARAMS["similarity"])
     assert np.array_equal(tr["status"][:m], st) and np.array_equal(tr["src"][:m], src) and np.array_equal(tr["tgt"][:m], tgt)

@@ -10,7 +10,11 @@ Measured on an MI355X (profiles/fpfh_pytest_gpu.log): neighbour counts exact on 
 reference's f64 bins, summed over bins, 4 on the view (5 192 slack pairs), 4 on the view with 76 invalid points, 0 on the box and
 on the duplicates; weighting 0 of 659 868 / 99 000 / 657 492 / 49 500 components differ at all, fma off and on; the fma chain
 changes no neighbour set on the box and the duplicates; pose invariance, median L1 0.0002 of 300 on the GPU and 0.0002 in the
-reference (31.6 between unrelated points)."""
+reference (31.6 between unrelated points).
+
+The targets of the walk cases (fpfh_cases.WALK, WALK_SURFACE) and the four grid resolutions were added later and were NOT
+measured on a GPU when they were written: no device could be had.  They were run once against a stand-in context whose
+descriptor is the numpy reference."""
 import importlib
 
 import numpy as np
@@ -74,6 +78,13 @@ def inputs(name, mvr, ctx):
             _inputs[name] = FC.box()
         elif name == "duplicates":
             _inputs[name] = FC.duplicates()
+        elif name in FC.WALK + FC.WALK_SURFACE:
+            p, nrm, radius = FC.walk(name, mvr)
+            if nrm is None:                                               # the library's radius-mode normals of the patch
+                ctx.upload(2, p)
+                ctx.estimate_normals(2, radius=FC.walk_normal_radius(p))
+                nrm = ctx.download_normals(2)
+            _inputs[name] = (p, nrm, radius)
     return _inputs[name]
 
 
@@ -92,7 +103,7 @@ def gpu(name, mvr, ctx, fma=False):
     return _gpu[key]
 
 
-CASES = ["view", "box", "invalid", "duplicates"]
+CASES = ["view", "box", "invalid", "duplicates"] + list(FC.WALK + FC.WALK_SURFACE)
 
 
 # ------------------------------------------------------------------ the first pass: counts
@@ -183,6 +194,34 @@ def test_bit_identical_from_run_to_run_and_fma(mvr, ctx):
         if len(changed) == 0:
             v = ca["valid"]
             assert np.abs(a[0][v].astype(F64) - b[0][v].astype(F64)).max() < 1e-3
+
+
+# ------------------------------------------------------------------ the grid's resolution must not show
+
+@pytest.mark.parametrize("name", ["box", "patch_far_1e6"])
+def test_results_do_not_depend_on_the_grid_resolution(name, mvr, ctx):
+    """seq_cell_points 4 (the default), 1, 64 and 4096 change the cell edge of every grid built afterwards (the cloud is uploaded
+    again after each tune).  Neighbour counts and the SPFH table are byte-identical: the counts are integers of per-pair f32
+    features, the order of the walk cannot show.  The f64 sums of the weighting run in walk order, so identical bits are not
+    promised for the signature: at every resolution it is within one f32 ulp of the reference's weighting of that SPFH"""
+    p, nrm, radius = inputs(name, mvr, ctx)
+    c = reference(name, mvr, ctx)
+    v = c["valid"]
+    try:
+        base = None
+        for cp in (4, 1, 64, 4096):
+            ctx.tune(seq_cell_points=cp)
+            f, s, cnt = run(ctx, p, nrm, radius, slot=7)
+            if base is None:
+                base = (f, s, cnt)
+                assert np.array_equal(cnt.astype(np.int64), c["n"])
+            assert np.array_equal(cnt, base[2]) and same_bits(s, base[1]), (name, cp)
+            want = R.fpfh_from_spfh(p, s, c["I"], c["J"], v)
+            assert np.isnan(f[~v]).all() and within_one_ulp(f[v], want[v]).all(), (name, cp)
+            print("%s seq_cell_points=%d: %d of %d signature components differ from the default resolution's"
+                  % (name, cp, int((bits(f[v]) != bits(base[0][v])).sum()), f[v].size))
+    finally:
+        ctx.tune(seq_cell_points=4)
 
 
 # ------------------------------------------------------------------ pose invariance

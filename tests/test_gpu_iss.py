@@ -11,7 +11,8 @@ from its threshold and every pair of neighbouring saliencies GAP apart (view, vi
 the downloaded points equal the reference's exactly.
 
 NOT measured on a GPU when this was written: no device was available.  The comparisons below were run once against a stand-in
-context whose detector is the numpy reference, so they are known to hold for a correct implementation."""
+context whose detector is the numpy reference, so they are known to hold for a correct implementation.  The same holds for the
+targets of the walk cases (iss_cases.WALK) and for the four grid resolutions, added later."""
 import importlib
 
 import numpy as np
@@ -70,9 +71,7 @@ def gpu_run(name, fma, mvr, ctx):
     return _gpu[(name, fma)]
 
 
-@pytest.mark.parametrize("name,fma", RUNS, ids=IDS)
-def test_counts_are_exact(name, fma, mvr, ctx):
-    c, ref, g = gpu_run(name, fma, mvr, ctx)
+def check_counts(c, ref, g):
     assert np.array_equal(g["salient_count"], ref["salient_count"])
     ball = np.diff(ref["sets"][1][1]).astype(np.uint32)
     assert np.array_equal(g["nms_count"], np.where(g["saliency"] != 0, ball, 0))      # K5: 0 for a point that is not salient
@@ -81,9 +80,7 @@ def test_counts_are_exact(name, fma, mvr, ctx):
     assert (g["salient_count"][~ref["valid"]] == 0).all() and (g["saliency"][~ref["valid"]] == 0).all()
 
 
-@pytest.mark.parametrize("name,fma", RUNS, ids=IDS)
-def test_saliency_against_the_reference(name, fma, mvr, ctx):
-    c, ref, g = gpu_run(name, fma, mvr, ctx)
+def check_saliency(c, ref, g, name, fma):
     s = ref["salient"]
     rel = np.abs(g["saliency"][s] - ref["saliency"][s]) / ref["saliency"][s]
     off = R.decided(ref) & ~s
@@ -94,10 +91,7 @@ def test_saliency_against_the_reference(name, fma, mvr, ctx):
     assert np.isfinite(g["saliency"]).all() and (g["saliency"] >= 0).all()
 
 
-@pytest.mark.parametrize("name,fma", RUNS, ids=IDS)
-def test_keypoints_are_the_suppression_of_the_gpus_own_saliencies(name, fma, mvr, ctx):
-    """no tolerance, on the degenerate and tie-ridden sets too"""
-    c, ref, g = gpu_run(name, fma, mvr, ctx)
+def check_suppression(c, ref, g):
     flat, offs = ref["sets"][1]
     cnt, key = R.nms(g["saliency"], flat, offs, c["min_neighbors"])
     assert np.array_equal(g["index"], np.nonzero(key)[0].astype(np.uint32))
@@ -105,6 +99,46 @@ def test_keypoints_are_the_suppression_of_the_gpus_own_saliencies(name, fma, mvr
     out = c["p"][g["index"].astype(np.int64)].copy()
     out[:, 3] = 1.0
     assert same_bits(g["points"], out)                                 # K6: ascending original index, w = 1
+
+
+@pytest.mark.parametrize("name,fma", RUNS, ids=IDS)
+def test_counts_are_exact(name, fma, mvr, ctx):
+    check_counts(*gpu_run(name, fma, mvr, ctx))
+
+
+@pytest.mark.parametrize("name,fma", RUNS, ids=IDS)
+def test_saliency_against_the_reference(name, fma, mvr, ctx):
+    check_saliency(*gpu_run(name, fma, mvr, ctx), name, fma)
+
+
+@pytest.mark.parametrize("name,fma", RUNS, ids=IDS)
+def test_keypoints_are_the_suppression_of_the_gpus_own_saliencies(name, fma, mvr, ctx):
+    """no tolerance, on the degenerate and tie-ridden sets too"""
+    check_suppression(*gpu_run(name, fma, mvr, ctx))
+
+
+@pytest.mark.parametrize("name", ["box", "view_tight", "patch_far_1e6"])
+def test_results_do_not_depend_on_the_grid_resolution(name, mvr, ctx):
+    """seq_cell_points 4 (the default), 1, 64 and 4096 change the cell edge of every grid built afterwards (the cloud is uploaded
+    again after each tune): the three checks above hold at each, and on the exact cases the keypoints are the reference's --
+    hence the same at every resolution.  The f64 sums of the scatter run in walk order: identical saliency bits are not promised"""
+    c, ref, base = gpu_run(name, False, mvr, ctx)
+    try:
+        for cp in (4, 1, 64, 4096):
+            ctx.tune(seq_cell_points=cp)
+            ctx.upload(8, c["p"])
+            g = detect(ctx, c, 9, 8)
+            g["points"] = ctx.download(9)
+            check_counts(c, ref, g)
+            check_saliency(c, ref, g, "%s seq_cell_points=%d" % (name, cp), False)
+            check_suppression(c, ref, g)
+            assert same_bits(g["salient_count"], base["salient_count"]) and same_bits(g["nms_count"], base["nms_count"]), (name, cp)
+            if c["exact"]:
+                assert np.array_equal(g["index"], ref["index"]) and same_bits(g["points"], base["points"]), (name, cp)
+            print("%s seq_cell_points=%d: %d of %d saliencies differ in a bit from the default resolution's, %d keypoints"
+                  % (name, cp, int((bits(g["saliency"]) != bits(base["saliency"])).sum()), len(g["saliency"]), len(g["index"])))
+    finally:
+        ctx.tune(seq_cell_points=4)
 
 
 @pytest.mark.parametrize("name,fma", [r for r in RUNS if r[0] in IC.EXACT], ids=[i for i, r in zip(IDS, RUNS) if r[0] in IC.EXACT])

@@ -167,6 +167,31 @@ def test_kept_set_on_the_walk_cases(ctx, mvr, name):
                     assert len(idx) == (len(p) if len(p) >= 3 else 0)
 
 
+def test_results_do_not_depend_on_the_grid_resolution(ctx, view20k):
+    """seq_cell_points 4 (the default), 1, 64 and 4096 change the cell edge of every grid built afterwards (mls() uploads the
+    cloud again after each tune): the kept index is identical, and the values are held to the reference at each resolution --
+    the f64 sums of the fit run in walk order, so identical bits are not promised beyond that"""
+    p, radius = view20k[0], 2.5
+    F = ref_fit("view20k", p, radius)
+    ref = R.result(p, F, 2)
+    bad, flat = R.excluded(F, 2)[F["keep"]], R.curvature_unpinned(F)[F["keep"]]
+    assert bad.sum() == 0
+    try:
+        base = None
+        for cp in (4, 1, 64, 4096):
+            ctx.tune(seq_cell_points=cp)
+            out, idx, curv = mls(ctx, p, radius, order=2, compute_normals=True)
+            nrm = ctx.download_normals(1)
+            if base is None:
+                base = (out, idx, curv, nrm)
+            assert np.array_equal(idx, ref["index"]) and np.array_equal(idx, base[1]), cp
+            compare_values("20k view, radius 2.5, order 2, seq_cell_points %d" % cp, out[:, :3], nrm[:, :3], curv, ref, bad, flat)
+            print("seq_cell_points=%d: %d of %d coordinates differ in a bit from the default resolution's"
+                  % (cp, int((bits(out[:, :3]) != bits(base[0][:, :3])).sum()), out[:, :3].size))
+    finally:
+        ctx.tune(seq_cell_points=4)
+
+
 def test_non_finite_points_are_dropped_and_nobodys_neighbour(ctx, view20k):
     p, bad = with_non_finite(view20k[0])
     fin = R.finite_mask(p)

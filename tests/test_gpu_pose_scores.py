@@ -92,6 +92,31 @@ def test_chunks_do_not_change_a_bit(ctx, scene):
     assert np.array_equal(again[1].view(np.uint64), base[1].view(np.uint64))
 
 
+def test_results_do_not_depend_on_the_grid_resolution(ctx, scene):
+    """seq_cell_points 4 (the default), 1, 64 and 4096 change the cell edge of every grid built afterwards; source and target
+    are uploaded again after each tune (the source's grid gives the blocks their points, the target's is walked).  The inliers
+    are identical; the block sums follow the source's grid order, so the error is held to the anchor at each resolution"""
+    s, t, P = scene
+    want = anchor(ctx, SRC, TGT, P, AC.SCORE_MAX_DIST)
+    try:
+        base = None
+        for cp in (4, 1, 64, 4096):
+            ctx.tune(seq_cell_points=cp)
+            ctx.upload(SRC, s)
+            ctx.upload(TGT, t)
+            got = ctx.pose_scores(SRC, TGT, P, AC.SCORE_MAX_DIST)
+            if base is None:
+                base = got
+            assert np.array_equal(got[0], base[0]), cp
+            check(got, want, len(s))
+            print("seq_cell_points=%d: %d of %d errors differ in a bit from the default resolution's"
+                  % (cp, int((got[1].view(np.uint64) != base[1].view(np.uint64)).sum()), len(P)))
+    finally:
+        ctx.tune(seq_cell_points=4)
+        ctx.upload(SRC, s)
+        ctx.upload(TGT, t)
+
+
 def test_non_finite_source_points_are_no_inliers(ctx, scene, mvr):
     s, t, P = scene
     import mls_cases as K

@@ -5,7 +5,11 @@ exactly, the exported symbol and its argument refusals, and the resources of the
 Measured here on the reference: view 19 951 salient / 1 715 keypoints (29.1 and 12.0 neighbours per ball), closest ratio 3.4e-4
 from its threshold, closest pair of neighbouring saliencies 1.1e-6 apart; view_tight 14 263 / 1 734, 2.8e-6, 1.1e-6; box
 2 974 / 142, 1.2e-4, 5.4e-5; non_finite 5 916 / 434, 3.5e-4, 1.9e-6.  The smallest e3 / e1 of a salient point is 1.5e-4.  The
-second implementation (cyclic Jacobi, shuffled order of the sums) gives the same flags and saliencies within 1e-12 relative."""
+second implementation (cyclic Jacobi, shuffled order of the sums) gives the same flags and saliencies within 1e-12 relative.
+On the targets of the walk cases (iss_cases.WALK) every point is decided except all 5 000 of
+planar_sheet (rank-deficient; none is salient) -- every_target_duplicated at 5 grid edges: at 3.5 it has 20 balls of three
+distinct points twice, rank 2, 8 of which the reference calls salient on rounding alone; keypoints: 68 / 66 / 63 on the patches at 0 / 1e5 / 1e6 mm (10 exact saliency ties between
+neighbours at 1e6), 132 on lattice_3d (1 832 ties), 6 and 12 on the two cluster cases, 1 to 4 elsewhere."""
 import ctypes as C
 import math
 import os
@@ -134,6 +138,34 @@ def test_the_other_cases_reach_the_edges(mvr):
         assert not R.decided(r).all()                                     # rank-deficient scatters: e3 is rounding, nothing to compare but the counts
     c, r = IC.reference("huge_coordinates", mvr)
     assert r["salient"].sum() > 1000 and R.decided(r).all()
+
+
+@pytest.mark.parametrize("name", IC.WALK)
+def test_what_the_reference_decides_on_the_walk_cases(name, mvr):
+    """a record, and two conditions the GPU test leans on: every point is decided (iss_ref.decided) except on the two sets named
+    below, and the patches, the lattice and the clusters have keypoints to suppress"""
+    c, r = IC.reference(name, mvr)
+    m = R.margins(r)
+    und = int((~R.decided(r)).sum())
+    print("%s: %d points, radii %.4g / %.4g, %d salient, %d keypoints, %.1f / %.1f neighbours, %d undecided, %d ties, closest ratio %.2e, "
+          "closest pair %.2e" % (name, len(c["p"]), c["salient_radius"], c["non_max_radius"], r["salient"].sum(), r["keypoint"].sum(),
+                                 r["salient_count"].mean(), r["nms_count"].mean(), und, m["ties"], m["ratio"], m["pair"]))
+    assert not c["exact"]
+    if name == "planar_sheet":
+        assert und == len(c["p"])                                          # rank-deficient: e3 is rounding, the counts and the suppression remain
+    else:
+        assert und == 0
+    assert not (~R.decided(r) & r["salient"]).any()                        # what the GPU's saliency is held to is decided
+    if name == "every_target_duplicated":
+        assert r["salient_count"].min() >= 7 and m["ties"] > 1000          # no ball of three distinct points twice; twins tie
+    if name.startswith("patch_"):
+        assert 50 <= r["keypoint"].sum() <= 80
+    if name in IC.WALK_RADII_MM:
+        assert 4 <= r["keypoint"].sum() <= 16
+    if name == "lattice_3d":
+        assert m["ties"] > 1000                                            # equal saliencies by symmetry: K5 is strict, both stay
+    if name == "patch_far_1e6":
+        assert m["ties"] > 0
 
 
 # ------------------------------------------------------------------ the C-ABI
