@@ -572,21 +572,106 @@ class FPFHEstimation {
   double radius_ = 0.0;
 };
 
+// ---------------------------------------------------------------- boundary points
+// pcl::BoundaryEstimation<PointInT, PointNT, PointOutT> (features/boundary.h) in radius mode, the input cloud its own search
+// surface: setInputCloud, setInputNormals, setSearchMethod, setRadiusSearch, setAngleThreshold / getAngleThreshold (PCL's
+// default pi / 2), compute.  Semantics: mvr_cloud_boundary (mvr_hip.h) with min_neighbors 0 -- one call on the GPU per compute().
+// PointInT: any point whose first three floats are x, y, z; PointNT: any point with normal_x / y / z; PointOutT: any point
+// with a boundary_point member.  As PCL's Feature::compute, a missing input, missing normals, a normal cloud of another size,
+// a radius that is not finite and > 0 or an angle threshold outside [MVR_BOUNDARY_MIN_ANGLE, 2 pi) prints an error and leaves
+// `output` empty, and so does a non-zero setKSearch: the k-neighbour mode is not offered.
+template <typename PointInT, typename PointNT, typename PointOutT = Boundary>
+class BoundaryEstimation {
+ public:
+  typedef PointCloud<PointInT> PointCloudIn;
+  typedef typename PointCloudIn::ConstPtr PointCloudConstPtr;
+  typedef PointCloud<PointNT> PointCloudN;
+  typedef typename PointCloudN::ConstPtr PointCloudNConstPtr;
+  typedef PointCloud<PointOutT> PointCloudOut;
+  typedef search::KdTree<PointInT> KdTree;
+  typedef typename KdTree::Ptr KdTreePtr;
+
+  void setInputCloud(const PointCloudConstPtr &c) { input_ = c; }
+  PointCloudConstPtr getInputCloud() const { return input_; }
+  void setInputNormals(const PointCloudNConstPtr &n) { normals_ = n; }
+  PointCloudNConstPtr getInputNormals() const { return normals_; }
+  void setSearchMethod(const KdTreePtr &tree) { tree_ = tree; }
+  KdTreePtr getSearchMethod() const { return tree_; }
+  void setRadiusSearch(double r) { radius_ = r; }
+  double getRadiusSearch() const { return radius_; }
+  void setKSearch(int k) { k_ = k; }
+  int getKSearch() const { return k_; }
+  void setAngleThreshold(float angle) { angle_threshold_ = angle; }
+  float getAngleThreshold() const { return angle_threshold_; }
+
+  void compute(PointCloudOut &output)
+  {
+    static_assert(sizeof(PointInT) % 4 == 0 && sizeof(PointInT) >= 12, "points that begin with x, y, z expected");
+    output.clear();
+    if (!input_) { std::fprintf(stderr, "[pcl::BoundaryEstimation::compute] No input dataset was given!\n"); return; }
+    if (!normals_ || normals_->size() != input_->size()) {
+      std::fprintf(stderr, "[pcl::BoundaryEstimation::compute] The number of points in the input dataset differs from the number of points in the dataset containing the normals!\n");
+      return;
+    }
+    if (k_ != 0) {
+      std::fprintf(stderr, "[pcl::BoundaryEstimation::compute] The k-neighbour mode (setKSearch %d) is not offered: use setRadiusSearch.\n", k_);
+      return;
+    }
+    if (!(std::isfinite(radius_) && radius_ > 0.0) || !(angle_threshold_ >= MVR_BOUNDARY_MIN_ANGLE && (double)angle_threshold_ < 2.0 * 3.14159265358979323846)) {
+      std::fprintf(stderr, "[pcl::BoundaryEstimation::compute] The search radius (%f) must be finite and > 0 (setRadiusSearch), the angle threshold (%f) in [pi / 4, 2 pi).\n",
+                   radius_, (double)angle_threshold_);
+      return;
+    }
+    const size_t n = input_->size();
+    output.resize(n);
+    if (!n) return;
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.check(mvr_cloud_upload(d.ctx(), s.s, input_->points[0].data, n, sizeof(PointInT)), "mvr_cloud_upload");
+    std::vector<float> nrm(4 * n);
+    for (size_t i = 0; i < n; ++i) {
+      const PointNT &q = normals_->points[i];
+      nrm[4 * i] = q.normal_x; nrm[4 * i + 1] = q.normal_y; nrm[4 * i + 2] = q.normal_z; nrm[4 * i + 3] = 0.f;
+    }
+    d.check(mvr_cloud_upload_normals(d.ctx(), s.s, nrm.data(), n, 16), "mvr_cloud_upload_normals");
+    mvr_boundary_params p;
+    p.radius = radius_; p.angle_threshold = angle_threshold_; p.min_neighbors = 0; p.fma_dist = 0;
+    std::vector<uint8_t> flag(n);
+    d.check(mvr_cloud_boundary(d.ctx(), s.s, &p, flag.data(), nullptr, nullptr), "mvr_cloud_boundary");
+    for (size_t i = 0; i < n; ++i) output.points[i].boundary_point = flag[i];
+  }
+
+ private:
+  PointCloudConstPtr input_;
+  PointCloudNConstPtr normals_;
+  KdTreePtr tree_;
+  double radius_ = 0.0;
+  int k_ = 0;
+  float angle_threshold_ = 1.57079632679489661923f;
+};
+
 // ---------------------------------------------------------------- intrinsic shape signature keypoints
-// pcl::ISSKeypoint3D<PointInT, PointOutT> (keypoints/iss_3d.h) without border estimation: setInputCloud, setSearchMethod,
-// setSalientRadius, setNonMaxRadius, setThreshold21, setThreshold32, setMinNeighbors, setNumberOfThreads, compute,
-// getKeypointsIndices, PCL's defaults (both thresholds 0.975, 5 neighbours; the radii must be set).  Semantics:
-// mvr_cloud_iss_keypoints (mvr_hip.h) -- one call on the GPU per compute().  PointInT / PointOutT: any point whose first three
-// floats are x, y, z.  `output` may be the input cloud itself.  A missing input, a radius that is not finite and > 0, a
-// non-finite threshold or a negative neighbour count prints an error and leaves the output empty (untouched when it is the
-// input), and so does a non-zero setBorderRadius / setNormalRadius: the border estimation is not offered, and computing
-// something else in silence would be worse than computing nothing.
-template <typename PointInT, typename PointOutT = PointInT>
+// pcl::ISSKeypoint3D<PointInT, PointOutT, NormalT> (keypoints/iss_3d.h): setInputCloud, setSearchMethod, setSalientRadius,
+// setNonMaxRadius, setThreshold21, setThreshold32, setMinNeighbors, setNumberOfThreads, setBorderRadius, setNormalRadius,
+// setNormals, setAngleThreshold, compute, getKeypointsIndices, PCL's defaults (both thresholds 0.975, 5 neighbours, angle
+// threshold pi / 2, no border; the radii must be set).  Semantics: mvr_cloud_iss_keypoints_border (mvr_hip.h) -- one call on
+// the GPU per compute().  PointInT / PointOutT: any point whose first three floats are x, y, z; NormalT: any point with
+// normal_x / y / z.  `output` may be the input cloud itself.  With setBorderRadius > 0 the points that have a boundary point
+// within that radius are dropped before the saliency test (rules K9-K11); the normals the boundary test needs are those of
+// setNormals, or -- without them, with setNormalRadius > 0 -- those of the library's radius-mode normal estimation at that
+// radius (mvr_cloud_estimate_normals; their sign does not matter to the test).  A missing input, a radius that is not finite
+// and > 0, a non-finite threshold or a negative neighbour count prints an error and leaves the output empty (untouched when
+// it is the input), and so do: a border radius with neither normals nor a normal radius; a normal cloud of another size than
+// the input; and a normal radius with a zero border radius (DEVIATION: PCL ignores the radius there) -- computing something
+// else in silence would be worse than computing nothing.
+template <typename PointInT, typename PointOutT = PointInT, typename NormalT = Normal>
 class ISSKeypoint3D {
  public:
   typedef PointCloud<PointInT> PointCloudIn;
   typedef typename PointCloudIn::ConstPtr PointCloudInConstPtr;
   typedef PointCloud<PointOutT> PointCloudOut;
+  typedef PointCloud<NormalT> PointCloudN;
+  typedef typename PointCloudN::ConstPtr PointCloudNConstPtr;
   typedef search::KdTree<PointInT> KdTree;
   typedef typename KdTree::Ptr KdTreePtr;
 
@@ -600,8 +685,10 @@ class ISSKeypoint3D {
   void setThreshold32(double g) { p_.gamma_32 = g; }
   void setMinNeighbors(int m) { p_.min_neighbors = m; }
   void setNumberOfThreads(unsigned int = 0) {}
-  void setBorderRadius(double r) { border_radius_ = r; }
+  void setBorderRadius(double r) { b_.border_radius = r; }
   void setNormalRadius(double r) { normal_radius_ = r; }
+  void setNormals(const PointCloudNConstPtr &normals) { normals_ = normals; }
+  void setAngleThreshold(float angle) { b_.angle_threshold = angle; }
   PointIndices::ConstPtr getKeypointsIndices() const { return indices_; }
 
   void compute(PointCloudOut &output)
@@ -610,9 +697,15 @@ class ISSKeypoint3D {
     indices_->indices.clear();
     const bool alias = (const void *)&output == (const void *)input_.get();
     if (!input_) { std::fprintf(stderr, "[pcl::ISSKeypoint3D::compute] No input dataset given!\n"); output.clear(); return; }
-    if (border_radius_ != 0.0 || normal_radius_ != 0.0) {
-      std::fprintf(stderr, "[pcl::ISSKeypoint3D::compute] The border estimation (setBorderRadius %f, setNormalRadius %f) is not offered.\n",
-                   border_radius_, normal_radius_);
+    if ((b_.border_radius != 0.0 && !normals_ && normal_radius_ == 0.0) || (b_.border_radius == 0.0 && normal_radius_ != 0.0)) {
+      std::fprintf(stderr, "[pcl::ISSKeypoint3D::compute] The border estimation (setBorderRadius %f, setNormalRadius %f) needs a border radius and either setNormals or a normal radius.\n",
+                   b_.border_radius, normal_radius_);
+      if (!alias) output.clear();
+      return;
+    }
+    const bool border = b_.border_radius != 0.0;
+    if (border && normals_ && normals_->size() != input_->size()) {
+      std::fprintf(stderr, "[pcl::ISSKeypoint3D::compute] The number of points in the input dataset differs from the number of points in the dataset containing the normals!\n");
       if (!alias) output.clear();
       return;
     }
@@ -623,14 +716,41 @@ class ISSKeypoint3D {
       if (!alias) output.clear();
       return;
     }
+    if (border && (!(std::isfinite(b_.border_radius) && b_.border_radius > 0.0) || !(normals_ || (std::isfinite(normal_radius_) && normal_radius_ > 0.0)) ||
+                   !(b_.angle_threshold >= MVR_BOUNDARY_MIN_ANGLE && b_.angle_threshold < 2.0 * 3.14159265358979323846))) {
+      if (normals_)
+        std::fprintf(stderr, "[pcl::ISSKeypoint3D::compute] The border radius (%f) must be finite and > 0, the angle threshold (%f) in [pi / 4, 2 pi).\n",
+                     b_.border_radius, b_.angle_threshold);
+      else
+        std::fprintf(stderr, "[pcl::ISSKeypoint3D::compute] The border radius (%f) and, without setNormals, the normal radius (%f) must be finite and > 0, the angle threshold (%f) in [pi / 4, 2 pi).\n",
+                     b_.border_radius, normal_radius_, b_.angle_threshold);
+      if (!alias) output.clear();
+      return;
+    }
     Device &d = Device::instance();
     SlotGuard s;
     const size_t n = input_->size();
     // first: `output` may alias the input
     d.check(mvr_cloud_upload(d.ctx(), s.s, n ? input_->points[0].data : nullptr, n, sizeof(PointInT)), "mvr_cloud_upload");
+    if (border && n) {
+      if (normals_) {
+        std::vector<float> nrm(4 * n);
+        for (size_t i = 0; i < n; ++i) {
+          const NormalT &q = normals_->points[i];
+          nrm[4 * i] = q.normal_x; nrm[4 * i + 1] = q.normal_y; nrm[4 * i + 2] = q.normal_z; nrm[4 * i + 3] = 0.f;
+        }
+        d.check(mvr_cloud_upload_normals(d.ctx(), s.s, nrm.data(), n, 16), "mvr_cloud_upload_normals");
+      } else {
+        mvr_normal_params np;
+        np.k = 0; np.radius = normal_radius_; np.fma_dist = 0;
+        np.viewpoint[0] = np.viewpoint[1] = np.viewpoint[2] = 0.f;
+        d.check(mvr_cloud_estimate_normals(d.ctx(), 1, &s.s, &np, nullptr), "mvr_cloud_estimate_normals");
+      }
+    }
     std::vector<uint32_t> kept(n ? n : 1);
     size_t m = 0;
-    d.check(mvr_cloud_iss_keypoints(d.ctx(), s.s, s.s, &p_, &m, kept.data(), nullptr, nullptr, nullptr), "mvr_cloud_iss_keypoints");
+    d.check(mvr_cloud_iss_keypoints_border(d.ctx(), s.s, s.s, &p_, border ? &b_ : nullptr, &m, kept.data(), nullptr, nullptr, nullptr, nullptr, nullptr),
+            "mvr_cloud_iss_keypoints_border");
     std::vector<float> xyz(4 * (m ? m : 1));
     size_t got = 0;
     if (m) d.check(mvr_cloud_download(d.ctx(), s.s, xyz.data(), m, 16, &got), "mvr_cloud_download");
@@ -645,9 +765,11 @@ class ISSKeypoint3D {
 
  private:
   PointCloudInConstPtr input_;
+  PointCloudNConstPtr normals_;
   KdTreePtr tree_;
   mvr_iss_params p_ = {0.0, 0.0, 0.975, 0.975, 5, 0};
-  double border_radius_ = 0.0, normal_radius_ = 0.0;
+  mvr_iss_border_params b_ = {0.0, 1.57079632679489661923};
+  double normal_radius_ = 0.0;
   PointIndicesPtr indices_ = std::make_shared<PointIndices>();
 };
 

@@ -312,11 +312,48 @@ class ScanCloud {
     return true;
   }
 
+  // EXTENSION (pcl::BoundaryEstimation on the raw points, on the GPU; rules: mvr_cloud_boundary in mvr_hip.h): one flag per point,
+  // whether its neighbours within p.radius, projected onto its tangent plane, leave an angular gap above p.angle_threshold,
+  // with the normals of `rich` (estimateNormals, smooth with compute_normals, or a file that carries them).  Without one rich
+  // record per point, or with a parameter outside its range, it prints an error, leaves `boundary` empty and returns false.
+  // `points`, `rich` and the pose stay as they are.
+  bool detectBoundary(const mvr_boundary_params &p, std::vector<uint8_t> &boundary) const
+  {
+    boundary.clear();
+    const size_t n = points.size();
+    if (rich.size() != n) {
+      std::fprintf(stderr, "[ScanCloud::detectBoundary] The cloud has no normals (%zu points, %zu records): call estimateNormals first.\n", n, rich.size());
+      return false;
+    }
+    if (!(std::isfinite(p.radius) && p.radius > 0.0) || p.min_neighbors < 0 ||
+        !(p.angle_threshold >= MVR_BOUNDARY_MIN_ANGLE && p.angle_threshold < 2.0 * 3.14159265358979323846)) {
+      std::fprintf(stderr, "[ScanCloud::detectBoundary] The radius (%f) must be finite and > 0, the angle threshold (%f) in [pi / 4, 2 pi), min_neighbors (%d) >= 0.\n",
+                   p.radius, p.angle_threshold, p.min_neighbors);
+      return false;
+    }
+    boundary.resize(n);
+    if (!n) return true;
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.upload(s.s, points);
+    uploadRichNormals(d, s.s);
+    d.check(mvr_cloud_boundary(d.ctx(), s.s, &p, boundary.data(), nullptr, nullptr), "mvr_cloud_boundary");
+    return true;
+  }
+
   // EXTENSION (pcl::ISSKeypoint3D on the raw points, on the GPU; rules: mvr_cloud_iss_keypoints in mvr_hip.h): the indices,
   // ascending, of the points whose scatter over salient_radius passes both eigenvalue ratio tests and whose smallest eigenvalue
   // no neighbour within non_max_radius exceeds.  A parameter outside its range prints an error, leaves `indices` empty and
   // returns false.  `points`, `rich` and the pose stay as they are.
   bool detectKeypoints(const mvr_iss_params &p, std::vector<uint32_t> &indices) const
+  {
+    mvr_iss_border_params none = mvr_iss_border_params();
+    return detectKeypoints(p, none, indices);
+  }
+  // the same with the border handling of the detector (rules K9-K11): with b.border_radius > 0 the points that have a boundary
+  // point -- detectBoundary at that radius, b.angle_threshold and p.min_neighbors -- within it are dropped before the saliency
+  // test; the normals are those of `rich`, and a cloud without them is refused as in detectBoundary.  A radius of 0: no border.
+  bool detectKeypoints(const mvr_iss_params &p, const mvr_iss_border_params &b, std::vector<uint32_t> &indices) const
   {
     indices.clear();
     if (!(std::isfinite(p.salient_radius) && p.salient_radius > 0.0) || !(std::isfinite(p.non_max_radius) && p.non_max_radius > 0.0) ||
@@ -325,14 +362,27 @@ class ScanCloud {
                    p.salient_radius, p.non_max_radius, p.gamma_21, p.gamma_32, p.min_neighbors);
       return false;
     }
+    const bool border = b.border_radius != 0.0;
     const size_t n = points.size();
+    if (border && (!(std::isfinite(b.border_radius) && b.border_radius > 0.0) ||
+                   !(b.angle_threshold >= MVR_BOUNDARY_MIN_ANGLE && b.angle_threshold < 2.0 * 3.14159265358979323846))) {
+      std::fprintf(stderr, "[ScanCloud::detectKeypoints] The border radius (%f) must be 0 (no border) or finite and > 0, the angle threshold (%f) in [pi / 4, 2 pi).\n",
+                   b.border_radius, b.angle_threshold);
+      return false;
+    }
+    if (border && rich.size() != n) {
+      std::fprintf(stderr, "[ScanCloud::detectKeypoints] A border radius needs normals (%zu points, %zu records): call estimateNormals first.\n", n, rich.size());
+      return false;
+    }
     if (!n) return true;
     Device &d = Device::instance();
     SlotGuard s;
     d.upload(s.s, points);
+    if (border) uploadRichNormals(d, s.s);
     indices.resize(n);
     size_t kept = 0;
-    d.check(mvr_cloud_iss_keypoints(d.ctx(), -1, s.s, &p, &kept, indices.data(), nullptr, nullptr, nullptr), "mvr_cloud_iss_keypoints");
+    d.check(mvr_cloud_iss_keypoints_border(d.ctx(), -1, s.s, &p, border ? &b : nullptr, &kept, indices.data(), nullptr, nullptr, nullptr, nullptr, nullptr),
+            "mvr_cloud_iss_keypoints_border");
     indices.resize(kept);
     return true;
   }
@@ -345,13 +395,16 @@ class ScanCloud {
   // With use_keypoints, detectKeypoints(keypoints) runs on both scans first and the descriptor rows of the other points are
   // overwritten with NaN: such a row is never sampled (A1) and never matched (M3), so the matcher's work drops from
   // n_source x n_target pairs to keypoints x n_target while every pose is still scored over all points of the source.
+  // With a border radius (border.border_radius > 0; off by default) the keypoints are those of the detector's border variant.
   struct PrerejectiveParams {
     double feature_radius = 0.0;
     mvr_prerej_params align;
     mvr_iss_params keypoints;            // salient_radius / non_max_radius must be set when use_keypoints is
+    mvr_iss_border_params border;        // border_radius 0: no border handling (the default); angle_threshold pi / 2
     bool use_keypoints = false;
     PrerejectiveParams()
     {
+      border = mvr_iss_border_params(); border.angle_threshold = 1.57079632679489661923;
       align = mvr_prerej_params(); align.max_iterations = 10; align.nr_samples = 3; align.k = 2; align.similarity = 0.9; align.inlier_fraction = 0.25;
       keypoints = mvr_iss_params(); keypoints.gamma_21 = keypoints.gamma_32 = 0.975; keypoints.min_neighbors = 5;
     }
@@ -361,7 +414,7 @@ class ScanCloud {
     std::vector<FPFHSignature33> sf, tf;
     if (result) { *result = mvr_prerej_result(); result->best_iteration = -1; result->error = DBL_MAX; }
     if (!computeFPFH(params.feature_radius, sf) || !target.computeFPFH(params.feature_radius, tf)) return false;
-    if (params.use_keypoints && (!keepKeypointRows(params.keypoints, sf) || !target.keepKeypointRows(params.keypoints, tf))) return false;
+    if (params.use_keypoints && (!keepKeypointRows(params.keypoints, params.border, sf) || !target.keepKeypointRows(params.keypoints, params.border, tf))) return false;
     Device &d = Device::instance();
     SlotGuard s, t;
     d.upload(s.s, points);
@@ -378,8 +431,13 @@ class ScanCloud {
   // the descriptor rows of the points detectKeypoints does not list become NaN (false: the detector refused its parameters)
   bool keepKeypointRows(const mvr_iss_params &p, std::vector<FPFHSignature33> &feat) const
   {
+    mvr_iss_border_params none = mvr_iss_border_params();
+    return keepKeypointRows(p, none, feat);
+  }
+  bool keepKeypointRows(const mvr_iss_params &p, const mvr_iss_border_params &b, std::vector<FPFHSignature33> &feat) const
+  {
     std::vector<uint32_t> key;
-    if (!detectKeypoints(p, key)) return false;
+    if (!detectKeypoints(p, b, key)) return false;
     std::vector<char> keep(feat.size(), 0);
     for (uint32_t i : key) keep[i] = 1;
     for (size_t i = 0; i < feat.size(); ++i)
@@ -420,6 +478,15 @@ class ScanCloud {
   }
 
  private:
+  // the normals of `rich` (one record per point) into a slot that holds `points`
+  void uploadRichNormals(Device &d, int slot) const
+  {
+    const size_t n = points.size();
+    std::vector<float> nrm(4 * n);
+    for (size_t i = 0; i < n; ++i) { nrm[4 * i] = rich[i].normal_x; nrm[4 * i + 1] = rich[i].normal_y; nrm[4 * i + 2] = rich[i].normal_z; nrm[4 * i + 3] = 0.f; }
+    d.check(mvr_cloud_upload_normals(d.ctx(), slot, nrm.data(), n, 16), "mvr_cloud_upload_normals");
+  }
+
   // one of the two filters (the other pointer null) in place on `points`; `rich` follows through kept_index
   size_t removeOutliers(const mvr_sor_params *sor, const mvr_ror_params *ror)
   {

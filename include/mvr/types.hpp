@@ -71,6 +71,13 @@ struct FPFHSignature33 {
 };
 static_assert(sizeof(FPFHSignature33) == 132, "FPFHSignature33 must match pcl::FPFHSignature33");
 
+// pcl::Boundary: whether a point lies on the rim of its surface (mvr_cloud_boundary in mvr_hip.h)
+struct Boundary {
+  uint8_t boundary_point;
+  Boundary() : boundary_point(0) {}
+};
+static_assert(sizeof(Boundary) == 1, "Boundary must match pcl::Boundary");
+
 // pcl::PointIndices (the member MovingLeastSquares::getCorrespondingIndices hands out)
 struct PointIndices {
   typedef std::shared_ptr<PointIndices> Ptr;

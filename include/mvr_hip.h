@@ -499,8 +499,9 @@ int  mvr_align_prerejective(mvr_ctx *ctx, int src_slot, int tgt_slot, const floa
 /* ---- intrinsic shape signature keypoints (EXTENSION: pcl::ISSKeypoint3D) -----------------------------------------------
  * What chooses the points that carry a descriptor into the matcher: a row of a feature table that is overwritten with NaN is
  * ineligible as a sample (A1) and never listed as a match (M3), so a non-keypoint is a NaN row.  The reference pins no PCL
- * version and PCL was not at hand; the model is pcl/keypoints/impl/iss_3d.hpp (getScatterMatrix, detectKeypoints) with
- * border_radius == 0, as published; deviations are marked.
+ * version and PCL was not at hand; the model is pcl/keypoints/impl/iss_3d.hpp (getScatterMatrix, getBoundaryPoints,
+ * detectKeypoints), as published; deviations are marked.  K1-K8 are the detector with border_radius == 0
+ * (mvr_cloud_iss_keypoints); K9-K11 add the border handling (mvr_cloud_iss_keypoints_border).
  *  K1. A point is VALID when its three coordinates are finite.  An invalid point is nobody's neighbour and never a keypoint;
  *      its saliency is 0 and both its counts are 0; no query walks the grid because of one (rules N2 and N5 above).
  *  K2. Neighbourhood of radius r: every valid j with d2(i, j) <= (float)(r * r) under the f32 distance of mvr_nn / mvr_knn,
@@ -524,8 +525,19 @@ int  mvr_align_prerejective(mvr_ctx *ctx, int src_slot, int tgt_slot, const floa
  *      non-finite or <= 0, a non-finite gamma, min_neighbors < 0, a cloud above 0x7FFFFFF0 points, or a cloud whose points are
  *      stale because a pipelined run is in flight.  An empty cloud is MVR_OK with an empty output.
  *  K8. Bit-identical from run to run on one grid: one thread per query, sums in walk order, no floating-point atomics.
- * Out of scope: the border estimation (setBorderRadius, setNormalRadius, setAngleThreshold -- border_radius is 0 throughout),
- * setSearchSurface, and the other keypoint detectors (Harris3D, SIFT, NARF, ...). */
+ *  K9. mvr_cloud_iss_keypoints_border with border parameters whose border_radius > 0 (setBorderRadius; angle_threshold is
+ *      setAngleThreshold): the source slot must have normals, else MVR_E_ARG.  edge[i] = rule B of mvr_cloud_boundary at
+ *      border_radius with the caller's angle_threshold, this call's min_neighbors and fma_dist.  On top of K7, MVR_E_ARG for
+ *      a border_radius that is non-finite or < 0 and for an angle_threshold outside B6's range.
+ *  K10. border[i] = i is valid and some j of its neighbourhood of border_radius (K2; i included) has edge[j].
+ *  K11. A border point has saliency 0, salient_count 0 and nms_count 0 and is never a keypoint; everything else of K3-K6 is
+ *      unchanged.  A border point therefore never suppresses a neighbour.  (PCL skips the border points before the saliency
+ *      test in the same way.)  edge / border (optional, host) receive one byte per SOURCE point.
+ *  With NULL border parameters, or border_radius == 0 (the threshold is then not looked at), every result equals
+ *  mvr_cloud_iss_keypoints bit for bit -- that entry IS this call with NULL -- and edge / border are all 0.
+ * Out of scope: setSearchSurface, estimating the normals inside the call (setNormalRadius: pcl::ISSKeypoint3D of
+ * mvr/registration.hpp does it with mvr_cloud_estimate_normals first), and the other keypoint detectors (Harris3D, SIFT,
+ * NARF, ...). */
 typedef struct {
   double salient_radius;     /* setSalientRadius: finite, > 0 */
   double non_max_radius;     /* setNonMaxRadius:  finite, > 0 */
@@ -536,6 +548,61 @@ typedef struct {
 int  mvr_cloud_iss_keypoints(mvr_ctx *ctx, int dst_slot /* -1: none */, int src_slot, const mvr_iss_params *p,
                              size_t *n_out, uint32_t *kept_index, double *saliency /* n */,
                              uint32_t *salient_count /* n */, uint32_t *nms_count /* n */);
+typedef struct {
+  double border_radius;      /* setBorderRadius: finite, >= 0; 0: no border */
+  double angle_threshold;    /* setAngleThreshold (PCL default pi / 2): B6's range */
+} mvr_iss_border_params;
+int  mvr_cloud_iss_keypoints_border(mvr_ctx *ctx, int dst_slot /* -1: none */, int src_slot, const mvr_iss_params *p,
+                             const mvr_iss_border_params *border_params /* NULL or radius 0: none */, size_t *n_out,
+                             uint32_t *kept_index, double *saliency /* n */, uint32_t *salient_count /* n */,
+                             uint32_t *nms_count /* n */, uint8_t *edge /* n, optional */, uint8_t *border /* n, optional */);
+
+/* ---- boundary points (EXTENSION: pcl::BoundaryEstimation) --------------------------------------------------------------
+ * Which points of a partial surface lie on its rim: the neighbours of a point are projected onto its tangent plane and the
+ * point is a boundary point when they leave an angular gap wider than a threshold.  PCL was not at hand; the model is
+ * pcl/features/impl/boundary.hpp (isBoundaryPoint, getCoordinateSystemOnPlane, computeFeature), as published, in radius mode
+ * with the cloud its own search surface; deviations are marked.
+ *  B1. Valid points and neighbourhoods are those of K1 and K2 above: the f32 distance with d2 <= (float)(radius * radius), i
+ *      itself included, fma_dist = 1 the fma chain.  neighbor_count[i] = the size of that neighbourhood, 0 for an invalid
+ *      point.  The cloud is its own search surface.
+ *  B2. Tangent basis from the point's normal n (f32, the slot's): Eigen's generic unitOrthogonal, then u = n x v.
+ *      maxi = the first index of the largest |n_c|; sndi = (maxi == 0) ? 1 : 0;
+ *      inv = 1.0f / sqrtf(n[sndi] * n[sndi] + n[maxi] * n[maxi]); v[maxi] = -n[sndi] * inv, v[sndi] = n[maxi] * inv, the third
+ *      component 0; u = (n.y v.z - n.z v.y, n.z v.x - n.x v.z, n.x v.y - n.y v.x), every operation rounded to f32, never
+ *      contracted.  The normal is taken as it is: it is not normalised, and its sign does not change any result.
+ *      DEVIATION: a normal with a non-finite component, or one for which a component of u or v comes out non-finite (the zero
+ *      normal), makes the point NOT a boundary point with max_gap = 0; its neighbor_count is still B1's.  (PCL sorts NaNs.)
+ *  B3. An angle for every neighbour j, in walk order: d = p_j - p_i in f32; j is skipped when all three differences are
+ *      exactly 0 (i itself and its exact copies); otherwise a_j = atan2f(v.x d.x + v.y d.y + v.z d.z, u.x d.x + u.y d.y +
+ *      u.z d.z), the sums left to right in f32.
+ *  B4. max_dif = the largest, in f32 and starting from FLT_MIN, of the differences of consecutive angles in ascending order
+ *      and of the wrap-around (2 * (float)M_PI - a_last) + a_first.
+ *  B5. Point i is a boundary point iff all of: i is valid; neighbor_count[i] >= 3; neighbor_count[i] >= min_neighbors; at least
+ *      one angle was taken; max_dif > (float)angle_threshold, strictly.  min_neighbors = 0 is
+ *      pcl::BoundaryEstimation::computeFeature; the ISS detector passes its own (K9).
+ *      max_gap (optional): the angles are not sorted.  The circle is cut into 16 equal sectors, sector(a) = floor((a + pi)
+ *      * 16 / 2 pi) in f32, clamped to 0..15; max_gap[i] is the largest, from FLT_MIN, of (smallest angle of the next occupied
+ *      sector - largest angle of this one) over the occupied sectors in ascending order and of the wrap-around of B4 from the
+ *      last maximum and the first minimum.  Those are the differences of B4 that lie between two sectors, from the same f32
+ *      operands; two angles of one sector are less than a sector width (pi / 8) apart.  So max_gap[i] == max_dif whenever
+ *      max_dif is at least a sector width, and is below a sector width otherwise; with angle_threshold >= two sector widths
+ *      (B6) the test of B5 on max_gap IS the test on max_dif.  max_gap[i] = 0 for an invalid point, under B2's deviation, and
+ *      when no angle was taken.
+ *  B6. MVR_E_ARG, before any GPU work and with nothing written, for a NULL ctx / params, a bad slot, a slot without normals,
+ *      a radius that is non-finite or <= 0, min_neighbors < 0, an angle_threshold outside [MVR_BOUNDARY_MIN_ANGLE, 2 pi) (a
+ *      non-finite one included), a cloud above 0x7FFFFFF0 points, or a cloud whose points are stale because a pipelined run
+ *      is in flight.  An empty cloud is MVR_OK.  All three outputs NULL: MVR_OK after the work.
+ *  B7. The slot is not modified.  Bit-identical from run to run on one grid: one thread per query, minima and maxima only.
+ * Out of scope: the k-neighbour mode (setKSearch), setSearchSurface / setIndices, the organized-cloud border extractors. */
+#define MVR_BOUNDARY_MIN_ANGLE 0.78539816339744830962 /* pi / 4: two of the 16 sectors */
+typedef struct {
+  double radius;             /* setRadiusSearch: finite, > 0 */
+  double angle_threshold;    /* setAngleThreshold (PCL default pi / 2): [MVR_BOUNDARY_MIN_ANGLE, 2 pi) */
+  int    min_neighbors;      /* >= 0; 0: pcl::BoundaryEstimation */
+  int    fma_dist;
+} mvr_boundary_params;
+int  mvr_cloud_boundary(mvr_ctx *ctx, int slot, const mvr_boundary_params *p, uint8_t *boundary /* n */,
+                        float *max_gap /* n, optional */, uint32_t *neighbor_count /* n, optional */);
 
 /* CorrespondenceEstimation::determineReciprocalCorrespondences(corrs, max_d)
  * (registrator.cpp:496-502, 644-649); reciprocal = 0 gives

@@ -14,6 +14,7 @@ Import with importlib (the directory name has hyphens):
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import sys
 import warnings
@@ -139,6 +140,17 @@ class IssParams(C.Structure):
                 ("min_neighbors", C.c_int), ("fma_dist", C.c_int)]
 
 
+class IssBorderParams(C.Structure):
+    """mvr_iss_border_params"""
+    _fields_ = [("border_radius", C.c_double), ("angle_threshold", C.c_double)]
+
+
+class BoundaryParams(C.Structure):
+    """mvr_boundary_params"""
+    _fields_ = [("radius", C.c_double), ("angle_threshold", C.c_double), ("min_neighbors", C.c_int), ("fma_dist", C.c_int)]
+
+
+BOUNDARY_MIN_ANGLE = math.pi / 4   # MVR_BOUNDARY_MIN_ANGLE: the smallest angle_threshold the boundary rule accepts
 FPFH_BINS = 11          # MVR_FPFH_BINS: a signature is 3 * 11 = 33 floats
 PREREJ_MAX_SAMPLES = 8  # MVR_PREREJ_MAX_SAMPLES
 
@@ -163,7 +175,7 @@ class PrerejTrace(C.Structure):
 
 _fp, _dp, _u32p, _i32p = (C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                           C.POINTER(C.c_int32))
-_vp, _sz = C.c_void_p, C.c_size_t
+_vp, _sz, _u8p = C.c_void_p, C.c_size_t, C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes); also the list the symbol-export test checks
 SIGNATURES = {
@@ -188,6 +200,9 @@ SIGNATURES = {
     "mvr_cloud_mls": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(MlsParams), C.POINTER(_sz), _u32p, _fp]),
     "mvr_cloud_fpfh": (C.c_int, [_vp, C.c_int, C.POINTER(FpfhParams), _fp, _fp, _u32p]),
     "mvr_cloud_iss_keypoints": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(IssParams), C.POINTER(_sz), _u32p, _dp, _u32p, _u32p]),
+    "mvr_cloud_iss_keypoints_border": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(IssParams), C.POINTER(IssBorderParams), C.POINTER(_sz), _u32p,
+                                                 _dp, _u32p, _u32p, _u8p, _u8p]),
+    "mvr_cloud_boundary": (C.c_int, [_vp, C.c_int, C.POINTER(BoundaryParams), _u8p, _fp, _u32p]),
     "mvr_feature_knn": (C.c_int, [_vp, _fp, _sz, _fp, _sz, C.c_int, C.c_int, _u32p, _fp]),
     "mvr_pose_scores": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _sz, C.c_double, C.c_int, _u32p, _dp]),
     "mvr_align_prerejective": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, C.POINTER(PrerejParams), _fp, C.POINTER(PrerejResult),
@@ -702,14 +717,38 @@ class Context:
             res.append(cnt)
         return res[0] if len(res) == 1 else tuple(res)
 
+    def boundary(self, slot, radius, angle_threshold=math.pi / 2, min_neighbors=0, fma=False, return_gap=False, return_counts=False):
+        """pcl::BoundaryEstimation::compute of slot against itself, radius mode, with the slot's own normals (estimate_normals or
+        upload_normals first): one bool per point, whether the neighbours within radius, projected onto the point's tangent
+        plane, leave an angular gap above angle_threshold (rules B1-B7: mvr_cloud_boundary in mvr_hip.h; angle_threshold in
+        [BOUNDARY_MIN_ANGLE, 2 pi)).  min_neighbors > 0 also asks for that many neighbours, the point itself included.  Returns
+        the flags, or (flags[, max_gap][, neighbor_count]) with the return_* options: max_gap = one float32 per point, the
+        largest gap (exact from a sector width, pi / 8, upwards), neighbor_count = one uint32 per point."""
+        n = self.size(slot)
+        p = BoundaryParams(float(radius), float(angle_threshold), int(min_neighbors), int(bool(fma)))
+        flag = np.empty(max(n, 1), np.uint8)
+        gap = np.empty(max(n, 1), np.float32) if return_gap else None
+        cnt = np.empty(max(n, 1), np.uint32) if return_counts else None
+        _chk(_lib.mvr_cloud_boundary(self._h, int(slot), C.byref(p), _p(flag, C.c_uint8), _p(gap, C.c_float) if return_gap else None,
+                                     _p(cnt, C.c_uint32) if return_counts else None), self._h)
+        res = [flag[:n].astype(bool)]
+        if return_gap:
+            res.append(gap[:n])
+        if return_counts:
+            res.append(cnt[:n])
+        return res[0] if len(res) == 1 else tuple(res)
+
     def iss_keypoints(self, dst, src, salient_radius, non_max_radius, gamma_21=0.975, gamma_32=0.975, min_neighbors=5, fma=False,
-                      return_index=False, return_saliency=False, return_counts=False):
+                      return_index=False, return_saliency=False, return_counts=False, *, border_radius=0.0, angle_threshold=math.pi / 2,
+                      return_edges=False):
         """pcl::ISSKeypoint3D::compute of slot src into slot dst (may be src; -1: no output slot, the host arrays only): the
         points whose scatter over salient_radius passes both eigenvalue ratio tests and whose smallest eigenvalue no neighbour
-        within non_max_radius exceeds, in their original order; normals follow (rules K1-K8: mvr_cloud_iss_keypoints in
-        mvr_hip.h).  Returns n_out, or (n_out[, kept_index][, saliency][, salient_count, nms_count]) with the return_*
-        options: kept_index = original indices of the keypoints, saliency = one float64 per SOURCE point (0: not salient),
-        the counts one uint32 per SOURCE point."""
+        within non_max_radius exceeds, in their original order; normals follow (rules K1-K11: mvr_cloud_iss_keypoints in
+        mvr_hip.h).  border_radius > 0 (the slot then needs normals) first drops every point that has a boundary point --
+        Context.boundary at border_radius, angle_threshold and this call's min_neighbors -- within border_radius.  Returns
+        n_out, or (n_out[, kept_index][, saliency][, salient_count, nms_count][, edge, border]) with the return_* options:
+        kept_index = original indices of the keypoints, saliency = one float64 per SOURCE point (0: not salient), the counts
+        one uint32 per SOURCE point, edge / border = one bool per SOURCE point (all False without a border radius)."""
         n = self.size(src)
         p = IssParams(float(salient_radius), float(non_max_radius), float(gamma_21), float(gamma_32), int(min_neighbors), int(bool(fma)))
         idx = np.empty(max(n, 1), np.uint32) if return_index else None
@@ -717,9 +756,20 @@ class Context:
         sc = np.empty(max(n, 1), np.uint32) if return_counts else None
         nc = np.empty(max(n, 1), np.uint32) if return_counts else None
         n_out = _sz()
-        _chk(_lib.mvr_cloud_iss_keypoints(self._h, int(dst), int(src), C.byref(p), C.byref(n_out),
-                                          _p(idx, C.c_uint32) if return_index else None, _p(sal, C.c_double) if return_saliency else None,
-                                          _p(sc, C.c_uint32) if return_counts else None, _p(nc, C.c_uint32) if return_counts else None), self._h)
+        args = (_p(idx, C.c_uint32) if return_index else None, _p(sal, C.c_double) if return_saliency else None,
+                _p(sc, C.c_uint32) if return_counts else None, _p(nc, C.c_uint32) if return_counts else None)
+        edge = border = None
+        if float(border_radius) == 0.0:
+            _chk(_lib.mvr_cloud_iss_keypoints(self._h, int(dst), int(src), C.byref(p), C.byref(n_out), *args), self._h)
+            if return_edges:
+                edge, border = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+        else:
+            b = IssBorderParams(float(border_radius), float(angle_threshold))
+            if return_edges:
+                edge, border = np.empty(max(n, 1), np.uint8), np.empty(max(n, 1), np.uint8)
+            _chk(_lib.mvr_cloud_iss_keypoints_border(self._h, int(dst), int(src), C.byref(p), C.byref(b), C.byref(n_out), *args,
+                                                     _p(edge, C.c_uint8) if return_edges else None,
+                                                     _p(border, C.c_uint8) if return_edges else None), self._h)
         out = [n_out.value]
         if return_index:
             out.append(idx[:n_out.value].copy())
@@ -727,6 +777,8 @@ class Context:
             out.append(sal[:n])
         if return_counts:
             out += [sc[:n], nc[:n]]
+        if return_edges:
+            out += [edge[:n].astype(bool), border[:n].astype(bool)]
         return out[0] if len(out) == 1 else tuple(out)
 
     def feature_knn(self, q, t, k):

@@ -1,8 +1,14 @@
-// csrc/mvr_iss.hip -- pcl::ISSKeypoint3D (border_radius == 0) on the GPU (gfx950); the rules K1-K8 are written next to
-// mvr_cloud_iss_keypoints in mvr_hip.h.
+// csrc/mvr_iss.hip -- pcl::ISSKeypoint3D on the GPU (gfx950); the rules K1-K11 are written next to mvr_cloud_iss_keypoints in
+// mvr_hip.h.
 //
 // One thread per query, in the order of the cloud's model grid (ensure_model_grid; the helpers of mvr_knn_walk.h), so the 64
 // lanes of a wave are neighbours on the surface and walk the same cells:
+//   0. with a border radius only: the boundary kernel (launch_boundary, mvr_boundary.hip) writes the edge flags of K9 by index
+//      and by grid position, and the saliency kernel below is its BORDER instantiation, which first asks whether the ball of
+//      the border radius holds an edge point (knn_ball_any over the flags in grid order, read beside the points as sal_grid
+//      is); a point that has one is a border point (K10): zeros are written and the scatter walk is skipped (K11).  The
+//      kernel is a template of mvr_knn_walk.h; its two BORDER instantiations are compiled in mvr_boundary.hip
+//      (launch_iss_saliency_border), so that this file holds the kernels it always held.
 //   1. iss_saliency_kernel: the ball walk (knn_ball_walk) at the salient radius adds the f64 second moments of the neighbours
 //      about the query point (Moments::add of mvr_plane.h; the first moments and its f64 count are never read here and the
 //      compiler drops them) and counts them; the eigenvalues come from the cyclic Jacobi of mvr_plane.h with the eigenvectors
@@ -23,42 +29,6 @@
 
 namespace mvr {
 namespace {
-
-constexpr int kIssThreads = kKnnThreads;
-
-struct IssArgs {
-  KnnSlot S;                       // the cloud searched against itself (nrm / curv / oidx / od2 unused; blk0 = 0)
-  double *sal_grid;                // saliency by grid position
-  double *sal;                     // saliency by index
-  uint32_t *salient_count;         // by index
-  uint32_t *nms_count;             // by index
-  uint8_t *flag;                   // by index: a keypoint
-  double gamma_21, gamma_32;
-  uint32_t min_neighbors;
-  float r2_salient, r2_nms;
-};
-
-template <bool FMA>
-__global__ void __launch_bounds__(kIssThreads) iss_saliency_kernel(IssArgs a)
-{
-  const KnnSlot &S = a.S;
-  float4 q; uint32_t qi;
-  if (!knn_query(S, &q, &qi)) return;
-  const uint32_t pos = blockIdx.x * kIssThreads + threadIdx.x;
-  Moments M;      // (a non-finite query walks nothing: K1)
-  uint32_t n = 0;
-  knn_ball_walk<FMA>(S, q, a.r2_salient, [&](const float4 p, uint32_t) { M.add(p, q); ++n; });
-  double s = 0.0;
-  if (n >= a.min_neighbors) {
-    const Eigenvalues3 e = scatter_eigenvalues(M);
-    const bool finite = isfinite(e.e1) && isfinite(e.e2) && isfinite(e.e3);
-    // K4 (a NaN ratio, 0 / 0 included, fails its test)
-    if (finite && e.e3 >= 0.0 && e.e2 / e.e1 < a.gamma_21 && e.e3 / e.e2 < a.gamma_32 && e.e3 > 0.0) s = e.e3;
-  }
-  a.sal_grid[pos] = s;
-  a.sal[qi] = s;
-  a.salient_count[qi] = n;
-}
 
 template <bool FMA>
 __global__ void __launch_bounds__(kIssThreads) iss_nms_kernel(IssArgs a)
@@ -82,12 +52,14 @@ __global__ void __launch_bounds__(kIssThreads) iss_nms_kernel(IssArgs a)
 }
 
 // dst null: the host arrays only
-int iss_cloud(Ctx *c, Cloud *dst, Cloud &src, const mvr_iss_params &p, size_t *n_out, uint32_t *kept_index, double *saliency,
-              uint32_t *salient_count, uint32_t *nms_count)
+// b null: no border
+int iss_cloud(Ctx *c, Cloud *dst, Cloud &src, const mvr_iss_params &p, const mvr_iss_border_params *b, size_t *n_out, uint32_t *kept_index,
+              double *saliency, uint32_t *salient_count, uint32_t *nms_count, uint8_t *edge, uint8_t *border)
 {
   const size_t n = src.n;
   const bool normals = src.has_normals;
   size_t kept = 0;
+  if (b && !normals && n > 0) return set_error(c, MVR_E_ARG, "iss keypoints: a border radius needs the slot's normals");      // K9
   if (int rc = knn_cloud_ok(c, src, "iss keypoints")) return rc;
   if (n > 0) {
     MVR_MAY_BLOCK(c, "iss keypoints reads back");
@@ -99,6 +71,7 @@ int iss_cloud(Ctx *c, Cloud *dst, Cloud &src, const mvr_iss_params &p, size_t *n
     Carver plan;
     plan.plan<double>(n); plan.plan<double>(n); plan.plan<uint32_t>(n); plan.plan<uint32_t>(n); plan.plan<uint8_t>(n);
     plan.plan<unsigned long long>(n); plan.plan<uint32_t>(4); plan.plan<float4>(n); plan.plan<uint32_t>(n); plan.plan<char>(sel_bytes);
+    if (b) { plan.plan<uint8_t>(n); plan.plan<uint8_t>(n); plan.plan<uint8_t>(n); }
     if (int rc = ensure(c, c->dn_arena, c->dn_arena_cap, plan.off + 256)) return rc;
     Carver s; s.base = c->dn_arena;
     a.sal_grid = s.take<double>(n);
@@ -111,12 +84,25 @@ int iss_cloud(Ctx *c, Cloud *dst, Cloud &src, const mvr_iss_params &p, size_t *n
     float4 *out = s.take<float4>(n);
     uint32_t *d_index = s.take<uint32_t>(n);
     char *tmp = s.take<char>(sel_bytes);
+    uint8_t *d_edge = nullptr;
+    if (b) {
+      d_edge = s.take<uint8_t>(n);
+      a.edge_grid = s.take<uint8_t>(n);
+      a.border = s.take<uint8_t>(n);
+      a.r2_border = clamp_r2(b->border_radius);
+    }
     a.gamma_21 = p.gamma_21; a.gamma_32 = p.gamma_32;
     a.min_neighbors = (uint32_t)p.min_neighbors;
     a.r2_salient = clamp_r2(p.salient_radius); a.r2_nms = clamp_r2(p.non_max_radius);
     const dim3 grid(blocks_for(n, kIssThreads)), block(kIssThreads);
-    if (p.fma_dist) hipLaunchKernelGGL(iss_saliency_kernel<true>, grid, block, 0, c->stream, a);
-    else hipLaunchKernelGGL(iss_saliency_kernel<false>, grid, block, 0, c->stream, a);
+    if (b) {
+      // K9: the edge flags, by index for the host and by grid position for the walk of the border instantiation
+      if (int rc = launch_boundary(c, a.S, src.nrm, a.r2_border, (float)b->angle_threshold, a.min_neighbors, p.fma_dist != 0, d_edge,
+                                   const_cast<uint8_t *>(a.edge_grid), nullptr, nullptr))
+        return rc;
+      if (int rc = launch_iss_saliency_border(c, a, p.fma_dist != 0)) return rc;
+    } else if (p.fma_dist) hipLaunchKernelGGL((iss_saliency_kernel<true, false>), grid, block, 0, c->stream, a);
+    else hipLaunchKernelGGL((iss_saliency_kernel<false, false>), grid, block, 0, c->stream, a);
     MVR_HIP_TRY(c, hipGetLastError());
     if (p.fma_dist) hipLaunchKernelGGL(iss_nms_kernel<true>, grid, block, 0, c->stream, a);
     else hipLaunchKernelGGL(iss_nms_kernel<false>, grid, block, 0, c->stream, a);
@@ -128,6 +114,10 @@ int iss_cloud(Ctx *c, Cloud *dst, Cloud &src, const mvr_iss_params &p, size_t *n
     if (saliency) MVR_HIP_TRY(c, hipMemcpyAsync(saliency, a.sal, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (salient_count) MVR_HIP_TRY(c, hipMemcpyAsync(salient_count, a.salient_count, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     if (nms_count) MVR_HIP_TRY(c, hipMemcpyAsync(nms_count, a.nms_count, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (b && edge) MVR_HIP_TRY(c, hipMemcpyAsync(edge, d_edge, n * sizeof(uint8_t), hipMemcpyDeviceToHost, c->stream));
+    if (b && border) MVR_HIP_TRY(c, hipMemcpyAsync(border, a.border, n * sizeof(uint8_t), hipMemcpyDeviceToHost, c->stream));
+    if (!b && edge) std::memset(edge, 0, n);          // no border radius: nobody is an edge or a border point
+    if (!b && border) std::memset(border, 0, n);
     MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
     kept = hc[0];
     // the output (no destination: the indices alone, the points gathered into the arena and left there)
@@ -151,15 +141,25 @@ using namespace mvr;
 
 #define API __attribute__((visibility("default")))
 
-API int mvr_cloud_iss_keypoints(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_iss_params *p, size_t *n_out, uint32_t *kept_index,
-                                double *saliency, uint32_t *salient_count, uint32_t *nms_count)
+API int mvr_cloud_iss_keypoints_border(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_iss_params *p, const mvr_iss_border_params *b,
+                                       size_t *n_out, uint32_t *kept_index, double *saliency, uint32_t *salient_count, uint32_t *nms_count,
+                                       uint8_t *edge, uint8_t *border)
 {
   if (!ctx || !p || !knn_slot_ok(src_slot) || !(dst_slot == -1 || knn_slot_ok(dst_slot))) return MVR_E_ARG;
   if (!(std::isfinite(p->salient_radius) && p->salient_radius > 0.0) || !(std::isfinite(p->non_max_radius) && p->non_max_radius > 0.0))
     return MVR_E_ARG;
   if (!std::isfinite(p->gamma_21) || !std::isfinite(p->gamma_32) || p->min_neighbors < 0) return MVR_E_ARG;
+  if (b && b->border_radius == 0.0) b = nullptr;      // radius 0: no border, whatever the threshold
+  if (b && (!(std::isfinite(b->border_radius) && b->border_radius > 0.0) || !boundary_angle_ok(b->angle_threshold))) return MVR_E_ARG;
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   MVR_HIP_TRY(c, hipSetDevice(c->device));
-  return iss_cloud(c, dst_slot < 0 ? nullptr : &c->slots[dst_slot], c->slots[src_slot], *p, n_out, kept_index, saliency, salient_count,
-                   nms_count);
+  return iss_cloud(c, dst_slot < 0 ? nullptr : &c->slots[dst_slot], c->slots[src_slot], *p, b, n_out, kept_index, saliency, salient_count,
+                   nms_count, edge, border);
+}
+
+API int mvr_cloud_iss_keypoints(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_iss_params *p, size_t *n_out, uint32_t *kept_index,
+                                double *saliency, uint32_t *salient_count, uint32_t *nms_count)
+{
+  return mvr_cloud_iss_keypoints_border(ctx, dst_slot, src_slot, p, nullptr, n_out, kept_index, saliency, salient_count, nms_count, nullptr,
+                                        nullptr);
 }

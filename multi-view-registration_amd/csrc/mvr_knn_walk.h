@@ -3,15 +3,18 @@
 // mvr_mls.hip: moving least squares; mvr_fpfh.hip: FPFH descriptors; mvr_feature.hip: the scores of posed copies):
 //   * knn_shell_walk: shells of cells outward from the query's cell until a visitor's k-best list is full and every unvisited
 //     cell lies beyond it (the f64 bound of knn_unvisited_bound);
-//   * knn_ball_walk: every point within a radius of the query, in grid order.
+//   * knn_ball_walk: every point within a radius of the query, in grid order (knn_ball_any: the same ball, left at the first
+//     point a predicate holds for).
 // Around them the search side of a slot, the query of a thread, the cell lookup of the compact table, the row ranges, the
-// library's f32 distance, and the host-side checks every caller makes.  Not installed.
+// library's f32 distance, and the host-side checks every caller makes; at the end what mvr_boundary.hip and mvr_iss.hip share (the
+// boundary launch and the template of the ISS saliency kernel).  Not installed.
 #pragma once
 
 #include <limits>
 #include <string>
 
 #include "mvr_internal.h"
+#include "mvr_plane.h"
 
 namespace mvr {
 
@@ -187,6 +190,25 @@ __device__ __forceinline__ void knn_ball_walk(const KnnSlot &S, const float4 q, 
     }
 }
 
+// The same ball, asked a question: whether pred(p, j) holds for any point of it.  It ends at the first that does.
+template <bool FMA, class P>
+__device__ __forceinline__ bool knn_ball_any(const KnnSlot &S, const float4 q, const float r2, P &&pred)
+{
+  if (S.nt == 0 || !finite3(q)) return false;
+  int x0, x1, y0, y1, z0, z1;
+  knn_ball_cells(S, q, r2, &x0, &x1, &y0, &y1, &z0, &z1);
+  for (int z = z0; z <= z1; ++z)
+    for (int y = y0; y <= y1; ++y) {
+      uint32_t j, e;
+      knn_row_range(S, x0, x1, y, z, &j, &e);
+      for (; j < e; ++j) {
+        const float4 p = S.gt[j];
+        if (knn_dist2<FMA>(p, q) <= r2 && pred(p, j)) return true;
+      }
+    }
+  return false;
+}
+
 // ---- the host side
 inline bool knn_slot_ok(int s) { return s >= 0 && s < MVR_MAX_SLOTS; }
 
@@ -230,5 +252,69 @@ inline void fill_queries(const Cloud &q, KnnSlot &S)
   S.q_by_pos = grid ? 0u : 1u;
   S.nq = (uint32_t)q.n;
 }
+
+// pcl::BoundaryEstimation over a filled slot (mvr_boundary.hip; rules B1-B5 at mvr_cloud_boundary in mvr_hip.h), queued on the
+// context's stream: flag / max_gap / count by index, flag_grid by the query's grid position (the position a later walk of the
+// same slot finds the point at); each of the four may be null.  nrm: the cloud's normals, by index.
+int launch_boundary(Ctx *c, const KnnSlot &S, const float4 *nrm, float r2, float angle_threshold, uint32_t min_neighbors, bool fma,
+                    uint8_t *flag, uint8_t *flag_grid, float *max_gap, uint32_t *count);
+bool boundary_angle_ok(double angle_threshold);      // B6: [MVR_BOUNDARY_MIN_ANGLE, 2 pi)
+
+// ---- the saliency kernel of pcl::ISSKeypoint3D (rules K3, K4 and K9-K11 at mvr_cloud_iss_keypoints in mvr_hip.h) and the
+// arguments of the detector's kernels.  It is a template of two parameters that two files instantiate -- mvr_iss.hip the
+// detector without a border, mvr_boundary.hip the one that first looks for an edge point within the border radius -- and it
+// stands in this header, which every object is rebuilt after, so that the two can never disagree about IssArgs.
+constexpr int kIssThreads = kKnnThreads;
+
+struct IssArgs {
+  KnnSlot S;                       // the cloud searched against itself (nrm / curv / oidx / od2 unused; blk0 = 0)
+  double *sal_grid;                // saliency by grid position
+  double *sal;                     // saliency by index
+  uint32_t *salient_count;         // by index
+  uint32_t *nms_count;             // by index
+  uint8_t *flag;                   // by index: a keypoint
+  double gamma_21, gamma_32;
+  uint32_t min_neighbors;
+  float r2_salient, r2_nms;
+  // the BORDER instantiation only
+  const uint8_t *edge_grid;        // K9's flags by grid position
+  uint8_t *border;                 // K10's flags by index
+  float r2_border;
+};
+
+template <bool FMA, bool BORDER>
+__global__ void __launch_bounds__(kIssThreads) iss_saliency_kernel(IssArgs a)
+{
+  const KnnSlot &S = a.S;
+  float4 q; uint32_t qi;
+  if (!knn_query(S, &q, &qi)) return;
+  const uint32_t pos = blockIdx.x * kIssThreads + threadIdx.x;
+  if constexpr (BORDER) {
+    const bool border = knn_ball_any<FMA>(S, q, a.r2_border, [&](const float4, const uint32_t j) { return a.edge_grid[j] != 0; });
+    a.border[qi] = border ? 1 : 0;
+    if (border) {      // K11
+      a.sal_grid[pos] = 0.0;
+      a.sal[qi] = 0.0;
+      a.salient_count[qi] = 0u;
+      return;
+    }
+  }
+  Moments M;      // (a non-finite query walks nothing: K1)
+  uint32_t n = 0;
+  knn_ball_walk<FMA>(S, q, a.r2_salient, [&](const float4 p, uint32_t) { M.add(p, q); ++n; });
+  double s = 0.0;
+  if (n >= a.min_neighbors) {
+    const Eigenvalues3 e = scatter_eigenvalues(M);
+    const bool finite = isfinite(e.e1) && isfinite(e.e2) && isfinite(e.e3);
+    // K4 (a NaN ratio, 0 / 0 included, fails its test)
+    if (finite && e.e3 >= 0.0 && e.e2 / e.e1 < a.gamma_21 && e.e3 / e.e2 < a.gamma_32 && e.e3 > 0.0) s = e.e3;
+  }
+  a.sal_grid[pos] = s;
+  a.sal[qi] = s;
+  a.salient_count[qi] = n;
+}
+
+// the BORDER instantiations (mvr_boundary.hip), over n = a.S.nq queries, queued on the context's stream
+int launch_iss_saliency_border(Ctx *c, const IssArgs &a, bool fma);
 
 }  // namespace mvr
