@@ -773,6 +773,143 @@ class ISSKeypoint3D {
   PointIndicesPtr indices_ = std::make_shared<PointIndices>();
 };
 
+// ---------------------------------------------------------------- plane segmentation
+// pcl::SACSegmentation<PointT> (segmentation/sac_segmentation.h) for SACMODEL_PLANE and SACMODEL_PERPENDICULAR_PLANE with
+// SAC_RANSAC: setInputCloud, setModelType, setMethodType, setDistanceThreshold, setMaxIterations, setProbability,
+// setOptimizeCoefficients, setAxis, setEpsAngle, segment, with PCL's defaults (50 iterations, probability 0.99, coefficients
+// optimised; the model and the threshold must be set).  Semantics: mvr_cloud_segment_plane (mvr_hip.h) -- one call on the GPU per
+// segment().  PCL draws with rand(); here the result is a pure function of the input and of setSeed (ours).  Any other model
+// or method throws mvr::Error at the setter: computing something else in silence would be worse.  As PCL, a missing input, a
+// parameter outside its range or a cloud without a plane prints an error and leaves indices and coefficients empty.
+template <typename PointT>
+class SACSegmentation {
+ public:
+  typedef PointCloud<PointT> PointCloudT;
+  typedef typename PointCloudT::ConstPtr PointCloudConstPtr;
+
+  explicit SACSegmentation(bool /*random*/ = false) {}
+  void setInputCloud(const PointCloudConstPtr &c) { input_ = c; }
+  PointCloudConstPtr getInputCloud() const { return input_; }
+  void setModelType(int model)
+  {
+    if (model != SACMODEL_PLANE && model != SACMODEL_PERPENDICULAR_PLANE)
+      throw Error(MVR_E_ARG, "pcl::SACSegmentation::setModelType: only SACMODEL_PLANE and SACMODEL_PERPENDICULAR_PLANE are offered");
+    model_ = model;
+  }
+  int getModelType() const { return model_; }
+  void setMethodType(int method)
+  {
+    if (method != SAC_RANSAC) throw Error(MVR_E_ARG, "pcl::SACSegmentation::setMethodType: only SAC_RANSAC is offered");
+  }
+  int getMethodType() const { return SAC_RANSAC; }
+  void setDistanceThreshold(double t) { p_.threshold = t; }
+  double getDistanceThreshold() const { return p_.threshold; }
+  void setMaxIterations(int n) { p_.max_iterations = n; }
+  int getMaxIterations() const { return p_.max_iterations; }
+  void setProbability(double pr) { p_.probability = pr; }
+  double getProbability() const { return p_.probability; }
+  void setOptimizeCoefficients(bool o) { p_.optimize = o ? 1 : 0; }
+  bool getOptimizeCoefficients() const { return p_.optimize != 0; }
+  void setAxis(float x, float y, float z) { p_.axis[0] = x; p_.axis[1] = y; p_.axis[2] = z; }
+  template <class V> void setAxis(const V &ax) { setAxis((float)ax[0], (float)ax[1], (float)ax[2]); }      // (an Eigen::Vector3f, an array)
+  void setEpsAngle(double ea) { p_.eps_angle = ea; }
+  double getEpsAngle() const { return p_.eps_angle; }
+  void setSeed(uint64_t seed) { p_.seed = seed; }
+  const mvr_sac_result &getResult() const { return result_; }      // ours: iterations, attempts, the RANSAC plane before the refinement
+
+  void segment(PointIndices &inliers, ModelCoefficients &model_coefficients)
+  {
+    static_assert(sizeof(PointT) % 4 == 0 && sizeof(PointT) >= 12, "points that begin with x, y, z expected");
+    inliers.indices.clear();
+    model_coefficients.values.clear();
+    result_ = mvr_sac_result();
+    if (!input_) { std::fprintf(stderr, "[pcl::SACSegmentation::segment] No input dataset given!\n"); return; }
+    if (model_ < 0) { std::fprintf(stderr, "[pcl::SACSegmentation::initSACModel] No valid model given!\n"); return; }
+    mvr_sac_params p = p_;
+    p.model = model_ == SACMODEL_PLANE ? 0 : 1;
+    const double *a = p.axis;
+    const bool axis_ok = std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]) && (a[0] != 0.0 || a[1] != 0.0 || a[2] != 0.0);
+    if (!(std::isfinite(p.threshold) && p.threshold > 0.0) || p.max_iterations < 1 || p.max_iterations > (1 << 24) ||
+        !(p.probability > 0.0 && p.probability < 1.0) || (p.model == 1 && (!axis_ok || !(p.eps_angle > 0.0 && p.eps_angle <= 1.57079632679489661923)))) {
+      std::fprintf(stderr, "[pcl::SACSegmentation::segment] The distance threshold (%f) must be finite and > 0, the iterations (%d) in 1..2^24, the probability (%f) in (0, 1); the perpendicular model needs an axis and an angle (%f) in (0, pi / 2].\n",
+                   p.threshold, p.max_iterations, p.probability, p.eps_angle);
+      return;
+    }
+    Device &d = Device::instance();
+    SlotGuard s;
+    const size_t n = input_->size();
+    d.check(mvr_cloud_upload(d.ctx(), s.s, n ? input_->points[0].data : nullptr, n, sizeof(PointT)), "mvr_cloud_upload");
+    std::vector<uint32_t> index(n ? n : 1);
+    d.check(mvr_cloud_segment_plane(d.ctx(), -1, s.s, &p, &result_, nullptr, index.data(), nullptr, nullptr, 0), "mvr_cloud_segment_plane");
+    if (!result_.found || result_.inliers == 0) {
+      std::fprintf(stderr, "[pcl::SACSegmentation::segment] Error segmenting the model! No solution found.\n");
+      return;
+    }
+    inliers.indices.assign(index.begin(), index.begin() + (std::ptrdiff_t)result_.inliers);
+    model_coefficients.values.assign(result_.coefficients, result_.coefficients + 4);
+  }
+
+ private:
+  PointCloudConstPtr input_;
+  int model_ = -1;
+  mvr_sac_params p_ = {0, 0.0, 50, 0.99, 1, {0.0, 0.0, 0.0}, 0.0, 0, 0, 0};
+  mvr_sac_result result_ = mvr_sac_result();
+};
+
+// pcl::ExtractIndices<PointT> (filters/extract_indices.h): setInputCloud, setIndices, setNegative, filter.  One call of
+// mvr_cloud_extract_indices per filter(): the listed points -- or with setNegative(true) all the others -- in ascending index.
+// `output` may be the input cloud itself.  A missing input or index list, or an index outside the cloud, prints an error and
+// leaves the output empty (untouched when it is the input).
+template <typename PointT>
+class ExtractIndices {
+ public:
+  typedef PointCloud<PointT> PointCloudT;
+  typedef typename PointCloudT::ConstPtr PointCloudConstPtr;
+  typedef std::shared_ptr<const std::vector<int> > IndicesConstPtr;
+
+  void setInputCloud(const PointCloudConstPtr &c) { input_ = c; }
+  PointCloudConstPtr getInputCloud() const { return input_; }
+  void setIndices(const PointIndices::ConstPtr &i) { indices_ = i ? std::make_shared<const std::vector<int> >(i->indices) : IndicesConstPtr(); }
+  void setIndices(const PointIndices::Ptr &i) { setIndices(PointIndices::ConstPtr(i)); }
+  void setIndices(const IndicesConstPtr &i) { indices_ = i; }
+  IndicesConstPtr getIndices() const { return indices_; }
+  void setNegative(bool negative) { negative_ = negative; }
+  bool getNegative() const { return negative_; }
+
+  void filter(PointCloudT &output)
+  {
+    static_assert(sizeof(PointT) == 16, "16-byte XYZ points expected");
+    const bool alias = (const void *)&output == (const void *)input_.get();
+    if (!input_ || !indices_) {
+      std::fprintf(stderr, "[pcl::ExtractIndices::filter] No input dataset or no indices given!\n");
+      if (!alias) output.clear();
+      return;
+    }
+    const size_t n = input_->size();
+    std::vector<uint32_t> index(indices_->size() ? indices_->size() : 1);
+    for (size_t k = 0; k < indices_->size(); ++k) {
+      const int i = (*indices_)[k];
+      if (i < 0 || (size_t)i >= n) {
+        std::fprintf(stderr, "[pcl::ExtractIndices::filter] The index %d is outside the input dataset of %zu points!\n", i, n);
+        if (!alias) output.clear();
+        return;
+      }
+      index[k] = (uint32_t)i;
+    }
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.upload(s.s, *input_);              // first: `output` may alias the input
+    size_t m = 0;
+    d.check(mvr_cloud_extract_indices(d.ctx(), s.s, s.s, index.data(), indices_->size(), negative_ ? 1 : 0, &m), "mvr_cloud_extract_indices");
+    d.download(s.s, output);
+  }
+
+ private:
+  PointCloudConstPtr input_;
+  IndicesConstPtr indices_;
+  bool negative_ = false;
+};
+
 // ---------------------------------------------------------------- sample-consensus alignment
 // pcl::SampleConsensusPrerejective<PointSource, PointTarget, FeatureT> (registration/sample_consensus_prerejective.h):
 // setInputSource, setInputTarget, setSourceFeatures, setTargetFeatures, setMaximumIterations, setNumberOfSamples,

@@ -282,6 +282,68 @@ class ScanCloud {
     return before - kept;
   }
 
+  // EXTENSION (pcl::SACSegmentation with SAC_RANSAC on the raw points, on the GPU; rules: mvr_cloud_segment_plane in mvr_hip.h):
+  // the largest plane of the scan -- the platter or the table the object stands on -- within `threshold`; with an axis the
+  // model is SACMODEL_PERPENDICULAR_PLANE (the plane's normal within eps_angle of the axis: a turntable's platter), without
+  // one SACMODEL_PLANE.  segmentPlane fills the inliers' indices (ascending) and the four coefficients and changes nothing;
+  // removePlane takes the inliers out of `points` (ExtractIndices with setNegative(true)), `rich` following as in denoise(), and
+  // returns the number of points removed.  Parameters outside their range print an error and change nothing; so does a scan
+  // without a plane (segmentPlane then returns false).
+  struct PlaneParams {
+    double threshold = 0.5;
+    int max_iterations = 1000;
+    double probability = 0.99;
+    bool optimize = true;
+    bool perpendicular = false;            // with it: the axis and the largest angle between it and the plane's normal
+    double axis[3] = {0.0, 0.0, 1.0}, eps_angle = 0.1;
+    uint64_t seed = 0;
+  };
+  bool segmentPlane(const PlaneParams &pp, std::vector<uint32_t> &inliers, float coefficients[4], mvr_sac_result *result = nullptr) const
+  {
+    inliers.clear();
+    for (int k = 0; k < 4; ++k) coefficients[k] = 0.f;
+    mvr_sac_params p;
+    if (!planeParams(pp, false, p)) return false;
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.upload(s.s, points);
+    std::vector<uint32_t> index(points.size() ? points.size() : 1);
+    mvr_sac_result r;
+    d.check(mvr_cloud_segment_plane(d.ctx(), -1, s.s, &p, &r, nullptr, index.data(), nullptr, nullptr, 0), "mvr_cloud_segment_plane");
+    if (result) *result = r;
+    if (!r.found) return false;
+    inliers.assign(index.begin(), index.begin() + (std::ptrdiff_t)r.inliers);
+    for (int k = 0; k < 4; ++k) coefficients[k] = r.coefficients[k];
+    return true;
+  }
+  size_t removePlane(const PlaneParams &pp, float coefficients[4] = nullptr)
+  {
+    mvr_sac_params p;
+    if (!planeParams(pp, true, p)) return 0;
+    Device &d = Device::instance();
+    SlotGuard s;
+    const size_t before = points.size();
+    d.upload(s.s, points);
+    std::vector<uint32_t> index(before ? before : 1);
+    mvr_sac_result r;
+    size_t kept = 0;
+    d.check(mvr_cloud_segment_plane(d.ctx(), s.s, s.s, &p, &r, &kept, index.data(), nullptr, nullptr, 0), "mvr_cloud_segment_plane");
+    if (coefficients) for (int k = 0; k < 4; ++k) coefficients[k] = r.coefficients[k];
+    if (!r.found || r.inliers == 0) return 0;
+    d.download(s.s, points);
+    if (rich.size() == before) {                   // colours and normals follow their points
+      io::RichCloud out(kept);
+      size_t k = 0, w = 0;
+      for (size_t i = 0; i < before; ++i) {
+        if (k < r.inliers && index[k] == i) ++k;
+        else out[w++] = rich[i];
+      }
+      rich.swap(out);
+    }
+    touch();
+    return before - kept;
+  }
+
   // EXTENSION (pcl::FPFHEstimation on the raw points, on the GPU; rules: mvr_cloud_fpfh in mvr_hip.h): one 33-bin signature per
   // point from every neighbour within `radius`, with the normals of `rich` (estimateNormals, smooth with compute_normals, or
   // a file that carries them).  Without one rich record per point, or with a radius that is not finite and > 0, it prints an
@@ -485,6 +547,23 @@ class ScanCloud {
     std::vector<float> nrm(4 * n);
     for (size_t i = 0; i < n; ++i) { nrm[4 * i] = rich[i].normal_x; nrm[4 * i + 1] = rich[i].normal_y; nrm[4 * i + 2] = rich[i].normal_z; nrm[4 * i + 3] = 0.f; }
     d.check(mvr_cloud_upload_normals(d.ctx(), slot, nrm.data(), n, 16), "mvr_cloud_upload_normals");
+  }
+
+  // PlaneParams -> mvr_sac_params, checked as the C-ABI checks them (P12)
+  static bool planeParams(const PlaneParams &pp, bool negative, mvr_sac_params &p)
+  {
+    p.model = pp.perpendicular ? 1 : 0; p.threshold = pp.threshold; p.max_iterations = pp.max_iterations; p.probability = pp.probability;
+    p.optimize = pp.optimize ? 1 : 0; p.eps_angle = pp.eps_angle; p.seed = pp.seed; p.negative = negative ? 1 : 0; p.fma_dist = 0;
+    for (int k = 0; k < 3; ++k) p.axis[k] = pp.axis[k];
+    const double *a = p.axis;
+    const bool axis_ok = std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]) && (a[0] != 0.0 || a[1] != 0.0 || a[2] != 0.0);
+    if (!(std::isfinite(p.threshold) && p.threshold > 0.0) || p.max_iterations < 1 || p.max_iterations > (1 << 24) ||
+        !(p.probability > 0.0 && p.probability < 1.0) || (p.model == 1 && (!axis_ok || !(p.eps_angle > 0.0 && p.eps_angle <= 1.57079632679489661923)))) {
+      std::fprintf(stderr, "[ScanCloud::segmentPlane] The threshold (%f) must be finite and > 0, the iterations (%d) in 1..2^24, the probability (%f) in (0, 1); the perpendicular model needs an axis and an angle (%f) in (0, pi / 2].\n",
+                   p.threshold, p.max_iterations, p.probability, p.eps_angle);
+      return false;
+    }
+    return true;
   }
 
   // one of the two filters (the other pointer null) in place on `points`; `rich` follows through kept_index
@@ -751,6 +830,19 @@ class Registrator {
     return true;
   }
 
+  // EXTENSION, off by default: every saveRegisteredPoints below first takes the platter out of the merged cloud -- the plane
+  // perpendicular to the turntable axis (getAxisNormal, refined or not) within eps_angle, found by ScanCloud::removePlane with
+  // SACMODEL_PERPENDICULAR_PLANE at this distance threshold.  threshold 0 switches it off again.  A merged cloud without such
+  // a plane is written as it is.
+  void setPlatterRemoval(double threshold, double eps_angle = 0.1, int max_iterations = 1000, uint64_t seed = 0)
+  {
+    platter_.threshold = threshold; platter_.eps_angle = eps_angle; platter_.max_iterations = max_iterations; platter_.seed = seed;
+    platter_.perpendicular = true;
+    platter_on_ = threshold != 0.0;
+  }
+  bool getPlatterRemoval() const { return platter_on_; }
+  size_t lastPlatterPoints() const { return platter_removed_; }      // what the last saveRegisteredPoints took out
+
   // ---- the merged object (registrator.cpp:344-400, the step registration() ends with, :719-744): every registered
   // view's points (and normals) moved by its pose -- the normals by the FULL affine including the translation, as
   // the reference does -- concatenated in view order and written as <folder>/points.pcd
@@ -760,6 +852,13 @@ class Registrator {
   {
     io::RichCloud merged;
     mergeRegisteredPoints(object, merged);
+    if (platter_on_) {
+      ScanCloud whole;
+      whole.rich.swap(merged);
+      for (const io::RichPoint &q : whole.rich) whole.points.push_back(PCLPoint(q.x, q.y, q.z));
+      removePlatter(whole);
+      merged.swap(whole.rich);
+    }
     const bool ok = io::savePCDFile(folder + "/points.pcd", merged, io::PCD_BINARY_COMPRESSED) && io::savePointsASC(folder + "/points.asc", merged);
     const size_t n = merged.size();
     if (merged_out) merged_out->swap(merged);
@@ -775,6 +874,7 @@ class Registrator {
     ScanCloud merged;
     mergeRegisteredPoints(object, merged.rich);
     for (const io::RichPoint &q : merged.rich) merged.points.push_back(PCLPoint(q.x, q.y, q.z));
+    removePlatter(merged);
     merged.voxelDownsample(leaf_size);
     const bool ok = io::savePCDFile(folder + "/points.pcd", merged.rich, io::PCD_BINARY_COMPRESSED) &&
                     io::savePointsASC(folder + "/points.asc", merged.rich);
@@ -800,6 +900,7 @@ class Registrator {
     ScanCloud merged;
     mergeRegisteredPoints(object, merged.rich);
     for (const io::RichPoint &q : merged.rich) merged.points.push_back(PCLPoint(q.x, q.y, q.z));
+    removePlatter(merged);
     merged.smooth(mls_radius, polynomial_order, false);
     if (leaf_size > 0.f) merged.voxelDownsample(leaf_size);
     const bool ok = io::savePCDFile(folder + "/points.pcd", merged.rich, io::PCD_BINARY_COMPRESSED) &&
@@ -854,6 +955,15 @@ class Registrator {
     }
   }
 
+  // setPlatterRemoval's step on a merged cloud (points and rich records, one per point)
+  void removePlatter(ScanCloud &merged)
+  {
+    platter_removed_ = 0;
+    if (!platter_on_) return;
+    for (int k = 0; k < 3; ++k) platter_.axis[k] = axis_[k];
+    platter_removed_ = merged.removePlane(platter_);
+  }
+
   // raw scans -> device slots (once per object and per revision of its clouds); posed copies get slots of their own
   void ensureResident(int object)
   {
@@ -879,6 +989,9 @@ class Registrator {
   TurntableModel *model_;
   float pivot_[3] = {0, 0, 0};
   float axis_[3] = {0, 0, 1};
+  ScanCloud::PlaneParams platter_;      // setPlatterRemoval
+  bool platter_on_ = false;
+  size_t platter_removed_ = 0;
   int resident_object_ = -1;
   unsigned long long resident_rev_ = 0;
   std::vector<std::unique_ptr<SlotGuard> > raw_guard_, posed_guard_;

@@ -86,6 +86,20 @@ struct PointIndices {
 };
 typedef PointIndices::Ptr PointIndicesPtr;
 
+// pcl::ModelCoefficients (what SACSegmentation::segment fills: a, b, c, d of a x + b y + c z + d = 0 for the plane models)
+struct ModelCoefficients {
+  typedef std::shared_ptr<ModelCoefficients> Ptr;
+  typedef std::shared_ptr<const ModelCoefficients> ConstPtr;
+  std::vector<float> values;
+};
+typedef ModelCoefficients::Ptr ModelCoefficientsPtr;
+
+// pcl::SacModel / the method types of sample_consensus (model_types.h, method_types.h), PCL's names and values; the library
+// offers SACMODEL_PLANE and SACMODEL_PERPENDICULAR_PLANE with SAC_RANSAC (mvr_cloud_segment_plane in mvr_hip.h)
+enum SacModel { SACMODEL_PLANE = 0, SACMODEL_LINE, SACMODEL_CIRCLE2D, SACMODEL_CIRCLE3D, SACMODEL_SPHERE, SACMODEL_CYLINDER, SACMODEL_CONE,
+                SACMODEL_TORUS, SACMODEL_PARALLEL_LINE, SACMODEL_PERPENDICULAR_PLANE, SACMODEL_PARALLEL_LINES, SACMODEL_NORMAL_PLANE };
+enum { SAC_RANSAC = 0, SAC_LMEDS = 1, SAC_MSAC = 2, SAC_RRANSAC = 3, SAC_RMSAC = 4, SAC_MLESAC = 5, SAC_PROSAC = 6 };
+
 // pcl::PointCloud<PointT> (the members the reference touches: points, size,
 // at, operator[], push_back, clear, operator+=, Ptr; registrator.cpp:548-576,
 // point_cloud.cpp:290-303).

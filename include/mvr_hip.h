@@ -604,6 +604,97 @@ typedef struct {
 int  mvr_cloud_boundary(mvr_ctx *ctx, int slot, const mvr_boundary_params *p, uint8_t *boundary /* n */,
                         float *max_gap /* n, optional */, uint32_t *neighbor_count /* n, optional */);
 
+/* ---- plane segmentation (EXTENSION: pcl::SACSegmentation with SAC_RANSAC, pcl::ExtractIndices) ---------------------------
+ * Takes the largest plane -- the platter or the table a scanned object stands on -- out of a cloud.  PCL was not at hand; the
+ * model is pcl/sample_consensus/impl/ransac.hpp, sac_model_plane.hpp, sac_model_perpendicular_plane.hpp,
+ * pcl/segmentation/impl/sac_segmentation.hpp and pcl/filters/impl/extract_indices.hpp, as published; deviations are marked.
+ * Every f32 operation below is rounded on its own and never contracted (the build has -ffp-contract=off).
+ *  P1. Valid points: a point is VALID when its three coordinates are finite; nv = their number.  An invalid point is never
+ *      sampled and never an inlier.  nv < 3: MVR_OK with found = 0 and no attempt made.
+ *  P2. Draws: mix / draw of rule A2, unchanged.  Sample j (0..2) of ATTEMPT t: r = draw(t, j, nv - j); then, for the earlier
+ *      samples of this attempt TAKEN IN ASCENDING ORDER OF THEIR VALUE r (not in the order they were drawn): if (r >= that) ++r.
+ *      The point is the r-th valid point in ascending original index.  The three are distinct by construction.
+ *      DEVIATION: PCL draws with rand() and has an isSampleGood retry loop; there is none here.
+ *  P3. Model from the samples p0, p1, p2, in f32: e1 = p1 - p0, e2 = p2 - p0; n = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z,
+ *      e1.x e2.y - e1.y e2.x); len2 = (n.x n.x + n.y n.y) + n.z n.z; len = sqrtf(len2); (a, b, c) = n / len, a division per
+ *      component; d = -((a p0.x + b p0.y) + c p0.z).  The attempt is SKIPPED (status 0; its traced coefficients and count are 0)
+ *      when len2 is not > 0 or any of a, b, c, d is non-finite.  DEVIATION: PCL tests collinearity by a ratio of differences.
+ *  P4. SACMODEL_PERPENDICULAR_PLANE (model 1): cs = |(a A.x + b A.y) + c A.z| / (sqrt((a a + b b) + c c) * sqrt((A.x A.x +
+ *      A.y A.y) + A.z A.z)) in f64 from the f32 normal and the caller's axis A, the second root taken once on the host.  The
+ *      model is INVALID (status 3) iff cs < cos(eps_angle), the cosine taken once on the host.  An invalid model is a COUNTED
+ *      attempt with 0 inliers, as in PCL, whose countWithinDistance returns 0 for it.
+ *  P5. Distance of a point (x, y, z) in f32: t = a x; t = t + b y; t = t + c z; t = t + d; with fma_dist the two middle steps
+ *      are t = fmaf(b, y, t) and t = fmaf(c, z, t).  The point is an inlier iff (double)fabsf(t) < threshold, strictly (the
+ *      kernels compare with the smallest f32 that is >= threshold, which is the same test).  An invalid point gives a
+ *      non-finite t and is never an inlier.
+ *  P6. The count of an attempt is the exact integer number of inliers: independent of order and of launch shape.
+ *  P7. The loop is PCL's, replayed on the host over the attempts t = 0, 1, ... in order:
+ *        iterations = 0, skipped = 0, k = 1, best_count = -1;
+ *        while (iterations < k && skipped < 10 * max_iterations) {
+ *          attempt t; if it is skipped { ++skipped; continue; }
+ *          if (count > best_count) {                 -- strictly: the first of equal counts stays
+ *            best_count = count; best = t; w = best_count / (double)nv;      DEVIATION: PCL divides by all indices
+ *            pno = 1 - w * w * w, clamped to [DBL_EPSILON, 1 - DBL_EPSILON]; k = log(1 - probability) / log(pno); }
+ *          ++iterations; if (iterations > max_iterations) break; }
+ *      The break is PCL's own off-by-one -- up to max_iterations + 1 counted attempts -- and is kept.  `attempts` = the attempts
+ *      made (iterations + skipped).  found = (best_count > 0): some counted attempt had an inlier.  Under model 0 a counted
+ *      attempt has its own three samples within any sensible threshold, so there found means "an attempt was counted";
+ *      under model 1 every attempt may be invalid.  (PCL would keep a model without inliers and SACSegmentation would return
+ *      empty indices: here that is found = 0.)  best_attempt = best when found, else -1.
+ *  P8. Attempts are generated and scored in chunks (tune key "sac_chunk": 1..256 attempts per chunk; 0, default: chosen by the
+ *      library); the attempts of a chunk beyond the point where the loop stops are discarded.  Result and trace are
+ *      bit-identical for every chunk size.
+ *  P9. The inliers are those of P5 under the best attempt's coefficients: ransac_coefficients and ransac_inliers.
+ *  P10. optimize (setOptimizeCoefficients): with q = the first sample of the best attempt, the sums of dx, dy, dz, dx dx,
+ *      dx dy, dx dz, dy dy, dy dz, dz dz over the inliers, (dx, dy, dz) = (double)p - (double)q, in f64 in a fixed order as in
+ *      rule S2: one partial per block of 256 consecutive ORIGINAL indices (a point that is no inlier adds +0), the fixed tree
+ *      v[i] += v[i + s] for s = 128, 64, ..., 1 inside a block, the partials added in ascending order.  Mean and covariance
+ *      from them as the normals do (inv = 1 / count; m = sum * inv; C.xy = xy * inv - m.x * m.y); the eigenvector of the
+ *      smallest eigenvalue by the library's cyclic Jacobi, normalised; turned so that its dot product with the RANSAC normal
+ *      is >= 0 (DEVIATION: PCL leaves the sign to Eigen); d = -((n.x M.x + n.y M.y) + n.z M.z) with M = q + m, all in f64;
+ *      then the four are cast to f32.  The inliers are selected again (P5) with the refined coefficients, as
+ *      SACSegmentation::segment does.  With fewer than 3 inliers, or a non-finite refined coefficient, the RANSAC
+ *      coefficients and inliers stay.  `coefficients` and `inliers` are the final ones either way.
+ *  P11. Output: inlier_index (optional, host, capacity = source size) = the inliers' original indices, ascending;
+ *      inlier_flag (optional, host) = one byte per SOURCE point.  dst_slot receives the inliers, or with `negative` every
+ *      other point of the source, invalid points included, as ExtractIndices::setNegative does; in ascending original index,
+ *      normals following their points; a NEW point set as in K6; dst_slot may equal src_slot; dst_slot == -1 leaves every slot
+ *      untouched.  *n_out (optional) = the number of points of that output set.  found = 0: no inliers, so the output is
+ *      empty, or with `negative` a copy of the source.  trace[t] (optional) for every attempt made, t < trace_cap: status
+ *      (0 skipped, 1 counted, 3 invalid under P4), the samples' original indices, the coefficients, the count (0 unless
+ *      status 1) and k after the attempt.
+ *  P12. MVR_E_ARG, before any GPU work and with nothing written, for a NULL ctx / params / result, a bad slot, dst_slot < -1,
+ *      a model outside 0..1, a threshold that is non-finite or <= 0, max_iterations < 1 or above 1 << 24, a probability
+ *      outside (0, 1), under model 1 an axis with a non-finite component or all zero or an eps_angle outside (0, pi / 2], a
+ *      cloud above 0x7FFFFFF0 points, or a cloud whose points are stale because a pipelined run is in flight.  An empty cloud
+ *      is MVR_OK with found = 0.  Bit-identical from run to run: integer atomics only, every f64 sum in the order of P10.
+ * Out of scope: other models (sphere, cylinder, line, normal plane), other estimators (LMedS, MSAC, PROSAC),
+ * setSamplesMaxDist, setIndices on the segmentation, Euclidean cluster extraction. */
+typedef struct {
+  int      model;            /* 0: SACMODEL_PLANE, 1: SACMODEL_PERPENDICULAR_PLANE */
+  double   threshold;        /* setDistanceThreshold: finite, > 0 */
+  int      max_iterations;   /* setMaxIterations: >= 1 */
+  double   probability;      /* setProbability: in (0, 1) */
+  int      optimize;         /* setOptimizeCoefficients */
+  double   axis[3];          /* setAxis (model 1): finite, not all zero */
+  double   eps_angle;        /* setEpsAngle (model 1): in (0, pi/2] */
+  uint64_t seed;             /* ours: PCL draws with rand() */
+  int      negative;         /* ExtractIndices::setNegative, for dst_slot */
+  int      fma_dist;
+} mvr_sac_params;
+typedef struct { int found; uint32_t inliers, ransac_inliers; int iterations, attempts, skipped, best_attempt;
+                 double k; float coefficients[4], ransac_coefficients[4]; } mvr_sac_result;
+typedef struct { int status; uint32_t sample[3]; float coefficients[4]; uint32_t inliers; double k; } mvr_sac_trace;
+int  mvr_cloud_segment_plane(mvr_ctx *ctx, int dst_slot /* -1: none */, int src_slot, const mvr_sac_params *p,
+                             mvr_sac_result *result, size_t *n_out, uint32_t *inlier_index /* cap = source size */,
+                             uint8_t *inlier_flag /* n, optional */, mvr_sac_trace *trace /* optional */, size_t trace_cap);
+/* pcl::ExtractIndices::filter: dst_slot (may be src_slot) receives the points of src_slot whose index is listed in `index`
+ * (host, count entries, each below the source size, in any order, repeats allowed -- a point is taken once), or with
+ * `negative` all the others; ascending original index, normals following, a new point set (P11's tail).  MVR_E_ARG for a NULL
+ * ctx, a bad slot, a NULL index with count > 0, an index out of range, or a stale or oversized cloud. */
+int  mvr_cloud_extract_indices(mvr_ctx *ctx, int dst_slot, int src_slot, const uint32_t *index, size_t count, int negative,
+                               size_t *n_out);
+
 /* CorrespondenceEstimation::determineReciprocalCorrespondences(corrs, max_d)
  * (registrator.cpp:496-502, 644-649); reciprocal = 0 gives
  * determineCorrespondences.  Outputs are host arrays of capacity `cap`
@@ -936,7 +1027,9 @@ enum { MVR_K_NN = 0, MVR_K_REDUCE = 1, MVR_K_XFORM = 2, MVR_K_GLUE = 3,
  * same permutations), "pipeline_multi_rank" (1: passes with a collective over more than one rank may be queued ahead of their poses
  * too; 0, default, until a recorded two-GPU run);
  * feature matching and pose scoring: "feat_split" (blocks the target of mvr_feature_knn is split over, 1..64; 0, default: by the
- * launch size), "score_chunk" (poses per launch of mvr_pose_scores, default 256).
+ * launch size), "score_chunk" (poses per launch of mvr_pose_scores, default 256);
+ * plane segmentation: "sac_chunk" (attempts generated and scored per chunk, 1..256; 0, default: 64 for the first chunk of a
+ * call and 256 from then on).
  * Results never depend on them. */
 int  mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value);
 /* wall milliseconds of every pass of the LAST mvr_ring_run / mvr_ring_run_sharded on this context (from the end of the

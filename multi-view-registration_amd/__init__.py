@@ -150,6 +150,27 @@ class BoundaryParams(C.Structure):
     _fields_ = [("radius", C.c_double), ("angle_threshold", C.c_double), ("min_neighbors", C.c_int), ("fma_dist", C.c_int)]
 
 
+class SacParams(C.Structure):
+    """mvr_sac_params"""
+    _fields_ = [("model", C.c_int), ("threshold", C.c_double), ("max_iterations", C.c_int), ("probability", C.c_double),
+                ("optimize", C.c_int), ("axis", C.c_double * 3), ("eps_angle", C.c_double), ("seed", C.c_uint64),
+                ("negative", C.c_int), ("fma_dist", C.c_int)]
+
+
+class SacResult(C.Structure):
+    """mvr_sac_result"""
+    _fields_ = [("found", C.c_int), ("inliers", C.c_uint32), ("ransac_inliers", C.c_uint32), ("iterations", C.c_int),
+                ("attempts", C.c_int), ("skipped", C.c_int), ("best_attempt", C.c_int), ("k", C.c_double),
+                ("coefficients", C.c_float * 4), ("ransac_coefficients", C.c_float * 4)]
+
+
+class SacTrace(C.Structure):
+    """mvr_sac_trace"""
+    _fields_ = [("status", C.c_int), ("sample", C.c_uint32 * 3), ("coefficients", C.c_float * 4), ("inliers", C.c_uint32),
+                ("k", C.c_double)]
+
+
+SAC_MODELS = {"plane": 0, "perpendicular_plane": 1}   # mvr_sac_params.model: SACMODEL_PLANE, SACMODEL_PERPENDICULAR_PLANE
 BOUNDARY_MIN_ANGLE = math.pi / 4   # MVR_BOUNDARY_MIN_ANGLE: the smallest angle_threshold the boundary rule accepts
 FPFH_BINS = 11          # MVR_FPFH_BINS: a signature is 3 * 11 = 33 floats
 PREREJ_MAX_SAMPLES = 8  # MVR_PREREJ_MAX_SAMPLES
@@ -203,6 +224,9 @@ SIGNATURES = {
     "mvr_cloud_iss_keypoints_border": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(IssParams), C.POINTER(IssBorderParams), C.POINTER(_sz), _u32p,
                                                  _dp, _u32p, _u32p, _u8p, _u8p]),
     "mvr_cloud_boundary": (C.c_int, [_vp, C.c_int, C.POINTER(BoundaryParams), _u8p, _fp, _u32p]),
+    "mvr_cloud_segment_plane": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(SacParams), C.POINTER(SacResult), C.POINTER(_sz), _u32p, _u8p,
+                                          C.POINTER(SacTrace), _sz]),
+    "mvr_cloud_extract_indices": (C.c_int, [_vp, C.c_int, C.c_int, _u32p, _sz, C.c_int, C.POINTER(_sz)]),
     "mvr_feature_knn": (C.c_int, [_vp, _fp, _sz, _fp, _sz, C.c_int, C.c_int, _u32p, _fp]),
     "mvr_pose_scores": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _sz, C.c_double, C.c_int, _u32p, _dp]),
     "mvr_align_prerejective": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, C.POINTER(PrerejParams), _fp, C.POINTER(PrerejResult),
@@ -780,6 +804,51 @@ class Context:
         if return_edges:
             out += [edge[:n].astype(bool), border[:n].astype(bool)]
         return out[0] if len(out) == 1 else tuple(out)
+
+    def segment_plane(self, dst, src, threshold, model="plane", max_iterations=1000, probability=0.99, optimize=True, axis=None,
+                      eps_angle=None, seed=0, negative=False, fma=False, return_index=False, return_trace=False):
+        """pcl::SACSegmentation (SAC_RANSAC; model "plane" or "perpendicular_plane" with axis and eps_angle) of slot src, then
+        pcl::ExtractIndices into slot dst (may be src; -1: no output slot): the largest plane's inliers, or with negative
+        everything else (rules P1-P12: mvr_cloud_segment_plane in mvr_hip.h).  A pure function of its arguments, seed
+        included.  Returns a dict(found, inliers, ransac_inliers, iterations, attempts, skipped, best_attempt, k,
+        coefficients (4) float32, ransac_coefficients (4) float32, n_out), followed with return_index by the inliers' original
+        indices (ascending, uint32) and with return_trace by dict(status[t], sample[t, 3], coefficients[t, 4], inliers[t],
+        k[t]) over the attempts made."""
+        if model not in SAC_MODELS:
+            raise ValueError("model must be one of %s" % sorted(SAC_MODELS))
+        n = self.size(src)
+        ax = (0.0, 0.0, 0.0) if axis is None else tuple(float(v) for v in axis)
+        p = SacParams(SAC_MODELS[model], float(threshold), int(max_iterations), float(probability), int(bool(optimize)),
+                      (C.c_double * 3)(*ax), 0.0 if eps_angle is None else float(eps_angle), int(seed), int(bool(negative)), int(bool(fma)))
+        res = SacResult()
+        n_out = _sz()
+        idx = np.empty(max(n, 1), np.uint32) if return_index else None
+        cap = 11 * max(int(max_iterations), 0) + 1 if return_trace else 0      # counted attempts <= max_iterations + 1, skipped <= 10 x
+        tr = (SacTrace * cap)() if return_trace else None
+        _chk(_lib.mvr_cloud_segment_plane(self._h, int(dst), int(src), C.byref(p), C.byref(res), C.byref(n_out),
+                                          _p(idx, C.c_uint32) if return_index else None, None, tr, cap), self._h)
+        out = [dict(found=bool(res.found), inliers=int(res.inliers), ransac_inliers=int(res.ransac_inliers), iterations=res.iterations,
+                    attempts=res.attempts, skipped=res.skipped, best_attempt=res.best_attempt, k=res.k,
+                    coefficients=np.array(res.coefficients, np.float32), ransac_coefficients=np.array(res.ransac_coefficients, np.float32),
+                    n_out=n_out.value)]
+        if return_index:
+            out.append(idx[:res.inliers].copy())
+        if return_trace:
+            dt = np.dtype([("status", np.int32), ("sample", np.uint32, 3), ("coefficients", np.float32, 4), ("inliers", np.uint32),
+                           ("k", np.float64)], align=True)
+            assert dt.itemsize == C.sizeof(SacTrace)
+            a = np.frombuffer(tr, dtype=dt, count=cap)[:res.attempts].copy()
+            out.append({k: np.ascontiguousarray(a[k]) for k in ("status", "sample", "coefficients", "inliers", "k")})
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def extract_indices(self, dst, src, index, negative=False) -> int:
+        """pcl::ExtractIndices::filter: slot dst (may be src) gets the points of slot src listed in index, or with negative all
+        the others, in ascending original index, normals following (mvr_cloud_extract_indices).  Returns their number."""
+        idx = np.ascontiguousarray(index, np.uint32).ravel()
+        n_out = _sz()
+        _chk(_lib.mvr_cloud_extract_indices(self._h, int(dst), int(src), _p(idx, C.c_uint32) if len(idx) else None, len(idx),
+                                            int(bool(negative)), C.byref(n_out)), self._h)
+        return n_out.value
 
     def feature_knn(self, q, t, k):
         """exact k nearest neighbours of every row of q among the rows of t in feature space (33 floats per row, FLANN's

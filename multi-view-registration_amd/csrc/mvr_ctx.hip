@@ -2476,6 +2476,7 @@ API int mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value)
   else if (!std::strcmp(key, "pair_fused")) c->pair_fused = value != 0;
   else if (!std::strcmp(key, "feat_split")) { if (value < 0 || value > 64) return MVR_E_ARG; c->feat_split = value; }
   else if (!std::strcmp(key, "score_chunk")) { if (value < 1 || value > 65535) return MVR_E_ARG; c->score_chunk = value; }
+  else if (!std::strcmp(key, "sac_chunk")) { if (value < 0 || value > 256) return MVR_E_ARG; c->sac_chunk = value; }
   else if (!std::strcmp(key, "posed_refresh")) c->posed_refresh = value != 0;
   else if (!std::strcmp(key, "pair_groups")) { if (value < 1 || value > 8) return MVR_E_ARG; c->pair_groups = value; }
   else if (!std::strcmp(key, "inplace_ratio")) c->inplace_ratio = value;

@@ -269,16 +269,7 @@ int pose_scores_device(Ctx *c, Cloud &src, Cloud &tgt, const float *dT, size_t c
 
 constexpr int kMaxSamples = MVR_PREREJ_MAX_SAMPLES;
 
-__host__ __device__ inline uint64_t prerej_mix(uint64_t z)
-{
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__host__ __device__ inline uint32_t prerej_draw(uint64_t seed, uint64_t i, uint64_t j, uint64_t m)
-{
-  return (uint32_t)(((prerej_mix(seed + 0x9E3779B97F4A7C15ull * (16ull * i + j + 1ull)) >> 32) * m) >> 32);
-}
+// (prerej_mix / prerej_draw, rule A2: mvr_internal.h -- the plane segmentation draws with them too)
 
 struct HypArgs {
   const float4 *sp, *tp;           // the slots' points by index

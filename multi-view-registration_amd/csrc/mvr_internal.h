@@ -276,6 +276,7 @@ struct Ctx {
   // scoring launch -- results never depend on either; wall milliseconds of the last mvr_align_prerejective by phase
   int feat_split = 0, score_chunk = 256;
   double prerej_ms[3] = {0.0, 0.0, 0.0};                 // matching, hypothesis generation, scoring
+  int sac_chunk = 0;                                     // mvr_cloud_segment_plane: attempts per chunk (0: 64 for a call's first chunk, 256 from then on); results never depend on it
   char *dn_arena = nullptr; size_t dn_arena_cap = 0;     // scratch of mvr_cloud_denoise and mvr_cloud_voxel_grid (one buffer, carved per call)
   double *h_table = nullptr; size_t h_table_cap = 0;     // pinned host memory the final kernels of mvr_ring_step write straight into (zero-copy)
   // workspace of the fused batch (culled mode): forward keys of all pairs, reverse keys + flags, per-pair partial rows
@@ -426,6 +427,18 @@ int ensure(Ctx *c, T *&p, size_t &cap, size_t want)
   MVR_HIP_TRY(c, hipMalloc(&p, ncap * sizeof(T)));
   cap = ncap;
   return MVR_OK;
+}
+
+// rule A2's draws (mvr_hip.h): mvr_align_prerejective (mvr_feature.hip) and mvr_cloud_segment_plane (mvr_sac.hip, rule P2)
+__host__ __device__ inline uint64_t prerej_mix(uint64_t z)
+{
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__host__ __device__ inline uint32_t prerej_draw(uint64_t seed, uint64_t i, uint64_t j, uint64_t m)
+{
+  return (uint32_t)(((prerej_mix(seed + 0x9E3779B97F4A7C15ull * (16ull * i + j + 1ull)) >> 32) * m) >> 32);
 }
 
 inline unsigned blocks_for(size_t n, int threads) { return (unsigned)((n + (size_t)threads - 1) / (size_t)threads); }
