@@ -1022,7 +1022,7 @@ enum { MVR_K_NN = 0, MVR_K_REDUCE = 1, MVR_K_XFORM = 2, MVR_K_GLUE = 3,
  * own query order, i.e. the forward searches; 0: off; also MVR_GRID_STAGE), "grid_stage_stat" (1: counters of the staged walk's waves by outcome, read with
  * mvr_ctx_stat "stage_staged" / "stage_rows" / "stage_width" / "stage_points"), "grid_index" (a grid's cell-start table, for grids
  * built from then on: 2, default = dense, built through the compact form and expanded; 1 = compact: a directory of 32-cell segments
- * + records of the occupied ones, a tenth of the bytes, walks 8-11 % slower; 0 = the round-3 dense build; also MVR_GRID_INDEX),
+ * + records of the occupied ones, a tenth of the bytes, walks 8-11 % slower; any other value: MVR_E_ARG; also MVR_GRID_INDEX),
  * "order_batch" (1, default: the orderings several point sets need are built in one composite sort; 0: one after the other -- the
  * same permutations), "pipeline_multi_rank" (1: passes with a collective over more than one rank may be queued ahead of their poses
  * too; 0, default, until a recorded two-GPU run);

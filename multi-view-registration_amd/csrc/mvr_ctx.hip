@@ -389,7 +389,7 @@ static int ctx_create_impl(mvr_ctx **out, int device_id, void *hip_stream, bool 
   if (const char *m = std::getenv("MVR_INPLACE_RATIO")) c->inplace_ratio = std::atoi(m);
   if (const char *m = std::getenv("MVR_PAIR_FUSED")) c->pair_fused = std::atoi(m) != 0;
   if (const char *m = std::getenv("MVR_PIPELINE")) c->pipeline = std::atoi(m) != 0;      // 0: no pass is enqueued ahead of its poses
-  if (const char *m = std::getenv("MVR_GRID_INDEX")) c->grid_index = std::max(0, std::min(2, std::atoi(m)));      // 0 dense cell starts, 1 compact, 2 by size (default)
+  if (const char *m = std::getenv("MVR_GRID_INDEX")) { const int v = std::atoi(m); if (v == 1 || v == 2) c->grid_index = v; }      // 1 compact cell starts, 2 dense (default); any other value is ignored
   if (const char *m = std::getenv("MVR_GRID_STAGE")) c->grid_stage = std::max(0, std::min(2, std::atoi(m)));      // the staged walk: 0 off, 1 forward launches, 2 all (default)
   if (const char *m = std::getenv("MVR_POSED_REFRESH")) c->posed_refresh = std::atoi(m) != 0;
   if (const char *m = std::getenv("MVR_PAIR_GROUPS")) c->pair_groups = std::max(1, std::min(8, std::atoi(m)));
@@ -2466,7 +2466,7 @@ API int mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value)
     if (!value && c->stage_stat) { (void)hipFree(c->stage_stat); c->stage_stat = nullptr; }
   }
   else if (!std::strcmp(key, "order_batch")) c->order_batch = value != 0;
-  else if (!std::strcmp(key, "grid_index")) { if (value < 0 || value > 2) return MVR_E_ARG; c->grid_index = value; }
+  else if (!std::strcmp(key, "grid_index")) { if (value < 1 || value > 2) return MVR_E_ARG; c->grid_index = value; }
   else if (!std::strcmp(key, "grid_cell_points")) { if (value < 1) return MVR_E_ARG; c->grid_cell_points = value; }
   else if (!std::strcmp(key, "pipeline")) c->pipeline = value != 0;
   else if (!std::strcmp(key, "pipeline_multi_rank")) c->pipeline_multi_rank = value != 0;

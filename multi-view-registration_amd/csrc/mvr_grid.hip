@@ -10,7 +10,7 @@
 //
 // Structure: a UNIFORM GRID over every point set in its canonical (upload) coordinates -- pose-invariant like the
 // Hilbert ordering, built once per scan (cell ids -> radix sort -> dense cell-start array: O(1) lookup, no hashing) and
-// shared by all posed copies; plus a one-byte-per-cell distance map ("how many cells to the nearest occupied one").
+// shared by all posed copies; plus a distance map of one byte per 2 x 2 x 2 cells ("how many such cubes to the nearest occupied one").
 // Per pass a posed copy only refreshes its coordinates in grid order (one streaming launch for all views).
 // Search: the query is mapped into the target's canonical frame (inverse pose), the cells overlapped by the ball of its
 // bound (plus a margin far above every rounding involved) are walked row by row -- a row of cells along x is ONE
@@ -52,92 +52,6 @@ __device__ __forceinline__ int cell_of(float x, float lo, float inv_h, int dim)
   // [cell_of(a), cell_of(b)] -- what the search's cell range relies on.  Clamped: points ON the upper face.
   const float f = floorf((x - lo) * inv_h);
   return (int)fminf(fmaxf(f, 0.f), (float)(dim - 1));
-}
-
-__global__ void cell_id_kernel(const float4 *__restrict__ p, size_t n, GridGeom g, uint32_t *__restrict__ cid, uint32_t *__restrict__ idx)
-{
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float4 v = p[i];
-  const int x = cell_of(v.x, g.lo[0], g.inv_h, g.dim[0]), y = cell_of(v.y, g.lo[1], g.inv_h, g.dim[1]), z = cell_of(v.z, g.lo[2], g.inv_h, g.dim[2]);
-  cid[i] = (uint32_t)((z * g.dim[1] + y) * g.dim[0] + x);
-  idx[i] = (uint32_t)i;
-}
-
-// distance map: dt[c] = Chebyshev distance, in cells, from cell c to the nearest occupied cell, capped (255 = farther than
-// `steps`).  The Chebyshev ball is a cube, so the minimum over the occupied cells of max(|dx|, |dy|, |dz|) separates:
-//   a(c) = min over dx of |dx| with (x + dx, y, z) occupied;  b(c) = min over dy of max(|dy|, a(x, y + dy, z));
-//   dt(c) = min over dz of max(|dz|, b(x, y, z + dz))
-// -- three launches that each look at a window of 2 steps + 1 cells along one axis, instead of one dilation launch per
-// step over all 27 neighbours (round 2: up to 12 launches of 47 us per scan, half of a grid's build time).
-__global__ void dt_occupancy_kernel(const uint32_t *__restrict__ start, size_t cells, uint8_t *__restrict__ out)
-{
-  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < cells) out[c] = start[c + 1] > start[c] ? 0 : 255;
-}
-__global__ void dt_axis_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, int nx, int ny, int nz, int axis, int steps)
-{
-  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= (size_t)nx * ny * nz) return;
-  const int x = (int)(c % nx), y = (int)((c / nx) % ny), z = (int)(c / ((size_t)nx * ny));
-  const int pos = axis == 0 ? x : axis == 1 ? y : z, len = axis == 0 ? nx : axis == 1 ? ny : nz;
-  const size_t stride = axis == 0 ? 1 : axis == 1 ? (size_t)nx : (size_t)nx * ny;
-  auto val = [&](size_t cc) -> int { return (int)in[cc]; };
-  int best = val(c);
-  for (int d = 1; d <= steps && best > d; ++d) {           // a value found at distance d cannot be beaten by anything farther than it
-    if (pos - d >= 0) best = min(best, max(d, val(c - (size_t)d * stride)));
-    if (pos + d < len) best = min(best, max(d, val(c + (size_t)d * stride)));
-  }
-  out[c] = (uint8_t)(best > steps ? 255 : best);
-}
-
-// start[c] = first grid position whose cell id is >= c; start[cells] = n.  From the SORTED cell ids: the first point of a
-// run of equal ids knows its cell's start; an empty cell takes the start of the next occupied one -- a suffix minimum,
-// done as an inclusive min-scan over the reversed array.
-__global__ void cell_first_kernel(const uint32_t *__restrict__ sorted_cid, size_t n, size_t cells, uint32_t *__restrict__ start)
-{
-  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k == 0) start[cells] = (uint32_t)n;
-  if (k >= n) return;
-  const uint32_t c = sorted_cid[k];
-  if (k == 0 || sorted_cid[k - 1] != c) start[c] = (uint32_t)k;
-}
-struct MinU32 { __host__ __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a < b ? a : b; } };
-// a random-access iterator over p[len - 1], p[len - 2], ..., p[0] (hipCUB's scans take any such iterator)
-struct ReverseU32 {
-  typedef std::random_access_iterator_tag iterator_category;
-  typedef uint32_t value_type; typedef ptrdiff_t difference_type; typedef uint32_t *pointer; typedef uint32_t &reference;
-  uint32_t *last;       // &p[len - 1]
-  __host__ __device__ uint32_t &operator*() const { return *last; }
-  __host__ __device__ uint32_t &operator[](ptrdiff_t i) const { return *(last - i); }
-  __host__ __device__ ReverseU32 operator+(ptrdiff_t i) const { return ReverseU32{last - i}; }
-  __host__ __device__ ReverseU32 operator-(ptrdiff_t i) const { return ReverseU32{last + i}; }
-  __host__ __device__ ptrdiff_t operator-(const ReverseU32 &o) const { return o.last - last; }
-  __host__ __device__ ReverseU32 &operator+=(ptrdiff_t i) { last -= i; return *this; }
-  __host__ __device__ ReverseU32 &operator-=(ptrdiff_t i) { last += i; return *this; }
-  __host__ __device__ ReverseU32 &operator++() { --last; return *this; }
-  __host__ __device__ ReverseU32 operator++(int) { ReverseU32 t = *this; --last; return t; }
-  __host__ __device__ ReverseU32 &operator--() { ++last; return *this; }
-  __host__ __device__ bool operator==(const ReverseU32 &o) const { return last == o.last; }
-  __host__ __device__ bool operator!=(const ReverseU32 &o) const { return last != o.last; }
-  __host__ __device__ bool operator<(const ReverseU32 &o) const { return last > o.last; }
-};
-inline ReverseU32 thrust_like_reverse(uint32_t *p, size_t len) { return ReverseU32{p + (len ? len - 1 : 0)}; }
-// the eight entries behind start[cells] (the walk reads four consecutive starts with one load, the staged walk eight with two): all n
-constexpr size_t kStartPad = 8;
-__global__ void pad_start_kernel(uint32_t *__restrict__ start, size_t cells, uint32_t n)
-{
-  if (threadIdx.x < kStartPad) start[cells + 1 + threadIdx.x] = n;
-}
-
-__global__ void grid_gather_kernel(const float4 *__restrict__ p, const uint32_t *__restrict__ gperm, size_t n, float4 *__restrict__ graw)
-{
-  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const uint32_t o = gperm[k];
-  float4 v = p[o];
-  v.w = __uint_as_float(o);
-  graw[k] = v;
 }
 
 // (for several grids at once, blockIdx.y = grid: a registration's first pass asked for twelve, one launch each with the gap between them)
@@ -241,17 +155,16 @@ template <class A> __device__ __forceinline__ void cell_range_of(const A &a, uin
   s = (d0 & kSegOcc) ? a.recs[((d0 & ~kSegOcc) << 5) + (c0 & 31u)] : d0;
   e = cell_start_of(a, c1e);
 }
-// the distance map: per cell, or per cube of 2^dt_shift cells per axis; what its byte says about the nearest point, in mm
+// the distance map, per cube of 2^kDtShift cells per axis; what its byte says about the nearest point, in mm
 template <class A> __device__ __forceinline__ uint32_t dt_of(const A &a, int cx, int cy, int cz)
 {
-  if (a.dt_shift == 0) return a.dt[((size_t)cz * a.dim[1] + cy) * a.dim[0] + cx];
-  return a.dt[((size_t)(cz >> a.dt_shift) * a.dtdim[1] + (cy >> a.dt_shift)) * a.dtdim[0] + (cx >> a.dt_shift)];
+  return a.dt[((size_t)(cz >> kDtShift) * a.dtdim[1] + (cy >> kDtShift)) * a.dtdim[0] + (cx >> kDtShift)];
 }
 template <class A> __device__ __forceinline__ float dt_least_of(const A &a, uint32_t d)
 {
-  // the query's (clamped) cell -- or cube -- is d cells / cubes from the nearest occupied one: every point is at least (d - 1)
-  // cell / cube edges away along some axis; 255 = farther than the map was built for
-  return (d == 255u ? (float)a.dt_max : (float)d - 1.f) * a.h * (float)(1 << a.dt_shift);
+  // the cube of the query's (clamped) cell is d cubes from the nearest occupied one: every point is at least (d - 1) cube
+  // edges away along some axis; 255 = farther than the map was built for
+  return (d == 255u ? (float)a.dt_max : (float)d - 1.f) * a.h * (float)(1 << kDtShift);
 }
 
 // ---- wave-wide reductions and scans without the LDS crossbar: DPP row shifts inside the rows of 16 lanes, the four row results
@@ -856,29 +769,11 @@ __device__ __forceinline__ void nn_grid_wide_body(const GridBatch &batch, unsign
 // a grid carries an event its first user waits for.  `on` is the stream the build is enqueued on: the context's own, or its
 // side stream so that the grids of a registration are built WHILE its first pass searches (ring_passes).
 namespace {
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 __global__ void bbox_many_partial_kernel(const float4 *const *__restrict__ pts, const unsigned long long *__restrict__ n, float *__restrict__ part)
 {
   // blockIdx.y = cloud; 64 blocks per cloud; part[cloud][block][6]
   const int cl = blockIdx.y;
-  const float4 *p = pts[cl];
-  const size_t cnt = (size_t)n[cl];
-  float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (size_t)gridDim.x * blockDim.x) {
-    const float4 v = p[i];
-    lo[0] = fminf(lo[0], v.x); lo[1] = fminf(lo[1], v.y); lo[2] = fminf(lo[2], v.z);
-    hi[0] = fmaxf(hi[0], v.x); hi[1] = fmaxf(hi[1], v.y); hi[2] = fmaxf(hi[2], v.z);
-  }
-  __shared__ float sh[4][6];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], __shfl_xor(lo[k], o, 64)); hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], o, 64)); }
-  if ((threadIdx.x & 63) == 0) for (int k = 0; k < 3; ++k) { sh[threadIdx.x >> 6][k] = lo[k]; sh[threadIdx.x >> 6][3 + k] = hi[k]; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) for (int k = 0; k < 3; ++k) { sh[0][k] = fminf(sh[0][k], sh[w][k]); sh[0][3 + k] = fmaxf(sh[0][3 + k], sh[w][3 + k]); }
-    for (int k = 0; k < 6; ++k) part[((size_t)cl * gridDim.x + blockIdx.x) * 6 + k] = sh[0][k];
-  }
+  bbox_block_partial(pts[cl], (size_t)n[cl], part + ((size_t)cl * gridDim.x + blockIdx.x) * 6);
 }
 }  // namespace
 
@@ -979,7 +874,13 @@ __global__ void cg_fill_kernel(CGArgs a, uint8_t *__restrict__ dt_a)
   const size_t cells2 = (size_t)a.dtdim[g][0] * a.dtdim[g][1] * a.dtdim[g][2];
   for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < cells2; c += (size_t)gridDim.x * blockDim.x) dt_a[(size_t)a.dtoff[g] + c] = 255;
 }
-// dt_axis_kernel for all the grids of the batch: from -> to along `axis`; pass 1 of 3 writes the grids' own arrays (to_own), the
+// distance map: dt[c] = Chebyshev distance, in cubes of 2 x 2 x 2 cells, from cube c to the nearest occupied one, capped (255 =
+// farther than `steps`).  The Chebyshev ball is a cube, so the minimum over the occupied cubes of max(|dx|, |dy|, |dz|) separates:
+//   a(c) = min over dx of |dx| with (x + dx, y, z) occupied;  b(c) = min over dy of max(|dy|, a(x, y + dy, z));
+//   dt(c) = min over dz of max(|dz|, b(x, y, z + dz))
+// -- three launches that each look at a window of 2 steps + 1 cubes along one axis, instead of one dilation launch per
+// step over all 27 neighbours (round 2: up to 12 launches of 47 us per scan, half of a grid's build time).
+// One pass, for all the grids of the batch: from -> to along `axis`; pass 1 of 3 writes the grids' own arrays (to_own), the
 // others the scratch buffer -- (a, own, a, own): scratch -> own -> scratch -> own
 __global__ void cg_dt_axis_kernel(CGArgs a, const uint8_t *__restrict__ from_s, uint8_t *__restrict__ to_s, int axis, int from_own, int to_own)
 {
@@ -1092,40 +993,26 @@ int ensure_grids(Ctx *c, Cloud *const *canon, int count, double reach, hipStream
   // ---- bounding boxes of all of them: one launch, one round trip
   const int m = (int)todo.size();
   constexpr int kBoxBlocks = 64;
-  constexpr size_t kCellsCap = 32000000;
   std::vector<const float4 *> hp((size_t)m); std::vector<unsigned long long> hn((size_t)m);
-  size_t nmax = 0, cells_max = 0;
-  for (int k = 0; k < m; ++k) { hp[(size_t)k] = todo[(size_t)k]->pts; hn[(size_t)k] = todo[(size_t)k]->n; nmax = std::max(nmax, todo[(size_t)k]->n); }
+  for (int k = 0; k < m; ++k) { hp[(size_t)k] = todo[(size_t)k]->pts; hn[(size_t)k] = todo[(size_t)k]->n; }
   const size_t head = align256((size_t)m * 8) * 2 + align256((size_t)m * kBoxBlocks * 6 * sizeof(float));
   bool have_boxes = true;          // every cloud brought its bounding box along from its upload: no launch, no round trip
   for (int k = 0; k < m; ++k) have_boxes = have_boxes && todo[(size_t)k]->bbox_set == todo[(size_t)k]->set_id && todo[(size_t)k]->bbox_set != 0;
-  const bool legacy = c->grid_index == 0;          // (the round-3 build: its temporaries; the other forms size their own in build_compact_grids)
-  // (sized ONCE for the largest grid there can be: growing it later would mean freeing it under the pass this build overlaps)
-  size_t sort_bytes = 0, scan_bytes = 0;
-  if (legacy) {
-    uint32_t *z = nullptr;
-    MVR_HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, z, z, z, z, (int)nmax, 0, 32, on));
-    auto rit = thrust_like_reverse(z, kCellsCap + 1);
-    MVR_HIP_TRY(c, hipcub::DeviceScan::InclusiveScan(nullptr, scan_bytes, rit, rit, MinU32(), (int)(kCellsCap + 1), on));
-  }
-  const size_t cub_bytes = std::max(sort_bytes, scan_bytes) + 256;
-  const size_t o_cid_a = 0, o_cid_b = o_cid_a + align256(nmax * 4), o_idx = o_cid_b + align256(nmax * 4), o_dtt = o_idx + align256(nmax * 4),
-               o_cub = o_dtt + align256(kCellsCap), tmp_total = o_cub + align256(cub_bytes);
-  if (legacy || !have_boxes) { if (int rc = ensure(c, c->scratch, c->scratch_cap, legacy ? std::max(head, tmp_total) : head)) return rc; }
-  const float4 **d_pts = reinterpret_cast<const float4 **>(c->scratch);
-  unsigned long long *d_n = reinterpret_cast<unsigned long long *>(c->scratch + align256((size_t)m * 8));
-  float *d_part = reinterpret_cast<float *>(c->scratch + 2 * align256((size_t)m * 8));
   std::vector<float> h_part((size_t)m * kBoxBlocks * 6);
   if (have_boxes) {
     for (int k = 0; k < m; ++k)
       for (int b = 0; b < kBoxBlocks; ++b)
         for (int j = 0; j < 6; ++j) h_part[((size_t)k * kBoxBlocks + b) * 6 + j] = todo[(size_t)k]->bbox[j];
   } else {
-  MVR_HIP_TRY(c, hipMemcpyAsync(d_pts, hp.data(), (size_t)m * 8, hipMemcpyHostToDevice, on));
-  MVR_HIP_TRY(c, hipMemcpyAsync(d_n, hn.data(), (size_t)m * 8, hipMemcpyHostToDevice, on));
-  hipLaunchKernelGGL(bbox_many_partial_kernel, dim3(kBoxBlocks, (unsigned)m), dim3(256), 0, on, d_pts, d_n, d_part);
-  MVR_HIP_TRY(c, hipMemcpyAsync(h_part.data(), d_part, h_part.size() * sizeof(float), hipMemcpyDeviceToHost, on));
-  MVR_HIP_TRY(c, hipStreamSynchronize(on));
+    if (int rc = ensure(c, c->scratch, c->scratch_cap, head)) return rc;      // (the build's temporaries are sized in build_compact_grids)
+    const float4 **d_pts = reinterpret_cast<const float4 **>(c->scratch);
+    unsigned long long *d_n = reinterpret_cast<unsigned long long *>(c->scratch + align256((size_t)m * 8));
+    float *d_part = reinterpret_cast<float *>(c->scratch + 2 * align256((size_t)m * 8));
+    MVR_HIP_TRY(c, hipMemcpyAsync(d_pts, hp.data(), (size_t)m * 8, hipMemcpyHostToDevice, on));
+    MVR_HIP_TRY(c, hipMemcpyAsync(d_n, hn.data(), (size_t)m * 8, hipMemcpyHostToDevice, on));
+    hipLaunchKernelGGL(bbox_many_partial_kernel, dim3(kBoxBlocks, (unsigned)m), dim3(256), 0, on, d_pts, d_n, d_part);
+    MVR_HIP_TRY(c, hipMemcpyAsync(h_part.data(), d_part, h_part.size() * sizeof(float), hipMemcpyDeviceToHost, on));
+    MVR_HIP_TRY(c, hipStreamSynchronize(on));
   }
   host_mark("    grids: bounding boxes back");
   // ---- geometry and one allocation per grid
@@ -1156,112 +1043,33 @@ int ensure_grids(Ctx *c, Cloud *const *canon, int count, double reach, hipStream
     }
     g->h = (float)h; g->inv_h = (float)(1.0 / h);
     const size_t cells = (size_t)g->dim[0] * g->dim[1] * g->dim[2];
-    cells_max = std::max(cells_max, cells);
-    const bool compact = c->grid_index == 1;
-    if (c->grid_index == 2) {
-      // the default: the DENSE table (one entry per lookup: 8-11 % faster walks), built through the compact form (its sort of all
-      // scans at once, its records, its distance map per 2 x 2 x 2 cells) and expanded by one streaming launch
-      g->dt_shift = 1;
-      for (int j = 0; j < 3; ++j) g->dtdim[j] = (g->dim[j] + 1) >> 1;
-      g->nseg = (uint32_t)((cells + 1 + 31) / 32);
-      const size_t cells2 = (size_t)g->dtdim[0] * g->dtdim[1] * g->dtdim[2];
-      const size_t o_start = 0, o_gperm = o_start + align256((cells + 1 + kStartPad) * 4), o_graw = o_gperm + align256(n * 4), o_g2h = o_graw + align256(n * sizeof(float4)),
-                   o_h2g = o_g2h + align256(n * 4), o_dt = o_h2g + align256(n * 4), total = o_dt + align256(cells2);
-      if (hipMalloc(&g->block, total) != hipSuccess) { (void)hipGetLastError(); return set_error(c, MVR_E_NOMEM, "grid build: out of device memory"); }
-      g->start = reinterpret_cast<uint32_t *>(g->block + o_start); g->gperm = reinterpret_cast<uint32_t *>(g->block + o_gperm);
-      g->graw = reinterpret_cast<float4 *>(g->block + o_graw); g->g2h = reinterpret_cast<uint32_t *>(g->block + o_g2h);
-      g->h2g = reinterpret_cast<uint32_t *>(g->block + o_h2g); g->dt = reinterpret_cast<uint8_t *>(g->block + o_dt);
-      const int steps2 = (int)std::ceil(std::max(0.0, reach) / (2.0 * h)) + 2;
-      g->dt_steps = std::min(kGridDtMax, std::max(2, steps2));
-      g->via_compact = true;
-      gs[(size_t)k] = g;
-      continue;
-    }
-    if (compact) {
-      // segment directory + a record per occupied segment (at most one per point, at most one per segment) + the distance map per
-      // 2 x 2 x 2 cells; gperm / graw / g2h / h2g as in the dense form
-      g->nseg = (uint32_t)((cells + 1 + 31) / 32);
-      g->dt_shift = 1;
-      for (int j = 0; j < 3; ++j) g->dtdim[j] = (g->dim[j] + 1) >> 1;
-      const size_t cells2 = (size_t)g->dtdim[0] * g->dtdim[1] * g->dtdim[2], max_slots = std::min(n, (size_t)g->nseg + 1) + 1;
-      const size_t o_dir = 0, o_recs = o_dir + align256(((size_t)g->nseg + 2) * 4), o_gperm = o_recs + align256(max_slots * 32 * 4), o_graw = o_gperm + align256(n * 4),
-                   o_g2h = o_graw + align256(n * sizeof(float4)), o_h2g = o_g2h + align256(n * 4), o_dt = o_h2g + align256(n * 4), total = o_dt + align256(cells2);
-      if (hipMalloc(&g->block, total) != hipSuccess) { (void)hipGetLastError(); return set_error(c, MVR_E_NOMEM, "grid build: out of device memory"); }
-      g->dir = reinterpret_cast<uint32_t *>(g->block + o_dir); g->recs = reinterpret_cast<uint32_t *>(g->block + o_recs);
-      g->gperm = reinterpret_cast<uint32_t *>(g->block + o_gperm); g->graw = reinterpret_cast<float4 *>(g->block + o_graw);
-      g->g2h = reinterpret_cast<uint32_t *>(g->block + o_g2h); g->h2g = reinterpret_cast<uint32_t *>(g->block + o_h2g); g->dt = reinterpret_cast<uint8_t *>(g->block + o_dt);
-      const int steps2 = (int)std::ceil(std::max(0.0, reach) / (2.0 * h)) + 2;      // in cubes of two cells
-      g->dt_steps = std::min(kGridDtMax, std::max(2, steps2));
-      gs[(size_t)k] = g;
-      continue;
-    }
-    const size_t o_start = 0, o_gperm = o_start + align256((cells + 1 + kStartPad) * 4), o_graw = o_gperm + align256(n * 4), o_g2h = o_graw + align256(n * sizeof(float4)),
-                 o_h2g = o_g2h + align256(n * 4), o_dt = o_h2g + align256(n * 4), total = o_dt + align256(cells);
-    if (hipMalloc(&g->block, total) != hipSuccess) { (void)hipGetLastError(); return set_error(c, MVR_E_NOMEM, "grid build: out of device memory"); }
-    g->start = reinterpret_cast<uint32_t *>(g->block + o_start); g->gperm = reinterpret_cast<uint32_t *>(g->block + o_gperm);
-    g->graw = reinterpret_cast<float4 *>(g->block + o_graw); g->g2h = reinterpret_cast<uint32_t *>(g->block + o_g2h);
-    g->h2g = reinterpret_cast<uint32_t *>(g->block + o_h2g); g->dt = reinterpret_cast<uint8_t *>(g->block + o_dt);
-    for (int j = 0; j < 3; ++j) g->dtdim[j] = g->dim[j];
-    int steps = (int)std::ceil(std::max(0.0, reach) / h) + 2;       // enough to rule out `reach` (dt - 1 cell edges > reach + a cell), at most kGridDtMax
-    g->dt_steps = std::min(kGridDtMax, std::max(2, steps));
+    // the cell starts: the DENSE table (the default; one entry per lookup: 8-11 % faster walks) or the COMPACT one -- segment
+    // directory + a record per occupied segment (at most one per point, at most one per segment), a tenth of the bytes.  Either
+    // way built through the compact form in build_compact_grids (the sort of all scans at once, the records, the distance map
+    // per 2 x 2 x 2 cells), which expands a dense grid's table by one streaming launch.
+    const bool dense = c->grid_index == 2;
+    g->nseg = (uint32_t)((cells + 1 + 31) / 32);
+    for (int j = 0; j < 3; ++j) g->dtdim[j] = (g->dim[j] + 1) >> 1;
+    const GridBlockLayout l = grid_block_layout(n, cells, (size_t)g->dtdim[0] * g->dtdim[1] * g->dtdim[2], g->nseg, dense ? kGridBlockDense : kGridBlockCompact);
+    if (hipMalloc(&g->block, l.total) != hipSuccess) { (void)hipGetLastError(); return set_error(c, MVR_E_NOMEM, "grid build: out of device memory"); }
+    if (dense) g->start = reinterpret_cast<uint32_t *>(g->block + l.start);
+    else { g->dir = reinterpret_cast<uint32_t *>(g->block + l.dir); g->recs = reinterpret_cast<uint32_t *>(g->block + l.recs); }
+    g->gperm = reinterpret_cast<uint32_t *>(g->block + l.gperm); g->graw = reinterpret_cast<float4 *>(g->block + l.graw);
+    g->g2h = reinterpret_cast<uint32_t *>(g->block + l.g2h); g->h2g = reinterpret_cast<uint32_t *>(g->block + l.h2g); g->dt = reinterpret_cast<uint8_t *>(g->block + l.dt);
+    // enough dilation steps, in cubes of two cells, to rule out `reach` (dt - 1 cube edges > reach + a cube), at most kGridDtMax
+    const int steps2 = (int)std::ceil(std::max(0.0, reach) / (2.0 * h)) + 2;
+    g->dt_steps = std::min(kGridDtMax, std::max(2, steps2));
     gs[(size_t)k] = g;
   }
   host_mark("    grids: allocated");
-  {   // the compact grids: all of them together
-    std::vector<Cloud *> cc; std::vector<std::shared_ptr<CellGrid> > cg;
-    for (int k = 0; k < m; ++k) if (gs[(size_t)k]->dir || gs[(size_t)k]->via_compact) { cc.push_back(todo[(size_t)k]); cg.push_back(gs[(size_t)k]); }
-    if (!cc.empty()) {
-      if (int rc = build_compact_grids(c, cc, cg, on)) return rc;
-      hipEvent_t ev = nullptr;          // (one event for the batch: every grid of it is ready behind it)
-      for (size_t k = 0; k < cc.size(); ++k) {
-        if (side) {
-          MVR_HIP_TRY(c, hipEventCreateWithFlags(&cg[k]->ready, hipEventDisableTiming));
-          MVR_HIP_TRY(c, hipEventRecord(cg[k]->ready, on));
-        }
-        cc[k]->grid = cg[k];
-        c->grids[cc[k]->set_id] = cg[k];
-      }
-      (void)ev;
-    }
-  }
-  // ---- temporaries: cell ids (two buffers for the sort), indices, the distance map's second buffer, hipCUB's scratch
-  (void)cells_max;
-  uint32_t *cid_a = reinterpret_cast<uint32_t *>(c->scratch + o_cid_a), *cid_b = reinterpret_cast<uint32_t *>(c->scratch + o_cid_b),
-           *idx_a = reinterpret_cast<uint32_t *>(c->scratch + o_idx);
-  uint8_t *dt_tmp = reinterpret_cast<uint8_t *>(c->scratch + o_dtt);
-  void *cub = c->scratch + o_cub;
+  if (int rc = build_compact_grids(c, todo, gs, on)) return rc;
   for (int k = 0; k < m; ++k) {
-    if (gs[(size_t)k]->dir || gs[(size_t)k]->via_compact) continue;
-    Cloud &cl = *todo[(size_t)k];
-    CellGrid &g = *gs[(size_t)k];
-    const size_t n = g.n, cells = (size_t)g.dim[0] * g.dim[1] * g.dim[2];
-    GridGeom gg;
-    for (int j = 0; j < 3; ++j) { gg.lo[j] = g.lo[j]; gg.dim[j] = g.dim[j]; }
-    gg.inv_h = g.inv_h;
-    const unsigned nb = (unsigned)((n + 255) / 256), cb = (unsigned)((cells + 255) / 256);
-    hipLaunchKernelGGL(cell_id_kernel, dim3(nb), dim3(256), 0, on, cl.pts, n, gg, cid_a, idx_a);
-    int bits = 1;
-    while (((size_t)1 << bits) < cells) ++bits;
-    size_t b1 = cub_bytes;
-    MVR_HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(cub, b1, cid_a, cid_b, idx_a, g.gperm, (int)n, 0, bits, on));
-    MVR_HIP_TRY(c, hipMemsetAsync(g.start, 0xFF, (cells + 1 + kStartPad) * 4, on));
-    hipLaunchKernelGGL(cell_first_kernel, dim3(nb), dim3(256), 0, on, cid_b, n, cells, g.start);
-    auto rit = thrust_like_reverse(g.start, cells + 1);
-    size_t b2 = cub_bytes;
-    MVR_HIP_TRY(c, hipcub::DeviceScan::InclusiveScan(cub, b2, rit, rit, MinU32(), (int)(cells + 1), on));
-    hipLaunchKernelGGL(pad_start_kernel, dim3(1), dim3(64), 0, on, g.start, cells, (uint32_t)n);
-    hipLaunchKernelGGL(grid_gather_kernel, dim3(nb), dim3(256), 0, on, cl.pts, g.gperm, n, g.graw);
-    hipLaunchKernelGGL(dt_occupancy_kernel, dim3(cb), dim3(256), 0, on, g.start, cells, dt_tmp);
-    hipLaunchKernelGGL(dt_axis_kernel, dim3(cb), dim3(256), 0, on, dt_tmp, g.dt, g.dim[0], g.dim[1], g.dim[2], 0, g.dt_steps);
-    hipLaunchKernelGGL(dt_axis_kernel, dim3(cb), dim3(256), 0, on, g.dt, dt_tmp, g.dim[0], g.dim[1], g.dim[2], 1, g.dt_steps);
-    hipLaunchKernelGGL(dt_axis_kernel, dim3(cb), dim3(256), 0, on, dt_tmp, g.dt, g.dim[0], g.dim[1], g.dim[2], 2, g.dt_steps);
-    MVR_HIP_TRY(c, hipGetLastError());
     if (side) {               // whoever uses the grid first on another stream waits for this
-      MVR_HIP_TRY(c, hipEventCreateWithFlags(&g.ready, hipEventDisableTiming));
-      MVR_HIP_TRY(c, hipEventRecord(g.ready, on));
+      MVR_HIP_TRY(c, hipEventCreateWithFlags(&gs[(size_t)k]->ready, hipEventDisableTiming));
+      MVR_HIP_TRY(c, hipEventRecord(gs[(size_t)k]->ready, on));
     }
-    cl.grid = gs[(size_t)k];
-    c->grids[cl.set_id] = gs[(size_t)k];
+    todo[(size_t)k]->grid = gs[(size_t)k];
+    c->grids[todo[(size_t)k]->set_id] = gs[(size_t)k];
   }
   for (auto i2 = c->grids.begin(); i2 != c->grids.end();) i2 = i2->second.expired() ? c->grids.erase(i2) : std::next(i2);
   host_mark("    grids: builds enqueued");
@@ -1305,15 +1113,12 @@ int ensure_model_grid(Ctx *c, Cloud &t, bool *ok, bool *no_finite)
   g->h = sz.h; g->inv_h = sz.inv_h;
   const size_t cells = (size_t)g->dim[0] * g->dim[1] * g->dim[2], n = t.n;
   g->nseg = (uint32_t)((cells + 1 + 31) / 32);
-  g->dt_shift = 1;
   for (int j = 0; j < 3; ++j) g->dtdim[j] = (g->dim[j] + 1) >> 1;
-  const size_t cells2 = (size_t)g->dtdim[0] * g->dtdim[1] * g->dtdim[2], max_slots = std::min(n, (size_t)g->nseg + 1) + 1;
-  const size_t o_dir = 0, o_recs = o_dir + align256(((size_t)g->nseg + 2) * 4), o_gperm = o_recs + align256(max_slots * 32 * 4), o_graw = o_gperm + align256(n * 4),
-               o_dt = o_graw + align256((n + 4) * sizeof(float4)), total = o_dt + align256(cells2);
-  if (hipMalloc(&g->block, total) != hipSuccess) { (void)hipGetLastError(); return set_error(c, MVR_E_NOMEM, "model grid: out of device memory"); }
-  g->dir = reinterpret_cast<uint32_t *>(g->block + o_dir); g->recs = reinterpret_cast<uint32_t *>(g->block + o_recs);
-  g->gperm = reinterpret_cast<uint32_t *>(g->block + o_gperm); g->graw = reinterpret_cast<float4 *>(g->block + o_graw);
-  g->dt = reinterpret_cast<uint8_t *>(g->block + o_dt);
+  const GridBlockLayout l = grid_block_layout(n, cells, (size_t)g->dtdim[0] * g->dtdim[1] * g->dtdim[2], g->nseg, kGridBlockModel);
+  if (hipMalloc(&g->block, l.total) != hipSuccess) { (void)hipGetLastError(); return set_error(c, MVR_E_NOMEM, "model grid: out of device memory"); }
+  g->dir = reinterpret_cast<uint32_t *>(g->block + l.dir); g->recs = reinterpret_cast<uint32_t *>(g->block + l.recs);
+  g->gperm = reinterpret_cast<uint32_t *>(g->block + l.gperm); g->graw = reinterpret_cast<float4 *>(g->block + l.graw);
+  g->dt = reinterpret_cast<uint8_t *>(g->block + l.dt);
   g->dt_steps = 2;
   std::vector<Cloud *> cc{&t}; std::vector<std::shared_ptr<CellGrid> > cg{g};
   if (int rc = build_compact_grids(c, cc, cg, c->stream)) return rc;
@@ -1403,7 +1208,7 @@ GridPair make_grid_pair(const Cloud &q, size_t q_begin, size_t q_count, const Cl
   GridPair p;
   const CellGrid &g = *t.grid;
   p.qs = q.sorted; p.q_begin = (uint32_t)q_begin; p.q_count = (uint32_t)q_count;
-  p.gts = t.gsorted; p.ts = t.sorted; p.start = g.start; p.dir = g.dir; p.recs = g.recs; p.dt_shift = g.dt_shift; for (int k = 0; k < 3; ++k) p.dtdim[k] = g.dtdim[k]; p.dt = g.dt; p.g2h = g.g2h; p.h2g = g.h2g; p.tinv = t.order ? t.order->inv : nullptr; p.dt_max = g.dt_steps;
+  p.gts = t.gsorted; p.ts = t.sorted; p.start = g.start; p.dir = g.dir; p.recs = g.recs; for (int k = 0; k < 3; ++k) p.dtdim[k] = g.dtdim[k]; p.dt = g.dt; p.g2h = g.g2h; p.h2g = g.h2g; p.tinv = t.order ? t.order->inv : nullptr; p.dt_max = g.dt_steps;
   p.stretch = std::nextafterf((float)(t.pose_stretch * (1.0 + 1e-6)), INFINITY);      // (the ball is in posed space, the cells in the canonical frame)
   for (int k = 0; k < 3; ++k) { p.lo[k] = g.lo[k]; p.dim[k] = g.dim[k]; }
   p.inv_h = g.inv_h; p.h = g.h;

@@ -1,6 +1,7 @@
 // csrc/mvr_grid_size.h -- the sizing of a cloud's own grid (ensure_model_grid, mvr_grid.hip): bounding box and point count in;
-// origin, cell edge and cells per axis out.  Plain host C++ with no GPU header, so tests/cxx/grid_size_driver.cpp compiles it
-// alone under the sanitizers.  Not installed.
+// origin, cell edge and cells per axis out; and the layout of the device block every grid's arrays are carved out of
+// (ensure_grids, ensure_model_grid).  Plain host C++ with no GPU header, so tests/cxx/grid_size_driver.cpp compiles it alone
+// under the sanitizers.  Not installed.
 #pragma once
 
 #include <algorithm>
@@ -56,6 +57,38 @@ inline ModelGridStatus model_grid_size(const float bb[6], size_t n, int cell_poi
   out->h64 = h; out->h = (float)h; out->inv_h = (float)(1.0 / h);
   out->cells = (size_t)out->dim[0] * (size_t)out->dim[1] * (size_t)out->dim[2];
   return kModelGridOk;
+}
+
+// ---- where the arrays of a grid lie in its ONE device block (CellGrid::block): byte offsets, each a multiple of 256, in
+// ascending order, and the block's size.  A scan's grid keeps its cell starts as the dense table or as the compact one
+// (directory + records) and carries the maps between grid order and Hilbert order; a cloud's own grid (ensure_model_grid) is
+// compact, holds four points more (its walks read four at a time) and has no Hilbert maps.
+enum GridBlockForm { kGridBlockDense, kGridBlockCompact, kGridBlockModel };
+// the eight entries behind start[cells] (the walk reads four consecutive starts with one load, the staged walk eight with two): all n
+constexpr size_t kStartPad = 8;
+constexpr size_t kGridBlockNone = ~(size_t)0;      // the form has no such array
+struct GridBlockLayout {
+  size_t start, dir, recs;       // uint32 [cells + 1 + kStartPad] | [nseg + 2], [32 x (min(n, nseg + 1) + 1)]
+  size_t gperm, graw;            // uint32 [n], float4 [n] (model: [n + 4])
+  size_t g2h, h2g;               // uint32 [n] each (scan grids)
+  size_t dt;                     // uint8 [cells2]: the distance map per 2 x 2 x 2 cells
+  size_t total;
+};
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+inline GridBlockLayout grid_block_layout(size_t n, size_t cells, size_t cells2, size_t nseg, GridBlockForm form)
+{
+  GridBlockLayout l;
+  size_t at = 0;
+  auto take = [&at](size_t bytes) { const size_t o = at; at += align256(bytes); return o; };
+  l.start = l.dir = l.recs = l.g2h = l.h2g = kGridBlockNone;
+  if (form == kGridBlockDense) l.start = take((cells + 1 + kStartPad) * 4);
+  else { l.dir = take((nseg + 2) * 4); l.recs = take((std::min(n, nseg + 1) + 1) * 32 * 4); }
+  l.gperm = take(n * 4);
+  l.graw = take((form == kGridBlockModel ? n + 4 : n) * 16);
+  if (form != kGridBlockModel) { l.g2h = take(n * 4); l.h2g = take(n * 4); }
+  l.dt = take(cells2);
+  l.total = at;
+  return l;
 }
 
 }  // namespace mvr

@@ -605,24 +605,7 @@ struct OrderBatchArgs { const float4 *pts[kBatchClouds]; unsigned long long n[kB
 __global__ void bbox_many_kernel(OrderBatchArgs a, float *__restrict__ part /* [cloud][64 blocks][6] */)
 {
   const int cl = blockIdx.y;
-  const float4 *p = a.pts[cl];
-  const size_t cnt = (size_t)a.n[cl];
-  float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (size_t)gridDim.x * blockDim.x) {
-    const float4 v = p[i];
-    lo[0] = fminf(lo[0], v.x); lo[1] = fminf(lo[1], v.y); lo[2] = fminf(lo[2], v.z);
-    hi[0] = fmaxf(hi[0], v.x); hi[1] = fmaxf(hi[1], v.y); hi[2] = fmaxf(hi[2], v.z);
-  }
-  __shared__ float sh[4][6];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], __shfl_xor(lo[k], o, 64)); hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], o, 64)); }
-  if ((threadIdx.x & 63) == 0) for (int k = 0; k < 3; ++k) { sh[threadIdx.x >> 6][k] = lo[k]; sh[threadIdx.x >> 6][3 + k] = hi[k]; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) for (int k = 0; k < 3; ++k) { sh[0][k] = fminf(sh[0][k], sh[w][k]); sh[0][3 + k] = fmaxf(sh[0][3 + k], sh[w][3 + k]); }
-    for (int k = 0; k < 6; ++k) part[((size_t)cl * gridDim.x + blockIdx.x) * 6 + k] = sh[0][k];
-  }
+  bbox_block_partial(a.pts[cl], (size_t)a.n[cl], part + ((size_t)cl * gridDim.x + blockIdx.x) * 6);
 }
 // codes of all clouds: the bounding box of a cloud from its 64 partial rows (every block folds them itself: 384 floats from the L2),
 // then exactly morton_kernel's arithmetic

@@ -66,21 +66,23 @@ struct Order {
 // their cells.  A search in a posed copy maps the query into the canonical frame (inverse of the copy's pose), walks the
 // cells its search ball overlaps, and evaluates the candidates in the POSED frame (same float arithmetic as every other
 // search kernel: bit-identical distances).  See mvr_grid.hip.
+constexpr int kDtShift = 1;            // a grid's distance map is kept per cube of 2 x 2 x 2 cells: an eighth of the bytes and of the build
 struct CellGrid {
   size_t n = 0;
   float lo[3] = {0, 0, 0};
   float h = 1.f, inv_h = 1.f;            // cell edge
   int dim[3] = {1, 1, 1};                // cells per axis; cell id = (z * dim[1] + y) * dim[0] + x
-  uint32_t *start = nullptr;             // [cells + 1] first grid position of every cell (points sorted by cell id)
-  // COMPACT form of the same table (round 4; `start` is then null): the cell ids are cut into segments of 32 consecutive ids; an
-  // occupied segment has a record of its 32 starts in recs[], an empty one -- all its cells begin at the same position -- is the
-  // directory entry itself: dir[seg] = slot | 0x80000000 or that position.  A 200k-point scan occupies ~1/20 of its 375k segments:
-  // 1.5 MB of directory + 2.5 MB of records instead of 48 MB of which a walk touched a 128-byte line per row for three entries.
+  // Where a cell's points begin, in ONE of two forms (the tune key grid_index; both built by build_compact_grids, same walks' results):
+  // DENSE (the default): start[c] = first grid position of cell c (points sorted by cell id), start[cells] = n, kStartPad more
+  // entries of n behind it; dir and recs are null.
+  // COMPACT (`start` is then null): the cell ids are cut into segments of 32 consecutive ids; an occupied segment has a record of
+  // its 32 starts in recs[], an empty one -- all its cells begin at the same position -- is the directory entry itself:
+  // dir[seg] = slot | 0x80000000 or that position.  A 200k-point scan occupies ~1/20 of its 375k segments: 1.5 MB of directory +
+  // 2.5 MB of records instead of 48 MB of which a walk touched a 128-byte line per row for three entries.
+  uint32_t *start = nullptr;
   uint32_t *dir = nullptr, *recs = nullptr;
   uint32_t nseg = 0;
-  bool via_compact = false;              // a DENSE table that was built through the compact form and expanded (the default)
-  int dt_shift = 0;                      // the distance map is kept per cube of 2^dt_shift cells per axis (compact form: 1 -- an eighth of the bytes and of the build)
-  int dtdim[3] = {1, 1, 1};              // its dimensions
+  int dtdim[3] = {1, 1, 1};              // the distance map's dimensions: one byte per cube of 2^kDtShift cells per axis
   uint32_t *gperm = nullptr;             // [n] grid position -> original index
   float4 *graw = nullptr;                // [n] canonical coordinates in grid order, w = bits(original index)
   uint32_t *g2h = nullptr;               // [n] grid position -> position in the set's Hilbert ordering (what the fused pass's keys carry)
@@ -88,8 +90,8 @@ struct CellGrid {
   char *block = nullptr;                 // the ONE device allocation the arrays below are carved out of
   hipEvent_t ready = nullptr;            // set when the grid was built on the context's side stream: recorded behind its last build kernel
   bool ready_waited = false;             // ... and the context's main stream has been made to wait for it
-  uint8_t *dt = nullptr;                 // [cells] Chebyshev distance, in cells, to the nearest occupied cell (0 = occupied, 255 = farther than dt_steps): "is there any point near here at all" in ONE byte
-  int dt_steps = 0;                      // dilation steps dt was built with: 255 means "farther than dt_steps cells"
+  uint8_t *dt = nullptr;                 // [cubes] Chebyshev distance, in cubes, to the nearest occupied cube (0 = occupied, 255 = farther than dt_steps): "is there any point near here at all" in ONE byte
+  int dt_steps = 0;                      // dilation steps dt was built with: 255 means "farther than dt_steps cubes"
   const Order *built_for = nullptr;      // the ordering g2h refers to
   ~CellGrid();
 };
@@ -284,7 +286,7 @@ struct Ctx {
   nnkey_t *brkeys = nullptr; size_t brkeys_cap = 0;
   uint32_t *bwide = nullptr; size_t bwide_cap = 0;       // [sources + targets of all pairs] grid search: ordinals of the wide bounded queries
   int grid_cell_points = 4;                              // points per occupied cell the grid's cell edge aims at (grids built from then on)
-  int grid_index = 2;                                    // a grid's cell-start table (grids built from then on): 2 (default) = DENSE, built through the compact form (all scans sorted at once, distance map per 2 x 2 x 2 cells) and expanded; 1 = COMPACT (segment directory + records of the occupied segments: a tenth of the bytes, walks 8-11 % slower); 0 = dense by the round-3 build (a sort, a scan over all cells and a per-cell distance map per grid)
+  int grid_index = 2;                                    // a grid's cell-start table (grids built from then on): 2 (default) = DENSE, built through the compact form (all scans sorted at once, distance map per 2 x 2 x 2 cells) and expanded; 1 = COMPACT (segment directory + records of the occupied segments: a tenth of the bytes, walks 8-11 % slower)
   // the STAGED walk (mvr_grid.hip): a wave of the one-lane-per-query walk copies the box of its lanes' cells into LDS with a few
   // coalesced loads and every lane walks its own cells there -- the walk is bound by the number of vector memory instructions a
   // wave issues, not by bytes.  0: the plain walk; 1 (default): launches over a scan's own query order (the forward searches); 2: every
@@ -443,6 +445,28 @@ __host__ __device__ inline uint32_t prerej_draw(uint64_t seed, uint64_t i, uint6
 
 inline unsigned blocks_for(size_t n, int threads) { return (unsigned)((n + (size_t)threads - 1) / (size_t)threads); }
 __device__ __forceinline__ bool finite3(const float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
+
+// one block's share of a cloud's bounding box: row[6] = {lo xyz, hi xyz} over the points this block of 256 threads strides over
+// (the block of the bounding-box launches of the batched builds, blockIdx.x of gridDim.x per cloud: mvr_grid.hip, mvr_index.hip)
+__device__ __forceinline__ void bbox_block_partial(const float4 *__restrict__ p, size_t cnt, float *__restrict__ row)
+{
+  float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (size_t)gridDim.x * blockDim.x) {
+    const float4 v = p[i];
+    lo[0] = fminf(lo[0], v.x); lo[1] = fminf(lo[1], v.y); lo[2] = fminf(lo[2], v.z);
+    hi[0] = fmaxf(hi[0], v.x); hi[1] = fmaxf(hi[1], v.y); hi[2] = fmaxf(hi[2], v.z);
+  }
+  __shared__ float sh[4][6];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+    for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], __shfl_xor(lo[k], o, 64)); hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], o, 64)); }
+  if ((threadIdx.x & 63) == 0) for (int k = 0; k < 3; ++k) { sh[threadIdx.x >> 6][k] = lo[k]; sh[threadIdx.x >> 6][3 + k] = hi[k]; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) for (int k = 0; k < 3; ++k) { sh[0][k] = fminf(sh[0][k], sh[w][k]); sh[0][3 + k] = fmaxf(sh[0][3 + k], sh[w][3 + k]); }
+    for (int k = 0; k < 6; ++k) row[k] = sh[0][k];
+  }
+}
 
 // several clouds per launch (kernel arguments by value)
 constexpr int kBatchClouds = 16;
@@ -624,7 +648,7 @@ struct GridPair {
   const float4 *ts = nullptr;                 // target in Hilbert order (only to price the seed: the previous match's position)
   const uint32_t *start = nullptr, *g2h = nullptr, *h2g = nullptr, *tinv = nullptr;      // (tinv: original index -> Hilbert position in the searched cloud)
   const uint32_t *dir = nullptr, *recs = nullptr;      // the compact form of the cell starts (CellGrid): used when dir is set
-  int dt_shift = 0, dtdim[3] = {1, 1, 1};
+  int dtdim[3] = {1, 1, 1};
   const uint8_t *dt = nullptr;
   float lo[3] = {0, 0, 0}, inv_h = 1.f, h = 1.f;
   int dim[3] = {1, 1, 1};

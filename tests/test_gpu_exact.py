@@ -177,7 +177,7 @@ def test_sequential_align_over_the_source_grid_equals_the_culled_search(mvr, orc
     different sizes and with a radius ten times as wide (wide balls leave the thread-per-query walk).  The forward
     searches' seeds, the iteration row's two ways to the host and the native driver change nothing either.  The tune keys of
     the forward searches that were removed (seq_search 2 and 3 and their knobs; the ring walk's grid_lanes, seed_delta_um and
-    rim_cert_um) are refused.  The first align's
+    rim_cert_um; grid_index 0, the round-3 grid build) are refused, grid_index 1 and 2 accepted.  The first align's
     correspondences equal the oracle's."""
     V, N, max_d = 8, 9000, 4.0
     sp = mvr.synth_params(V, 3)
@@ -234,10 +234,12 @@ def test_sequential_align_over_the_source_grid_equals_the_culled_search(mvr, orc
     # ... and against the oracle: the first align's correspondences, one by one
     with mvr.Context(0) as ctx:
         for gone in (dict(seq_search=2), dict(seq_search=3), dict(seq_model_tail=0), dict(parts_lanes=4), dict(parts_max_rows=8),
-                     dict(grid_lanes=4), dict(seed_delta_um=50), dict(rim_cert_um=200)):
+                     dict(grid_lanes=4), dict(seed_delta_um=50), dict(rim_cert_um=200), dict(grid_index=0)):
             with pytest.raises(mvr.MvrError) as refused:
                 ctx.tune(**gone)
             assert refused.value.status == mvr.E_ARG, gone
+        for kept in (1, 2):      # (the two forms of the cell-start table that remain; 2 is the default)
+            ctx.tune(grid_index=kept)
         for v in range(V):
             ctx.upload(16 + v, scans[v])
         ctx.transform(0, 16, poses0[0]); ctx.transform(1, 17, poses0[1])

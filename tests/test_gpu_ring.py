@@ -245,7 +245,7 @@ def test_grid_search_equals_culled_search_over_passes(mvr, orc):
     dict(pipeline=0), dict(pipeline=0, grid_index=1),
     # the compact cell-start tables (round 4): forced for these small grids, with the staged walk everywhere, with tiny / huge cells, dense forced
     dict(grid_index=1), dict(grid_index=1, grid_stage=2), dict(grid_index=1, grid_cell_points=1), dict(grid_index=1, grid_cell_points=40, grid_light_rows=64, grid_probe=0),
-    dict(grid_index=1, grid_stage=0), dict(grid_index=1, grid_sets=2, grid_light_rows=1, grid_cluster=1), dict(grid_index=0),
+    dict(grid_index=1, grid_stage=0), dict(grid_index=1, grid_sets=2, grid_light_rows=1, grid_cluster=1),
     dict(grid_stage=2, grid_light_rows=64, grid_probe=0), dict(grid_stage=1, grid_cell_points=2, grid_light_rows=64, grid_probe=0), dict(grid_stage=2, grid_cell_points=12, grid_wide=0),
 ], ids=lambda k: ",".join("%s=%s" % kv for kv in k.items()))
 def test_grid_search_knobs_never_show_in_a_result(mvr, knobs):

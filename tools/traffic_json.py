@@ -83,7 +83,7 @@ out = {
                         "reports for one-line-per-lane gathers, the walk's dominant access: the truth lies between the uncorrected and the doubled figure",
     "per_step_note": ("more than 12 pairs: the launches of a step are summed and halved -- forward / reverse figures are the per-step mean of both" if V > 12 else None),
     "hbm_bytes_per_step": fwd + rev,
-    "kernel": ("nn_grid_kernel<false,false> (exact grid walk of the bounded queries, fused launch over the %d scan pairs of a ring step)" if GRID else
+    "kernel": ("nn_grid_kernel<false,true> (exact grid walk of the bounded queries, staged: what the forward and the reverse launches run by default; fused launch over the %d scan pairs of a ring step)" if GRID else
                "nn_cull_kernel<false,1,1> (exact culled NN, fused launch over the %d scan pairs of a ring step)") % V,
     "source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE in separate passes over tools/step_probe.py %d %d %d %d, MVR_PAIR_GROUPS=1 "
               "(tools/measure_traffic.sh); mean over the %d timed steps" % (V, N, STEPS, WARM, STEPS),
