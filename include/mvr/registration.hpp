@@ -17,8 +17,11 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
+#include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../mvr_hip.h"
@@ -80,6 +83,216 @@ struct SlotGuard {
   SlotGuard &operator=(const SlotGuard &) = delete;
 };
 
+// ---- clouds whose points carry normals (PointNormal): the points go up as 16-byte x, y, z, 1 and the normals beside them
+namespace detail {
+template <typename P> auto has_normal_test(int) -> decltype((void)std::declval<P>().normal_x, std::true_type());
+template <typename P> std::false_type has_normal_test(...);
+template <typename P> struct has_normal : decltype(has_normal_test<P>(0)) {};
+
+template <typename PointT>
+void upload_cloud(Device &d, int slot, const PointCloud<PointT> &c, std::false_type) { d.upload(slot, c); }
+template <typename PointT>
+void upload_cloud(Device &d, int slot, const PointCloud<PointT> &c, std::true_type)
+{
+  const size_t n = c.size();
+  std::vector<float> xyz(4 * n), nrm(4 * n);
+  for (size_t i = 0; i < n; ++i) {
+    const PointT &q = c.points[i];
+    xyz[4 * i] = q.x; xyz[4 * i + 1] = q.y; xyz[4 * i + 2] = q.z; xyz[4 * i + 3] = 1.f;
+    nrm[4 * i] = q.normal_x; nrm[4 * i + 1] = q.normal_y; nrm[4 * i + 2] = q.normal_z; nrm[4 * i + 3] = 0.f;
+  }
+  d.check(mvr_cloud_upload(d.ctx(), slot, n ? xyz.data() : nullptr, n, 16), "mvr_cloud_upload");
+  d.check(mvr_cloud_upload_normals(d.ctx(), slot, n ? nrm.data() : nullptr, n, 16), "mvr_cloud_upload_normals");
+}
+template <typename PointT>
+void upload_cloud(Device &d, int slot, const PointCloud<PointT> &c) { upload_cloud(d, slot, c, has_normal<PointT>()); }
+
+template <typename PointT>
+void download_cloud(Device &d, int slot, PointCloud<PointT> &c, std::false_type) { d.download(slot, c); }
+// (the cloud keeps whatever else its points hold: the caller sized it from the input)
+template <typename PointT>
+void download_cloud(Device &d, int slot, PointCloud<PointT> &c, std::true_type)
+{
+  size_t n = 0, got = 0;
+  d.check(mvr_cloud_size(d.ctx(), slot, &n), "mvr_cloud_size");
+  c.resize(n);
+  if (!n) return;
+  std::vector<float> xyz(4 * n), nrm(4 * n, 0.f);
+  d.check(mvr_cloud_download(d.ctx(), slot, xyz.data(), n, 16, &got), "mvr_cloud_download");
+  d.check(mvr_cloud_download_normals(d.ctx(), slot, nrm.data(), n, 16, &got), "mvr_cloud_download_normals");
+  for (size_t i = 0; i < n; ++i) {
+    PointT &q = c.points[i];
+    q.x = xyz[4 * i]; q.y = xyz[4 * i + 1]; q.z = xyz[4 * i + 2];
+    if (got == n) { q.normal_x = nrm[4 * i]; q.normal_y = nrm[4 * i + 1]; q.normal_z = nrm[4 * i + 2]; }
+  }
+}
+template <typename PointT>
+void download_cloud(Device &d, int slot, PointCloud<PointT> &c) { download_cloud(d, slot, c, has_normal<PointT>()); }
+}  // namespace detail
+
+// ---------------------------------------------------------------- correspondence rejectors
+// pcl::registration::CorrespondenceRejector and the five rejectors of mvr_hip.h (rules R1-R10 at
+// mvr_correspondences_rejected).  A rejector is a parameter record: added to an IterativeClosestPoint
+// (addCorrespondenceRejector) it becomes a stage of the chain that mvr_icp_align_rejected runs on the GPU between the search
+// and the estimator of every iteration; on its own, with setInputCorrespondences, getCorrespondences runs
+// mvr_reject_correspondences on the list.  Survivors come in ascending query index.
+namespace registration {
+
+class CorrespondenceRejector {
+ public:
+  typedef std::shared_ptr<CorrespondenceRejector> Ptr;
+  typedef std::shared_ptr<const CorrespondenceRejector> ConstPtr;
+  virtual ~CorrespondenceRejector() {}
+  virtual void setInputCorrespondences(const CorrespondencesConstPtr &c) { input_correspondences_ = c; }
+  CorrespondencesConstPtr getInputCorrespondences() { return input_correspondences_; }
+  void getCorrespondences(Correspondences &out)
+  {
+    out.clear();
+    if (!input_correspondences_ || input_correspondences_->empty()) return;
+    getRemainingCorrespondences(*input_correspondences_, out);
+  }
+  virtual void getRemainingCorrespondences(const Correspondences &original, Correspondences &remaining)
+  {
+    Device &d = Device::instance();
+    const size_t n = original.size();
+    std::vector<int32_t> q(n), m(n), qo(n), mo(n);
+    std::vector<float> dd(n), dout(n);
+    size_t ns = 0, nt = 0, kept = 0;
+    for (size_t k = 0; k < n; ++k) {
+      q[k] = original[k].index_query; m[k] = original[k].index_match; dd[k] = original[k].distance;
+      if (q[k] >= 0) ns = std::max(ns, (size_t)q[k] + 1);
+      if (m[k] >= 0) nt = std::max(nt, (size_t)m[k] + 1);
+    }
+    SlotGuard s, t;
+    prepareSlots(d, s.s, t.s, ns, nt);
+    const mvr_rejector r = stage();
+    mvr_rejector_stage st = mvr_rejector_stage();
+    remaining.clear();
+    const int rc = mvr_reject_correspondences(d.ctx(), s.s, t.s, q.data(), m.data(), dd.data(), n, &r, 1, qo.data(), mo.data(), dout.data(), n, &kept, &st);
+    if (rc == MVR_E_ARG) {
+      std::fprintf(stderr, "[pcl::registration::%s::getRemainingCorrespondences] %s\n", getClassName().c_str(), mvr_last_error(d.ctx()));
+      return;
+    }
+    d.check(rc, "mvr_reject_correspondences");
+    remaining.resize(kept);
+    for (size_t k = 0; k < kept; ++k) remaining[k] = Correspondence(qo[k], mo[k], dout[k]);
+    noteStage(st);
+  }
+  const std::string &getClassName() const { return rejection_name_; }
+  // ours: the stage of the C-ABI chain this rejector stands for, and what the last run of that stage reported
+  virtual mvr_rejector stage() const = 0;
+  virtual void noteStage(const mvr_rejector_stage &) {}
+
+ protected:
+  // the list's slots: only their sizes matter (R8), so two clouds of zeros large enough for the indices
+  virtual void prepareSlots(Device &d, int s, int t, size_t ns, size_t nt)
+  {
+    std::vector<float> z(4 * std::max(ns, nt), 0.f);
+    d.check(mvr_cloud_upload(d.ctx(), s, ns ? z.data() : nullptr, ns, 16), "mvr_cloud_upload");
+    d.check(mvr_cloud_upload(d.ctx(), t, nt ? z.data() : nullptr, nt, 16), "mvr_cloud_upload");
+  }
+  std::string rejection_name_;
+  CorrespondencesConstPtr input_correspondences_;
+};
+typedef CorrespondenceRejector::Ptr CorrespondenceRejectorPtr;
+
+class CorrespondenceRejectorDistance : public CorrespondenceRejector {
+ public:
+  typedef std::shared_ptr<CorrespondenceRejectorDistance> Ptr;
+  CorrespondenceRejectorDistance() { rejection_name_ = "CorrespondenceRejectorDistance"; }
+  void setMaximumDistance(float distance) { max_distance_ = distance; }      // (PCL keeps the square; getMaximumDistance returns the root)
+  float getMaximumDistance() const { return max_distance_; }
+  mvr_rejector stage() const override { return mvr_rejector{MVR_REJ_DISTANCE, (double)max_distance_, 0u}; }
+
+ private:
+  float max_distance_ = FLT_MAX;
+};
+
+class CorrespondenceRejectorMedianDistance : public CorrespondenceRejector {
+ public:
+  typedef std::shared_ptr<CorrespondenceRejectorMedianDistance> Ptr;
+  CorrespondenceRejectorMedianDistance() { rejection_name_ = "CorrespondenceRejectorMedianDistance"; }
+  void setMedianFactor(double factor) { factor_ = factor; }
+  double getMedianFactor() const { return factor_; }
+  // the median the last run cut at (of the squared distances the correspondences carry, R3's upper median)
+  double getMedianDistance() const { return median_distance_; }
+  mvr_rejector stage() const override { return mvr_rejector{MVR_REJ_MEDIAN, factor_, 0u}; }
+  void noteStage(const mvr_rejector_stage &st) override { median_distance_ = (double)st.threshold; }
+
+ private:
+  double factor_ = 1.0, median_distance_ = 0.0;
+};
+
+class CorrespondenceRejectorTrimmed : public CorrespondenceRejector {
+ public:
+  typedef std::shared_ptr<CorrespondenceRejectorTrimmed> Ptr;
+  CorrespondenceRejectorTrimmed() { rejection_name_ = "CorrespondenceRejectorTrimmed"; }
+  void setOverlapRatio(float ratio) { overlap_ratio_ = std::min(1.0f, std::max(0.0f, ratio)); }
+  float getOverlapRatio() const { return overlap_ratio_; }
+  void setMinCorrespondences(unsigned int n) { nr_min_correspondences_ = n; }
+  unsigned int getMinCorrespondences() const { return nr_min_correspondences_; }
+  mvr_rejector stage() const override { return mvr_rejector{MVR_REJ_TRIMMED, (double)overlap_ratio_, (uint32_t)nr_min_correspondences_}; }
+
+ private:
+  float overlap_ratio_ = 0.5f;
+  unsigned int nr_min_correspondences_ = 0;
+};
+
+class CorrespondenceRejectorOneToOne : public CorrespondenceRejector {
+ public:
+  typedef std::shared_ptr<CorrespondenceRejectorOneToOne> Ptr;
+  CorrespondenceRejectorOneToOne() { rejection_name_ = "CorrespondenceRejectorOneToOne"; }
+  mvr_rejector stage() const override { return mvr_rejector{MVR_REJ_ONE_TO_ONE, 0.0, 0u}; }
+};
+
+// setThreshold takes a cosine, as in PCL.  In an IterativeClosestPoint the normals are those of the clouds the ICP holds
+// (PointNormal clouds: align uploads them); the data container calls are accepted, and used when the rejector runs on its own.
+class CorrespondenceRejectorSurfaceNormal : public CorrespondenceRejector {
+ public:
+  typedef std::shared_ptr<CorrespondenceRejectorSurfaceNormal> Ptr;
+  CorrespondenceRejectorSurfaceNormal() { rejection_name_ = "CorrespondenceRejectorSurfaceNormal"; }
+  void setThreshold(double threshold) { threshold_ = threshold; }
+  double getThreshold() const { return threshold_; }
+  template <typename PointT, typename NormalT> void initializeDataContainer() {}
+  template <typename PointT> void setInputSource(const typename PointCloud<PointT>::ConstPtr &c) { take(src_xyz_, *c); }
+  template <typename PointT> void setInputTarget(const typename PointCloud<PointT>::ConstPtr &c) { take(tgt_xyz_, *c); }
+  template <typename PointT, typename NormalT> void setInputNormals(const typename PointCloud<NormalT>::ConstPtr &c) { takeNormals(src_nrm_, *c); }
+  template <typename PointT, typename NormalT> void setTargetNormals(const typename PointCloud<NormalT>::ConstPtr &c) { takeNormals(tgt_nrm_, *c); }
+  mvr_rejector stage() const override { return mvr_rejector{MVR_REJ_SURFACE_NORMAL, threshold_, 0u}; }
+
+ protected:
+  void prepareSlots(Device &d, int s, int t, size_t ns, size_t nt) override
+  {
+    one(d, s, src_xyz_, src_nrm_, ns);
+    one(d, t, tgt_xyz_, tgt_nrm_, nt);
+  }
+
+ private:
+  template <typename C> static void take(std::vector<float> &out, const C &c)
+  {
+    out.resize(4 * c.size());
+    for (size_t i = 0; i < c.size(); ++i) { out[4 * i] = c.points[i].x; out[4 * i + 1] = c.points[i].y; out[4 * i + 2] = c.points[i].z; out[4 * i + 3] = 1.f; }
+  }
+  template <typename C> static void takeNormals(std::vector<float> &out, const C &c)
+  {
+    out.resize(4 * c.size());
+    for (size_t i = 0; i < c.size(); ++i) { out[4 * i] = c.points[i].normal_x; out[4 * i + 1] = c.points[i].normal_y; out[4 * i + 2] = c.points[i].normal_z; out[4 * i + 3] = 0.f; }
+  }
+  // the normals decide; points are only there to size the slot (zeros when the caller gave none)
+  static void one(Device &d, int slot, const std::vector<float> &xyz, const std::vector<float> &nrm, size_t need)
+  {
+    const size_t n = std::max(need, nrm.size() / 4);
+    std::vector<float> p(4 * n, 0.f);
+    if (xyz.size() == 4 * n) p = xyz;
+    d.check(mvr_cloud_upload(d.ctx(), slot, n ? p.data() : nullptr, n, 16), "mvr_cloud_upload");
+    if (nrm.size() == 4 * n && n) d.check(mvr_cloud_upload_normals(d.ctx(), slot, nrm.data(), n, 16), "mvr_cloud_upload_normals");
+  }
+  double threshold_ = 1.0;
+  std::vector<float> src_xyz_, tgt_xyz_, src_nrm_, tgt_nrm_;
+};
+
+}  // namespace registration
+
 // ---------------------------------------------------------------- ICP
 template <typename PointSource, typename PointTarget, typename Scalar = float>
 class IterativeClosestPoint {
@@ -113,6 +326,19 @@ class IterativeClosestPoint {
   PointCloudSourcePtr const getInputSource() const { return input_; }
   PointCloudTargetPtr const getInputTarget() const { return target_; }
 
+  // the rejector chain (rules R1-R10 in mvr_hip.h): with at least one rejector align runs mvr_icp_align_rejected, the chain in
+  // the order of the calls; at most MVR_MAX_REJECTORS of them
+  typedef registration::CorrespondenceRejector::Ptr CorrespondenceRejectorPtr;
+  void addCorrespondenceRejector(const CorrespondenceRejectorPtr &rejector) { rejectors_.push_back(rejector); }
+  std::vector<CorrespondenceRejectorPtr> getCorrespondenceRejectors() { return rejectors_; }
+  bool removeCorrespondenceRejector(unsigned int i)
+  {
+    if (i >= rejectors_.size()) return false;
+    rejectors_.erase(rejectors_.begin() + i);
+    return true;
+  }
+  void clearCorrespondenceRejectors() { rejectors_.clear(); }
+
   // align(output): `output` may be the very cloud handed to setInputSource
   // (registrator.cpp:920 `icp_.align(*source_)`): the input is uploaded first.
   void align(PointCloudSource &output)
@@ -121,10 +347,22 @@ class IterativeClosestPoint {
     converged_ = false; final_ = Matrix4::Identity(); stats_ = mvr_icp_stats();
     if (!input_ || !target_) { state_ = MVR_CONV_NO_CORRESPONDENCES; return; }
     // the caller may have mutated either cloud since the last call (:576)
-    d.upload(src_.s, *input_);
-    d.upload(tgt_.s, *target_);
+    detail::upload_cloud(d, src_.s, *input_);
+    detail::upload_cloud(d, tgt_.s, *target_);
     float T[16];
-    const int rc = mvr_icp_align(d.ctx(), src_.s, tgt_.s, out_.s, &p_, T, &stats_);
+    int rc;
+    if (rejectors_.empty()) rc = mvr_icp_align(d.ctx(), src_.s, tgt_.s, out_.s, &p_, T, &stats_);
+    else {
+      if (rejectors_.size() > (size_t)MVR_MAX_REJECTORS) throw Error(MVR_E_ARG, "mvr: more than MVR_MAX_REJECTORS correspondence rejectors");
+      std::vector<mvr_rejector> chain;
+      for (const CorrespondenceRejectorPtr &r : rejectors_) chain.push_back(r->stage());
+      std::vector<mvr_icp_iter_trace> trace((size_t)std::max(1, p_.max_iterations));
+      rc = mvr_icp_align_rejected(d.ctx(), src_.s, tgt_.s, out_.s, &p_, chain.data(), (int)chain.size(), T, &stats_, trace.data(), (int)trace.size());
+      if (rc == MVR_OK || rc == MVR_E_NOCORR) {      // every rejector learns what its stage did in the last iteration
+        const size_t last = std::min(trace.size() - 1, (size_t)std::max(0, stats_.iterations - (rc == MVR_OK ? 1 : 0)));
+        for (size_t k = 0; k < rejectors_.size(); ++k) rejectors_[k]->noteStage(trace[last].stages[k]);
+      }
+    }
     if (rc != MVR_OK && rc != MVR_E_NOCORR) d.check(rc, "mvr_icp_align");
     if (rc == MVR_E_NOCORR)
       std::fprintf(stderr, "[mvr::IterativeClosestPoint::computeTransformation] Not enough correspondences found. "
@@ -132,7 +370,8 @@ class IterativeClosestPoint {
     for (int k = 0; k < 16; ++k) final_.m[k] = (Scalar)T[k];
     converged_ = stats_.converged != 0;
     state_ = stats_.state;
-    d.download(out_.s, output);
+    if (detail::has_normal<PointSource>::value && &output != input_.get()) output = *input_;      // (the fields beside x, y, z and the normal)
+    detail::download_cloud(d, out_.s, output);
     aligned_once_ = true;
   }
 
@@ -147,8 +386,8 @@ class IterativeClosestPoint {
   double getFitnessScore(double max_range = DBL_MAX)
   {
     Device &d = Device::instance();
-    if (!aligned_once_) { if (!input_ || !target_) return DBL_MAX; d.upload(src_.s, *input_); d.upload(tgt_.s, *target_); }
-    else if (input_) d.upload(src_.s, *input_);       // PCL transforms *input_ as it is NOW (App. C.2)
+    if (!aligned_once_) { if (!input_ || !target_) return DBL_MAX; detail::upload_cloud(d, src_.s, *input_); detail::upload_cloud(d, tgt_.s, *target_); }
+    else if (input_) detail::upload_cloud(d, src_.s, *input_);       // PCL transforms *input_ as it is NOW (App. C.2)
     float T[16];
     for (int k = 0; k < 16; ++k) T[k] = (float)final_.m[k];
     double score = DBL_MAX;
@@ -164,6 +403,7 @@ class IterativeClosestPoint {
   Matrix4 final_;
   bool converged_ = false, aligned_once_ = false;
   int state_ = MVR_CONV_NOT;
+  std::vector<CorrespondenceRejectorPtr> rejectors_;
   SlotGuard src_, tgt_, out_;
 };
 

@@ -143,6 +143,7 @@ struct Correspondence {
 };
 typedef std::vector<Correspondence> Correspondences;
 typedef std::shared_ptr<Correspondences> CorrespondencesPtr;
+typedef std::shared_ptr<const Correspondences> CorrespondencesConstPtr;
 
 // ---- small fixed matrices with Eigen's storage: column-major, operator()(row, col)
 template <typename S>

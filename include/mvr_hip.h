@@ -815,6 +815,77 @@ int  mvr_moments_from_moments2(const mvr_pair_moments2_t *m2, mvr_pair_moments_t
 int  mvr_icp_align(mvr_ctx *ctx, int src_slot, int tgt_slot, int out_slot,
                    const mvr_icp_params *params, float T_out[16], mvr_icp_stats *stats);
 
+/* ---- correspondence rejectors (EXTENSION: pcl::registration::CorrespondenceRejector*, ICP::addCorrespondenceRejector) ------
+ * What stands between the correspondence search of an ICP iteration and its estimator.  Views 30 degrees apart overlap only
+ * partly: a fixed distance cap wide enough for the first iterations lets every rim point outside the overlap pull on the solve.
+ * PCL was not at hand; the model is pcl/registration/correspondence_rejection_distance.h, _median_distance.h, _trimmed.h,
+ * _surface_normal.h, _one_to_one.h (and their impl/ *.hpp) and pcl/registration/impl/icp.hpp, as published; deviations are marked.
+ * Opt-in: mvr_icp_align, mvr_correspondences and every other entry keep their behaviour and their bits.
+ *  R1. The table: a correspondence is (query i, match j, d2), d2 the f32 squared distance the search found; the chain never
+ *      recomputes it (the rejectors carry no data container, which is what IterativeClosestPoint gives them).  Stages run in
+ *      chain order, each sees only what the stage before kept.  LIVE = kept so far; m = the number live at a stage's entry.
+ *  R2. DISTANCE: keep iff (double)d2 < value * value, strictly; the product is taken once on the host.
+ *  R3. MEDIAN: med = the element at 0-based position m / 2 (integer division) of the live d2 in ascending order -- the upper
+ *      median, what nth_element gives.  Keep iff (double)d2 <= (double)med * value.  With m == 0 nothing happens.
+ *  R4. TRIMMED: nv = max((uint32_t)floor(value * (double)m), min_correspondences) (a product of 4294967295 or more counts as
+ *      "all").  nv >= m keeps all.  Otherwise exactly the nv smallest by the key (d2 bits, query index) ascending are kept
+ *      (nv == 0: none).  DEVIATION: PCL's nth_element leaves the choice among equal distances open; here the lower query
+ *      index wins.
+ *  R5. SURFACE_NORMAL: dot = (n.x * t.x + n.y * t.y) + n.z * t.z in f32, each operation rounded; n = the current source normal
+ *      of i, t = the target normal of j.  Keep iff (double)dot > value; a NaN fails.  Both clouds must carry normals
+ *      (mvr_cloud_upload_normals / mvr_cloud_estimate_normals), else MVR_E_ARG before any GPU work.
+ *  R6. ONE_TO_ONE: among the live correspondences with the same match j the one with the smallest (d2 bits, query index) stays.
+ *  R7. Output: the survivors in ascending query index (deterministic, where PCL's trimmed order is not).  *m may exceed cap:
+ *      the lists are then truncated, as mvr_correspondences does.  stages[s] (optional, n_chain records) = the number live
+ *      before and after stage s and the f32 d2 it cut at: MEDIAN the median, TRIMMED the largest d2 kept, both 0 when the
+ *      stage had nothing to select from (m == 0, or nv == 0); 0 for the other kinds.  Bit-identical from run to run and for
+ *      every launch shape: integer atomics only.
+ *  R8. mvr_reject_correspondences runs the chain on the caller's list (query, match, dist2: host arrays of `count` entries):
+ *      query indices below the source size and distinct, match indices below the target size, dist2 not NaN and >= 0 (+inf is
+ *      allowed and sorts last); any violation is MVR_E_ARG with nothing written.  The slots are needed only for their sizes
+ *      and, under R5, their normals.
+ *  R9. mvr_icp_align_rejected is PCL's computeTransformation with rejectors.  Each iteration: the search of mvr_icp_align
+ *      (max_corr_dist, use_reciprocal); the chain; fewer than 3 survivors: MVR_E_NOCORR with state NO_CORRESPONDENCES; the
+ *      estimator (SVD, or point_to_plane) on the survivors; mse = the f64 sum of the survivors' f32 d2 / their number; the
+ *      convergence criteria as in mvr_icp_align.  The current source of the next iteration is exactly what
+ *      mvr_cloud_transform_f32 with the iteration's incremental transformation makes of the current one, points and (if
+ *      present) normals, by the same kernels: PCL's incremental transformCloud.  T_out = the product of the incremental
+ *      transformations by mvr_mat4f_mul.  trace[k] (optional, k < trace_cap) records iteration k.  With n_chain == 0 the
+ *      result equals mvr_icp_align's in iterations / state / n_corr and in T within rounding (the sums run in another order,
+ *      so the bits need not match).  Between the search and the sums nothing comes to the host: the chain rewrites the
+ *      device's match table in place, and the counts and thresholds of its stages ride along with the iteration's sums.
+ *  R10. MVR_E_ARG, before any GPU work and with nothing written, for a NULL ctx, a NULL chain with n_chain > 0, n_chain outside
+ *      0..MVR_MAX_REJECTORS, an unknown kind, a non-finite value, a negative value of DISTANCE / MEDIAN / TRIMMED, a bad slot,
+ *      a cloud above 0x7FFFFFF0 points or one whose points are stale because a pipelined run is in flight.  Empty clouds:
+ *      MVR_OK with *m = 0.
+ * Out of scope: CorrespondenceRejectorVarTrimmed, ...SampleConsensus, ...Features, ...OrganizedBoundary; rejectors in the ring /
+ * LUM passes, in mvr_seq_run, mvr_seq_align_sharded and the Registrator drivers. */
+#define MVR_MAX_REJECTORS 8
+enum { MVR_REJ_DISTANCE = 0, MVR_REJ_MEDIAN = 1, MVR_REJ_TRIMMED = 2, MVR_REJ_SURFACE_NORMAL = 3, MVR_REJ_ONE_TO_ONE = 4 };
+typedef struct {
+  int      kind;                 /* MVR_REJ_* */
+  double   value;                /* DISTANCE: max distance (not squared); MEDIAN: factor; TRIMMED: overlap ratio;
+                                    SURFACE_NORMAL: threshold (a cosine); ONE_TO_ONE: unused */
+  uint32_t min_correspondences;  /* TRIMMED only */
+} mvr_rejector;
+typedef struct { uint32_t in, out; float threshold; } mvr_rejector_stage;
+typedef struct {
+  uint32_t n_found;                                /* correspondences the search found, before the chain */
+  mvr_rejector_stage stages[MVR_MAX_REJECTORS];
+  uint32_t n_corr;                                 /* survivors: what the estimator saw */
+  double   mse;
+  float    tr[16];                                 /* the iteration's incremental transformation (identity if none was solved) */
+} mvr_icp_iter_trace;
+int  mvr_correspondences_rejected(mvr_ctx *ctx, int src_slot, int tgt_slot, double max_dist, int reciprocal, int fma_dist,
+                                  const mvr_rejector *chain, int n_chain, int32_t *query, int32_t *match, float *dist2,
+                                  size_t cap, size_t *m, mvr_rejector_stage *stages /* n_chain, optional */);
+int  mvr_reject_correspondences(mvr_ctx *ctx, int src_slot, int tgt_slot, const int32_t *query, const int32_t *match,
+                                const float *dist2, size_t count, const mvr_rejector *chain, int n_chain, int32_t *q_out,
+                                int32_t *m_out, float *d_out, size_t cap, size_t *m, mvr_rejector_stage *stages);
+int  mvr_icp_align_rejected(mvr_ctx *ctx, int src_slot, int tgt_slot, int out_slot, const mvr_icp_params *params,
+                            const mvr_rejector *chain, int n_chain, float T_out[16], mvr_icp_stats *stats,
+                            mvr_icp_iter_trace *trace /* optional */, int trace_cap);
+
 /* Registration::getFitnessScore(max_range) (registrator.cpp:572,923,1015):
  * mean squared distance of T*input to its unbounded 1-NN in the target.
  * DBL_MAX when no point qualifies. */

@@ -87,6 +87,28 @@ class IcpStats(C.Structure):
                 ("fwd_queries", C.c_double), ("ms", C.c_double)]
 
 
+class Rejector(C.Structure):
+    """mvr_rejector"""
+    _fields_ = [("kind", C.c_int), ("value", C.c_double), ("min_correspondences", C.c_uint32)]
+
+
+class RejectorStage(C.Structure):
+    """mvr_rejector_stage"""
+    _fields_ = [("in_", C.c_uint32), ("out", C.c_uint32), ("threshold", C.c_float)]
+
+
+MAX_REJECTORS = 8       # MVR_MAX_REJECTORS
+REJ_DISTANCE, REJ_MEDIAN, REJ_TRIMMED, REJ_SURFACE_NORMAL, REJ_ONE_TO_ONE = 0, 1, 2, 3, 4
+REJ_KINDS = {"distance": REJ_DISTANCE, "median": REJ_MEDIAN, "trimmed": REJ_TRIMMED, "surface_normal": REJ_SURFACE_NORMAL,
+             "one_to_one": REJ_ONE_TO_ONE}
+
+
+class IcpIterTrace(C.Structure):
+    """mvr_icp_iter_trace"""
+    _fields_ = [("n_found", C.c_uint32), ("stages", RejectorStage * MAX_REJECTORS), ("n_corr", C.c_uint32), ("mse", C.c_double),
+                ("tr", C.c_float * 16)]
+
+
 class PairMoments(C.Structure):
     _fields_ = [("n", C.c_double), ("mean_src", C.c_double * 3), ("mean_tgt", C.c_double * 3),
                 ("mse", C.c_double), ("sigma", C.c_double * 9)]
@@ -267,6 +289,12 @@ SIGNATURES = {
     "mvr_moments_from_moments2": (C.c_int, [C.POINTER(PairMoments2), C.POINTER(PairMoments)]),
     "mvr_icp_align": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams), _fp,
                                 C.POINTER(IcpStats)]),
+    "mvr_correspondences_rejected": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(Rejector), C.c_int,
+                                               _i32p, _i32p, _fp, _sz, C.POINTER(_sz), C.POINTER(RejectorStage)]),
+    "mvr_reject_correspondences": (C.c_int, [_vp, C.c_int, C.c_int, _i32p, _i32p, _fp, _sz, C.POINTER(Rejector), C.c_int,
+                                             _i32p, _i32p, _fp, _sz, C.POINTER(_sz), C.POINTER(RejectorStage)]),
+    "mvr_icp_align_rejected": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams), C.POINTER(Rejector), C.c_int, _fp,
+                                         C.POINTER(IcpStats), C.POINTER(IcpIterTrace), C.c_int]),
     "mvr_fitness": (C.c_int, [_vp, C.c_int, C.c_int, _fp, C.c_double, C.c_int, _dp]),
     "mvr_lum_edge_from_moments": (C.c_int, [C.POINTER(PairMoments2), _dp, _dp, _dp, _dp, _dp]),
     "mvr_lum_edge_from_moments_x4": (C.c_int, [C.POINTER(PairMoments2), _dp, _dp, _dp, _dp, _dp]),
@@ -355,6 +383,22 @@ def icp_params(reciprocal=True, max_dist=4.0, max_iter=10, teps=1e-6, feps=64.0,
     (max_iterations is the caller's; with feps=64 every align is one iteration)."""
     return IcpParams(int(reciprocal), float(max_dist), int(max_iter), float(teps), float(feps),
                      int(fma), int(point_to_plane))
+
+
+def rejector(kind, value=0.0, min_correspondences=0) -> Rejector:
+    """One stage of a rejector chain (mvr_rejector): kind = "distance" (value: the largest distance), "median" (the factor),
+    "trimmed" (the overlap ratio; min_correspondences), "surface_normal" (the smallest cosine), "one_to_one", or a REJ_* number."""
+    return Rejector(REJ_KINDS[kind] if isinstance(kind, str) else int(kind), float(value), int(min_correspondences))
+
+
+def _chain(chain):
+    chain = list(chain or ())
+    arr = (Rejector * max(1, len(chain)))(*chain)
+    return arr, len(chain)
+
+
+def _stage_dicts(st, n):
+    return [dict(n_in=st[k].in_, n_out=st[k].out, threshold=np.float32(st[k].threshold)) for k in range(n)]
 
 
 def synth_params(n_views=12, config_id=0) -> SynthParams:
@@ -926,6 +970,48 @@ class Context:
                                       C.byref(cnt)), self._h)
         k = cnt.value
         return q[:k].copy(), m[:k].copy(), d[:k].copy()
+
+    def correspondences_rejected(self, s, t, max_dist, chain, reciprocal=True, fma=False):
+        """mvr_correspondences_rejected: the correspondences of slots s -> t that the rejector chain (a list of rejector(...))
+        leaves -> (query, match, d2, stages), stages = one dict(n_in, n_out, threshold) per stage."""
+        n = self.size(s)
+        q, m, d = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32)
+        arr, nc = _chain(chain)
+        st, cnt = (RejectorStage * MAX_REJECTORS)(), _sz()
+        _chk(_lib.mvr_correspondences_rejected(self._h, s, t, float(max_dist), int(reciprocal), int(fma), arr, nc, _p(q, C.c_int32),
+                                               _p(m, C.c_int32), _p(d, C.c_float), n, C.byref(cnt), st), self._h)
+        k = cnt.value
+        return q[:k].copy(), m[:k].copy(), d[:k].copy(), _stage_dicts(st, nc)
+
+    def reject_correspondences(self, s, t, query, match, dist2, chain):
+        """mvr_reject_correspondences: the chain on the caller's list -> (query, match, d2, stages), ascending query index."""
+        qi, mi = np.ascontiguousarray(query, np.int32), np.ascontiguousarray(match, np.int32)
+        di = np.ascontiguousarray(dist2, np.float32)
+        n = len(qi)
+        q, m, d = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32)
+        arr, nc = _chain(chain)
+        st, cnt = (RejectorStage * MAX_REJECTORS)(), _sz()
+        _chk(_lib.mvr_reject_correspondences(self._h, s, t, _p(qi, C.c_int32), _p(mi, C.c_int32), _p(di, C.c_float), n, arr, nc,
+                                             _p(q, C.c_int32), _p(m, C.c_int32), _p(d, C.c_float), n, C.byref(cnt), st), self._h)
+        k = cnt.value
+        return q[:k].copy(), m[:k].copy(), d[:k].copy(), _stage_dicts(st, nc)
+
+    def icp_align_rejected(self, src, tgt, out, params: IcpParams, chain, return_trace=False):
+        """mvr_icp_align_rejected -> (T (4,4) float32, stats dict, rc[, trace]); rc is OK or E_NOCORR.  trace: one dict per iteration
+        (n_found, stages, n_corr, mse, tr (4,4) float32: the incremental transformation)."""
+        T, st = np.empty(16, np.float32), IcpStats()
+        arr, nc = _chain(chain)
+        cap = max(1, int(params.max_iterations)) if return_trace else 0
+        tr = (IcpIterTrace * max(1, cap))()
+        rc = _chk(_lib.mvr_icp_align_rejected(self._h, src, tgt, out, C.byref(params), arr, nc, _p(T, C.c_float), C.byref(st),
+                                              tr if return_trace else None, cap), self._h, allow=(E_NOCORR,))
+        stats = self._stats(st)
+        if not return_trace:
+            return from_cm(T), stats, rc
+        n_it = min(cap, stats["iterations"] + (1 if rc == E_NOCORR else 0))
+        trace = [dict(n_found=tr[k].n_found, stages=_stage_dicts(tr[k].stages, nc), n_corr=tr[k].n_corr, mse=tr[k].mse,
+                      tr=from_cm(np.array(tr[k].tr, np.float32))) for k in range(n_it)]
+        return from_cm(T), stats, rc, trace
 
     def pair_batch_correspondences(self, k, cap):
         """(query, match, d2) of pair k of the last fused batch / ring step (mvr_pair_batch_correspondences)"""

@@ -456,6 +456,9 @@ API int mvr_ctx_destroy(mvr_ctx *ctx)
   if (c->h_stall) (void)hipHostFree(c->h_stall);
   if (c->seq_keys) (void)hipFree(c->seq_keys);
   if (c->seq_row) (void)hipFree(c->seq_row);
+  if (c->rej_row) (void)hipFree(c->rej_row);
+  if (c->rej_win) (void)hipFree(c->rej_win);
+  if (c->rej_host) (void)hipHostFree(c->rej_host);
   if (c->h_pose_in) (void)hipHostFree(c->h_pose_in);
   if (c->pose_tab) (void)hipFree(c->pose_tab);
   if (c->done_counter) (void)hipFree(c->done_counter);
@@ -2172,6 +2175,232 @@ API int mvr_icp_align(mvr_ctx *ctx, int ss, int ts, int os, const mvr_icp_params
   if (st) {
     st->iterations = iters; st->converged = converged; st->state = state; st->n_corr = ncorr; st->mse = cur_mse;
     st->evals = evals; st->fwd_queries = fwdq; st->ms = now_ms() - t0;
+  }
+  return status;
+}
+
+// ---- correspondence rejectors (rules R1-R10 in mvr_hip.h; kernels in mvr_reject.hip)
+namespace {
+// R10, and R5's normals: everything that is refused before any GPU work
+int reject_args(Ctx *c, int ss, int ts, const mvr_rejector *chain, int n_chain, bool *one_to_one)
+{
+  if (n_chain < 0 || n_chain > MVR_MAX_REJECTORS || (n_chain > 0 && !chain)) return set_error(c, MVR_E_ARG, "rejector chain: n_chain outside 0..MVR_MAX_REJECTORS or a NULL chain");
+  const Cloud &s = c->slots[ss], &t = c->slots[ts];
+  if (s.n > 0x7FFFFFF0ull || t.n > 0x7FFFFFF0ull) return set_error(c, MVR_E_ARG, "rejector chain: cloud too large");
+  if (s.pts_stale || t.pts_stale) return set_error(c, MVR_E_ARG, "rejector chain: a cloud's points are not current (pipelined run)");
+  *one_to_one = false;
+  for (int k = 0; k < n_chain; ++k) {
+    const mvr_rejector &r = chain[k];
+    if (r.kind < MVR_REJ_DISTANCE || r.kind > MVR_REJ_ONE_TO_ONE) return set_error(c, MVR_E_ARG, "rejector chain: unknown kind");
+    if (!std::isfinite(r.value)) return set_error(c, MVR_E_ARG, "rejector chain: a value is not finite");
+    if (r.kind <= MVR_REJ_TRIMMED && r.value < 0.0) return set_error(c, MVR_E_ARG, "rejector chain: a negative distance, factor or ratio");
+    if (r.kind == MVR_REJ_SURFACE_NORMAL && s.n && t.n && !(s.has_normals && t.has_normals))
+      return set_error(c, MVR_E_ARG, "the surface-normal rejector needs the normals of both clouds (mvr_cloud_upload_normals)");
+    if (r.kind == MVR_REJ_ONE_TO_ONE) *one_to_one = true;
+  }
+  return MVR_OK;
+}
+
+inline const uint32_t *reject_words(const Ctx *c) { return reinterpret_cast<const uint32_t *>(c->rej_host + kRejRowDoubles); }
+
+void reject_stages(const Ctx *c, int n_chain, uint32_t *n_found, mvr_rejector_stage *stages, uint32_t *n_corr)
+{
+  const uint32_t *w = reject_words(c);
+  uint32_t live = w[0];
+  if (n_found) *n_found = live;
+  for (int s = 0; s < n_chain; ++s) {
+    const uint32_t *sw = w + kRejHeadWords + s * kRejStageWords;
+    if (stages) { stages[s].in = live; stages[s].out = sw[0]; std::memcpy(&stages[s].threshold, &sw[1], 4); }
+    live = sw[0];
+  }
+  if (n_corr) *n_corr = live;
+}
+
+// the table after the chain -> the caller's lists (R7), and the stage records
+int reject_collect(Ctx *c, size_t ns, int n_chain, int32_t *query, int32_t *match, float *dist2, size_t cap, size_t *m, mvr_rejector_stage *stages)
+{
+  std::vector<int32_t> hm(ns);
+  std::vector<nnkey_t> hk(ns);
+  MVR_HIP_TRY(c, hipMemcpyAsync(hm.data(), c->match, ns * 4, hipMemcpyDeviceToHost, c->stream));
+  MVR_HIP_TRY(c, hipMemcpyAsync(hk.data(), c->keys, ns * 8, hipMemcpyDeviceToHost, c->stream));
+  MVR_HIP_TRY(c, hipMemcpyAsync(c->rej_host, c->rej_row, kRejCopyBytes, hipMemcpyDeviceToHost, c->stream));
+  MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  size_t k = 0;
+  for (size_t i = 0; i < ns; ++i) {
+    if (hm[i] < 0) continue;
+    if (k < cap) {
+      if (query) query[k] = (int32_t)i;
+      if (match) match[k] = hm[i];
+      if (dist2) { const uint32_t b = (uint32_t)(hk[i] >> 32); std::memcpy(&dist2[k], &b, 4); }
+    }
+    ++k;
+  }
+  uint32_t n_corr = 0;
+  reject_stages(c, n_chain, nullptr, stages, &n_corr);
+  if ((size_t)n_corr != k) return set_error(c, MVR_E_HIP, "rejector chain: the stage counts and the table disagree");
+  *m = k;
+  return MVR_OK;
+}
+}  // namespace
+
+API int mvr_correspondences_rejected(mvr_ctx *ctx, int ss, int ts, double max_dist, int reciprocal, int fma, const mvr_rejector *chain,
+                                     int n_chain, int32_t *query, int32_t *match, float *dist2, size_t cap, size_t *m,
+                                     mvr_rejector_stage *stages)
+{
+  if (!ctx || !slot_ok(ss) || !slot_ok(ts) || !m) return MVR_E_ARG;
+  Ctx *c = CTX(ctx);
+  bool oto = false;
+  if (int rc = reject_args(c, ss, ts, chain, n_chain, &oto)) return rc;
+  MVR_HIP_TRY(c, hipSetDevice(c->device));
+  *m = 0;
+  if (stages) std::memset(stages, 0, sizeof(mvr_rejector_stage) * (size_t)n_chain);
+  const size_t ns = c->slots[ss].n, nt = c->slots[ts].n;
+  if (ns == 0 || nt == 0) return MVR_OK;
+  if (int rc = ensure_reject_state(c, nt, oto)) return rc;
+  SearchPlan plan;
+  if (int rc = pair_common(c, ss, ts, max_dist, reciprocal, fma, 0, ns, nullptr, &plan)) return rc;
+  if (int rc = launch_reject_chain(c, chain, n_chain, c->keys, c->match, ns, nt, c->slots[ss].nrm, c->slots[ts].nrm, c->moments, 0u)) return rc;
+  return reject_collect(c, ns, n_chain, query, match, dist2, cap, m, stages);
+}
+
+API int mvr_reject_correspondences(mvr_ctx *ctx, int ss, int ts, const int32_t *query, const int32_t *match, const float *dist2, size_t count,
+                                   const mvr_rejector *chain, int n_chain, int32_t *q_out, int32_t *m_out, float *d_out, size_t cap,
+                                   size_t *m, mvr_rejector_stage *stages)
+{
+  if (!ctx || !slot_ok(ss) || !slot_ok(ts) || !m || (count && (!query || !match || !dist2))) return MVR_E_ARG;
+  Ctx *c = CTX(ctx);
+  bool oto = false;
+  if (int rc = reject_args(c, ss, ts, chain, n_chain, &oto)) return rc;
+  const size_t ns = c->slots[ss].n, nt = c->slots[ts].n;
+  // R8: the list, checked on the host while it is laid out as the search would have left it
+  if (count > ns) return set_error(c, MVR_E_ARG, "rejector list: more entries than source points (query indices must be distinct)");
+  std::vector<int32_t> hm(ns, -1);
+  std::vector<nnkey_t> hk(ns, kKeyInit);
+  for (size_t k = 0; k < count; ++k) {
+    if (query[k] < 0 || (size_t)query[k] >= ns || match[k] < 0 || (size_t)match[k] >= nt) return set_error(c, MVR_E_ARG, "rejector list: index out of range");
+    if (hm[query[k]] >= 0) return set_error(c, MVR_E_ARG, "rejector list: a query index appears twice");
+    if (!(dist2[k] >= 0.0f)) return set_error(c, MVR_E_ARG, "rejector list: a squared distance is negative or NaN");
+    uint32_t b; std::memcpy(&b, &dist2[k], 4);
+    if (b == 0x80000000u) b = 0u;                      // (-0 compares >= 0: taken as +0, so that the patterns order as the values)
+    hm[query[k]] = match[k];
+    hk[query[k]] = ((nnkey_t)b << 32) | (nnkey_t)(uint32_t)match[k];
+  }
+  MVR_HIP_TRY(c, hipSetDevice(c->device));
+  *m = 0;
+  if (stages) std::memset(stages, 0, sizeof(mvr_rejector_stage) * (size_t)n_chain);
+  if (ns == 0 || nt == 0 || count == 0) return MVR_OK;
+  if (int rc = ensure_reject_state(c, nt, oto)) return rc;
+  if (int rc = ensure(c, c->keys, c->keys_cap, ns)) return rc;
+  if (int rc = ensure(c, c->match, c->match_cap, ns)) return rc;
+  MVR_HIP_TRY(c, hipMemcpyAsync(c->match, hm.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  MVR_HIP_TRY(c, hipMemcpyAsync(c->keys, hk.data(), ns * sizeof(nnkey_t), hipMemcpyHostToDevice, c->stream));
+  MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));     // (pageable sources: the vectors are reused below)
+  if (int rc = launch_reject_chain(c, chain, n_chain, c->keys, c->match, ns, nt, c->slots[ss].nrm, c->slots[ts].nrm, nullptr, (uint32_t)count)) return rc;
+  return reject_collect(c, ns, n_chain, q_out, m_out, d_out, cap, m, stages);
+}
+
+// PCL's computeTransformation with rejectors (R9).  The loop of mvr_icp_align with the chain between the search and the sums;
+// the sums are the raw second moments over the rewritten match[] (and the point-to-plane normal equations), which come to the
+// host in ONE copy together with the stages' counts and thresholds.
+API int mvr_icp_align_rejected(mvr_ctx *ctx, int ss, int ts, int os, const mvr_icp_params *p, const mvr_rejector *chain, int n_chain,
+                               float T_out[16], mvr_icp_stats *st, mvr_icp_iter_trace *trace, int trace_cap)
+{
+  if (!ctx || !slot_ok(ss) || !slot_ok(ts) || (os >= 0 && !slot_ok(os)) || !p || !T_out || (trace && trace_cap < 0)) return MVR_E_ARG;
+  Ctx *c = CTX(ctx);
+  bool oto = false;
+  if (int rc = reject_args(c, ss, ts, chain, n_chain, &oto)) return rc;
+  Cloud &tgt = c->slots[ts];
+  if (p->point_to_plane && tgt.n && !tgt.has_normals)
+    return set_error(c, MVR_E_ARG, "point-to-plane needs target normals (mvr_cloud_upload_normals)");
+  MVR_HIP_TRY(c, hipSetDevice(c->device));
+  const double t0 = now_ms();
+  const size_t ns = c->slots[ss].n, nt = tgt.n;
+  const bool src_normals = c->slots[ss].has_normals && ns;
+  Cloud &scratch = c->slots[kScratchCur];
+  Cloud *curp = &c->slots[ss];
+  bool on_scratch = false;
+  const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  float fin[16], tr[16];
+  std::memcpy(fin, I, sizeof I); std::memcpy(tr, I, sizeof I);
+  Criteria crit(p);
+  double cur_mse = 0.0, fwdq = 0.0, origin[3] = {0.0, 0.0, 0.0};
+  int iters = 0, converged = 0, state = MVR_CONV_NOT, ncorr = 0, status = MVR_OK;
+  if (ns == 0 || nt == 0) { state = MVR_CONV_NO_CORRESPONDENCES; status = MVR_E_NOCORR; }
+  else {
+    if (int rc = ensure_reject_state(c, nt, oto)) return rc;
+    if (c->nn_mode != 0) { if (int rc = ensure_index(c, c->slots[ss])) return rc; }
+  }
+  while (status == MVR_OK && !converged) {
+    SearchPlan plan;
+    if (int rc = run_search(c, *curp, tgt, 0, ns, p->max_corr_dist, p->use_reciprocal != 0, p->fma_dist != 0, nullptr, &plan)) return rc;
+    if (int rc = launch_pass1(c, curp->pts, tgt.pts, c->keys, c->rkeys, plan.slot, plan.count, plan.qperm, plan.tinv, 0, ns,
+                              p->max_corr_dist * p->max_corr_dist, p->use_reciprocal != 0, c->match, c->moments)) return rc;
+    if (int rc = launch_reject_chain(c, chain, n_chain, c->keys, c->match, ns, nt, curp->nrm, tgt.nrm, c->moments, 0u)) return rc;
+    if (int rc = launch_moments2(c, curp->pts, tgt.pts, c->match, c->keys, plan.qperm, 0, ns, origin, c->rej_row)) return rc;
+    if (p->point_to_plane) { if (int rc = launch_p2plane(c, curp->pts, tgt.pts, tgt.nrm, c->match, plan.qperm, 0, ns, c->rej_row + 32)) return rc; }
+    MVR_HIP_TRY(c, hipMemcpyAsync(c->rej_host, c->rej_row, kRejCopyBytes, hipMemcpyDeviceToHost, c->stream));      // the iteration's one round trip
+    MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const double *h = c->rej_host;
+    mvr_icp_iter_trace *tk = (trace && iters < trace_cap) ? &trace[iters] : nullptr;
+    uint32_t n_found = 0, n_live = 0;
+    if (tk) std::memset(tk, 0, sizeof *tk);
+    reject_stages(c, n_chain, &n_found, tk ? tk->stages : nullptr, &n_live);
+    if ((double)n_live != h[0]) return set_error(c, MVR_E_HIP, "mvr_icp_align_rejected: the stage counts and the sums disagree");
+    fwdq += (double)ns;
+    ncorr = (int)n_live;
+    if (tk) { tk->n_found = n_found; tk->n_corr = n_live; std::memcpy(tk->tr, I, sizeof I); }
+    if (n_live < 3u) { state = MVR_CONV_NO_CORRESPONDENCES; converged = 0; status = MVR_E_NOCORR; break; }
+    mvr_pair_moments2_t m2;
+    static_assert(sizeof m2 == 32 * sizeof(double), "moments2 layout");
+    std::memcpy(&m2, h, sizeof m2);
+    mvr_pair_moments_t mom;
+    if (int rc = mvr_moments_from_moments2(&m2, &mom)) return set_error(c, rc, "moments of the rejected align");
+    if (p->point_to_plane) {
+      if (p2plane_solve(h + 32, h + 32 + 21, tr) != MVR_OK) { state = MVR_CONV_NO_CORRESPONDENCES; converged = 0; status = MVR_E_SINGULAR; break; }
+    } else umeyama_from_moments(mom.mean_src, mom.mean_tgt, mom.sigma, tr, nullptr);
+    cur_mse = h[31] / h[0];                          // mean of the survivors' (f32) squared distances, summed in f64
+    for (int k = 0; k < 3; ++k) origin[k] = mom.mean_tgt[k];      // the next iteration's sums are taken about this one's target mean
+    if (tk) { tk->mse = cur_mse; std::memcpy(tk->tr, tr, sizeof tr); }
+    mvr_mat4f_mul(tr, fin, fin);
+    ++iters;
+    converged = crit.converged(tr, cur_mse, iters, &state) ? 1 : 0;
+    if (!converged) {          // the current source moves as mvr_cloud_transform_f32 moves a cloud: points and normals
+      if (!on_scratch) {
+        scratch.n = 0;
+        if (int rc = cloud_reserve(c, scratch, ns, false)) return rc;
+        if (src_normals) { if (int rc = ensure(c, scratch.nrm, scratch.nrm_cap, ns)) return rc; }
+        if (int rc = launch_transform_f32(c, curp->pts, scratch.pts, ns, tr)) return rc;
+        if (src_normals) { if (int rc = launch_rotate_normals_f32(c, curp->nrm, scratch.nrm, ns, tr)) return rc; }
+        scratch.n = ns;
+        inherit_point_set(scratch, c->slots[ss]);
+        on_scratch = true;
+        curp = &scratch;
+      } else {
+        if (int rc = launch_transform_f32(c, curp->pts, curp->pts, ns, tr)) return rc;
+        if (src_normals) { if (int rc = launch_rotate_normals_f32(c, curp->nrm, curp->nrm, ns, tr)) return rc; }
+      }
+      curp->stale_coords();
+      curp->pose_known = false; curp->grid.reset();
+    }
+  }
+  scratch.has_normals = false;
+  if (os >= 0) {            // output = final * (*input), from the ORIGINAL input, as mvr_icp_align writes it
+    if (os != ss) { c->slots[os].n = 0; if (int rc = cloud_reserve(c, c->slots[os], ns, false)) return rc; }
+    if (int rc = launch_transform_f32(c, c->slots[ss].pts, c->slots[os].pts, ns, fin)) return rc;
+    c->slots[os].n = ns;
+    if (os != ss) inherit_point_set(c->slots[os], c->slots[ss]);
+    else c->slots[os].forget_pose();
+    c->slots[os].stale_coords();
+    if (src_normals) {
+      if (int rc = ensure(c, c->slots[os].nrm, c->slots[os].nrm_cap, ns)) return rc;
+      if (int rc = launch_rotate_normals_f32(c, c->slots[ss].nrm, c->slots[os].nrm, ns, fin)) return rc;
+    }
+    c->slots[os].has_normals = c->slots[ss].has_normals;
+  }
+  std::memcpy(T_out, fin, sizeof fin);
+  if (st) {
+    st->iterations = iters; st->converged = converged; st->state = state; st->n_corr = ncorr; st->mse = cur_mse;
+    st->evals = 0.0; st->fwd_queries = fwdq; st->ms = now_ms() - t0;
   }
   return status;
 }

@@ -244,6 +244,11 @@ struct Ctx {
   double *h_align = nullptr, *d_align = nullptr;      // pinned host, 64 doubles + the word (at double 64), and the device's view of it
   uint32_t align_seq = 0;
   int align_spin = 1;
+  // correspondence rejectors (mvr_reject.hip): the chain's device state -- kRejRowDoubles doubles of sums (raw moments at 0,
+  // point-to-plane at 32), then the stage words, which one copy brings to rej_host together; then histogram and block counts
+  double *rej_row = nullptr, *rej_host = nullptr;     // device, pinned host (the copied part only)
+  nnkey_t *rej_win = nullptr; size_t rej_win_cap = 0; // ONE_TO_ONE: per target the smallest (d2 bits << 32 | query); all ~0 between calls
+  bool rej_win_dirty = false;                         // ... unless a chain failed between marking and clearing: filled again before the next use
   int seq_rider = 1;                                  // mvr_seq_run: the model's tail is refreshed by the launch that poses the next source
   // index-build scratch
   uint32_t *codes_a = nullptr, *codes_b = nullptr, *idx_a = nullptr; size_t sort_cap = 0;
@@ -826,6 +831,20 @@ int launch_moments2(Ctx *c, const float4 *src, const float4 *tgt, const int32_t 
 // out[27] = count, out[28] = sum d^2  (d = n . (q - p)); device pointer
 int launch_p2plane(Ctx *c, const float4 *src, const float4 *tgt, const float4 *tnrm, const int32_t *match,
                    const uint32_t *qperm, size_t q_begin, size_t q_count, double *out);
+// ---- correspondence rejectors (mvr_reject.hip; rules R1-R10 at mvr_correspondences_rejected in mvr_hip.h)
+// Layout of Ctx::rej_row: doubles [0, kRejRowDoubles) = the iteration's sums; then uint32 words: [0] the number found, then
+// kRejStageWords per stage {out, threshold bits, prefix, rank, none, pad...}; the copy to the host ends there.  Behind it the
+// radix histogram and the per-block tie counts.
+constexpr int kRejRowDoubles = 64, kRejStageWords = 8, kRejHeadWords = 8;
+constexpr int kRejCopyWords = kRejHeadWords + MVR_MAX_REJECTORS * kRejStageWords;
+constexpr int kRejHistBins = 2048, kRejTieBlocks = 1024;
+constexpr size_t kRejCopyBytes = (size_t)kRejRowDoubles * sizeof(double) + (size_t)kRejCopyWords * sizeof(uint32_t);
+constexpr size_t kRejRowBytes = kRejCopyBytes + (size_t)(kRejHistBins + kRejTieBlocks) * sizeof(uint32_t);
+int ensure_reject_state(Ctx *c, size_t nt, bool one_to_one);
+// the chain over keys[] / match[] (ns entries, by source index) in place: a rejected entry gets match = -1.  found: a device
+// double holding the number live at entry (pass 1's moments[0]), or null: found_host.  Nothing comes to the host.
+int launch_reject_chain(Ctx *c, const mvr_rejector *chain, int n_chain, const nnkey_t *keys, int32_t *match, size_t ns, size_t nt,
+                        const float4 *snrm, const float4 *tnrm, const double *found, uint32_t found_host);
 int launch_rotate_normals_f32(Ctx *c, const float4 *in, float4 *out, size_t n, const float T[16]);
 int launch_rotate_normals_f64(Ctx *c, const float4 *in, float4 *out, size_t n, const double T[16]);
 int launch_fitness(Ctx *c, const nnkey_t *keys, size_t n, double max_range, double *moments);
