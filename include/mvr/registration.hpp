@@ -407,6 +407,133 @@ class IterativeClosestPoint {
   SlotGuard src_, tgt_, out_;
 };
 
+// ---------------------------------------------------------------- Generalized ICP
+// pcl::GeneralizedIterativeClosestPoint over mvr_icp_align_gicp (rules G1-G10 in mvr_hip.h).  The side covariances come from
+// normals: a cloud without them (PointXYZ) gets the normals of its k nearest neighbours from mvr_cloud_estimate_normals with
+// k = the correspondence randomness (PCL's k-neighbourhood covariance, regularised, is I - (1 - eps) n n^T of exactly that
+// normal).  DEVIATION: a cloud that carries normals (PointNormal) uses them as they are; PCL recomputes the covariances from
+// the neighbours in every case.  DEVIATION: the inner optimiser is Levenberg-Marquardt on the device, not BFGS (G7).
+// setSourceCovariances / setTargetCovariances are not offered.
+template <typename PointSource, typename PointTarget>
+class GeneralizedIterativeClosestPoint {
+ public:
+  typedef PointCloud<PointSource> PointCloudSource;
+  typedef PointCloud<PointTarget> PointCloudTarget;
+  typedef typename PointCloudSource::Ptr PointCloudSourcePtr;
+  typedef typename PointCloudTarget::Ptr PointCloudTargetPtr;
+  typedef Mat4<float> Matrix4;
+  typedef registration::CorrespondenceRejector::Ptr CorrespondenceRejectorPtr;
+
+  GeneralizedIterativeClosestPoint() { mvr_gicp_default_params(&p_); }      // PCL's defaults
+
+  void setInputSource(const PointCloudSourcePtr &c) { input_ = c; }
+  void setInputTarget(const PointCloudTargetPtr &c) { target_ = c; }
+  PointCloudSourcePtr const getInputSource() const { return input_; }
+  PointCloudTargetPtr const getInputTarget() const { return target_; }
+  void setMaxCorrespondenceDistance(double d) { p_.max_corr_dist = d; }
+  double getMaxCorrespondenceDistance() const { return p_.max_corr_dist; }
+  void setMaximumIterations(int n) { p_.max_iterations = n; }
+  int getMaximumIterations() const { return p_.max_iterations; }
+  void setTransformationEpsilon(double e) { p_.transformation_epsilon = e; }
+  double getTransformationEpsilon() const { return p_.transformation_epsilon; }
+  void setRotationEpsilon(double e) { p_.rotation_epsilon = e; }
+  double getRotationEpsilon() const { return p_.rotation_epsilon; }
+  void setCorrespondenceRandomness(int k) { k_correspondences_ = k; }
+  int getCorrespondenceRandomness() const { return k_correspondences_; }
+  void setMaximumOptimizerIterations(int n) { p_.max_inner_iterations = n; }
+  int getMaximumOptimizerIterations() const { return p_.max_inner_iterations; }
+  void setUseReciprocalCorrespondences(bool b) { p_.use_reciprocal = b ? 1 : 0; }
+  bool getUseReciprocalCorrespondences() const { return p_.use_reciprocal != 0; }
+  // EXTENSION: gicp_epsilon, the small eigenvalue of the side covariances (a protected constant 0.001 in PCL)
+  void setCovarianceEpsilon(double e) { p_.gicp_epsilon = e; }
+  double getCovarianceEpsilon() const { return p_.gicp_epsilon; }
+
+  void addCorrespondenceRejector(const CorrespondenceRejectorPtr &rejector) { rejectors_.push_back(rejector); }
+  std::vector<CorrespondenceRejectorPtr> getCorrespondenceRejectors() { return rejectors_; }
+  bool removeCorrespondenceRejector(unsigned int i)
+  {
+    if (i >= rejectors_.size()) return false;
+    rejectors_.erase(rejectors_.begin() + i);
+    return true;
+  }
+  void clearCorrespondenceRejectors() { rejectors_.clear(); }
+
+  void align(PointCloudSource &output) { align(output, Matrix4::Identity(), false); }
+  // the source starts under `guess` (PCL's Registration::align): the result is what the align finds from there, times guess
+  void align(PointCloudSource &output, const Matrix4 &guess) { align(output, guess, true); }
+
+  Matrix4 getFinalTransformation() const { return final_; }
+  bool hasConverged() const { return converged_; }
+  int getConvergenceState() const { return state_; }
+  const mvr_icp_stats &getStats() const { return stats_; }
+
+  // as IterativeClosestPoint::getFitnessScore
+  double getFitnessScore(double max_range = DBL_MAX)
+  {
+    Device &d = Device::instance();
+    if (!input_ || !target_) return DBL_MAX;
+    detail::upload_cloud(d, src_.s, *input_);
+    if (!aligned_once_) detail::upload_cloud(d, tgt_.s, *target_);
+    double score = DBL_MAX;
+    d.check(mvr_fitness(d.ctx(), src_.s, tgt_.s, final_.data(), max_range, p_.fma_dist, &score), "mvr_fitness");
+    return score;
+  }
+
+ private:
+  template <typename P>
+  void upload_with_normals(Device &d, int slot, const PointCloud<P> &c)
+  {
+    detail::upload_cloud(d, slot, c);
+    if (!detail::has_normal<P>::value && !c.empty()) {
+      mvr_normal_params np = mvr_normal_params();
+      np.k = k_correspondences_;
+      d.check(mvr_cloud_estimate_normals(d.ctx(), 1, &slot, &np, nullptr), "mvr_cloud_estimate_normals");
+    }
+  }
+
+  void align(PointCloudSource &output, const Matrix4 &guess, bool with_guess)
+  {
+    Device &d = Device::instance();
+    converged_ = false; final_ = with_guess ? guess : Matrix4::Identity(); stats_ = mvr_icp_stats();
+    if (!input_ || !target_) { state_ = MVR_CONV_NO_CORRESPONDENCES; return; }
+    if (rejectors_.size() > (size_t)MVR_MAX_REJECTORS) throw Error(MVR_E_ARG, "mvr: more than MVR_MAX_REJECTORS correspondence rejectors");
+    upload_with_normals(d, src_.s, *input_);
+    upload_with_normals(d, tgt_.s, *target_);
+    if (with_guess) d.check(mvr_cloud_transform_f32(d.ctx(), src_.s, src_.s, guess.data()), "mvr_cloud_transform_f32");
+    std::vector<mvr_rejector> chain;
+    for (const CorrespondenceRejectorPtr &r : rejectors_) chain.push_back(r->stage());
+    std::vector<mvr_gicp_iter_trace> trace((size_t)std::max(1, p_.max_iterations));
+    float T[16];
+    const int rc = mvr_icp_align_gicp(d.ctx(), src_.s, tgt_.s, out_.s, &p_, chain.data(), (int)chain.size(), T, &stats_, trace.data(), (int)trace.size());
+    if (rc == MVR_OK || rc == MVR_E_NOCORR) {        // every rejector learns what its stage did in the last iteration
+      const size_t last = std::min(trace.size() - 1, (size_t)std::max(0, stats_.iterations - (rc == MVR_OK ? 1 : 0)));
+      for (size_t k = 0; k < rejectors_.size(); ++k) rejectors_[k]->noteStage(trace[last].stages[k]);
+    }
+    if (rc != MVR_OK && rc != MVR_E_NOCORR && rc != MVR_E_SINGULAR) d.check(rc, "mvr_icp_align_gicp");
+    if (rc == MVR_E_NOCORR)
+      std::fprintf(stderr, "[mvr::GeneralizedIterativeClosestPoint::computeTransformation] Not enough correspondences found. "
+                           "Relax your threshold parameters.\n");
+    if (with_guess) { float F[16]; mvr_mat4f_mul(T, guess.data(), F); for (int k = 0; k < 16; ++k) final_.m[k] = F[k]; }
+    else for (int k = 0; k < 16; ++k) final_.m[k] = T[k];
+    converged_ = stats_.converged != 0;
+    state_ = stats_.state;
+    if (detail::has_normal<PointSource>::value && &output != input_.get()) output = *input_;      // (the fields beside x, y, z and the normal)
+    detail::download_cloud(d, out_.s, output);
+    aligned_once_ = true;
+  }
+
+  mvr_gicp_params p_;
+  mvr_icp_stats stats_ = mvr_icp_stats();
+  int k_correspondences_ = 20;
+  PointCloudSourcePtr input_;
+  PointCloudTargetPtr target_;
+  Matrix4 final_;
+  bool converged_ = false, aligned_once_ = false;
+  int state_ = MVR_CONV_NOT;
+  std::vector<CorrespondenceRejectorPtr> rejectors_;
+  SlotGuard src_, tgt_, out_;
+};
+
 // ---------------------------------------------------------------- normals
 namespace search {
 // pcl::search::KdTree: accepted and ignored -- the neighbour search is the library's grid walk on the GPU

@@ -490,6 +490,47 @@ class ScanCloud {
     pose = PclMatrixCaster<RowMatrixd>(Matrix4f(res.T));
     return true;
   }
+  // EXTENSION (pcl::GeneralizedIterativeClosestPoint on the raw points, on the GPU; rules G1-G10 at mvr_icp_align_gicp in
+  // mvr_hip.h): the plane-to-plane refinement of this scan against `target`, both as their `points` lie.  A scan whose `rich`
+  // holds one record per point uses those normals (estimateNormals, smooth with compute_normals, or a file that carries them);
+  // otherwise the normals of its k_normals nearest neighbours are estimated in the slot.  On true, `pose` takes this scan's
+  // points onto the target's (setMatrix(pose * getMatrix()) when both lie under their poses already).  false (pose
+  // untouched): too few correspondences, or a singular system; `stats` (optional) says which.  Refused parameters throw.
+  struct GICPParams {
+    mvr_gicp_params gicp;
+    int k_normals = 20;                  // setCorrespondenceRandomness
+    GICPParams() { mvr_gicp_default_params(&gicp); }
+  };
+  bool alignGICP(const ScanCloud &target, const GICPParams &params, RowMatrixd &pose, mvr_icp_stats *stats = nullptr) const
+  {
+    Device &d = Device::instance();
+    SlotGuard s, t;
+    uploadWithNormals(d, s.s, params.k_normals);
+    target.uploadWithNormals(d, t.s, params.k_normals);
+    float T[16];
+    mvr_icp_stats st = mvr_icp_stats();
+    const int rc = mvr_icp_align_gicp(d.ctx(), s.s, t.s, -1, &params.gicp, nullptr, 0, T, &st, nullptr, 0);
+    if (stats) *stats = st;
+    if (rc == MVR_E_NOCORR || rc == MVR_E_SINGULAR) return false;
+    d.check(rc, "mvr_icp_align_gicp");
+    pose = PclMatrixCaster<RowMatrixd>(Matrix4f(T));
+    return true;
+  }
+  void uploadWithNormals(Device &d, int slot, int k_normals) const
+  {
+    const size_t n = points.size();
+    d.upload(slot, points);
+    if (!n) return;
+    if (rich.size() == n) {
+      std::vector<float> nrm(4 * n);
+      for (size_t i = 0; i < n; ++i) { nrm[4 * i] = rich[i].normal_x; nrm[4 * i + 1] = rich[i].normal_y; nrm[4 * i + 2] = rich[i].normal_z; nrm[4 * i + 3] = 0.f; }
+      d.check(mvr_cloud_upload_normals(d.ctx(), slot, nrm.data(), n, 16), "mvr_cloud_upload_normals");
+    } else {
+      mvr_normal_params np = mvr_normal_params();
+      np.k = k_normals;
+      d.check(mvr_cloud_estimate_normals(d.ctx(), 1, &slot, &np, nullptr), "mvr_cloud_estimate_normals");
+    }
+  }
   // the descriptor rows of the points detectKeypoints does not list become NaN (false: the detector refused its parameters)
   bool keepKeypointRows(const mvr_iss_params &p, std::vector<FPFHSignature33> &feat) const
   {

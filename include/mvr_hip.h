@@ -886,6 +886,94 @@ int  mvr_icp_align_rejected(mvr_ctx *ctx, int src_slot, int tgt_slot, int out_sl
                             const mvr_rejector *chain, int n_chain, float T_out[16], mvr_icp_stats *stats,
                             mvr_icp_iter_trace *trace /* optional */, int trace_cap);
 
+/* ---- Generalized ICP (EXTENSION: pcl::GeneralizedIterativeClosestPoint) ----------------------------------------------------
+ * Plane-to-plane ICP: every correspondence is weighed by the surface each of its two points lies on, so two scans that sample
+ * the same surface at different points -- every pair of turntable views -- are not pulled point onto point.  PCL was not at
+ * hand; the model is pcl/registration/gicp.h and impl/gicp.hpp as published; deviations are marked.  Opt-in: no other entry
+ * changes.
+ *  G1. Inputs: both slots carry normals (mvr_cloud_upload_normals / mvr_cloud_estimate_normals), else MVR_E_ARG before any GPU
+ *      work, as under R5.  A normal is used as a direction only: neither its sign nor its length matters.  PCL's regularised
+ *      covariance of a k-neighbourhood (eigenvalues 1, 1, eps along its principal directions) is exactly I - (1 - eps) n n^T
+ *      with n the eigenvector of the smallest eigenvalue, which is what mvr_cloud_estimate_normals in k mode leaves.
+ *  G2. An outer iteration: the search of mvr_icp_align_rejected (max_corr_dist, use_reciprocal, fma_dist); the rejector chain
+ *      (R1-R7); fewer than 3 live correspondences: MVR_E_NOCORR with state NO_CORRESPONDENCES; the inner optimisation (G5-G7)
+ *      over the live correspondences (i, j) with the current source points p_i and normals s_i and the target's q_j and n_j.
+ *  G3. Side matrices, all arithmetic in f64.  n^ = n / |n| when the three components are finite and |n|^2 > 0.
+ *      A_i = I - (1 - eps) s^ s^T, B_j = I - (1 - eps) n^ n^T, eps = gicp_epsilon in (0, 1] (PCL: 0.001).  A side whose normal
+ *      fails the test takes I: the library's rule (PCL has no such case, its covariances come from neighbourhoods).
+ *  G4. W_i = (A_i + B_j)^-1, fixed for the whole inner optimisation: the current normals already carry the rotation
+ *      accumulated so far, which is PCL's R C_s R^T + C_t.  A + B has eigenvalues in [2 eps, 2]; the inverse is the closed-form
+ *      symmetric one (cofactors over the determinant) in f64.
+ *  G5. The objective at X = (R, t): F = (1 / m) sum r^T W r, y = R p + t, r = y - q.  Linearised by y' = Exp(w) y + v,
+ *      delta = (w, v), rotation first as in the point-to-plane row: J = [-[y]x | I].  The 29 sums: 0..20 the upper triangle of
+ *      H = sum J^T W J, row-major; 21..26 g = sum J^T W r; 27 the count m; 28 f = sum r^T W r.  f64, in a fixed order,
+ *      bit-identical from run to run: block partials and a one-block final sum, as the point-to-plane sums.
+ *  G6. A step: (H + lambda diag(H)) delta = -g by a 6x6 Cholesky in f64; a pivot that is <= 0 or not finite ends the
+ *      optimisation with MVR_E_SINGULAR.  The candidate is R_c = E R, t_c = E t + v, E the Rodrigues matrix of w
+ *      (|w| < 1e-8: I + K + K^2 / 2, K = [w]x).  (The damping makes the system positive definite whenever diag(H) > 0: a
+ *      rank-deficient H is caught here only when a diagonal entry is 0, e.g. every point at the origin; otherwise by G7's
+ *      lambda > 1e9.)
+ *  G7. The inner loop is Levenberg-Marquardt.  DEVIATION: PCL runs BFGS on (x, y, z, roll, pitch, yaw); the objective is the
+ *      same and so is its minimum.  Start at X = I with lambda = 1e-3 and evaluate G5 there.  While evaluations <
+ *      max_inner_iterations (PCL: 20): step by G6, evaluate at the candidate, decide.  ACCEPT when f_c < f (strictly; a NaN
+ *      fails): X and the sums become the candidate's, lambda = max(lambda / 10, 1e-9), and the loop ends when |w|_2 <
+ *      inner_rot_tol (default 1e-6 rad) and |v|_2 < inner_trans_tol (default 1e-5).  REJECT otherwise: lambda = 10 lambda,
+ *      and the loop ends when lambda > 1e9.  The loop runs on the device: the host queues inner_chunk evaluation + step pairs
+ *      behind each other and reads the state once per chunk (0: all max_inner_iterations at once; default 4); a pair queued behind the
+ *      end does nothing, so the result is bit-identical for every inner_chunk.
+ *  G8. The outer step: tr = X rounded to f32; fin = tr * fin by mvr_mat4f_mul; the current source moves exactly as in R9,
+ *      points and normals.  delta = the largest of |fin_new - fin_old| / rotation_epsilon over the 3x3 block and
+ *      |fin_new - fin_old| / transformation_epsilon over the translation column, taken in f64 from the f32 entries (PCL:
+ *      rotation_epsilon 2e-3, transformation_epsilon 5e-4, max_iterations 200, max_corr_dist 5).  ++iterations; delta < 1:
+ *      MVR_CONV_TRANSFORM; else iterations >= max_iterations: MVR_CONV_ITERATIONS; both with converged = 1, as PCL.  mse = the
+ *      mean of the survivors' f32 d2, as in R9.
+ *  G9. out_slot, T_out and the stats as in mvr_icp_align_rejected.  trace[k] (optional, k < trace_cap) records iteration k.
+ *  G10. All of R10; also MVR_E_ARG before any GPU work, with nothing written, for gicp_epsilon outside (0, 1], an epsilon or
+ *      a tolerance that is not positive and finite (transformation_epsilon, rotation_epsilon, inner_rot_tol, inner_trans_tol),
+ *      max_inner_iterations < 1.  An inner_chunk below 1 or above max_inner_iterations counts as 0.  Empty clouds follow R9
+ *      and R10.
+ * mvr_gicp_sums / mvr_gicp_solve are G5 and G5-G7 on the caller's correspondence list (query / match: host arrays of `count`
+ * entries, validated as in R8; the slots supply points and normals).  X, X_out: 4x4 column-major f64.  mvr_gicp_solve
+ * returns MVR_E_NOCORR for fewer than 3 entries and MVR_E_SINGULAR as G6; X_out and info hold the state reached.
+ * Out of scope: PCL's BFGS; setSourceCovariances / setTargetCovariances; GICP in the ring / LUM passes, in mvr_seq_run, the
+ * sharded entries and the Registrator drivers. */
+typedef struct {
+  double max_corr_dist;            /* setMaxCorrespondenceDistance (PCL's GICP: 5)                                      */
+  int    use_reciprocal;           /* setUseReciprocalCorrespondences                                                   */
+  int    fma_dist;
+  int    max_iterations;           /* setMaximumIterations (PCL's GICP: 200)                                            */
+  int    max_inner_iterations;     /* setMaximumOptimizerIterations: evaluations of the objective per outer iteration   */
+  double transformation_epsilon;   /* setTransformationEpsilon (PCL's GICP: 5e-4)                                       */
+  double rotation_epsilon;         /* setRotationEpsilon (2e-3)                                                         */
+  double gicp_epsilon;             /* the small eigenvalue of the side covariances (0.001)                              */
+  double inner_rot_tol;            /* G7: an accepted step below both tolerances ends the inner loop                    */
+  double inner_trans_tol;
+  int    inner_chunk;              /* evaluation + step pairs queued per host round trip; 0 = max_inner_iterations;
+                                      default 4, the fastest of 1 / 4 / 0 on the 200k view pair (profiles/gicp_bench.json)     */
+} mvr_gicp_params;
+void mvr_gicp_default_params(mvr_gicp_params *p);
+typedef struct {
+  uint32_t n_found;                                /* correspondences the search found, before the chain */
+  mvr_rejector_stage stages[MVR_MAX_REJECTORS];
+  uint32_t n_corr;                                 /* survivors: what the optimiser saw */
+  double   mse;
+  double   f0, f1;                                 /* the objective per correspondence at identity and at X */
+  uint32_t inner_evals, inner_accepted;
+  double   lambda;
+  float    tr[16];                                 /* X rounded to f32 (identity if none was solved) */
+} mvr_gicp_iter_trace;
+typedef struct {
+  uint32_t evaluations, accepted;
+  double   lambda, f0, f1;
+} mvr_gicp_info;
+int  mvr_icp_align_gicp(mvr_ctx *ctx, int src_slot, int tgt_slot, int out_slot, const mvr_gicp_params *params,
+                        const mvr_rejector *chain, int n_chain, float T_out[16], mvr_icp_stats *stats,
+                        mvr_gicp_iter_trace *trace /* optional */, int trace_cap);
+int  mvr_gicp_sums(mvr_ctx *ctx, int src_slot, int tgt_slot, const int32_t *query, const int32_t *match, size_t count,
+                   const double X[16], double gicp_epsilon, double out[29]);
+int  mvr_gicp_solve(mvr_ctx *ctx, int src_slot, int tgt_slot, const int32_t *query, const int32_t *match, size_t count,
+                    const mvr_gicp_params *params, double X_out[16], mvr_gicp_info *info);
+
 /* Registration::getFitnessScore(max_range) (registrator.cpp:572,923,1015):
  * mean squared distance of T*input to its unbounded 1-NN in the target.
  * DBL_MAX when no point qualifies. */

@@ -109,6 +109,25 @@ class IcpIterTrace(C.Structure):
                 ("tr", C.c_float * 16)]
 
 
+class GicpParams(C.Structure):
+    """mvr_gicp_params"""
+    _fields_ = [("max_corr_dist", C.c_double), ("use_reciprocal", C.c_int), ("fma_dist", C.c_int), ("max_iterations", C.c_int),
+                ("max_inner_iterations", C.c_int), ("transformation_epsilon", C.c_double), ("rotation_epsilon", C.c_double),
+                ("gicp_epsilon", C.c_double), ("inner_rot_tol", C.c_double), ("inner_trans_tol", C.c_double), ("inner_chunk", C.c_int)]
+
+
+class GicpIterTrace(C.Structure):
+    """mvr_gicp_iter_trace"""
+    _fields_ = [("n_found", C.c_uint32), ("stages", RejectorStage * MAX_REJECTORS), ("n_corr", C.c_uint32), ("mse", C.c_double),
+                ("f0", C.c_double), ("f1", C.c_double), ("inner_evals", C.c_uint32), ("inner_accepted", C.c_uint32),
+                ("lambda_", C.c_double), ("tr", C.c_float * 16)]
+
+
+class GicpInfo(C.Structure):
+    """mvr_gicp_info"""
+    _fields_ = [("evaluations", C.c_uint32), ("accepted", C.c_uint32), ("lambda_", C.c_double), ("f0", C.c_double), ("f1", C.c_double)]
+
+
 class PairMoments(C.Structure):
     _fields_ = [("n", C.c_double), ("mean_src", C.c_double * 3), ("mean_tgt", C.c_double * 3),
                 ("mse", C.c_double), ("sigma", C.c_double * 9)]
@@ -295,6 +314,11 @@ SIGNATURES = {
                                              _i32p, _i32p, _fp, _sz, C.POINTER(_sz), C.POINTER(RejectorStage)]),
     "mvr_icp_align_rejected": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams), C.POINTER(Rejector), C.c_int, _fp,
                                          C.POINTER(IcpStats), C.POINTER(IcpIterTrace), C.c_int]),
+    "mvr_gicp_default_params": (None, [C.POINTER(GicpParams)]),
+    "mvr_icp_align_gicp": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(GicpParams), C.POINTER(Rejector), C.c_int, _fp,
+                                     C.POINTER(IcpStats), C.POINTER(GicpIterTrace), C.c_int]),
+    "mvr_gicp_sums": (C.c_int, [_vp, C.c_int, C.c_int, _i32p, _i32p, _sz, _dp, C.c_double, _dp]),
+    "mvr_gicp_solve": (C.c_int, [_vp, C.c_int, C.c_int, _i32p, _i32p, _sz, C.POINTER(GicpParams), _dp, C.POINTER(GicpInfo)]),
     "mvr_fitness": (C.c_int, [_vp, C.c_int, C.c_int, _fp, C.c_double, C.c_int, _dp]),
     "mvr_lum_edge_from_moments": (C.c_int, [C.POINTER(PairMoments2), _dp, _dp, _dp, _dp, _dp]),
     "mvr_lum_edge_from_moments_x4": (C.c_int, [C.POINTER(PairMoments2), _dp, _dp, _dp, _dp, _dp]),
@@ -389,6 +413,20 @@ def rejector(kind, value=0.0, min_correspondences=0) -> Rejector:
     """One stage of a rejector chain (mvr_rejector): kind = "distance" (value: the largest distance), "median" (the factor),
     "trimmed" (the overlap ratio; min_correspondences), "surface_normal" (the smallest cosine), "one_to_one", or a REJ_* number."""
     return Rejector(REJ_KINDS[kind] if isinstance(kind, str) else int(kind), float(value), int(min_correspondences))
+
+
+def gicp_params(**kw) -> GicpParams:
+    """mvr_gicp_params with PCL's defaults (mvr_gicp_default_params); keywords = the fields: max_corr_dist, use_reciprocal,
+    fma_dist, max_iterations, max_inner_iterations, transformation_epsilon, rotation_epsilon, gicp_epsilon, inner_rot_tol,
+    inner_trans_tol, inner_chunk."""
+    p = GicpParams()
+    _lib.mvr_gicp_default_params(C.byref(p))
+    names = {f[0]: f[1] for f in GicpParams._fields_}
+    for k, v in kw.items():
+        if k not in names:
+            raise TypeError("gicp_params: no field %r" % k)
+        setattr(p, k, float(v) if names[k] is C.c_double else int(v))
+    return p
 
 
 def _chain(chain):
@@ -1012,6 +1050,43 @@ class Context:
         trace = [dict(n_found=tr[k].n_found, stages=_stage_dicts(tr[k].stages, nc), n_corr=tr[k].n_corr, mse=tr[k].mse,
                       tr=from_cm(np.array(tr[k].tr, np.float32))) for k in range(n_it)]
         return from_cm(T), stats, rc, trace
+
+    def icp_align_gicp(self, src, tgt, out, params: GicpParams, chain=(), return_trace=False):
+        """mvr_icp_align_gicp -> (T (4,4) float32, stats dict, rc[, trace]); rc is OK, E_NOCORR or E_SINGULAR.  trace: one dict per
+        outer iteration (n_found, stages, n_corr, mse, f0, f1, inner_evals, inner_accepted, lambda, tr (4,4) float32)."""
+        T, st = np.empty(16, np.float32), IcpStats()
+        arr, nc = _chain(chain)
+        cap = max(1, int(params.max_iterations)) if return_trace else 0
+        tr = (GicpIterTrace * max(1, cap))()
+        rc = _chk(_lib.mvr_icp_align_gicp(self._h, src, tgt, out, C.byref(params), arr, nc, _p(T, C.c_float), C.byref(st),
+                                          tr if return_trace else None, cap), self._h, allow=(E_NOCORR, E_SINGULAR))
+        stats = self._stats(st)
+        if not return_trace:
+            return from_cm(T), stats, rc
+        n_it = min(cap, stats["iterations"] + (1 if rc != OK else 0))
+        trace = [{"n_found": tr[k].n_found, "stages": _stage_dicts(tr[k].stages, nc), "n_corr": tr[k].n_corr, "mse": tr[k].mse,
+                  "f0": tr[k].f0, "f1": tr[k].f1, "inner_evals": tr[k].inner_evals, "inner_accepted": tr[k].inner_accepted,
+                  "lambda": tr[k].lambda_, "tr": from_cm(np.array(tr[k].tr, np.float32))} for k in range(n_it)]
+        return from_cm(T), stats, rc, trace
+
+    def gicp_sums(self, s, t, query, match, X=None, gicp_epsilon=1e-3):
+        """mvr_gicp_sums: the 29 sums of rule G5 at X ((4,4) float64, identity by default) over the caller's list -> float64[29]"""
+        qi, mi = np.ascontiguousarray(query, np.int32), np.ascontiguousarray(match, np.int32)
+        Xc = to_cm(np.eye(4) if X is None else X, np.float64)
+        out = np.empty(29, np.float64)
+        _chk(_lib.mvr_gicp_sums(self._h, s, t, _p(qi, C.c_int32), _p(mi, C.c_int32), len(qi), _p(Xc, C.c_double), float(gicp_epsilon),
+                                _p(out, C.c_double)), self._h)
+        return out
+
+    def gicp_solve(self, s, t, query, match, params: GicpParams):
+        """mvr_gicp_solve: the inner optimisation (rules G5-G7) over the caller's list -> (X (4,4) float64, info dict(evaluations,
+        accepted, lambda, f0, f1), rc); rc is OK, E_NOCORR or E_SINGULAR."""
+        qi, mi = np.ascontiguousarray(query, np.int32), np.ascontiguousarray(match, np.int32)
+        X, info = np.empty(16, np.float64), GicpInfo()
+        rc = _chk(_lib.mvr_gicp_solve(self._h, s, t, _p(qi, C.c_int32), _p(mi, C.c_int32), len(qi), C.byref(params), _p(X, C.c_double),
+                                      C.byref(info)), self._h, allow=(E_NOCORR, E_SINGULAR))
+        return from_cm(X), {"evaluations": info.evaluations, "accepted": info.accepted, "lambda": info.lambda_, "f0": info.f0,
+                            "f1": info.f1}, rc
 
     def pair_batch_correspondences(self, k, cap):
         """(query, match, d2) of pair k of the last fused batch / ring step (mvr_pair_batch_correspondences)"""

@@ -459,6 +459,8 @@ API int mvr_ctx_destroy(mvr_ctx *ctx)
   if (c->rej_row) (void)hipFree(c->rej_row);
   if (c->rej_win) (void)hipFree(c->rej_win);
   if (c->rej_host) (void)hipHostFree(c->rej_host);
+  if (c->gicp_state) (void)hipFree(c->gicp_state);
+  if (c->gicp_host) (void)hipHostFree(c->gicp_host);
   if (c->h_pose_in) (void)hipHostFree(c->h_pose_in);
   if (c->pose_tab) (void)hipFree(c->pose_tab);
   if (c->done_counter) (void)hipFree(c->done_counter);
@@ -2385,6 +2387,224 @@ API int mvr_icp_align_rejected(mvr_ctx *ctx, int ss, int ts, int os, const mvr_i
   }
   scratch.has_normals = false;
   if (os >= 0) {            // output = final * (*input), from the ORIGINAL input, as mvr_icp_align writes it
+    if (os != ss) { c->slots[os].n = 0; if (int rc = cloud_reserve(c, c->slots[os], ns, false)) return rc; }
+    if (int rc = launch_transform_f32(c, c->slots[ss].pts, c->slots[os].pts, ns, fin)) return rc;
+    c->slots[os].n = ns;
+    if (os != ss) inherit_point_set(c->slots[os], c->slots[ss]);
+    else c->slots[os].forget_pose();
+    c->slots[os].stale_coords();
+    if (src_normals) {
+      if (int rc = ensure(c, c->slots[os].nrm, c->slots[os].nrm_cap, ns)) return rc;
+      if (int rc = launch_rotate_normals_f32(c, c->slots[ss].nrm, c->slots[os].nrm, ns, fin)) return rc;
+    }
+    c->slots[os].has_normals = c->slots[ss].has_normals;
+  }
+  std::memcpy(T_out, fin, sizeof fin);
+  if (st) {
+    st->iterations = iters; st->converged = converged; st->state = state; st->n_corr = ncorr; st->mse = cur_mse;
+    st->evals = 0.0; st->fwd_queries = fwdq; st->ms = now_ms() - t0;
+  }
+  return status;
+}
+
+// ---- Generalized ICP (rules G1-G10 in mvr_hip.h; kernels and the optimiser's driver in mvr_gicp.hip)
+API void mvr_gicp_default_params(mvr_gicp_params *p)
+{
+  if (!p) return;
+  p->max_corr_dist = 5.0; p->use_reciprocal = 0; p->fma_dist = 0; p->max_iterations = 200; p->max_inner_iterations = 20;
+  p->transformation_epsilon = 5e-4; p->rotation_epsilon = 2e-3; p->gicp_epsilon = 1e-3; p->inner_rot_tol = 1e-6;
+  p->inner_trans_tol = 1e-5; p->inner_chunk = 4;
+}
+
+namespace {
+// G10's own refusals and G1's normals
+int gicp_args(Ctx *c, int ss, int ts, const mvr_gicp_params *p)
+{
+  const auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+  if (!(p->gicp_epsilon > 0.0 && p->gicp_epsilon <= 1.0)) return set_error(c, MVR_E_ARG, "GICP: gicp_epsilon outside (0, 1]");
+  if (!pos(p->transformation_epsilon) || !pos(p->rotation_epsilon) || !pos(p->inner_rot_tol) || !pos(p->inner_trans_tol))
+    return set_error(c, MVR_E_ARG, "GICP: an epsilon or a tolerance is not positive and finite");
+  if (p->max_inner_iterations < 1) return set_error(c, MVR_E_ARG, "GICP: max_inner_iterations < 1");
+  const Cloud &s = c->slots[ss], &t = c->slots[ts];
+  if (s.n && t.n && !(s.has_normals && t.has_normals))
+    return set_error(c, MVR_E_ARG, "GICP needs the normals of both clouds (mvr_cloud_upload_normals / mvr_cloud_estimate_normals)");
+  return MVR_OK;
+}
+
+// the caller's list, validated as in R8 and laid out as the search would have left it: match[] by source index
+int gicp_list(Ctx *c, int ss, int ts, const int32_t *query, const int32_t *match, size_t count)
+{
+  const Cloud &s = c->slots[ss], &t = c->slots[ts];
+  if (s.n > 0x7FFFFFF0ull || t.n > 0x7FFFFFF0ull) return set_error(c, MVR_E_ARG, "GICP list: cloud too large");
+  if (s.pts_stale || t.pts_stale) return set_error(c, MVR_E_ARG, "GICP list: a cloud's points are not current (pipelined run)");
+  if (count > s.n) return set_error(c, MVR_E_ARG, "GICP list: more entries than source points (query indices must be distinct)");
+  if (count && !(s.has_normals && t.has_normals))
+    return set_error(c, MVR_E_ARG, "GICP needs the normals of both clouds (mvr_cloud_upload_normals / mvr_cloud_estimate_normals)");
+  std::vector<int32_t> hm(s.n, -1);
+  for (size_t k = 0; k < count; ++k) {
+    if (query[k] < 0 || (size_t)query[k] >= s.n || match[k] < 0 || (size_t)match[k] >= t.n) return set_error(c, MVR_E_ARG, "GICP list: index out of range");
+    if (hm[query[k]] >= 0) return set_error(c, MVR_E_ARG, "GICP list: a query index appears twice");
+    hm[query[k]] = match[k];
+  }
+  if (count == 0) return MVR_OK;
+  MVR_HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = ensure_gicp_state(c)) return rc;
+  if (int rc = ensure(c, c->match, c->match_cap, s.n)) return rc;
+  MVR_HIP_TRY(c, hipMemcpyAsync(c->match, hm.data(), s.n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));     // hm goes out of scope
+  return MVR_OK;
+}
+
+inline const uint32_t *gicp_host_words(const Ctx *c) { return reinterpret_cast<const uint32_t *>(c->gicp_host + kGicpWordsAt); }
+
+// R row-major + t of the state block -> 4x4 column-major
+void gicp_mat(const double *x, double *T)
+{
+  for (int k = 0; k < 16; ++k) T[k] = 0.0;
+  for (int r = 0; r < 3; ++r) { for (int k = 0; k < 3; ++k) T[r + 4 * k] = x[3 * r + k]; T[12 + r] = x[9 + r]; }
+  T[15] = 1.0;
+}
+
+int gicp_ride(Ctx *c)      // the chain's words and the sum of the survivors' d2 come with the optimiser's first round trip
+{
+  MVR_HIP_TRY(c, hipMemcpyAsync(c->rej_host, c->rej_row, kRejCopyBytes, hipMemcpyDeviceToHost, c->stream));
+  return MVR_OK;
+}
+}  // namespace
+
+API int mvr_gicp_sums(mvr_ctx *ctx, int ss, int ts, const int32_t *query, const int32_t *match, size_t count, const double X[16],
+                      double eps, double out[29])
+{
+  if (!ctx || !slot_ok(ss) || !slot_ok(ts) || !X || !out || (count && (!query || !match))) return MVR_E_ARG;
+  Ctx *c = CTX(ctx);
+  if (!(eps > 0.0 && eps <= 1.0)) return set_error(c, MVR_E_ARG, "GICP: gicp_epsilon outside (0, 1]");
+  for (int k = 0; k < 16; ++k) if (!std::isfinite(X[k])) return set_error(c, MVR_E_ARG, "GICP: X is not finite");
+  if (int rc = gicp_list(c, ss, ts, query, match, count)) return rc;
+  for (int k = 0; k < 29; ++k) out[k] = 0.0;
+  if (count == 0) return MVR_OK;
+  const Cloud &s = c->slots[ss], &t = c->slots[ts];
+  if (int rc = launch_gicp_init(c, X)) return rc;
+  if (int rc = launch_gicp_pairs(c, s.pts, s.nrm, t.pts, t.nrm, c->match, nullptr, 0, s.n, nullptr, eps, true, 1)) return rc;
+  if (int rc = read_gicp_state(c)) return rc;
+  std::memcpy(out, c->gicp_host + kGicpSums, 29 * sizeof(double));
+  return MVR_OK;
+}
+
+API int mvr_gicp_solve(mvr_ctx *ctx, int ss, int ts, const int32_t *query, const int32_t *match, size_t count, const mvr_gicp_params *p,
+                       double X_out[16], mvr_gicp_info *info)
+{
+  if (!ctx || !slot_ok(ss) || !slot_ok(ts) || !p || !X_out || (count && (!query || !match))) return MVR_E_ARG;
+  Ctx *c = CTX(ctx);
+  if (int rc = gicp_args(c, ss, ts, p)) return rc;
+  if (int rc = gicp_list(c, ss, ts, query, match, count)) return rc;
+  const double I[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+  gicp_mat(I, X_out);
+  if (info) std::memset(info, 0, sizeof *info);
+  if (count < 3) return set_error(c, MVR_E_NOCORR, "GICP: fewer than 3 correspondences");
+  const Cloud &s = c->slots[ss], &t = c->slots[ts];
+  if (int rc = gicp_optimise(c, s.pts, s.nrm, t.pts, t.nrm, c->match, nullptr, 0, s.n, p, nullptr)) return rc;
+  const double *h = c->gicp_host;
+  const uint32_t *w = gicp_host_words(c);
+  gicp_mat(h + kGicpX, X_out);
+  if (info) { info->evaluations = w[kGicpEvals]; info->accepted = w[kGicpAccepted]; info->lambda = h[kGicpLambda]; info->f0 = h[kGicpF0]; info->f1 = h[kGicpF1]; }
+  const int status = (int)w[kGicpStatus];
+  if (status != MVR_OK) return set_error(c, status, "GICP: the inner optimisation stopped (a pivot of the damped system is not positive)");
+  return MVR_OK;
+}
+
+// PCL's GeneralizedIterativeClosestPoint::computeTransformation (G2, G8): the loop of mvr_icp_align_rejected with the device's
+// Levenberg-Marquardt in the estimator's place.  Search, chain, the sum of the survivors' d2 and the first chunk of the
+// optimiser are queued behind each other; the first round trip of the optimiser brings the chain's words along.
+API int mvr_icp_align_gicp(mvr_ctx *ctx, int ss, int ts, int os, const mvr_gicp_params *p, const mvr_rejector *chain, int n_chain,
+                           float T_out[16], mvr_icp_stats *st, mvr_gicp_iter_trace *trace, int trace_cap)
+{
+  if (!ctx || !slot_ok(ss) || !slot_ok(ts) || (os >= 0 && !slot_ok(os)) || !p || !T_out || (trace && trace_cap < 0)) return MVR_E_ARG;
+  Ctx *c = CTX(ctx);
+  bool oto = false;
+  if (int rc = reject_args(c, ss, ts, chain, n_chain, &oto)) return rc;
+  if (int rc = gicp_args(c, ss, ts, p)) return rc;
+  Cloud &tgt = c->slots[ts];
+  MVR_HIP_TRY(c, hipSetDevice(c->device));
+  const double t0 = now_ms();
+  const size_t ns = c->slots[ss].n, nt = tgt.n;
+  Cloud &scratch = c->slots[kScratchCur];
+  Cloud *curp = &c->slots[ss];
+  bool on_scratch = false;
+  const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  float fin[16], tr[16];
+  std::memcpy(fin, I, sizeof I); std::memcpy(tr, I, sizeof I);
+  const double origin[3] = {0.0, 0.0, 0.0};
+  double cur_mse = 0.0, fwdq = 0.0;
+  int iters = 0, converged = 0, state = MVR_CONV_NOT, ncorr = 0, status = MVR_OK;
+  if (ns == 0 || nt == 0) { state = MVR_CONV_NO_CORRESPONDENCES; status = MVR_E_NOCORR; }
+  else {
+    if (int rc = ensure_reject_state(c, nt, oto)) return rc;
+    if (int rc = ensure_gicp_state(c)) return rc;
+    if (c->nn_mode != 0) { if (int rc = ensure_index(c, c->slots[ss])) return rc; }
+  }
+  while (status == MVR_OK && !converged) {
+    SearchPlan plan;
+    if (int rc = run_search(c, *curp, tgt, 0, ns, p->max_corr_dist, p->use_reciprocal != 0, p->fma_dist != 0, nullptr, &plan)) return rc;
+    if (int rc = launch_pass1(c, curp->pts, tgt.pts, c->keys, c->rkeys, plan.slot, plan.count, plan.qperm, plan.tinv, 0, ns,
+                              p->max_corr_dist * p->max_corr_dist, p->use_reciprocal != 0, c->match, c->moments)) return rc;
+    if (int rc = launch_reject_chain(c, chain, n_chain, c->keys, c->match, ns, nt, curp->nrm, tgt.nrm, c->moments, 0u)) return rc;
+    if (int rc = launch_moments2(c, curp->pts, tgt.pts, c->match, c->keys, plan.qperm, 0, ns, origin, c->rej_row)) return rc;      // (count and the sum of d2)
+    if (int rc = gicp_optimise(c, curp->pts, curp->nrm, tgt.pts, tgt.nrm, c->match, plan.qperm, 0, ns, p, gicp_ride)) return rc;
+    const double *h = c->rej_host, *g = c->gicp_host;
+    const uint32_t *w = gicp_host_words(c);
+    mvr_gicp_iter_trace *tk = (trace && iters < trace_cap) ? &trace[iters] : nullptr;
+    uint32_t n_found = 0, n_live = 0;
+    if (tk) std::memset(tk, 0, sizeof *tk);
+    reject_stages(c, n_chain, &n_found, tk ? tk->stages : nullptr, &n_live);
+    if ((double)n_live != h[0] || (double)n_live != g[kGicpSums + 27]) return set_error(c, MVR_E_HIP, "mvr_icp_align_gicp: the stage counts and the sums disagree");
+    fwdq += (double)ns;
+    ncorr = (int)n_live;
+    if (tk) { tk->n_found = n_found; tk->n_corr = n_live; std::memcpy(tk->tr, I, sizeof I); }
+    if (n_live < 3u) { state = MVR_CONV_NO_CORRESPONDENCES; converged = 0; status = MVR_E_NOCORR; break; }
+    cur_mse = h[31] / h[0];                          // mean of the survivors' (f32) squared distances, summed in f64
+    if (tk) {
+      tk->mse = cur_mse; tk->f0 = g[kGicpF0]; tk->f1 = g[kGicpF1]; tk->inner_evals = w[kGicpEvals]; tk->inner_accepted = w[kGicpAccepted];
+      tk->lambda = g[kGicpLambda];
+    }
+    if ((int)w[kGicpStatus] != MVR_OK) { state = MVR_CONV_NO_CORRESPONDENCES; converged = 0; status = (int)w[kGicpStatus]; break; }
+    double Xd[16];
+    gicp_mat(g + kGicpX, Xd);
+    for (int k = 0; k < 16; ++k) tr[k] = (float)Xd[k];                 // G8: X rounded to f32
+    if (tk) std::memcpy(tk->tr, tr, sizeof tr);
+    float before[16];
+    std::memcpy(before, fin, sizeof fin);
+    mvr_mat4f_mul(tr, fin, fin);
+    double delta = 0.0;
+    for (int k = 0; k < 3; ++k) {
+      for (int r = 0; r < 3; ++r) delta = std::max(delta, std::fabs((double)fin[r + 4 * k] - (double)before[r + 4 * k]) / p->rotation_epsilon);
+      delta = std::max(delta, std::fabs((double)fin[12 + k] - (double)before[12 + k]) / p->transformation_epsilon);
+    }
+    ++iters;
+    if (delta < 1.0) { state = MVR_CONV_TRANSFORM; converged = 1; }
+    else if (iters >= p->max_iterations) { state = MVR_CONV_ITERATIONS; converged = 1; }
+    if (!converged) {          // the current source moves as mvr_cloud_transform_f32 moves a cloud: points and normals
+      if (!on_scratch) {
+        scratch.n = 0;
+        if (int rc = cloud_reserve(c, scratch, ns, false)) return rc;
+        if (int rc = ensure(c, scratch.nrm, scratch.nrm_cap, ns)) return rc;
+        if (int rc = launch_transform_f32(c, curp->pts, scratch.pts, ns, tr)) return rc;
+        if (int rc = launch_rotate_normals_f32(c, curp->nrm, scratch.nrm, ns, tr)) return rc;
+        scratch.n = ns;
+        inherit_point_set(scratch, c->slots[ss]);
+        on_scratch = true;
+        curp = &scratch;
+      } else {
+        if (int rc = launch_transform_f32(c, curp->pts, curp->pts, ns, tr)) return rc;
+        if (int rc = launch_rotate_normals_f32(c, curp->nrm, curp->nrm, ns, tr)) return rc;
+      }
+      curp->stale_coords();
+      curp->pose_known = false; curp->grid.reset();
+    }
+  }
+  scratch.has_normals = false;
+  if (status == MVR_E_SINGULAR) (void)set_error(c, MVR_E_SINGULAR, "mvr_icp_align_gicp: a pivot of the damped system is not positive");
+  if (os >= 0) {            // output = final * (*input), from the ORIGINAL input, as mvr_icp_align writes it
+    const bool src_normals = c->slots[ss].has_normals && ns;
     if (os != ss) { c->slots[os].n = 0; if (int rc = cloud_reserve(c, c->slots[os], ns, false)) return rc; }
     if (int rc = launch_transform_f32(c, c->slots[ss].pts, c->slots[os].pts, ns, fin)) return rc;
     c->slots[os].n = ns;

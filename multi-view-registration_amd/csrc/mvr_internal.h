@@ -249,6 +249,8 @@ struct Ctx {
   double *rej_row = nullptr, *rej_host = nullptr;     // device, pinned host (the copied part only)
   nnkey_t *rej_win = nullptr; size_t rej_win_cap = 0; // ONE_TO_ONE: per target the smallest (d2 bits << 32 | query); all ~0 between calls
   bool rej_win_dirty = false;                         // ... unless a chain failed between marking and clearing: filled again before the next use
+  // Generalized ICP (mvr_gicp.hip): the optimiser's state block (layout at kGicpStateDoubles below) and its pinned host copy
+  double *gicp_state = nullptr, *gicp_host = nullptr;
   int seq_rider = 1;                                  // mvr_seq_run: the model's tail is refreshed by the launch that poses the next source
   // index-build scratch
   uint32_t *codes_a = nullptr, *codes_b = nullptr, *idx_a = nullptr; size_t sort_cap = 0;
@@ -845,6 +847,25 @@ int ensure_reject_state(Ctx *c, size_t nt, bool one_to_one);
 // double holding the number live at entry (pass 1's moments[0]), or null: found_host.  Nothing comes to the host.
 int launch_reject_chain(Ctx *c, const mvr_rejector *chain, int n_chain, const nnkey_t *keys, int32_t *match, size_t ns, size_t nt,
                         const float4 *snrm, const float4 *tnrm, const double *found, uint32_t found_host);
+// ---- Generalized ICP (mvr_gicp.hip; rules G1-G10 at mvr_icp_align_gicp in mvr_hip.h)
+// Layout of Ctx::gicp_state, in doubles: X (R row-major, t), the candidate Xc, the 29 sums at X, lambda, the objective per
+// correspondence at identity and at X, the norms of the step that made the candidate; then four uint32 words.
+constexpr int kGicpX = 0, kGicpXc = 12, kGicpSums = 24, kGicpLambda = 53, kGicpF0 = 54, kGicpF1 = 55, kGicpStepRot = 56,
+              kGicpStepTrans = 57, kGicpWordsAt = 58, kGicpStateDoubles = 64;
+constexpr int kGicpEvals = 0, kGicpAccepted = 1, kGicpDone = 2, kGicpStatus = 3;
+constexpr size_t kGicpStateBytes = (size_t)kGicpStateDoubles * sizeof(double);
+int ensure_gicp_state(Ctx *c);
+// the state block at X (column-major 4x4, or null: identity), lambda = 1e-3, counters and `done` cleared
+int launch_gicp_init(Ctx *c, const double X[16]);
+// `pairs` evaluation + step launches over match[] (q_count entries from q_begin, through qperm if given); sums_only: one
+// evaluation whose 29 sums are left at kGicpSums (p may be null)
+int launch_gicp_pairs(Ctx *c, const float4 *src, const float4 *snrm, const float4 *tgt, const float4 *tnrm, const int32_t *match,
+                      const uint32_t *qperm, size_t q_begin, size_t q_count, const mvr_gicp_params *p, double eps, bool sums_only,
+                      int pairs);
+int read_gicp_state(Ctx *c);                       // state block -> Ctx::gicp_host, synchronised
+// the whole inner optimisation (G7) from X = I; `ride` (optional) queues the caller's own copies before the first round trip
+int gicp_optimise(Ctx *c, const float4 *src, const float4 *snrm, const float4 *tgt, const float4 *tnrm, const int32_t *match,
+                  const uint32_t *qperm, size_t q_begin, size_t q_count, const mvr_gicp_params *p, int (*ride)(Ctx *));
 int launch_rotate_normals_f32(Ctx *c, const float4 *in, float4 *out, size_t n, const float T[16]);
 int launch_rotate_normals_f64(Ctx *c, const float4 *in, float4 *out, size_t n, const double T[16]);
 int launch_fitness(Ctx *c, const nnkey_t *keys, size_t n, double max_range, double *moments);
