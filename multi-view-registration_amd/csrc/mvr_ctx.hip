@@ -2069,6 +2069,32 @@ struct Criteria {
     return false;
   }
 };
+
+// The output slot of an align: final * (the ORIGINAL input), alias-safe (registrator.cpp:920).  The one place that keeps the
+// slot's bookkeeping, next to finish_dst for the filters; its rule is mvr_cloud_transform_f32's.  To another slot: the source's
+// point set (its ordering, not its pose or grid) and the source's segment table -- a slot that was a shard must not number
+// the align's points by the table of what it held before.  In place: the slot's points moved by a FLOAT matrix -- they are
+// neither the set's upload coordinates nor a known f64 pose of them any more, and a grid built in the old frame must not be
+// walked with them; the table stays, as it does for a transform in place.  with_normals: ICP::transformCloud rotates the
+// source normals too (the sharded align has none).
+int finish_align_out(Ctx *c, int os, int ss, const float fin[16], bool with_normals)
+{
+  Cloud &o = c->slots[os];
+  const Cloud &s = c->slots[ss];
+  const size_t ns = s.n;
+  if (os != ss) { o.n = 0; if (int rc = cloud_reserve(c, o, ns, false)) return rc; }
+  if (int rc = launch_transform_f32(c, s.pts, o.pts, ns, fin)) return rc;
+  o.n = ns;
+  if (os != ss) { inherit_point_set(o, s); o.segs = s.segs; }
+  else o.forget_pose();
+  o.stale_coords();
+  if (with_normals && s.has_normals && ns) {
+    if (int rc = ensure(c, o.nrm, o.nrm_cap, ns)) return rc;
+    if (int rc = launch_rotate_normals_f32(c, s.nrm, o.nrm, ns, fin)) return rc;
+  }
+  o.has_normals = with_normals && s.has_normals;
+  return MVR_OK;
+}
 }  // namespace
 
 API int mvr_icp_align(mvr_ctx *ctx, int ss, int ts, int os, const mvr_icp_params *p, float T_out[16],
@@ -2151,24 +2177,7 @@ API int mvr_icp_align(mvr_ctx *ctx, int ss, int ts, int os, const mvr_icp_params
     }
   } while (!converged);
   // output = final * (*input), from the ORIGINAL input: alias-safe (registrator.cpp:920)
-  if (os >= 0) {
-    if (os != ss) { c->slots[os].n = 0; if (int rc = cloud_reserve(c, c->slots[os], ns, false)) return rc; }
-    if (int rc = launch_transform_f32(c, c->slots[ss].pts, c->slots[os].pts, ns, fin)) return rc;
-    c->slots[os].n = ns;
-    if (os != ss) inherit_point_set(c->slots[os], c->slots[ss]);      // (the output keeps the set's ordering, not its pose or grid)
-    else {
-      // the aliased align(*source_) of registrator.cpp:920: the slot's points moved in place by a FLOAT matrix -- they are
-      // neither the set's upload coordinates nor a known f64 pose of them any more, and a grid built in the old frame
-      // must not be walked with them (the other in-place paths: mvr_cloud_transform, _f32, _batch)
-      c->slots[os].forget_pose();
-    }
-    c->slots[os].stale_coords();
-    if (c->slots[ss].has_normals && ns) {      // ICP::transformCloud rotates the source normals too
-      if (int rc = ensure(c, c->slots[os].nrm, c->slots[os].nrm_cap, ns)) return rc;
-      if (int rc = launch_rotate_normals_f32(c, c->slots[ss].nrm, c->slots[os].nrm, ns, fin)) return rc;
-    }
-    c->slots[os].has_normals = c->slots[ss].has_normals;
-  }
+  if (os >= 0) { if (int rc = finish_align_out(c, os, ss, fin, true)) return rc; }      // output = final * (*input), from the ORIGINAL input
   std::memcpy(T_out, fin, sizeof fin);
   if (st && c->nn_mode != 0) {
     evals = evals_total;
@@ -2386,19 +2395,7 @@ API int mvr_icp_align_rejected(mvr_ctx *ctx, int ss, int ts, int os, const mvr_i
     }
   }
   scratch.has_normals = false;
-  if (os >= 0) {            // output = final * (*input), from the ORIGINAL input, as mvr_icp_align writes it
-    if (os != ss) { c->slots[os].n = 0; if (int rc = cloud_reserve(c, c->slots[os], ns, false)) return rc; }
-    if (int rc = launch_transform_f32(c, c->slots[ss].pts, c->slots[os].pts, ns, fin)) return rc;
-    c->slots[os].n = ns;
-    if (os != ss) inherit_point_set(c->slots[os], c->slots[ss]);
-    else c->slots[os].forget_pose();
-    c->slots[os].stale_coords();
-    if (src_normals) {
-      if (int rc = ensure(c, c->slots[os].nrm, c->slots[os].nrm_cap, ns)) return rc;
-      if (int rc = launch_rotate_normals_f32(c, c->slots[ss].nrm, c->slots[os].nrm, ns, fin)) return rc;
-    }
-    c->slots[os].has_normals = c->slots[ss].has_normals;
-  }
+  if (os >= 0) { if (int rc = finish_align_out(c, os, ss, fin, true)) return rc; }      // output = final * (*input), from the ORIGINAL input
   std::memcpy(T_out, fin, sizeof fin);
   if (st) {
     st->iterations = iters; st->converged = converged; st->state = state; st->n_corr = ncorr; st->mse = cur_mse;
@@ -2603,20 +2600,7 @@ API int mvr_icp_align_gicp(mvr_ctx *ctx, int ss, int ts, int os, const mvr_gicp_
   }
   scratch.has_normals = false;
   if (status == MVR_E_SINGULAR) (void)set_error(c, MVR_E_SINGULAR, "mvr_icp_align_gicp: a pivot of the damped system is not positive");
-  if (os >= 0) {            // output = final * (*input), from the ORIGINAL input, as mvr_icp_align writes it
-    const bool src_normals = c->slots[ss].has_normals && ns;
-    if (os != ss) { c->slots[os].n = 0; if (int rc = cloud_reserve(c, c->slots[os], ns, false)) return rc; }
-    if (int rc = launch_transform_f32(c, c->slots[ss].pts, c->slots[os].pts, ns, fin)) return rc;
-    c->slots[os].n = ns;
-    if (os != ss) inherit_point_set(c->slots[os], c->slots[ss]);
-    else c->slots[os].forget_pose();
-    c->slots[os].stale_coords();
-    if (src_normals) {
-      if (int rc = ensure(c, c->slots[os].nrm, c->slots[os].nrm_cap, ns)) return rc;
-      if (int rc = launch_rotate_normals_f32(c, c->slots[ss].nrm, c->slots[os].nrm, ns, fin)) return rc;
-    }
-    c->slots[os].has_normals = c->slots[ss].has_normals;
-  }
+  if (os >= 0) { if (int rc = finish_align_out(c, os, ss, fin, true)) return rc; }      // output = final * (*input), from the ORIGINAL input
   std::memcpy(T_out, fin, sizeof fin);
   if (st) {
     st->iterations = iters; st->converged = converged; st->state = state; st->n_corr = ncorr; st->mse = cur_mse;
@@ -2704,15 +2688,7 @@ API int mvr_seq_align_sharded(mvr_ctx *ctx, int ss, int ts, int os, const mvr_ic
     converged = crit.converged(tr, cur_mse, iters, &state) ? 1 : 0;
   } while (!converged);
   if (carry != MVR_OK) return carry;
-  if (os >= 0) {            // output = final * (*input), from the ORIGINAL input (App. A.1)
-    if (os != ss) { c->slots[os].n = 0; if (int rc = cloud_reserve(c, c->slots[os], ns, false)) return rc; }
-    if (int rc = launch_transform_f32(c, c->slots[ss].pts, c->slots[os].pts, ns, fin)) return rc;
-    c->slots[os].n = ns;
-    if (os != ss) inherit_point_set(c->slots[os], c->slots[ss]);
-    else c->slots[os].forget_pose();
-    c->slots[os].stale_coords();
-    c->slots[os].has_normals = false;
-  }
+  if (os >= 0) { if (int rc = finish_align_out(c, os, ss, fin, false)) return rc; }      // output = final * (*input), from the ORIGINAL input
   std::memcpy(T_out, fin, sizeof fin);
   if (st) {
     st->iterations = iters; st->converged = converged; st->state = state; st->n_corr = ncorr; st->mse = cur_mse;
