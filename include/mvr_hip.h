@@ -709,7 +709,12 @@ int  mvr_correspondences(mvr_ctx *ctx, int src_slot, int tgt_slot, double max_di
  * shardable per-pair unit of the ring/global mode (registrator.cpp:482-502,
  * 640-651).  q_begin/q_count restrict the SOURCE queries to a sub-range (for
  * splitting one pair over ranks; sums are then partial: n, n*mean, n*mse and
- * raw second moments add across sub-ranges) -- pass 0, SIZE_MAX for all. */
+ * raw second moments add across sub-ranges) -- pass 0, SIZE_MAX for all.
+ * A sub-range is a range of the walk's POSITIONS: source indices q_begin ..
+ * q_begin + q_count - 1 under the brute-force search; under the culled search
+ * the points at those positions of the context's ordering of the source
+ * (mvr_debug_order: position -> index).  Either way the sub-ranges of a split
+ * of 0 .. n - 1 cover every source point once, which is all a split needs. */
 int  mvr_pair_moments(mvr_ctx *ctx, int src_slot, int tgt_slot, double max_dist,
                       int reciprocal, int fma_dist, mvr_pair_moments_t *out);
 int  mvr_pair_moments2(mvr_ctx *ctx, int src_slot, int tgt_slot, double max_dist,
