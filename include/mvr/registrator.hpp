@@ -111,6 +111,8 @@ class ScanCloud {
   // point_cloud.cpp:423-465: drop the connected components (points linked when <= triangle_length apart -- the
   // reference's short Delaunay edges give the same components) with fewer than segment_threshold points; the
   // survivors are stored component after component, as the reference's denoised_cloud.  Returns the noise count.
+  // A point with a non-finite x, y or z (a scanner file with is_dense == false) is linked to nothing: a component of its own,
+  // kept exactly when segment_threshold <= 1, and no part of the grid's sizing (rules D1-D4 of mvr_cloud_denoise in mvr_hip.h).
   size_t denoise(int segment_threshold, double triangle_length)
   {
     Device &d = Device::instance();

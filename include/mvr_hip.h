@@ -135,8 +135,19 @@ int  mvr_cloud_clear(mvr_ctx *ctx, int slot);
  * host, capacity = old size) receives the original indices of the kept points.  One documented difference: exact
  * duplicate points are ordinary members of their component here, while CGAL's insert keeps only the first of them as a
  * vertex (the later copies become isolated and are dropped by any segment_threshold > 1).
- * Non-finite points: no rule.  A NaN stays out of the cell sizing (what it is linked to is unspecified); an infinite coordinate makes the
- * cell edge infinite, which puts every point into one cell (no undefined conversion, but a quadratic search): unsupported. */
+ * Distances: sqrt(dx*dx + dy*dy + dz*dz) in f64 from the f32 coordinates, each operation rounded; a pair is linked when
+ * `!(d > triangle_length)`, so d == triangle_length links.  segment_threshold <= 0 keeps everything.  triangle_length may be
+ * 0 (exact duplicates link, nothing else) or +inf (one component of all finite points); NaN or < 0 returns MVR_E_ARG and
+ * changes nothing.  Normals of the slot follow their points.  The output is a NEW point set, also when nothing is kept.
+ * Non-finite points (a NaN or an infinity in x, y or z; w is not looked at), worded like N1-N5 of mvr_knn and rule 2 of
+ * the outlier filters:
+ *  D1. Such a point is linked to nothing, whatever triangle_length is (+inf included: two points at the same infinite
+ *      coordinates are not linked either).
+ *  D2. It is a component of its own, of size 1: counted in n_components, kept exactly when segment_threshold <= 1, at its
+ *      place in the (smallest index of the component, index) order like any other point.
+ *  D3. It takes no part in the sizing of the grid: the cells are sized by the finite points alone, so the cost of a call
+ *      does not depend on where the non-finite coordinates are.
+ *  D4. A cloud with no finite point is sized like a single point: n components of size 1, MVR_OK. */
 int  mvr_cloud_denoise(mvr_ctx *ctx, int slot, int segment_threshold, double triangle_length,
                        size_t *n_kept, size_t *n_components, uint32_t *kept_index);
 /* ---- voxel-grid downsampling (EXTENSION: pcl::VoxelGrid<PointXYZ>::filter with setLeafSize(lx, ly, lz),

@@ -698,7 +698,10 @@ class Context:
         return curv[0] if one else curv
 
     def denoise(self, slot, segment_threshold=10, triangle_length=2.5):
-        """PointCloud::denoise in place.  Returns (kept original indices in output order, number of components)."""
+        """PointCloud::denoise in place.  Returns (kept original indices in output order, number of components).
+        A point with a non-finite x, y or z is linked to nothing: a component of its own (counted; kept exactly when
+        segment_threshold <= 1, at its place in the order) that takes no part in the sizing of the grid; a cloud with no
+        finite point is sized like a single point (rules D1-D4 of mvr_cloud_denoise in mvr_hip.h)."""
         n = self.size(slot)
         idx = np.empty(max(n, 1), np.uint32)
         kept, comps = C.c_size_t(), C.c_size_t()

@@ -17,6 +17,8 @@
 //   3. labels = roots = smallest index of each component (boost::connected_components numbers components by
 //      their first vertex), component sizes by atomicAdd, kept points ordered by (label, index) -- the order in
 //      which the reference pushes them into the denoised cloud -- with one 64-bit radix sort.
+// A point with a non-finite x, y or z (rules D1-D4 in mvr_hip.h) stays out of step 1's bounding box, gets cell 0 and is
+// neither end of a link in step 2: steps 3 on see it as a component of one point.
 // HBM/latency-bound integer work; nothing here is reshaped into a GEMM.
 #include <hipcub/hipcub.hpp>
 
@@ -28,11 +30,15 @@
 namespace mvr {
 namespace {
 
+// A point with a non-finite x, y or z (the rule in mvr_hip.h): it sizes no grid, gets cell 0 and is linked to nothing.
+__device__ __forceinline__ bool finite3(const float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
+
 __global__ void bbox_kernel(const float4 *__restrict__ p, size_t n, float *__restrict__ out /* 6, pre-set to +-max */)
 {
   float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const float4 v = p[i];
+    if (!finite3(v)) continue;                                 // fminf drops a NaN, an infinity it would keep
     lo[0] = fminf(lo[0], v.x); lo[1] = fminf(lo[1], v.y); lo[2] = fminf(lo[2], v.z);
     hi[0] = fmaxf(hi[0], v.x); hi[1] = fmaxf(hi[1], v.y); hi[2] = fmaxf(hi[2], v.z);
   }
@@ -70,7 +76,8 @@ __global__ void key_kernel(const float4 *__restrict__ p, size_t n, Grid g, uint3
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint32_t c[3];
-  key[i] = cell_key(p[i], g, c);
+  const float4 v = p[i];
+  key[i] = finite3(v) ? cell_key(v, g, c) : 0u;
   idx[i] = (uint32_t)i;
 }
 
@@ -102,6 +109,7 @@ __global__ void unite_kernel(const float4 *__restrict__ p, const uint32_t *__res
   if (a >= n) return;
   const uint32_t ka = skey[a], i = sidx[a];
   const float4 pi = p[i];
+  if (!finite3(pi)) return;                                    // a component of its own
   const int cx = (int)(ka & 1023u), cy = (int)((ka >> 10) & 1023u), cz = (int)(ka >> 20);
   for (int dz = -1; dz <= 1; ++dz)
     for (int dy = -1; dy <= 1; ++dy) {
@@ -116,7 +124,10 @@ __global__ void unite_kernel(const float4 *__restrict__ p, const uint32_t *__res
         if (j >= i) continue;                                  // every pair once
         const float4 pj = p[j];
         const double dx = (double)pi.x - (double)pj.x, dyy = (double)pi.y - (double)pj.y, dzz = (double)pi.z - (double)pj.z;
-        if (sqrt(dx * dx + dyy * dyy + dzz * dzz) > r) continue;      // point_cloud.cpp:490-491
+        const double d = sqrt(dx * dx + dyy * dyy + dzz * dzz);
+        // pi is finite, so d is finite exactly when pj is (f32 differences cannot overflow a double).  The comparison alone
+        // would not do: a NaN d is not > r, and neither is an infinite one under r = inf.
+        if (!isfinite(d) || d > r) continue;                   // point_cloud.cpp:490-491
         uf_unite(parent, i, j);
       }
     }
@@ -273,6 +284,7 @@ int denoise_cloud(Ctx *c, Cloud &cl, int segment_threshold, double triangle_leng
   MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
   Grid g;
   double ext = 0.0;
+  if (hb[0] > hb[3]) for (int k = 0; k < 3; ++k) hb[k] = hb[3 + k] = 0.0f;      // no finite point: sized like a single point
   for (int k = 0; k < 3; ++k) { g.lo[k] = hb[k]; ext = std::max(ext, (double)hb[3 + k] - (double)hb[k]); }
   const double h = std::max(std::max(triangle_length, ext / 1023.0) * 1.000001, 1e-30);     // cells >= r: neighbours within r are <= 1 cell away
   g.inv_h = 1.0 / h;
