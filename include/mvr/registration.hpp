@@ -291,6 +291,109 @@ class CorrespondenceRejectorSurfaceNormal : public CorrespondenceRejector {
   std::vector<float> src_xyz_, tgt_xyz_, src_nrm_, tgt_nrm_;
 };
 
+// pcl::registration::CorrespondenceRejectorSampleConsensus (rules C1-C12 at mvr_reject_sample_consensus in mvr_hip.h): keeps
+// the correspondences that agree with one rigid motion.  On its own list it uploads its clouds and runs the dedicated entry;
+// added to an IterativeClosestPoint or a GeneralizedIterativeClosestPoint it is a stage of the chain, which takes the points
+// from the clouds the registration holds (the current source of every iteration), and after align getBestTransformation() is
+// what mvr_ctx_last_sample_consensus returns.  setSeed is ours: PCL draws with rand().
+template <typename PointT>
+class CorrespondenceRejectorSampleConsensus : public CorrespondenceRejector {
+ public:
+  typedef std::shared_ptr<CorrespondenceRejectorSampleConsensus<PointT>> Ptr;
+  typedef std::shared_ptr<const CorrespondenceRejectorSampleConsensus<PointT>> ConstPtr;
+  typedef typename PointCloud<PointT>::Ptr PointCloudPtr;
+  typedef typename PointCloud<PointT>::ConstPtr PointCloudConstPtr;
+  CorrespondenceRejectorSampleConsensus() { rejection_name_ = "CorrespondenceRejectorSampleConsensus"; }
+
+  virtual void setInputSource(const PointCloudConstPtr &cloud) { input_ = cloud; }
+  virtual void setInputTarget(const PointCloudConstPtr &cloud) { target_ = cloud; }
+  virtual void setInputCloud(const PointCloudConstPtr &cloud) { input_ = cloud; }       // (the older names)
+  virtual void setTargetCloud(const PointCloudConstPtr &cloud) { target_ = cloud; }
+  PointCloudConstPtr const getInputSource() { return input_; }
+  PointCloudConstPtr const getInputTarget() { return target_; }
+  void setInlierThreshold(double threshold) { inlier_threshold_ = threshold; }
+  double getInlierThreshold() { return inlier_threshold_; }
+  void setMaximumIterations(int max_iterations) { max_iterations_ = std::max(max_iterations, 0); }
+  int getMaximumIterations() { return max_iterations_; }
+  void setRefineModel(const bool refine) { refine_ = refine; }
+  bool getRefineModel() const { return refine_; }
+  void setSaveInliers(bool s) { save_inliers_ = s; }
+  bool getSaveInliers() { return save_inliers_; }
+  // positions, in the list the rejector last ran on by itself, of the correspondences it kept (with setSaveInliers)
+  void getInliersIndices(std::vector<int> &indices) { indices = inlier_indices_; }
+  Mat4<float> getBestTransformation() { return best_transformation_; }
+  bool requiresSourcePoints() const { return true; }
+  bool requiresTargetPoints() const { return true; }
+  void setSeed(uint64_t seed) { seed_ = seed; }
+  uint64_t getSeed() const { return seed_; }
+  // ours: the whole record of the last run (mvr_rej_sac_result)
+  const mvr_rej_sac_result &getResult() const { return result_; }
+
+  mvr_rejector stage() const override
+  {
+    mvr_rejector r = mvr_rejector{MVR_REJ_SAMPLE_CONSENSUS, inlier_threshold_, 0u};
+    r.max_iterations = (uint32_t)max_iterations_; r.refine = refine_ ? 1 : 0; r.seed = seed_;
+    return r;
+  }
+  // (the registration calls this after align: the stage's record says nothing about the motion, the context does)
+  void noteStage(const mvr_rejector_stage &) override
+  {
+    mvr_rej_sac_result res;
+    if (mvr_ctx_last_sample_consensus(Device::instance().ctx(), &res) == MVR_OK) take(res);
+  }
+
+  void getRemainingCorrespondences(const Correspondences &original, Correspondences &remaining) override
+  {
+    remaining.clear();
+    inlier_indices_.clear();
+    if (!input_ || !target_) {
+      std::fprintf(stderr, "[pcl::registration::%s::getRemainingCorrespondences] No input cloud dataset was given!\n", getClassName().c_str());
+      return;
+    }
+    Device &d = Device::instance();
+    const size_t n = original.size();
+    std::vector<int32_t> q(n), m(n), qo(n), mo(n);
+    std::vector<float> dd(n), dout(n);
+    for (size_t k = 0; k < n; ++k) { q[k] = original[k].index_query; m[k] = original[k].index_match; dd[k] = original[k].distance; }
+    SlotGuard s, t;
+    d.upload(s.s, *input_);
+    d.upload(t.s, *target_);
+    const mvr_rejector r = stage();
+    mvr_rej_sac_result res;
+    size_t kept = 0;
+    const int rc = mvr_reject_sample_consensus(d.ctx(), s.s, t.s, q.data(), m.data(), dd.data(), n, &r, &res, qo.data(), mo.data(), dout.data(), n,
+                                               &kept, nullptr, 0);
+    if (rc == MVR_E_ARG) {
+      std::fprintf(stderr, "[pcl::registration::%s::getRemainingCorrespondences] %s\n", getClassName().c_str(), mvr_last_error(d.ctx()));
+      return;
+    }
+    d.check(rc, "mvr_reject_sample_consensus");
+    take(res);
+    remaining.resize(kept);
+    for (size_t k = 0; k < kept; ++k) remaining[k] = Correspondence(qo[k], mo[k], dout[k]);
+    if (save_inliers_) {
+      std::vector<int32_t> sorted(qo.begin(), qo.begin() + (std::ptrdiff_t)kept);      // (ascending already: R7)
+      for (size_t k = 0; k < n; ++k)
+        if (std::binary_search(sorted.begin(), sorted.end(), q[k])) inlier_indices_.push_back((int)k);
+    }
+  }
+
+ private:
+  void take(const mvr_rej_sac_result &res)
+  {
+    result_ = res;
+    for (int k = 0; k < 16; ++k) best_transformation_.m[k] = res.T[k];
+  }
+  double inlier_threshold_ = 0.05;
+  int max_iterations_ = 1000;
+  bool refine_ = false, save_inliers_ = false;
+  uint64_t seed_ = 0;
+  PointCloudConstPtr input_, target_;
+  Mat4<float> best_transformation_ = Mat4<float>::Identity();
+  mvr_rej_sac_result result_ = mvr_rej_sac_result();
+  std::vector<int> inlier_indices_;
+};
+
 }  // namespace registration
 
 // ---------------------------------------------------------------- ICP

@@ -473,7 +473,8 @@ int  mvr_cloud_fpfh(mvr_ctx *ctx, int slot, const mvr_fpfh_params *p,
  *  nr_samples outside 3..8, k outside 1..MVR_MAX_KNN, similarity outside [0, 1), max_dist not finite and > 0, or
  *  inlier_fraction outside (0, 1].  The draws, matches and polygon tests of all iterations are one launch; the surviving poses
  *  are solved on the host and scored through the kernel of mvr_pose_scores.
- * Out of scope: SampleConsensusInitialAlignment, CorrespondenceRejectorSampleConsensus, descriptors of other lengths. */
+ * Out of scope: SampleConsensusInitialAlignment, descriptors of other lengths.  (CorrespondenceRejectorSampleConsensus over the
+ * matches of mvr_feature_knn is mvr_reject_sample_consensus, rules C1-C12.) */
 int  mvr_feature_knn(mvr_ctx *ctx, const float *q, size_t nq, const float *t, size_t nt, int dim, int k,
                      uint32_t *idx /* nq * k */, float *d2 /* nq * k */);
 int  mvr_pose_scores(mvr_ctx *ctx, int src_slot, int tgt_slot, const float *T /* count * 16, column-major */, size_t count,
@@ -870,19 +871,26 @@ int  mvr_icp_align(mvr_ctx *ctx, int src_slot, int tgt_slot, int out_slot,
  *      result equals mvr_icp_align's in iterations / state / n_corr and in T within rounding (the sums run in another order,
  *      so the bits need not match).  Between the search and the sums nothing comes to the host: the chain rewrites the
  *      device's match table in place, and the counts and thresholds of its stages ride along with the iteration's sums.
+ *      This holds for chains WITHOUT a SAMPLE_CONSENSUS stage: that stage (rules C1-C12 below) replays PCL's RANSAC loop on the
+ *      host and costs round trips per chunk of attempts; its stage record still rides with the others.
  *  R10. MVR_E_ARG, before any GPU work and with nothing written, for a NULL ctx, a NULL chain with n_chain > 0, n_chain outside
  *      0..MVR_MAX_REJECTORS, an unknown kind, a non-finite value, a negative value of DISTANCE / MEDIAN / TRIMMED, a bad slot,
  *      a cloud above 0x7FFFFFF0 points or one whose points are stale because a pipelined run is in flight.  Empty clouds:
  *      MVR_OK with *m = 0.
- * Out of scope: CorrespondenceRejectorVarTrimmed, ...SampleConsensus, ...Features, ...OrganizedBoundary; rejectors in the ring /
- * LUM passes, in mvr_seq_run, mvr_seq_align_sharded and the Registrator drivers. */
+ * Out of scope: CorrespondenceRejectorVarTrimmed, ...Features, ...OrganizedBoundary; SampleConsensus's isSampleGood; rejectors in
+ * the ring / LUM passes, in mvr_seq_run, mvr_seq_align_sharded and the Registrator drivers. */
 #define MVR_MAX_REJECTORS 8
-enum { MVR_REJ_DISTANCE = 0, MVR_REJ_MEDIAN = 1, MVR_REJ_TRIMMED = 2, MVR_REJ_SURFACE_NORMAL = 3, MVR_REJ_ONE_TO_ONE = 4 };
+enum { MVR_REJ_DISTANCE = 0, MVR_REJ_MEDIAN = 1, MVR_REJ_TRIMMED = 2, MVR_REJ_SURFACE_NORMAL = 3, MVR_REJ_ONE_TO_ONE = 4,
+       MVR_REJ_SAMPLE_CONSENSUS = 5 };
 typedef struct {
   int      kind;                 /* MVR_REJ_* */
   double   value;                /* DISTANCE: max distance (not squared); MEDIAN: factor; TRIMMED: overlap ratio;
-                                    SURFACE_NORMAL: threshold (a cosine); ONE_TO_ONE: unused */
+                                    SURFACE_NORMAL: threshold (a cosine); ONE_TO_ONE: unused; SAMPLE_CONSENSUS: the inlier
+                                    threshold (setInlierThreshold, not squared; PCL's default is 0.05) */
   uint32_t min_correspondences;  /* TRIMMED only */
+  uint32_t max_iterations;       /* SAMPLE_CONSENSUS only: setMaximumIterations; 0 = PCL's 1000 */
+  int      refine;               /* SAMPLE_CONSENSUS only: setRefineModel */
+  uint64_t seed;                 /* SAMPLE_CONSENSUS only; ours: PCL draws with rand() */
 } mvr_rejector;
 typedef struct { uint32_t in, out; float threshold; } mvr_rejector_stage;
 typedef struct {
@@ -901,6 +909,63 @@ int  mvr_reject_correspondences(mvr_ctx *ctx, int src_slot, int tgt_slot, const 
 int  mvr_icp_align_rejected(mvr_ctx *ctx, int src_slot, int tgt_slot, int out_slot, const mvr_icp_params *params,
                             const mvr_rejector *chain, int n_chain, float T_out[16], mvr_icp_stats *stats,
                             mvr_icp_iter_trace *trace /* optional */, int trace_cap);
+
+/* ---- the sample-consensus rejector (EXTENSION: pcl::registration::CorrespondenceRejectorSampleConsensus) -------------------
+ * The one rejector that knows about the transformation: it keeps the correspondences that agree with ONE rigid motion, found by
+ * RANSAC over the correspondences themselves.  It is kind MVR_REJ_SAMPLE_CONSENSUS of a chain (any position, more than once) in
+ * mvr_correspondences_rejected, mvr_reject_correspondences, mvr_icp_align_rejected and mvr_icp_align_gicp, and it has an entry of
+ * its own that returns the full evidence.  The slots supply the points: in the two align entries the source is the CURRENT source
+ * of the iteration (what PCL's ICP hands over with setSourcePoints), in the list entries the source slot as it stands.  PCL was
+ * not at hand; the model is pcl/registration/impl/correspondence_rejection_sample_consensus.hpp,
+ * pcl/sample_consensus/impl/sac_model_registration.hpp and ransac.hpp, as published; deviations are marked.  Every f32 operation
+ * is rounded on its own and never contracted.
+ *  C1. The list L = the live correspondences (i, j, d2) in ascending query index, m of them.  A pair is VALID when p_i and q_j
+ *      both have three finite coordinates; nv = the number valid.  An invalid pair is never sampled and never an inlier.
+ *      nv < 3: found = 0 and no attempt is made.
+ *  C2. Draws: rule P2 unchanged over the valid pairs in ascending query index; sample r is the r-th valid pair.  The three are
+ *      distinct by construction.  DEVIATION: PCL's rand(), its isSampleGood spread test and its retry loop are not reproduced.
+ *  C3. Hypothesis: rule A5's estimator on the three pairs in sample order -- f64 means and covariance, the host SVD of
+ *      mvr_umeyama_from_moments (Eigen::umeyama without scaling), cast to f32.  The attempt is SKIPPED (status 0; its traced T
+ *      and count are 0) when any entry of T is non-finite.  The attempts of a chunk are drawn and their sample coordinates
+ *      gathered by one launch, solved on the host and uploaded as one block.
+ *  C4. Transformed point: mvr_cloud_transform_f32's arithmetic on p_i: x' = ((T00 x + T01 y) + T02 z) + T03, and so for y', z'.
+ *  C5. d2 = (dx dx + dy dy) + dz dz in f32 with d = p' - q_j, q_j the pair's OWN match (no search); with fma_dist
+ *      d2 = fmaf(dz, dz, fmaf(dy, dy, dx dx)) as everywhere.  fma_dist is the entry's argument or params; in
+ *      mvr_reject_correspondences and mvr_reject_sample_consensus, which have none, the non-fma form is the rule.  The pair is
+ *      an inlier iff (double)d2 < value * value, strictly; the product is taken once on the host (the kernels compare with the
+ *      smallest f32 that is >= it, which is the same test).
+ *  C6. The count of an attempt is the exact integer number of inliers: independent of order and of launch shape.
+ *  C7. The loop is P7 verbatim with this nv: strictly greater, w = best_count / (double)nv, pno = 1 - w^3 clamped, probability
+ *      0.99 (fixed, as in the PCL class), PCL's off-by-one of max_iterations + 1 counted attempts, skipped < 10 * max_iterations.
+ *      It is replayed on the host over a chunk's counts; the attempts beyond the stop are discarded.  Tune key "rej_sac_chunk":
+ *      1..256 attempts per chunk; 0 (default) = the library's choice.  Result and trace are bit-identical for every chunk size.
+ *  C8. found = (best_count >= 3).  Not found: PCL returns the original list; here the stage keeps every live entry, invalid ones
+ *      included: out = in, T = identity, best_attempt = -1.
+ *  C9. Found: the survivors are exactly the C5 inliers of the best attempt's T; every other entry gets match = -1.
+ *  C10. refine (setRefineModel).  DEVIATION from PCL's sigma / variance loop.  T_0 = the RANSAC T, I_0 = its inliers.  Round
+ *      r >= 1: T_r = the ICP SVD estimator over I_{r-1} -- the fixed-order f64 raw moments the align entries sum over the match
+ *      table (taken about the target point of the best attempt's first sample), mvr_moments_from_moments2, the host SVD, cast
+ *      to f32 --; I_r = C5 with T_r over all valid live pairs.  |I_r| < 3 or a non-finite T_r: stop with (T_{r-1}, I_{r-1}).
+ *      I_r = I_{r-1} as sets, or r = max_iterations (PCL's cap): stop with (T_r, I_r).  refine_rounds = the r reached.
+ *      ransac_T and ransac_inliers always record T_0 and |I_0|.
+ *  C11. Outputs follow R7: ascending query index, truncated at cap.  result: live = m, valid = nv, inliers = the survivors
+ *      (= m when not found).  trace[t] (optional) for every attempt made, t < trace_cap: status (0 skipped, 1 counted), the
+ *      sampled pairs' query and match indices, T, the count and k after the attempt.  The stage record is in, out, threshold 0.
+ *  C12. MVR_E_ARG, before any GPU work and with nothing written: everything of R8 and R10; a value that is not finite and > 0;
+ *      max_iterations above 1 << 24; a NULL rejector / result / m, or a rejector of another kind, in the dedicated entry.  Empty
+ *      clouds or lists: MVR_OK with found = 0 (T = identity).  Bit-identical from run to run: integer atomics only, every f64
+ *      sum in a fixed order.
+ * mvr_ctx_last_sample_consensus: the result of the last SAMPLE_CONSENSUS stage that ran on this context, inside any of the
+ * entries above (what getBestTransformation() reads after an align); MVR_E_ARG when none has run. */
+typedef struct { int found; uint32_t live, valid, inliers, ransac_inliers;
+                 int iterations, attempts, skipped, best_attempt, refine_rounds;
+                 double k; float T[16], ransac_T[16]; } mvr_rej_sac_result;      /* T: column-major 4 x 4 */
+typedef struct { int status; uint32_t query[3], match[3]; float T[16]; uint32_t inliers; double k; } mvr_rej_sac_trace;
+int  mvr_reject_sample_consensus(mvr_ctx *ctx, int src_slot, int tgt_slot, const int32_t *query, const int32_t *match,
+                                 const float *dist2, size_t count, const mvr_rejector *r, mvr_rej_sac_result *result,
+                                 int32_t *q_out, int32_t *m_out, float *d_out, size_t cap, size_t *m,
+                                 mvr_rej_sac_trace *trace /* optional */, size_t trace_cap);
+int  mvr_ctx_last_sample_consensus(mvr_ctx *ctx, mvr_rej_sac_result *result);
 
 /* ---- Generalized ICP (EXTENSION: pcl::GeneralizedIterativeClosestPoint) ----------------------------------------------------
  * Plane-to-plane ICP: every correspondence is weighed by the surface each of its two points lies on, so two scans that sample
@@ -1204,7 +1269,9 @@ enum { MVR_K_NN = 0, MVR_K_REDUCE = 1, MVR_K_XFORM = 2, MVR_K_GLUE = 3,
  * feature matching and pose scoring: "feat_split" (blocks the target of mvr_feature_knn is split over, 1..64; 0, default: by the
  * launch size), "score_chunk" (poses per launch of mvr_pose_scores, default 256);
  * plane segmentation: "sac_chunk" (attempts generated and scored per chunk, 1..256; 0, default: 64 for the first chunk of a
- * call and 256 from then on).
+ * call and 256 from then on);
+ * the sample-consensus rejector: "rej_sac_chunk" (attempts generated and scored per chunk, 1..256; 0, default: 64 for the first
+ * chunk of a stage and 256 from then on -- measured, profiles/reject_sac_bench.json).
  * Results never depend on them. */
 int  mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value);
 /* wall milliseconds of every pass of the LAST mvr_ring_run / mvr_ring_run_sharded on this context (from the end of the

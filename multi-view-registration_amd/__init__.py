@@ -89,7 +89,8 @@ class IcpStats(C.Structure):
 
 class Rejector(C.Structure):
     """mvr_rejector"""
-    _fields_ = [("kind", C.c_int), ("value", C.c_double), ("min_correspondences", C.c_uint32)]
+    _fields_ = [("kind", C.c_int), ("value", C.c_double), ("min_correspondences", C.c_uint32), ("max_iterations", C.c_uint32),
+                ("refine", C.c_int), ("seed", C.c_uint64)]
 
 
 class RejectorStage(C.Structure):
@@ -98,9 +99,22 @@ class RejectorStage(C.Structure):
 
 
 MAX_REJECTORS = 8       # MVR_MAX_REJECTORS
-REJ_DISTANCE, REJ_MEDIAN, REJ_TRIMMED, REJ_SURFACE_NORMAL, REJ_ONE_TO_ONE = 0, 1, 2, 3, 4
+REJ_DISTANCE, REJ_MEDIAN, REJ_TRIMMED, REJ_SURFACE_NORMAL, REJ_ONE_TO_ONE, REJ_SAMPLE_CONSENSUS = 0, 1, 2, 3, 4, 5
 REJ_KINDS = {"distance": REJ_DISTANCE, "median": REJ_MEDIAN, "trimmed": REJ_TRIMMED, "surface_normal": REJ_SURFACE_NORMAL,
-             "one_to_one": REJ_ONE_TO_ONE}
+             "one_to_one": REJ_ONE_TO_ONE, "sample_consensus": REJ_SAMPLE_CONSENSUS}
+
+
+class RejSacResult(C.Structure):
+    """mvr_rej_sac_result"""
+    _fields_ = [("found", C.c_int), ("live", C.c_uint32), ("valid", C.c_uint32), ("inliers", C.c_uint32), ("ransac_inliers", C.c_uint32),
+                ("iterations", C.c_int), ("attempts", C.c_int), ("skipped", C.c_int), ("best_attempt", C.c_int),
+                ("refine_rounds", C.c_int), ("k", C.c_double), ("T", C.c_float * 16), ("ransac_T", C.c_float * 16)]
+
+
+class RejSacTrace(C.Structure):
+    """mvr_rej_sac_trace"""
+    _fields_ = [("status", C.c_int), ("query", C.c_uint32 * 3), ("match", C.c_uint32 * 3), ("T", C.c_float * 16),
+                ("inliers", C.c_uint32), ("k", C.c_double)]
 
 
 class IcpIterTrace(C.Structure):
@@ -312,6 +326,10 @@ SIGNATURES = {
                                                _i32p, _i32p, _fp, _sz, C.POINTER(_sz), C.POINTER(RejectorStage)]),
     "mvr_reject_correspondences": (C.c_int, [_vp, C.c_int, C.c_int, _i32p, _i32p, _fp, _sz, C.POINTER(Rejector), C.c_int,
                                              _i32p, _i32p, _fp, _sz, C.POINTER(_sz), C.POINTER(RejectorStage)]),
+    "mvr_reject_sample_consensus": (C.c_int, [_vp, C.c_int, C.c_int, _i32p, _i32p, _fp, _sz, C.POINTER(Rejector),
+                                              C.POINTER(RejSacResult), _i32p, _i32p, _fp, _sz, C.POINTER(_sz),
+                                              C.POINTER(RejSacTrace), _sz]),
+    "mvr_ctx_last_sample_consensus": (C.c_int, [_vp, C.POINTER(RejSacResult)]),
     "mvr_icp_align_rejected": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(IcpParams), C.POINTER(Rejector), C.c_int, _fp,
                                          C.POINTER(IcpStats), C.POINTER(IcpIterTrace), C.c_int]),
     "mvr_gicp_default_params": (None, [C.POINTER(GicpParams)]),
@@ -409,10 +427,19 @@ def icp_params(reciprocal=True, max_dist=4.0, max_iter=10, teps=1e-6, feps=64.0,
                      int(fma), int(point_to_plane))
 
 
-def rejector(kind, value=0.0, min_correspondences=0) -> Rejector:
+def rejector(kind, value=0.0, min_correspondences=0, max_iterations=0, refine=0, seed=0) -> Rejector:
     """One stage of a rejector chain (mvr_rejector): kind = "distance" (value: the largest distance), "median" (the factor),
-    "trimmed" (the overlap ratio; min_correspondences), "surface_normal" (the smallest cosine), "one_to_one", or a REJ_* number."""
-    return Rejector(REJ_KINDS[kind] if isinstance(kind, str) else int(kind), float(value), int(min_correspondences))
+    "trimmed" (the overlap ratio; min_correspondences), "surface_normal" (the smallest cosine), "one_to_one",
+    "sample_consensus" (the inlier threshold; max_iterations, 0 = 1000; refine; seed), or a REJ_* number."""
+    return Rejector(REJ_KINDS[kind] if isinstance(kind, str) else int(kind), float(value), int(min_correspondences),
+                    int(max_iterations), int(bool(refine)), int(seed))
+
+
+def _rej_sac_dict(res) -> dict:
+    return dict(found=bool(res.found), live=int(res.live), valid=int(res.valid), inliers=int(res.inliers),
+                ransac_inliers=int(res.ransac_inliers), iterations=res.iterations, attempts=res.attempts, skipped=res.skipped,
+                best_attempt=res.best_attempt, refine_rounds=res.refine_rounds, k=res.k, T=from_cm(np.array(res.T, np.float32)),
+                ransac_T=from_cm(np.array(res.ransac_T, np.float32)))
 
 
 def gicp_params(**kw) -> GicpParams:
@@ -1036,6 +1063,40 @@ class Context:
                                              _p(q, C.c_int32), _p(m, C.c_int32), _p(d, C.c_float), n, C.byref(cnt), st), self._h)
         k = cnt.value
         return q[:k].copy(), m[:k].copy(), d[:k].copy(), _stage_dicts(st, nc)
+
+    def reject_sample_consensus(self, s, t, query, match, dist2, rejector, return_trace=False):
+        """mvr_reject_sample_consensus (rules C1-C12): pcl::registration::CorrespondenceRejectorSampleConsensus on the caller's
+        list, the points taken from slots s and t -> (query, match, d2, result[, trace]).  result: dict(found, live, valid,
+        inliers, ransac_inliers, iterations, attempts, skipped, best_attempt, refine_rounds, k, T, ransac_T ((4,4) float32));
+        trace: dict(status[t], query[t, 3], match[t, 3], T[t, 16] (column-major), inliers[t], k[t]) over the attempts made."""
+        qi, mi = np.ascontiguousarray(query, np.int32), np.ascontiguousarray(match, np.int32)
+        di = np.ascontiguousarray(dist2, np.float32)
+        n = len(qi)
+        q, m, d = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32)
+        res, cnt = RejSacResult(), _sz()
+        mi_ = int(rejector.max_iterations) or 1000
+        cap = 11 * mi_ + 1 if return_trace else 0      # counted attempts <= max_iterations + 1, skipped <= 10 x
+        dt = np.dtype([("status", np.int32), ("query", np.uint32, 3), ("match", np.uint32, 3), ("T", np.float32, 16),
+                       ("inliers", np.uint32), ("k", np.float64)], align=True)
+        assert dt.itemsize == C.sizeof(RejSacTrace)
+        tr = np.zeros(max(cap, 1), dt)
+        _chk(_lib.mvr_reject_sample_consensus(self._h, s, t, _p(qi, C.c_int32), _p(mi, C.c_int32), _p(di, C.c_float), n,
+                                              C.byref(rejector), C.byref(res), _p(q, C.c_int32), _p(m, C.c_int32), _p(d, C.c_float),
+                                              n, C.byref(cnt), C.cast(tr.ctypes.data, C.POINTER(RejSacTrace)) if return_trace else None,
+                                              cap), self._h)
+        k = cnt.value
+        out = (q[:k].copy(), m[:k].copy(), d[:k].copy(), _rej_sac_dict(res))
+        if return_trace:
+            a = tr[:res.attempts]
+            out += ({key: np.ascontiguousarray(a[key]) for key in ("status", "query", "match", "T", "inliers", "k")},)
+        return out
+
+    def last_sample_consensus(self) -> dict:
+        """mvr_ctx_last_sample_consensus: the result of the last sample-consensus stage that ran on this context (inside a chain
+        of any entry) -- what getBestTransformation() reads after an align."""
+        res = RejSacResult()
+        _chk(_lib.mvr_ctx_last_sample_consensus(self._h, C.byref(res)), self._h)
+        return _rej_sac_dict(res)
 
     def icp_align_rejected(self, src, tgt, out, params: IcpParams, chain, return_trace=False):
         """mvr_icp_align_rejected -> (T (4,4) float32, stats dict, rc[, trace]); rc is OK or E_NOCORR.  trace: one dict per iteration

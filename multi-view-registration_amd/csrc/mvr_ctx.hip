@@ -2202,12 +2202,16 @@ int reject_args(Ctx *c, int ss, int ts, const mvr_rejector *chain, int n_chain, 
   *one_to_one = false;
   for (int k = 0; k < n_chain; ++k) {
     const mvr_rejector &r = chain[k];
-    if (r.kind < MVR_REJ_DISTANCE || r.kind > MVR_REJ_ONE_TO_ONE) return set_error(c, MVR_E_ARG, "rejector chain: unknown kind");
+    if (r.kind < MVR_REJ_DISTANCE || r.kind > MVR_REJ_SAMPLE_CONSENSUS) return set_error(c, MVR_E_ARG, "rejector chain: unknown kind");
     if (!std::isfinite(r.value)) return set_error(c, MVR_E_ARG, "rejector chain: a value is not finite");
     if (r.kind <= MVR_REJ_TRIMMED && r.value < 0.0) return set_error(c, MVR_E_ARG, "rejector chain: a negative distance, factor or ratio");
     if (r.kind == MVR_REJ_SURFACE_NORMAL && s.n && t.n && !(s.has_normals && t.has_normals))
       return set_error(c, MVR_E_ARG, "the surface-normal rejector needs the normals of both clouds (mvr_cloud_upload_normals)");
     if (r.kind == MVR_REJ_ONE_TO_ONE) *one_to_one = true;
+    if (r.kind == MVR_REJ_SAMPLE_CONSENSUS) {      // C12
+      if (!(r.value > 0.0)) return set_error(c, MVR_E_ARG, "sample-consensus rejector: the inlier threshold is not > 0");
+      if (r.max_iterations > (1u << 24)) return set_error(c, MVR_E_ARG, "sample-consensus rejector: max_iterations above 1 << 24");
+    }
   }
   return MVR_OK;
 }
@@ -2270,13 +2274,16 @@ API int mvr_correspondences_rejected(mvr_ctx *ctx, int ss, int ts, double max_di
   if (int rc = ensure_reject_state(c, nt, oto)) return rc;
   SearchPlan plan;
   if (int rc = pair_common(c, ss, ts, max_dist, reciprocal, fma, 0, ns, nullptr, &plan)) return rc;
-  if (int rc = launch_reject_chain(c, chain, n_chain, c->keys, c->match, ns, nt, c->slots[ss].nrm, c->slots[ts].nrm, c->moments, 0u)) return rc;
+  if (int rc = launch_reject_chain(c, chain, n_chain, c->keys, c->match, ns, nt, c->slots[ss].nrm, c->slots[ts].nrm, c->moments, 0u,
+                                   c->slots[ss].pts, c->slots[ts].pts, fma != 0)) return rc;
   return reject_collect(c, ns, n_chain, query, match, dist2, cap, m, stages);
 }
 
-API int mvr_reject_correspondences(mvr_ctx *ctx, int ss, int ts, const int32_t *query, const int32_t *match, const float *dist2, size_t count,
-                                   const mvr_rejector *chain, int n_chain, int32_t *q_out, int32_t *m_out, float *d_out, size_t cap,
-                                   size_t *m, mvr_rejector_stage *stages)
+namespace {
+// R8: the chain on the caller's list (sac_trace: what a SAMPLE_CONSENSUS stage records, for the dedicated entry)
+int reject_list(mvr_ctx *ctx, int ss, int ts, const int32_t *query, const int32_t *match, const float *dist2, size_t count,
+                const mvr_rejector *chain, int n_chain, int32_t *q_out, int32_t *m_out, float *d_out, size_t cap, size_t *m,
+                mvr_rejector_stage *stages, mvr_rej_sac_trace *sac_trace, size_t sac_trace_cap)
 {
   if (!ctx || !slot_ok(ss) || !slot_ok(ts) || !m || (count && (!query || !match || !dist2))) return MVR_E_ARG;
   Ctx *c = CTX(ctx);
@@ -2306,8 +2313,44 @@ API int mvr_reject_correspondences(mvr_ctx *ctx, int ss, int ts, const int32_t *
   MVR_HIP_TRY(c, hipMemcpyAsync(c->match, hm.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   MVR_HIP_TRY(c, hipMemcpyAsync(c->keys, hk.data(), ns * sizeof(nnkey_t), hipMemcpyHostToDevice, c->stream));
   MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));     // (pageable sources: the vectors are reused below)
-  if (int rc = launch_reject_chain(c, chain, n_chain, c->keys, c->match, ns, nt, c->slots[ss].nrm, c->slots[ts].nrm, nullptr, (uint32_t)count)) return rc;
+  if (int rc = launch_reject_chain(c, chain, n_chain, c->keys, c->match, ns, nt, c->slots[ss].nrm, c->slots[ts].nrm, nullptr, (uint32_t)count,
+                                   c->slots[ss].pts, c->slots[ts].pts, false, sac_trace, sac_trace_cap)) return rc;
   return reject_collect(c, ns, n_chain, q_out, m_out, d_out, cap, m, stages);
+}
+}  // namespace
+
+API int mvr_reject_correspondences(mvr_ctx *ctx, int ss, int ts, const int32_t *query, const int32_t *match, const float *dist2, size_t count,
+                                   const mvr_rejector *chain, int n_chain, int32_t *q_out, int32_t *m_out, float *d_out, size_t cap,
+                                   size_t *m, mvr_rejector_stage *stages)
+{
+  return reject_list(ctx, ss, ts, query, match, dist2, count, chain, n_chain, q_out, m_out, d_out, cap, m, stages, nullptr, 0);
+}
+
+// the sample-consensus rejector on the caller's list, with its full evidence (rules C1-C12)
+API int mvr_reject_sample_consensus(mvr_ctx *ctx, int ss, int ts, const int32_t *query, const int32_t *match, const float *dist2, size_t count,
+                                    const mvr_rejector *r, mvr_rej_sac_result *result, int32_t *q_out, int32_t *m_out, float *d_out, size_t cap,
+                                    size_t *m, mvr_rej_sac_trace *trace, size_t trace_cap)
+{
+  if (!ctx || !r || !result || r->kind != MVR_REJ_SAMPLE_CONSENSUS) return MVR_E_ARG;
+  Ctx *c = CTX(ctx);
+  const bool had = c->last_sac_set;
+  c->last_sac_set = false;
+  const int rc = reject_list(ctx, ss, ts, query, match, dist2, count, r, 1, q_out, m_out, d_out, cap, m, nullptr, trace, trace_cap);
+  const bool ran = c->last_sac_set;
+  c->last_sac_set = had || ran;
+  if (rc != MVR_OK) return rc;
+  if (ran) *result = c->last_sac;
+  else reject_sac_identity(result);      // an empty cloud or list: no stage ran
+  return MVR_OK;
+}
+
+API int mvr_ctx_last_sample_consensus(mvr_ctx *ctx, mvr_rej_sac_result *result)
+{
+  if (!ctx || !result) return MVR_E_ARG;
+  Ctx *c = CTX(ctx);
+  if (!c->last_sac_set) return set_error(c, MVR_E_ARG, "no sample-consensus rejector has run on this context");
+  *result = c->last_sac;
+  return MVR_OK;
 }
 
 // PCL's computeTransformation with rejectors (R9).  The loop of mvr_icp_align with the chain between the search and the sums;
@@ -2346,7 +2389,8 @@ API int mvr_icp_align_rejected(mvr_ctx *ctx, int ss, int ts, int os, const mvr_i
     if (int rc = run_search(c, *curp, tgt, 0, ns, p->max_corr_dist, p->use_reciprocal != 0, p->fma_dist != 0, nullptr, &plan)) return rc;
     if (int rc = launch_pass1(c, curp->pts, tgt.pts, c->keys, c->rkeys, plan.slot, plan.count, plan.qperm, plan.tinv, 0, ns,
                               p->max_corr_dist * p->max_corr_dist, p->use_reciprocal != 0, c->match, c->moments)) return rc;
-    if (int rc = launch_reject_chain(c, chain, n_chain, c->keys, c->match, ns, nt, curp->nrm, tgt.nrm, c->moments, 0u)) return rc;
+    if (int rc = launch_reject_chain(c, chain, n_chain, c->keys, c->match, ns, nt, curp->nrm, tgt.nrm, c->moments, 0u, curp->pts, tgt.pts,
+                                     p->fma_dist != 0)) return rc;
     if (int rc = launch_moments2(c, curp->pts, tgt.pts, c->match, c->keys, plan.qperm, 0, ns, origin, c->rej_row)) return rc;
     if (p->point_to_plane) { if (int rc = launch_p2plane(c, curp->pts, tgt.pts, tgt.nrm, c->match, plan.qperm, 0, ns, c->rej_row + 32)) return rc; }
     MVR_HIP_TRY(c, hipMemcpyAsync(c->rej_host, c->rej_row, kRejCopyBytes, hipMemcpyDeviceToHost, c->stream));      // the iteration's one round trip
@@ -2544,7 +2588,8 @@ API int mvr_icp_align_gicp(mvr_ctx *ctx, int ss, int ts, int os, const mvr_gicp_
     if (int rc = run_search(c, *curp, tgt, 0, ns, p->max_corr_dist, p->use_reciprocal != 0, p->fma_dist != 0, nullptr, &plan)) return rc;
     if (int rc = launch_pass1(c, curp->pts, tgt.pts, c->keys, c->rkeys, plan.slot, plan.count, plan.qperm, plan.tinv, 0, ns,
                               p->max_corr_dist * p->max_corr_dist, p->use_reciprocal != 0, c->match, c->moments)) return rc;
-    if (int rc = launch_reject_chain(c, chain, n_chain, c->keys, c->match, ns, nt, curp->nrm, tgt.nrm, c->moments, 0u)) return rc;
+    if (int rc = launch_reject_chain(c, chain, n_chain, c->keys, c->match, ns, nt, curp->nrm, tgt.nrm, c->moments, 0u, curp->pts, tgt.pts,
+                                     p->fma_dist != 0)) return rc;
     if (int rc = launch_moments2(c, curp->pts, tgt.pts, c->match, c->keys, plan.qperm, 0, ns, origin, c->rej_row)) return rc;      // (count and the sum of d2)
     if (int rc = gicp_optimise(c, curp->pts, curp->nrm, tgt.pts, tgt.nrm, c->match, plan.qperm, 0, ns, p, gicp_ride)) return rc;
     const double *h = c->rej_host, *g = c->gicp_host;
@@ -2902,6 +2947,7 @@ API int mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value)
   else if (!std::strcmp(key, "feat_split")) { if (value < 0 || value > 64) return MVR_E_ARG; c->feat_split = value; }
   else if (!std::strcmp(key, "score_chunk")) { if (value < 1 || value > 65535) return MVR_E_ARG; c->score_chunk = value; }
   else if (!std::strcmp(key, "sac_chunk")) { if (value < 0 || value > 256) return MVR_E_ARG; c->sac_chunk = value; }
+  else if (!std::strcmp(key, "rej_sac_chunk")) { if (value < 0 || value > 256) return MVR_E_ARG; c->rej_sac_chunk = value; }
   else if (!std::strcmp(key, "posed_refresh")) c->posed_refresh = value != 0;
   else if (!std::strcmp(key, "pair_groups")) { if (value < 1 || value > 8) return MVR_E_ARG; c->pair_groups = value; }
   else if (!std::strcmp(key, "inplace_ratio")) c->inplace_ratio = value;

@@ -285,6 +285,8 @@ struct Ctx {
   // scoring launch -- results never depend on either; wall milliseconds of the last mvr_align_prerejective by phase
   int feat_split = 0, score_chunk = 256;
   double prerej_ms[3] = {0.0, 0.0, 0.0};                 // matching, hypothesis generation, scoring
+  int rej_sac_chunk = 0;                                 // the sample-consensus rejector: attempts per chunk (0: 64 for a stage's first chunk, 256 from then on -- profiles/reject_sac_bench.json); results never depend on it
+  mvr_rej_sac_result last_sac = {}; bool last_sac_set = false;      // the last sample-consensus stage that ran on this context (mvr_ctx_last_sample_consensus)
   int sac_chunk = 0;                                     // mvr_cloud_segment_plane: attempts per chunk (0: 64 for a call's first chunk, 256 from then on); results never depend on it
   char *dn_arena = nullptr; size_t dn_arena_cap = 0;     // scratch of mvr_cloud_denoise and mvr_cloud_voxel_grid (one buffer, carved per call)
   double *h_table = nullptr; size_t h_table_cap = 0;     // pinned host memory the final kernels of mvr_ring_step write straight into (zero-copy)
@@ -845,8 +847,16 @@ constexpr size_t kRejRowBytes = kRejCopyBytes + (size_t)(kRejHistBins + kRejTieB
 int ensure_reject_state(Ctx *c, size_t nt, bool one_to_one);
 // the chain over keys[] / match[] (ns entries, by source index) in place: a rejected entry gets match = -1.  found: a device
 // double holding the number live at entry (pass 1's moments[0]), or null: found_host.  Nothing comes to the host.
+// spts / tpts / fma / trace: what a SAMPLE_CONSENSUS stage needs (rules C1-C12) -- that stage alone synchronises the stream.
 int launch_reject_chain(Ctx *c, const mvr_rejector *chain, int n_chain, const nnkey_t *keys, int32_t *match, size_t ns, size_t nt,
-                        const float4 *snrm, const float4 *tnrm, const double *found, uint32_t found_host);
+                        const float4 *snrm, const float4 *tnrm, const double *found, uint32_t found_host, const float4 *spts = nullptr,
+                        const float4 *tpts = nullptr, bool fma = false, mvr_rej_sac_trace *sac_trace = nullptr, size_t sac_trace_cap = 0);
+// ---- the sample-consensus rejector (mvr_reject_sac.hip; rules C1-C12 at mvr_reject_sample_consensus in mvr_hip.h)
+// one stage over match[] (ns entries) in place; `stage` = the stage's device words (word 0 receives the number kept).  Leaves
+// its result in Ctx::last_sac.
+int reject_sac_stage(Ctx *c, const mvr_rejector &r, bool fma, const float4 *src, const float4 *tgt, int32_t *match, size_t ns, uint32_t *stage,
+                     mvr_rej_sac_trace *trace, size_t trace_cap);
+void reject_sac_identity(mvr_rej_sac_result *R);      // found = 0, T = identity
 // ---- Generalized ICP (mvr_gicp.hip; rules G1-G10 at mvr_icp_align_gicp in mvr_hip.h)
 // Layout of Ctx::gicp_state, in doubles: X (R row-major, t), the candidate Xc, the 29 sums at X, lambda, the objective per
 // correspondence at identity and at X, the norms of the step that made the candidate; then four uint32 words.

@@ -17,6 +17,8 @@
 //   ONE_TO_ONE        atomicMin of (d2 bits << 32 | query) per matched target, a pass that keeps the winners, and a pass that
 //                     puts the touched words back to ~0: the table is as large as the target but only what the matches touch
 //                     is ever written.
+//   SAMPLE_CONSENSUS  the one stage that needs the points and the host: mvr_reject_sac.hip (rules C1-C12).  It synchronises the
+//                     stream; the stages around it queue as before and its W_OUT word rides with theirs.
 // Counts are integer atomics (one per block), so every result is independent of the launch shape and of arrival order.
 #include "mvr_internal.h"
 
@@ -277,7 +279,8 @@ int ensure_reject_state(Ctx *c, size_t nt, bool one_to_one)
 }
 
 int launch_reject_chain(Ctx *c, const mvr_rejector *chain, int n_chain, const nnkey_t *keys, int32_t *match, size_t ns, size_t nt,
-                        const float4 *snrm, const float4 *tnrm, const double *found, uint32_t found_host)
+                        const float4 *snrm, const float4 *tnrm, const double *found, uint32_t found_host, const float4 *spts, const float4 *tpts,
+                        bool fma, mvr_rej_sac_trace *sac_trace, size_t sac_trace_cap)
 {
   uint32_t *words = reinterpret_cast<uint32_t *>(c->rej_row + kRejRowDoubles);
   uint32_t *hist = words + kRejCopyWords, *tie = hist + kRejHistBins;
@@ -320,6 +323,9 @@ int launch_reject_chain(Ctx *c, const mvr_rejector *chain, int n_chain, const nn
         hipLaunchKernelGGL(rej_oto_clear_kernel, dim3(blocks), dim3(kRejT), 0, c->stream, keys, ns, nt, c->rej_win);
         MVR_HIP_TRY(c, hipGetLastError());
         c->rej_win_dirty = false;
+        break;
+      case MVR_REJ_SAMPLE_CONSENSUS:
+        if (int rc = reject_sac_stage(c, r, fma, spts, tpts, match, ns, stage, sac_trace, sac_trace_cap)) return rc;
         break;
       default:
         return set_error(c, MVR_E_ARG, "unknown rejector kind");
