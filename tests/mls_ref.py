@@ -10,15 +10,25 @@ independent routes:
 
 Neighbour membership is the library's f32 rule, through outlier_ref.within_r2 (candidates from a kd-tree over the finite
 points with a wide margin).  Per point the reference reports the neighbour count, the relative eigen-gap (l1 - l0) / l2 of the
-covariance and the condition number of the 6 x 6 system.  A point is EXCLUDED from value comparisons when its gap is below
-1e-6, when its polynomial applies and the condition number exceeds 1e10, or when the two routes differ by more than 1e-9 mm (in
-a coordinate; 1e-9 in a component of the unit normal).  Kept set, order and counts are never excluded.
+covariance and the condition number of the 6 x 6 system, raw (`cond`) and written in units of the radius (`cond_r`).  A point
+is EXCLUDED from value comparisons when its gap is below 1e-6, when its polynomial applies and cond_r exceeds 1e10, or when the
+two routes differ by more than 1e-9 radii in a coordinate or 1e-9 in a component of the unit normal (`rel_plane`, `rel_poly`).
+Kept set, order and counts are never excluded.
+
+The exclusion rules know no unit of length.  The problem is homogeneous: the cloud and the radius times a power of two give
+route A's coordinates times that power, and its normals and curvature unchanged, bit for bit (tests/test_mls_host.py asserts
+it).  So the yardsticks are homogeneous too: the condition number is that of D A D with D = diag(r^-deg) over the basis 1, b,
+b^2, a, ab, a^2 -- the system of the offsets a / r, b / r --, route B solves its least-squares problem in those offsets (the
+cut-off of the pseudo-inverse compares singular values, which in raw offsets span 1 to r^2), and the routes' distance is
+taken in radii.  The raw condition number and the raw distances (`cond`, `diff_plane`, `diff_poly`, in the cloud's unit) are
+still reported; nothing is decided on them.
 
 The curvature |l0| / (l0 + l1 + l2) has a blind spot of its own: where the neighbours are coplanar -- always, with exactly 3
 of them -- l0 is exactly 0 and what any implementation computes is the rounding noise of its eigen-solver, about 1e-16 l2.
 The same third rule covers it: the curvature (and only the curvature) of a point is left out of value comparisons where the
 two routes' curvatures (eigh of the covariance; squared singular values of the centred neighbour matrix) differ by more than
-1e-9 relative (curvature_unpinned)."""
+1e-9 relative (curvature_unpinned).  A component of the unit normal that is exactly 0 has the same blind spot and the same rule
+(normal_unpinned)."""
 import numpy as np
 
 from outlier_ref import finite_mask, neighbor_counts, within_r2
@@ -53,7 +63,7 @@ def _chunks(p, radius, fma, rows, budget=4e6):
     r2 = F32(min(radius * radius, float(np.finfo(F32).max)))
     P64 = P.astype(F64)
     tree = cKDTree(P64)
-    rad = radius * (1.0 + 1e-4) + 1e-4 + 1e-6 * float(np.abs(P64).max())
+    rad = radius * (1.0 + 1e-4) + 1e-6 * float(np.abs(P64).max())         # (in the cloud's own unit: no absolute length)
     qf = fin[rows]
     q32 = np.where(qf[:, None], p[rows, :3], P[0]).astype(F32)        # (a non-finite query: a finite stand-in, masked below)
     Q = q32.astype(F64)
@@ -131,7 +141,19 @@ def _basis(a, b):
     return np.stack([np.ones_like(a), b, b * b, a, a * b, a * a], -1)
 
 
-def _route_a(q, X, member, g):
+_DEG = np.array([0.0, 1.0, 2.0, 1.0, 2.0, 2.0])          # the degrees of the basis 1, b, b^2, a, ab, a^2
+
+
+def _cond(A):
+    out = np.full(len(A), np.inf)
+    fin = np.isfinite(A).all(axis=(1, 2))
+    if fin.any():
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            out[fin] = np.linalg.cond(A[fin])
+    return out
+
+
+def _route_a(q, X, member, g, radius):
     """-> dict of per-point f64 results of route A"""
     m = len(q)
     w01 = member.astype(F64)
@@ -161,21 +183,25 @@ def _route_a(q, X, member, g):
     r = np.einsum("mk,mki->mi", w * f, Phi)
     applies = cnt >= 6
     A[~applies] = np.eye(6)
-    fin = np.isfinite(A).all(axis=(1, 2))
-    cond = np.full(m, np.inf)
-    if fin.any():
-        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-            cond[fin] = np.linalg.cond(A[fin])
+    cond = _cond(A)
+    # the same system in units of the radius, for the exclusion rule alone: D A D, D = diag(radius^-deg)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        D = float(radius) ** -_DEG
+        cond_r = _cond(A * D[None, :, None] * D[None, None, :])
     coef, ok = _cholesky_solve(A, r)
     ok &= applies
+    # a diagonal entry of A is a sum of terms w phi^2, none negative: exactly 0 in one order of summation, it is exactly 0 in
+    # every order, and its pivot is not positive -- the one abandoned fit that does not hang on a rounding
+    zero_diag = applies & (np.diagonal(A, axis1=1, axis2=2) == 0).any(1)
     c0 = np.where(ok, coef[:, 0], 0.0)
     poly = plane + c0[:, None] * n
     pn = _unit(n - coef[:, 3:4] * u - coef[:, 1:2] * v)
     pn = np.where(ok[:, None], pn, n)
-    return dict(count=cnt, gap=gap, cond=np.where(applies, cond, 1.0), curv=curv, plane=plane, normal=n, poly=poly, poly_normal=pn, fit=ok)
+    return dict(count=cnt, gap=gap, cond=np.where(applies, cond, 1.0), cond_r=np.where(applies, cond_r, 1.0), curv=curv, plane=plane,
+                normal=n, poly=poly, poly_normal=pn, fit=ok, zero_diag=zero_diag)
 
 
-def _route_b(q, X, member, g):
+def _route_b(q, X, member, g, radius):
     w01 = member.astype(F64)
     cnt = member.sum(1)
     c = np.maximum(cnt, 1).astype(F64)
@@ -197,9 +223,14 @@ def _route_b(q, X, member, g):
     a, b, f = _dot(dd, u[:, None, :]), _dot(dd, v[:, None, :]), _dot(dd, n[:, None, :])
     with np.errstate(over="ignore", under="ignore", invalid="ignore"):
         sw = np.sqrt(np.exp(-_dot(dd, dd) / g)) * w01
-    M = _basis(a, b) * sw[:, :, None]
+    # the least-squares problem in units of the radius: f / r over the basis of a / r, b / r; then c0 is in radii and c1, c3 are
+    # slopes, which have no unit (the other three are not used)
+    ir = 1.0 / float(radius)
+    M = _basis(a * ir, b * ir) * sw[:, :, None]
     M = np.where(np.isfinite(M), M, 0.0)
-    coef = np.einsum("mik,mk->mi", np.linalg.pinv(M), np.where(np.isfinite(f), f, 0.0) * sw) if M.shape[1] >= 6 else np.zeros((len(q), 6))
+    fr = f * ir
+    coef = np.einsum("mik,mk->mi", np.linalg.pinv(M), np.where(np.isfinite(fr), fr, 0.0) * sw) if M.shape[1] >= 6 else np.zeros((len(q), 6))
+    coef[:, 0] *= float(radius)
     poly = plane + coef[:, 0:1] * n
     pn = _unit(n - coef[:, 3:4] * u - coef[:, 1:2] * v)
     return dict(plane=plane, normal=n, poly=poly, poly_normal=pn, curv=curv)
@@ -211,36 +242,53 @@ def _sign_free_diff(a, b):
 
 def fit(p, radius, sqr_gauss_param=0.0, fma=False, rows=None, second_route=True):
     """Both orders at once for the queries `rows` (default: every point) of the cloud p, per query (f64 unless said):
-      count, gap, cond, curv, keep (count >= 3)
+      count, gap, cond (raw coordinates), cond_r (in units of the radius), curv, keep (count >= 3)
       plane / normal          the order-0/1 result (M4)
       poly / poly_normal      the order-2 result (M5; the plane's where the polynomial does not apply or was abandoned)
-      diff_plane / diff_poly  largest difference between the two routes, coordinates (mm) and normal components together
+      diff_plane / diff_poly  largest difference between the two routes, coordinates (in the cloud's unit) and normal components
+                              together
+      rel_plane / rel_poly    the same with the coordinates' difference in radii: what excluded() decides on
       diff_curv               relative difference between the two routes' curvatures
+      normal_b / poly_normal_b  route B's normals, on route A's side (the plane's where route A abandoned the fit)
       plane_b / poly_b        route B's coordinates (its polynomial is always solved, also where route A abandoned the fit)
+      fit                     the polynomial applied and its fit stood (bool)
+      zero_diag               the polynomial applied and a diagonal entry of the normal equations is exactly 0: the fit is
+                              abandoned whatever the order of the sums.  Any other abandoned fit hangs on the sign of a pivot
+                              that is rounding noise about 0 (a positive semi-definite matrix has no negative pivot), and
+                              another order of summation may well keep it (tests/test_mls_host.py shows it on the reference)
     """
     p = np.asarray(p, F32)
     n = len(p) if rows is None else len(rows)
     g = float(sqr_gauss_param) if sqr_gauss_param != 0.0 else float(radius) * float(radius)
     keys3 = ("plane", "normal", "poly", "poly_normal")
-    out = {k: np.full((n, 3), np.nan) for k in keys3 + ("plane_b", "poly_b")}
-    for k in ("gap", "cond", "curv", "diff_plane", "diff_poly", "diff_curv"):
+    out = {k: np.full((n, 3), np.nan) for k in keys3 + ("plane_b", "poly_b", "normal_b", "poly_normal_b")}
+    for k in ("gap", "cond", "cond_r", "curv", "diff_plane", "diff_poly", "diff_curv", "rel_plane", "rel_poly"):
         out[k] = np.full(n, np.nan)
     out["count"] = np.zeros(n, np.int64)
     out["fit"] = np.zeros(n, bool)
+    out["zero_diag"] = np.zeros(n, bool)
     o = 0
     for r, q, X, member in _chunks(p, radius, fma, rows):
         sl = slice(o, o + len(r))
         o += len(r)
-        A = _route_a(q, X, member, g)
-        for k in keys3 + ("gap", "cond", "curv", "count", "fit"):
+        A = _route_a(q, X, member, g, radius)
+        for k in keys3 + ("gap", "cond", "cond_r", "curv", "count", "fit", "zero_diag"):
             out[k][sl] = A[k]
         if second_route:
-            B = _route_b(q, X, member, g)
+            B = _route_b(q, X, member, g, radius)
             out["plane_b"][sl], out["poly_b"][sl] = B["plane"], B["poly"]
+            with np.errstate(invalid="ignore"):
+                nb = B["normal"] * np.where(_dot(A["normal"], B["normal"]) < 0, -1.0, 1.0)[:, None]
+                pb = B["poly_normal"] * np.where(_dot(A["poly_normal"], B["poly_normal"]) < 0, -1.0, 1.0)[:, None]
+            out["normal_b"][sl], out["poly_normal_b"][sl] = nb, np.where(A["fit"][:, None], pb, nb)
             out["diff_plane"][sl] = np.maximum(np.abs(A["plane"] - B["plane"]).max(1), _sign_free_diff(A["normal"], B["normal"]))
             # (route B always solves the least-squares problem; it is compared where route A's fit stood)
             dp = np.maximum(np.abs(A["poly"] - B["poly"]).max(1), _sign_free_diff(A["poly_normal"], B["poly_normal"]))
             out["diff_poly"][sl] = np.where(A["fit"], dp, out["diff_plane"][sl])
+            ir = 1.0 / float(radius)
+            out["rel_plane"][sl] = np.maximum(np.abs(A["plane"] - B["plane"]).max(1) * ir, _sign_free_diff(A["normal"], B["normal"]))
+            rp = np.maximum(np.abs(A["poly"] - B["poly"]).max(1) * ir, _sign_free_diff(A["poly_normal"], B["poly_normal"]))
+            out["rel_poly"][sl] = np.where(A["fit"], rp, out["rel_plane"][sl])
             big = np.maximum(A["curv"], B["curv"])
             out["diff_curv"][sl] = np.where(big > 0, np.abs(A["curv"] - B["curv"]) / np.where(big > 0, big, 1.0), 0.0)
     out["keep"] = out["count"] >= 3
@@ -250,9 +298,9 @@ def fit(p, radius, sqr_gauss_param=0.0, fma=False, rows=None, second_route=True)
 def excluded(R, order):
     """the points of fit()'s result that take no part in value comparisons at this order (dropped points are not counted)"""
     poly = (order == 2) & (R["count"] >= 6)
-    diff = np.where(poly, R["diff_poly"], R["diff_plane"])
+    diff = np.where(poly, R["rel_poly"], R["rel_plane"])
     with np.errstate(invalid="ignore"):
-        bad = (R["gap"] < MIN_GAP) | (poly & (R["cond"] > MAX_COND)) | ~(diff <= MAX_ROUTE_DIFF)
+        bad = (R["gap"] < MIN_GAP) | (poly & (R["cond_r"] > MAX_COND)) | ~(diff <= MAX_ROUTE_DIFF)
     return bad & R["keep"]
 
 
@@ -260,6 +308,18 @@ def curvature_unpinned(R):
     """the kept points whose curvature the reference cannot pin (coplanar neighbours: l0 is rounding noise)"""
     with np.errstate(invalid="ignore"):
         return ~(R["diff_curv"] <= MAX_ROUTE_DIFF) & R["keep"]
+
+
+def normal_unpinned(R, order):
+    """[n, 3] bool: the components of the kept points' normals that the reference cannot pin to an f32 ulp -- the two routes
+    differ by more than 1e-9 of the component itself.  That is a component that is 0 in exact arithmetic (an axis-aligned
+    normal on a lattice; three neighbours that share a coordinate in a far frame, where every coordinate is a multiple of
+    1 / 16): each route returns its own rounding noise, 1e-17 or an exact 0, and one f32 ulp of THAT is no bar any f64
+    arithmetic can meet.  Such a component is held to the bar the routes themselves are held to, 1e-9 absolute"""
+    a, b = (R["poly_normal"], R["poly_normal_b"]) if order == 2 else (R["normal"], R["normal_b"])
+    with np.errstate(invalid="ignore"):
+        # (two routes that both return an exact 0 agree, and pin nothing: below the routes' own bar the relative test is void)
+        return (~(np.abs(a - b) <= MAX_ROUTE_DIFF * np.abs(a)) | (np.abs(a) < MAX_ROUTE_DIFF)) & R["keep"][:, None]
 
 
 def flip(nf, ref):

@@ -2,9 +2,10 @@
 reference of tests/mls_ref.py and against a ground truth that passes through no reference: the generator's noise-free twin
 of every point (the same seed with noise_sigma = 0) and its analytic normal.
 
-Value comparisons leave out the points the reference itself cannot pin (mls_ref.excluded: eigen-gap below 1e-6, condition above
-1e10, the two f64 routes more than 1e-9 mm apart); their share is asserted to be 0 on the synthetic views.  Kept set, order and
-counts are compared everywhere.
+Value comparisons leave out the points the reference itself cannot pin (mls_ref.excluded: eigen-gap below 1e-6, condition of
+the system in units of the radius above 1e10, the two f64 routes more than 1e-9 radii apart); their share is asserted to be 0 on
+the synthetic views.  Kept set, order and counts are compared everywhere.  The bars themselves are in tests/mls_compare.py,
+shared with tests/test_gpu_mls_cases.py (adversarial clouds, other units of length).
 
 The curvature alone has a further blind spot (coplanar neighbours, always with exactly 3: l0 is rounding noise); it is left out
 where the reference's two routes disagree on it (mls_ref.curvature_unpinned); there the reference's curvature and the GPU's must
@@ -24,12 +25,11 @@ import mls_cases as K
 import mls_ref as R
 import walk_cases as W
 from conftest import PKG
+from mls_compare import DIFFER_CAP, FLAT, bits, compare_values, same_bits  # noqa: F401  (the bars, shared with test_gpu_mls_cases.py)
 
 pytestmark = pytest.mark.gpu
 
 F32, F64 = np.float32, np.float64
-DIFFER_CAP = 1e-5          # share of the non-excluded coordinates that may differ at all (by one ulp)
-FLAT = 1e-6                # curvature below which a neighbourhood counts as coplanar (l0 is then below 1e-6 of the trace)
 
 
 @pytest.fixture(scope="module")
@@ -42,14 +42,6 @@ def ctx(mvr):
     c = mvr.Context(0)
     yield c
     c.close()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
 
 
 synth, with_non_finite = K.synth, K.with_non_finite
@@ -90,30 +82,6 @@ def mls(ctx, p, radius, dst=1, src=0, normals=None, **kw):
 
 
 # ------------------------------------------------------------------ values
-
-def compare_values(what, got_xyz, got_nrm, got_curv, ref, bad, flat):
-    """bad: the kept points left out of every comparison; flat: those whose curvature alone is left out (coplanar
-    neighbours, mls_ref.curvature_unpinned)"""
-    ok = ~bad
-    n_ok = int(ok.sum())
-    one = R.within_one_ulp(got_xyz[ok], ref["xyz"][ok])
-    differ = bits(got_xyz[ok]) != bits(ref["xyz"][ok])
-    n1 = R.within_one_ulp(got_nrm[ok], ref["normal"][ok])
-    nd = bits(got_nrm[ok]) != bits(ref["normal"][ok])
-    okc = ok & ~flat
-    c1 = R.within_one_ulp(got_curv[okc], ref["curvature"][okc])
-    cd = bits(got_curv[okc]) != bits(ref["curvature"][okc])
-    print("%s: %d compared, %d excluded; coordinates beyond one ulp %d, differing %d of %d (share %.2e); normal components "
-          "beyond one ulp %d, differing %d; curvatures beyond one ulp %d, differing %d, not pinned by the reference %d"
-          % (what, n_ok, int(bad.sum()), int((~one).sum()), int(differ.sum()), differ.size, differ.mean() if differ.size else 0.0,
-             int((~n1).sum()), int(nd.sum()), int((~c1).sum()), int(cd.sum()), int(flat.sum())))
-    assert one.all() and n1.all() and c1.all()
-    assert differ.mean() <= DIFFER_CAP
-    # where the one-ulp check of the curvature is waived the neighbours are coplanar to rounding: the reference says so, and
-    # what the GPU returns must say the same
-    w = ok & flat
-    assert (ref["curvature"][w] < FLAT).all() and (got_curv[w] >= 0).all() and (got_curv[w] < FLAT).all()
-
 
 @pytest.mark.parametrize("fma", [False, True])
 @pytest.mark.parametrize("order", [1, 2])
