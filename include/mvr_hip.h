@@ -984,7 +984,8 @@ int  mvr_ctx_last_sample_consensus(mvr_ctx *ctx, mvr_rej_sac_result *result);
  *      fails the test takes I: the library's rule (PCL has no such case, its covariances come from neighbourhoods).
  *  G4. W_i = (A_i + B_j)^-1, fixed for the whole inner optimisation: the current normals already carry the rotation
  *      accumulated so far, which is PCL's R C_s R^T + C_t.  A + B has eigenvalues in [2 eps, 2]; the inverse is the closed-form
- *      symmetric one (cofactors over the determinant) in f64.
+ *      symmetric one (cofactors over the determinant) in f64.  Its accuracy is about 5e-16 / eps relative to |W|; nothing is
+ *      promised below eps = 1e-9.
  *  G5. The objective at X = (R, t): F = (1 / m) sum r^T W r, y = R p + t, r = y - q.  Linearised by y' = Exp(w) y + v,
  *      delta = (w, v), rotation first as in the point-to-plane row: J = [-[y]x | I].  The 29 sums: 0..20 the upper triangle of
  *      H = sum J^T W J, row-major; 21..26 g = sum J^T W r; 27 the count m; 28 f = sum r^T W r.  f64, in a fixed order,
@@ -995,7 +996,9 @@ int  mvr_ctx_last_sample_consensus(mvr_ctx *ctx, mvr_rej_sac_result *result);
  *      rank-deficient H is caught here only when a diagonal entry is 0, e.g. every point at the origin; otherwise by G7's
  *      lambda > 1e9.)
  *  G7. The inner loop is Levenberg-Marquardt.  DEVIATION: PCL runs BFGS on (x, y, z, roll, pitch, yaw); the objective is the
- *      same and so is its minimum.  Start at X = I with lambda = 1e-3 and evaluate G5 there.  While evaluations <
+ *      same and so is its minimum.  Start at X = I with lambda = 1e-3 and evaluate G5 there.  If f there is not finite -- a
+ *      listed point or an entry of a W is NaN or infinite -- the optimisation ends with MVR_E_SINGULAR, evaluations = 1 and
+ *      X = I (the searches never match a non-finite point; a caller's list may name one).  While evaluations <
  *      max_inner_iterations (PCL: 20): step by G6, evaluate at the candidate, decide.  ACCEPT when f_c < f (strictly; a NaN
  *      fails): X and the sums become the candidate's, lambda = max(lambda / 10, 1e-9), and the loop ends when |w|_2 <
  *      inner_rot_tol (default 1e-6 rad) and |v|_2 < inner_trans_tol (default 1e-5).  REJECT otherwise: lambda = 10 lambda,
@@ -1015,7 +1018,9 @@ int  mvr_ctx_last_sample_consensus(mvr_ctx *ctx, mvr_rej_sac_result *result);
  *      and R10.
  * mvr_gicp_sums / mvr_gicp_solve are G5 and G5-G7 on the caller's correspondence list (query / match: host arrays of `count`
  * entries, validated as in R8; the slots supply points and normals).  X, X_out: 4x4 column-major f64.  mvr_gicp_solve
- * returns MVR_E_NOCORR for fewer than 3 entries and MVR_E_SINGULAR as G6; X_out and info hold the state reached.
+ * returns MVR_E_NOCORR for fewer than 3 entries and MVR_E_SINGULAR as G6 and G7; X_out and info hold the state reached.
+ * mvr_gicp_sums has no such rule: on a list that names a non-finite point it returns MVR_OK, the exact count in out[27] and
+ * sums that are not finite.
  * Out of scope: PCL's BFGS; setSourceCovariances / setTargetCovariances; GICP in the ring / LUM passes, in mvr_seq_run, the
  * sharded entries and the Registrator drivers. */
 typedef struct {

@@ -2549,7 +2549,7 @@ API int mvr_gicp_solve(mvr_ctx *ctx, int ss, int ts, const int32_t *query, const
   gicp_mat(h + kGicpX, X_out);
   if (info) { info->evaluations = w[kGicpEvals]; info->accepted = w[kGicpAccepted]; info->lambda = h[kGicpLambda]; info->f0 = h[kGicpF0]; info->f1 = h[kGicpF1]; }
   const int status = (int)w[kGicpStatus];
-  if (status != MVR_OK) return set_error(c, status, "GICP: the inner optimisation stopped (a pivot of the damped system is not positive)");
+  if (status != MVR_OK) return set_error(c, status, "GICP: the inner optimisation stopped (a pivot of the damped system is not positive, or f at X = I is not finite)");
   return MVR_OK;
 }
 

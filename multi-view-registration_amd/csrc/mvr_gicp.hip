@@ -179,7 +179,11 @@ __global__ void __launch_bounds__(kRT) gicp_step_kernel(const double *__restrict
   if (evals == 0u) {                                               // the evaluation at X = I
     for (int k = 0; k < 29; ++k) state[kGicpSums + k] = s[k];
     if (s[27] < 3.0) { done = 1u; status = MVR_E_NOCORR; }
-    else { state[kGicpF0] = s[28] / s[27]; state[kGicpF1] = s[28] / s[27]; }
+    else {
+      const double f0 = s[28] / s[27];
+      state[kGicpF0] = f0; state[kGicpF1] = f0;
+      if (!isfinite(f0)) { done = 1u; status = MVR_E_SINGULAR; }   // G7: a listed point or a W that is not finite
+    }
   } else {
     const double f = state[kGicpSums + 28];
     if (s[28] < f) {                                               // accept: strictly below; a NaN fails

@@ -1,4 +1,5 @@
-"""shared inputs of the Generalized-ICP tests (tests/test_gicp_host.py on the CPU, tests/test_gpu_gicp.py on the GPU).  Sizes answer
+"""shared inputs of the Generalized-ICP tests (tests/test_gicp_host.py on the CPU, tests/test_gpu_gicp.py and
+tests/test_gpu_gicp_cases.py on the GPU).  Sizes answer
 to the launch shapes of csrc/mvr_gicp.hip: gicp_sums_kernel runs blocks of 256 threads (four waves of 64), one block per 256
 entries of the match table up to one block per compute unit, and strides beyond that; gicp_step_kernel is one block that adds the
 partial rows in 8 groups.  So 3 is the smallest list the optimiser takes, 64 / 65 a wave and a wave plus one, 257 a block plus
@@ -114,6 +115,196 @@ def big_list(n_cu):
     if ("big", n) not in _lists:
         _lists[("big", n)] = moved_pair(40, n)
     return _lists[("big", n)]
+
+
+# ------------------------------------------------------------------ the branch cases (tests/test_gpu_gicp_cases.py)
+#
+# The list cases above all take one path through G7: accepts only, ended by the step tolerance.  Each branch case is the source,
+# the normals and the list of a list case (rand_257 unless the name says otherwise) with a target of its own, rounded to f32
+# before anything sees it, built so that the reference takes another path.  What each is for is stated in BRANCH and asserted
+# on the reference alone by tests/test_gicp_host.py:
+#   pattern   a regular expression the string of decisions (A accept, R reject) matches in full
+#   end       "tol" (an accepted step below both tolerances), "cap" (max_inner_iterations), "lambda" (> 1e9), "singular"
+#   evals     the evaluation count, where it is a fixed number
+#   rejects   the number of rejects
+#   undecided the evaluations whose decision MAY be undecided (gicp_ref.decided); every other one is decided.  "last": the last
+#             one.  No case's first decision (evaluation 2) is among them.
+#   small_arm the last accepted step has |w| < 1e-8: the candidate comes from the small-angle arm of G6's Rodrigues matrix
+FAR_DIR = (0.61, -0.52, 0.6)
+BRANCH = {
+    "exact_fit": dict(pattern="R{13}", end="lambda", evals=14, rejects=13, undecided=()),
+    "exact_shift": dict(pattern="A{6}", end="tol", evals=7, rejects=0, undecided=(), small_arm=True),
+    "turn_0.1": dict(pattern="AARA+", end="tol", evals=10, rejects=1, undecided=("last",)),
+    "turn_0.3": dict(pattern="(AR){9}A", end="cap", evals=20, rejects=9, undecided=()),
+    "turn_0.3_long": dict(pattern="(AR){11}A(AR){2}A{6}", end="tol", evals=34, rejects=13, undecided=("last",), max_inner=60),
+    "turn_0.3_65": dict(pattern="(AR){3}A(AR){6}", end="cap", evals=20, rejects=9, undecided=()),
+    "turn_0.3_6001": dict(pattern="(AR){9}A", end="cap", evals=20, rejects=9, undecided=()),
+    "far_1e4": dict(pattern="A{8}RRA", end="tol", evals=12, rejects=2, undecided=(9, 10, 11, 12)),
+    "far_1e5": dict(pattern="A{5}(RA){7}", end="cap", evals=20, rejects=7, undecided=()),
+    "three_targets": dict(pattern="(AR){9}A", end="cap", evals=20, rejects=9, undecided=()),
+    "coplanar": dict(pattern="A+", end="tol", rejects=0, undecided=()),
+    "collinear": dict(pattern="A+", end="tol", rejects=0, undecided=()),
+    "collinear_origin": dict(pattern="", end="singular", evals=1, rejects=0, undecided=()),
+    "all_equal_away": dict(pattern="AAA", end="tol", evals=4, rejects=0, undecided=()),
+    "nan_point": dict(pattern="", end="singular", evals=1, rejects=0, undecided=()),
+    "inf_target": dict(pattern="", end="singular", evals=1, rejects=0, undecided=()),
+}
+BRANCH_NAMES = tuple(BRANCH)
+FAR_FRAMES = ("far_1e4", "far_1e5")                       # only TRANS_TOL on the displacement applies to these
+# turn_0.3_long is turn_0.3 with max_inner_iterations = 60: the run then ends by the tolerance, after 34 evaluations
+# the old list cases: all accepts, ended by the tolerance; at most their last LIST_UNDECIDED_TAIL decisions are undecided
+LIST_UNDECIDED_TAIL = 2
+
+
+def _base(name):
+    base = {"turn_0.3_65": "rand_65", "turn_0.3_6001": "rand_6001"}.get(name, "rand_257")
+    c = list_case(base)
+    return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in c.items()}
+
+
+def _set_target(c, pts):
+    """the target whose point match[k] is pts[query[k]] (pts: one per SOURCE point, f64), rounded to f32"""
+    perm = np.empty(len(c["src"]), np.int64)
+    perm[c["query"]] = c["match"]
+    tgt = np.ones((len(c["tgt"]), 4), F32)
+    tgt[perm, :3] = np.asarray(pts, np.float64).astype(F32)
+    c["tgt"] = tgt
+    return c
+
+
+def _moved(P, T):
+    return P @ T[:3, :3].T + T[:3, 3]
+
+
+def _turn(name, angle):
+    c = _base(name)
+    P = c["src"][:, :3].astype(np.float64)
+    c["T"] = small_motion(np.random.default_rng(5), angle=angle, shift=1.0, centre=P.mean(0))
+    return _set_target(c, _moved(P, c["T"]))
+
+
+def _far(c, dist):
+    """the pair moved by dist * FAR_DIR, each side rounded to f32"""
+    off = dist * np.array(FAR_DIR)
+    for key in ("src", "tgt"):
+        c[key][:, :3] = (c[key][:, :3].astype(np.float64) + off).astype(F32)
+    return c
+
+
+def _flat(name):
+    c = _base(name)
+    P = c["src"][:, :3].astype(np.float64)
+    # coplanar is fragile: its smallest decided margin is 1.32e-9 against the 1e-9 of gicp_ref.decided (the last decision, at
+    # f = 6.5e-10).  A change to the reference's arithmetic can tip it to undecided; tests/test_gicp_host.py then fails, loudly.
+    if name == "coplanar":                                # flattened to its own mean z: still some 900 units off the origin
+        P[:, 2] = P[:, 2].mean()
+    elif name == "collinear":                              # projected on the line through its own mean along x
+        P[:, 1:] = P[:, 1:].mean(0)
+    else:                                                  # collinear_origin: on the x axis, so that H[0][0] is exactly 0
+        P = np.stack([P[:, 0], np.zeros(len(P)), np.zeros(len(P))], axis=1)
+    c["src"][:, :3] = P.astype(F32)
+    return _set_target(c, _moved(c["src"][:, :3].astype(np.float64), small_motion(np.random.default_rng(4))))
+
+
+def branch_case(name):
+    if ("branch", name) in _lists:
+        return _lists["branch", name]
+    if name == "turn_0.3_long":
+        c = branch_case("turn_0.3")
+    elif name.startswith("turn_"):
+        c = _turn(name, float(name.split("_")[1]))
+    elif name in ("coplanar", "collinear", "collinear_origin"):
+        c = _flat(name)
+    else:
+        c = _base(name)
+        P = c["src"][:, :3].astype(np.float64)
+        if name == "exact_fit":
+            _set_target(c, P)
+        elif name == "exact_shift":
+            _set_target(c, P + np.array([0.25, -0.5, 1.0]))
+        elif name.startswith("far_"):
+            _far(c, float(name.split("_")[1]))
+        elif name == "three_targets":
+            c["match"] = (np.arange(len(c["query"])) % 3).astype(np.int32)
+        elif name == "all_equal_away":
+            c["src"][:, :3] = c["src"][0, :3]
+            _set_target(c, c["src"][:, :3].astype(np.float64) + 0.5)
+        elif name == "nan_point":
+            c["src"][c["query"][7], 1] = np.nan
+        elif name == "inf_target":
+            c["tgt"][c["match"][7], 1] = np.inf
+        else:
+            raise KeyError(name)
+    _lists["branch", name] = c
+    return c
+
+
+def unlisted_nan():
+    """`half` with a NaN in source points the list does not name: (the case, the same with the NaNs)"""
+    c = list_case("half")
+    d = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in c.items()}
+    free = np.setdiff1d(np.arange(len(c["src"])), c["query"])
+    assert len(free) >= 100
+    d["src"][free[3], 1] = np.nan
+    d["src"][free[40], :3] = np.nan
+    d["src"][free[41], 0] = np.inf
+    return c, d
+
+
+UNIT_SCALES = (2.0 ** -30, 2.0 ** -10, 2.0 ** 10, 2.0 ** 30)
+UNIT_CASES = ("rand_257", "turn_0.3")
+
+
+def branch_params(name, **kw):
+    """the keyword arguments of the case's run: the defaults, but for turn_0.3_long"""
+    if "max_inner" in BRANCH[name]:
+        kw.setdefault("max_inner_iterations", BRANCH[name]["max_inner"])
+    return kw
+
+
+_runs = {}
+
+
+def reference_run(name, eps=1e-3):
+    """(X, info, status, log) of gicp_ref.solve on a branch or a list case, at the case's parameters; computed once, not to be
+    written to"""
+    import gicp_ref as G
+    if (name, eps) not in _runs:
+        kw = branch_params(name, gicp_epsilon=eps) if name in BRANCH else dict(gicp_epsilon=eps)
+        log = []
+        X, info, status = G.solve(*gathered(any_case(name)), G.params(**kw), log=log)
+        _runs[name, eps] = (X, info, status, log)
+    return _runs[name, eps]
+
+
+def state_after(log, k):
+    """the reference's state after k evaluations -> (X, lambda, accepted)"""
+    if k == 1:
+        return np.eye(4), 1e-3, 0
+    e = log[k - 2]
+    return e["X"], e["lam_after"], e["accepted"]
+
+
+def decided_prefix(log):
+    """the number of evaluations up to which every decision is decided (1: not even the first decision is)"""
+    k = 1
+    for e in log:
+        if not e["decided"]:
+            break
+        k += 1
+    return k
+
+
+def any_case(name):
+    return branch_case(name) if name in BRANCH else list_case(name)
+
+
+def in_unit(c, s):
+    """the case with both clouds times s, a power of two (mls_cases.scaled asserts that this is exact in f32)"""
+    import mls_cases as MC
+    d = dict(c)
+    d["src"], d["tgt"] = MC.scaled(c["src"], s), MC.scaled(c["tgt"], s)
+    return d
 
 
 def gathered(c):

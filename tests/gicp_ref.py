@@ -72,7 +72,71 @@ def terms(p, s, q, n, X, eps):
 
 
 def fsum_columns(t):
-    return np.array([math.fsum(t[:, k]) for k in range(t.shape[1])]) if len(t) else np.zeros(t.shape[1])
+    """the exactly rounded sum of every column; a column that holds a NaN or infinities of both signs sums to NaN"""
+    def one(col):
+        try:
+            return math.fsum(col)
+        except (ValueError, OverflowError):
+            return float("nan")
+    return np.array([one(t[:, k]) for k in range(t.shape[1])]) if len(t) else np.zeros(t.shape[1])
+
+
+def terms_ld(p, s, q, n, X, eps):
+    """terms() once more with np.longdouble throughout and the closed-form inverse of G4 (cofactors over the determinant):
+    the reference of the sums over the range of gicp_epsilon, where np.linalg.inv in f64 is no better than the kernel"""
+    LD = np.longdouble
+    assert np.finfo(LD).eps < 2e-19
+    p, s, q, n, X = (np.asarray(a, F64).astype(LD) for a in (p, s, q, n, X))
+    eps, one = LD(eps), LD(1)
+    k = one - eps
+
+    def unit(v):
+        with np.errstate(invalid="ignore", over="ignore"):
+            l2 = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
+            ok = np.isfinite(v).all(1) & (l2 > 0)
+        u = np.zeros_like(v)
+        u[ok] = v[ok] / np.sqrt(l2[ok])[:, None]
+        return u
+    us, un = unit(s), unit(n)
+    M = {}
+    for a in range(3):
+        for b in range(a, 3):
+            M[a, b] = (LD(2) if a == b else LD(0)) - k * (us[:, a] * us[:, b]) - k * (un[:, a] * un[:, b])
+    a, b, c, d, e, f = M[0, 0], M[0, 1], M[0, 2], M[1, 1], M[1, 2], M[2, 2]
+    c00, c01, c02 = d * f - e * e, c * e - b * f, b * e - c * d
+    c11, c12, c22 = a * f - c * c, b * c - a * e, a * d - b * b
+    det = (a * c00 + b * c01) + c * c02
+    W = np.empty((len(p), 3, 3), LD)
+    W[:, 0, 0], W[:, 0, 1], W[:, 0, 2] = c00 / det, c01 / det, c02 / det
+    W[:, 1, 1], W[:, 1, 2], W[:, 2, 2] = c11 / det, c12 / det, c22 / det
+    W[:, 1, 0], W[:, 2, 0], W[:, 2, 1] = W[:, 0, 1], W[:, 0, 2], W[:, 1, 2]
+    y = np.stack([(X[r, 0] * p[:, 0] + X[r, 1] * p[:, 1]) + X[r, 2] * p[:, 2] + X[r, 3] for r in range(3)], axis=1)
+    r = y - q
+    J = np.zeros((len(p), 3, 6), LD)
+    J[:, 0, 1], J[:, 0, 2] = y[:, 2], -y[:, 1]
+    J[:, 1, 0], J[:, 1, 2] = -y[:, 2], y[:, 0]
+    J[:, 2, 0], J[:, 2, 1] = y[:, 1], -y[:, 0]
+    J[:, 0, 3] = J[:, 1, 4] = J[:, 2, 5] = one
+    WJ = (W[:, :, :, None] * J[:, None, :, :]).sum(2)                      # (m, 3, 6)
+    Wr = (W * r[:, None, :]).sum(2)
+    out = np.empty((len(p), 29), LD)
+    t = 0
+    for i in range(6):
+        for j in range(i, 6):
+            out[:, t] = (J[:, :, i] * WJ[:, :, j]).sum(1)
+            t += 1
+    for i in range(6):
+        out[:, 21 + i] = (J[:, :, i] * Wr).sum(1)
+    out[:, 27] = one
+    out[:, 28] = (r * Wr).sum(1)
+    assert out.dtype == LD
+    return out
+
+
+def sums_ld(p, s, q, n, X, eps):
+    """(the exactly rounded column sums of terms_ld cast to f64, those of their absolute values)"""
+    t = terms_ld(p, s, q, n, X, eps).astype(F64)
+    return fsum_columns(t), fsum_columns(np.abs(t))
 
 
 def sums(p, s, q, n, X, eps, with_abs=False):
@@ -124,17 +188,32 @@ def candidate(X, delta):
     return Xc
 
 
-def solve(p, s, q, n, prm):
-    """G7 -> (X, info dict(evaluations, accepted, lambda, f0, f1), status)"""
+def decided(f, fc, tot, totc):
+    """whether the comparison f_c < f of G7 is beyond what the sums are held to: every term at both poses is exactly 0 (then
+    f_c == f == 0 on any machine), or the two differ by more than 1e-9 of the terms' absolute values, ten times the bound
+    each side's sum 28 is held to"""
+    if tot == 0.0 and totc == 0.0:
+        return True
+    return bool(abs(fc - f) > 1e-9 * (tot + totc))
+
+
+def solve(p, s, q, n, prm, log=None):
+    """G7 -> (X, info dict(evaluations, accepted, lambda, f0, f1), status).  log (a list) gets one dict per evaluation after
+    the first: decision "A" / "R", lam = lambda before it, f and fc = sum 28 at X and at the candidate, tot and totc = the sums
+    of the absolute values of its terms there, w and v = |omega| and |v| of the step, decided, and the state after the
+    decision: X, lam_after, accepted, f1.  Entry e - 2 is evaluation e; the state after evaluation 1 is (I, 1e-3, 0)."""
     eps = prm["gicp_epsilon"]
     X, lam = np.eye(4), 1e-3
     info = dict(evaluations=0, accepted=0, f0=0.0, f1=0.0)
     info["lambda"] = lam
     if len(p) < 3:
         return X, info, E_NOCORR
-    sm = sums(p, s, q, n, X, eps)
+    sm, tot = sums(p, s, q, n, X, eps, with_abs=True)
     ev, status = 1, OK
     info["f0"] = info["f1"] = sm[28] / sm[27]
+    if not math.isfinite(info["f0"]):                                      # G7: a listed point or weight that is not finite
+        info["evaluations"] = 1
+        return X, info, E_SINGULAR
     while ev < prm["max_inner_iterations"]:
         H, g = unpack(sm)
         delta = cholesky_solve(H, g, lam)
@@ -142,20 +221,47 @@ def solve(p, s, q, n, prm):
             status = E_SINGULAR
             break
         Xc = candidate(X, delta)
-        sc = sums(p, s, q, n, Xc, eps)
+        sc, totc = sums(p, s, q, n, Xc, eps, with_abs=True)
         ev += 1
+        w, v = math.sqrt(float(delta[:3] @ delta[:3])), math.sqrt(float(delta[3:] @ delta[3:]))
+        entry = dict(lam=lam, f=float(sm[28]), fc=float(sc[28]), tot=float(tot[28]), totc=float(totc[28]), w=w, v=v,
+                     decided=decided(float(sm[28]), float(sc[28]), float(tot[28]), float(totc[28])))
+        end = False
         if sc[28] < sm[28]:
-            X, sm, lam = Xc, sc, max(lam / 10.0, 1e-9)
+            X, sm, tot, lam = Xc, sc, totc, max(lam / 10.0, 1e-9)
             info["accepted"] += 1
             info["f1"] = sm[28] / sm[27]
-            if math.sqrt(float(delta[:3] @ delta[:3])) < prm["inner_rot_tol"] and math.sqrt(float(delta[3:] @ delta[3:])) < prm["inner_trans_tol"]:
-                break
+            entry["decision"] = "A"
+            end = w < prm["inner_rot_tol"] and v < prm["inner_trans_tol"]
         else:
             lam = 10.0 * lam
-            if lam > 1e9:
-                break
+            entry["decision"] = "R"
+            end = lam > 1e9
+        if log is not None:
+            entry.update(X=X.copy(), lam_after=lam, accepted=info["accepted"], f1=info["f1"])
+            log.append(entry)
+        if end:
+            break
     info["evaluations"], info["lambda"] = ev, lam
     return X, info, status
+
+
+def pattern(log):
+    return "".join(e["decision"] for e in log)
+
+
+def lambda_of(decisions):
+    """G7's lambda after a string of decisions: 1e-3 * 10^(rejects - accepts), clipped below at 1e-9 where an accept meets it,
+    by the very operations of G7"""
+    lam = 1e-3
+    for d in decisions:
+        lam = max(lam / 10.0, 1e-9) if d == "A" else 10.0 * lam
+    return lam
+
+
+def undecided(log):
+    """the evaluation numbers (2, 3, ...) whose decision is not decided"""
+    return [k + 2 for k, e in enumerate(log) if not e["decided"]]
 
 
 def objective(p, s, q, n, X, eps):

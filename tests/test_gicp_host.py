@@ -4,6 +4,7 @@ before any device is touched, and the layout of the structs against the Python b
 import ctypes as C
 import importlib
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -91,6 +92,125 @@ def test_reference_refusals():
     assert status == G.E_SINGULAR and info["evaluations"] == 1 and np.array_equal(X, np.eye(4))
     X, info, status = G.solve(p, s, q, n, G.params(max_inner_iterations=1))
     assert status == G.OK and info["evaluations"] == 1 and np.array_equal(X, np.eye(4))
+
+
+def how_it_ended(info, status, log, prm):
+    if status == G.E_SINGULAR:
+        return "singular"
+    last = log[-1]
+    if last["decision"] == "R" and last["lam_after"] > 1e9:
+        return "lambda"
+    if last["decision"] == "A" and last["w"] < prm["inner_rot_tol"] and last["v"] < prm["inner_trans_tol"]:
+        return "tol"
+    assert info["evaluations"] == prm["max_inner_iterations"]
+    return "cap"
+
+
+def allowed_undecided(spec, evaluations):
+    return {evaluations if k == "last" else k for k in spec}
+
+
+@pytest.mark.parametrize("name", GC.BRANCH_NAMES)
+def test_branch_cases_reach_their_branches(name):
+    """what tests/gicp_cases.py says each branch case is for, on the reference alone"""
+    want, c = GC.BRANCH[name], GC.branch_case(name)
+    assert c["tgt"].dtype == np.float32 and c["src"].dtype == np.float32
+    X, info, status, log = GC.reference_run(name)
+    prm = G.params(**GC.branch_params(name))
+    pat, und = G.pattern(log), G.undecided(log)
+    margins = [abs(e["fc"] - e["f"]) / (e["tot"] + e["totc"]) for e in log if e["decided"] and e["tot"] + e["totc"] > 0]
+    print("%s: %s, %d evaluations, lambda %g, %s, undecided %s, smallest decided margin %.3g, f %.6g -> %.6g"
+          % (name, pat or "-", info["evaluations"], info["lambda"], how_it_ended(info, status, log, prm), und, min(margins) if margins else 0.0,
+             info["f0"], info["f1"]))
+    assert re.fullmatch(want["pattern"], pat), pat
+    assert how_it_ended(info, status, log, prm) == want["end"]
+    assert pat.count("R") == want["rejects"] and info["accepted"] == pat.count("A") and info["evaluations"] == len(log) + 1
+    assert info["evaluations"] == want.get("evals", info["evaluations"]) <= 34
+    # the cap on what may be undecided, and never the first decision
+    assert set(und) <= allowed_undecided(want["undecided"], info["evaluations"]) and 2 not in und, und
+    assert info["lambda"] == G.lambda_of(pat)
+    if want.get("small_arm"):
+        last = [e for e in log if e["decision"] == "A"][-1]
+        assert last is log[-1] and 0.0 < last["w"] < 1e-8
+    if name == "exact_fit":
+        assert all(e["tot"] == 0.0 and e["totc"] == 0.0 and e["decided"] for e in log)
+        assert info["lambda"] == 1e10 and info["f0"] == info["f1"] == 0.0 and np.array_equal(X, np.eye(4))
+    if want["end"] == "singular":
+        assert np.array_equal(X, np.eye(4)) and info["accepted"] == 0
+    if name == "collinear_origin":
+        p = GC.gathered(c)[0]
+        assert G.sums(*GC.gathered(c), np.eye(4), 1e-3)[0] == 0.0 and np.abs(p).max() > 10.0      # H[0][0] = 0 though the cloud does not sit at the origin
+        assert np.isfinite(info["f0"])
+    if name in ("nan_point", "inf_target"):
+        assert not np.isfinite(info["f0"])
+    if name == "turn_0.3_long":
+        d = GC.gathered(c)[0] @ (X - c["T"])[:3, :3].T + (X - c["T"])[:3, 3]
+        assert np.abs(X - c["T"]).max() < 3e-4 and np.abs(d).max() < 1e-3
+
+
+def test_the_old_list_cases_take_one_path():
+    """every list case, at both values of eps: accepts only, ended by the tolerance, and only the last decisions are undecided --
+    which is why tests/test_gpu_gicp.py holds their counters to the reference over the decided prefix only"""
+    for name in GC.LIST_NAMES + ("big",):                 # big: the list of the GPU test at the 256 compute units of an MI355X
+        for eps in (1e-3, 1.0):
+            if name == "big":
+                log = []
+                X, info, status = G.solve(*GC.gathered(GC.big_list(256)), G.params(gicp_epsilon=eps), log=log)
+            else:
+                X, info, status, log = GC.reference_run(name, eps)
+            pat, und = G.pattern(log), G.undecided(log)
+            print("%s eps %g: %s, undecided %s" % (name, eps, pat, und))
+            assert status == G.OK and re.fullmatch("A+", pat) and how_it_ended(info, status, log, G.params()) == "tol"
+            assert 1 <= len(und) <= GC.LIST_UNDECIDED_TAIL and min(und) > info["evaluations"] - GC.LIST_UNDECIDED_TAIL
+            assert GC.decided_prefix(log) >= 6
+
+
+def test_the_non_finite_rule_of_the_reference():
+    for name in ("nan_point", "inf_target"):
+        X, info, status, log = GC.reference_run(name)
+        assert status == G.E_SINGULAR and info["evaluations"] == 1 and info["accepted"] == 0 and log == [] and np.array_equal(X, np.eye(4))
+    c = GC.branch_case("inf_target")
+    sm = G.sums(*GC.gathered(c), np.eye(4), 1e-3)
+    assert sm[27] == len(c["query"]) and not np.isfinite(sm[28])
+    # a NaN in a source point the list does not name is not seen
+    a, b = GC.unlisted_nan()
+    assert not np.isfinite(b["src"][:, :3]).all() and all(np.array_equal(x, y) for x, y in zip(GC.gathered(a), GC.gathered(b)))
+
+
+@pytest.mark.parametrize("name", GC.UNIT_CASES)
+def test_the_reference_is_homogeneous_in_the_unit_of_length(name):
+    c = GC.any_case(name)
+    X0, i0, st0 = G.solve(*GC.gathered(c), G.params())
+    assert st0 == G.OK
+    for s in GC.UNIT_SCALES:
+        X, info, st = G.solve(*GC.gathered(GC.in_unit(c, s)), G.params(inner_trans_tol=1e-5 * s))
+        assert st == G.OK and np.array_equal(X[:3, :3], X0[:3, :3]) and np.array_equal(X[:3, 3] / s, X0[:3, 3])
+        assert (info["evaluations"], info["accepted"], info["lambda"]) == (i0["evaluations"], i0["accepted"], i0["lambda"])
+        assert info["f1"] / s ** 2 == i0["f1"] and info["f0"] / s ** 2 == i0["f0"]
+
+
+def test_long_double_terms_against_the_f64_terms():
+    """G.terms_ld is the reference of the sums over the range of gicp_epsilon; at 1e-3 and 1 it must agree with G.terms, whose
+    inverse is LAPACK's, within that one's error"""
+    for name in ("palette", "rand_65"):
+        g = GC.gathered(GC.list_case(name))
+        for X in (np.eye(4), GC.sums_pose()):
+            for eps in (1.0, 1e-3):
+                a, tot = G.sums(*g, X, eps, with_abs=True)
+                b, tot_ld = G.sums_ld(*g, X, eps)
+                assert a[27] == b[27] == len(g[0])
+                assert (np.abs(a - b) <= 1e-12 * tot).all() and (np.abs(tot - tot_ld) <= 1e-12 * tot).all()
+    # palette's parallel pairs: A + B has the eigenvalue 2 eps, so W has 1 / (2 eps) along the common normal
+    c = GC.list_case("palette")
+    p, s, q, n = GC.gathered(c)
+    par = c["kinds"][2]
+    ok = [k for k in par if np.isfinite(s[k]).all() and (s[k] ** 2).sum() > 0]
+    assert len(ok) >= 10
+    for eps in (1e-6, 1e-9):
+        k = np.isin(np.arange(len(p)), ok)
+        u = (s[k] / np.linalg.norm(s[k], axis=1, keepdims=True)).astype(np.longdouble)
+        t = G.terms_ld(u.astype(np.float64) * 0, s[k], -u.astype(np.float64), n[k], np.eye(4), eps)   # r = the unit normal
+        assert np.abs(t[:, 28].astype(np.float64) * 2 * eps - 1.0).max() < 1e-6
 
 
 @pytest.fixture(scope="module")

@@ -1,7 +1,8 @@
 """GPU tests of Generalized ICP (rules G1-G10 at mvr_icp_align_gicp in include/mvr_hip.h) against the numpy reference of
 tests/gicp_ref.py on the cases of tests/gicp_cases.py:
   1. gicp_sums == the reference's sums within 1e-10 of the sum of the terms' absolute values, the count exactly;
-  2. gicp_solve == the reference's solve within the parity bars, at or below scipy's minimum, == Umeyama at eps = 1, singular;
+  2. gicp_solve == the reference's solve within the parity bars, its counters and lambda exactly while the reference's decisions
+     are decided (gicp_ref.decided), at or below scipy's minimum, == Umeyama at eps = 1, singular;
   3. inner_chunk 1, 3 and 0 and two runs give the same bits; 4. an align replayed iteration by iteration from its trace;
   5. the accuracy conditions of synth_6001 on the GPU's result; 6. refusals, too few survivors, empty clouds, the slots are left
   alone, out = T_out applied to the input.
@@ -98,13 +99,22 @@ def test_solve_equals_the_reference(mvr, ctx, name):
     p, s, q, n = g = GC.gathered(c)
     for eps in (1e-3, 1.0):
         X, info, rc = ctx.gicp_solve(S, T_, c["query"], c["match"], mvr.gicp_params(gicp_epsilon=eps))
-        Xr, ir, status = G.solve(*g, G.params(gicp_epsilon=eps))
+        log = []
+        Xr, ir, status = G.solve(*g, G.params(gicp_epsilon=eps), log=log)
         assert rc == status == 0
         dr, dt = within_bars(X, Xr, (name, eps))
         F_gpu = G.objective(*g, X, eps)
         print("%s eps %g: rotation within %.2g, translation within %.2g; %d evaluations (reference %d), F %.12g (reference %.12g)"
               % (name, eps, dr, dt, info["evaluations"], ir["evaluations"], F_gpu, ir["f1"]))
-        assert 2 <= info["evaluations"] <= 20 and 1 <= info["accepted"] < info["evaluations"]
+        # the counters equal the reference's, exactly, for as long as the reference's decisions are decided (gicp_ref.decided;
+        # tests/test_gicp_host.py: all but the last one or two of these cases); max_inner_iterations = k is the state after k
+        prefix = GC.decided_prefix(log)
+        assert prefix >= 6
+        for k in range(1, prefix + 1):
+            _, ik, rck = ctx.gicp_solve(S, T_, c["query"], c["match"], mvr.gicp_params(gicp_epsilon=eps, max_inner_iterations=k))
+            _, lam, acc = GC.state_after(log, k)
+            assert rck == 0 and (ik["evaluations"], ik["accepted"], ik["lambda"]) == (k, acc, lam), (name, eps, k, ik)
+        assert prefix <= info["evaluations"] <= 20 and prefix - 1 <= info["accepted"] < info["evaluations"]
         assert abs(info["f1"] - F_gpu) <= 1e-9 * F_gpu and abs(info["f0"] - ir["f0"]) <= 1e-9 * ir["f0"] and info["f1"] < info["f0"]
         assert F_gpu <= ir["f1"] * (1 + 1e-9)
         if name != "big":                                  # (scipy's numerical gradient over 50 000 points takes many seconds)
