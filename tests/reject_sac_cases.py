@@ -7,12 +7,28 @@ A case is dict(src, tgt, q, m, d, value, max_iterations, refine, seed) plus
   planted   the indices (into the list sorted by query) a PLANTED case must keep, or None;
   check_c   True when check (c) of reject_sac_ref.verify is asserted on it (the reference then shows that >= 90 % of its
             counted attempts are well conditioned);
-  found     what `found` must be."""
+  found     what `found` must be.
+
+The second half of the file holds the HARDENING cases (build_hard; tests/test_gpu_reject_sac_cases.py on the GPU, their
+preconditions in tests/test_reject_sac_host.py).  The lists of build() have no pair within rounding distance of the threshold, so
+a count that is "exact" on them does not see how a kernel rounds.  The hardening cases do: GRADED lists whose residuals cross the
+threshold densely, near the origin and up to 1e6 mm from it, where the three products of C4 carry rounding errors of the size of
+the threshold's neighbourhood; a SMALL-MOTION lattice pair on which the search returns the planted pairs, so that a threshold can
+be put ON a d2 through every entry; CREEPING and SHEDDING lists on which C10 takes several rounds that change the set.
+
+Two stops of C10 have no case, and cannot have one at an honest threshold.  |I_r| < 3: T_r is the least-squares fit of I_{r-1}, so
+it cannot raise the sum of squared residuals of I_{r-1}, all of which were below value^2 under T_{r-1}, and the three sampled pairs
+of the best attempt have residuals of about zero; fewer than three inliers after a refit therefore needs a threshold at the level
+of the coordinates' rounding.  A non-finite T_r needs coordinates whose C4 already overflows, and such a pair is no inlier of
+T_{r-1}: it is not in the sums.  "rounding_level" (value = 2^-14 mm on pairs 900 mm out: one ulp of a coordinate) goes as near to
+the first as a list can -- a refit there loses four fifths of the pairs it was made from --; only the checks that need no
+reference are asserted on it."""
 import math
 
 import numpy as np
 
 import reject_cases as RC
+import walk_cases as WC
 
 F32, F64 = np.float32, np.float64
 THRESHOLD = 0.05          # PCL's default inlier threshold
@@ -146,3 +162,170 @@ def shuffled(case, seed=99):
     """the same list in another order"""
     o = np.random.default_rng(seed).permutation(len(case["q"]))
     return dict(case, q=case["q"][o], m=case["m"][o], d=case["d"][o])
+
+
+# ------------------------------------------------------------------ the hardening cases (see the module docstring)
+
+GRADED_VALUE = {0.0: 0.05, 1e3: 0.05, 1e5: 0.1, 1e6: 1.0}      # the threshold grows with the frame's ulp: 6e-5 mm at 1e3, 0.0039 at 1e5, 0.0625 at 1e6
+
+
+def _unit(rng, n):
+    v = rng.standard_normal((n, 3))
+    return v / np.linalg.norm(v, axis=1)[:, None]
+
+
+def graded(n, seed, far, value, rej_seed=0, shared=False, non_finite=False, outliers=0.5):
+    """n pairs: the source uniform in a 10 mm box moved `far` mm along walk_cases.FAR_DIR; the target a rigid motion about the box's
+    centre (tens of degrees, a few mm) plus a per-pair offset of random direction and a magnitude uniform in [0, 2 value], so the
+    residuals under any motion near the planted one cross the threshold densely; `outliers` of the pairs get a random target of
+    the box instead, so that about a fifth of the pairs count under a good attempt and the loop runs for hundreds of attempts
+    (every register of the counting kernel's chunk is then read by the loop).  shared: every fifth target is the match of two
+    queries (the second query a near copy of the first).  non_finite: non-finite coordinates in both clouds, the last query's
+    among them, so live != valid and an invalid pair is last in query order."""
+    rng = np.random.default_rng(seed)
+    c = np.full(3, 5.0) + WC.FAR_DIR * far
+    src = (rng.uniform(0.0, 10.0, (n, 3)) + WC.FAR_DIR * far).astype(F32)
+    if shared:
+        src[1::5] = (src[0::5][:len(src[1::5])].astype(F64) + rng.uniform(-0.5, 0.5, (len(src[1::5]), 3)) * value).astype(F32)
+    M = _motion(rng)
+    off = _unit(rng, n) * rng.uniform(0.0, 2.0 * value, n)[:, None]
+    tgt_of = ((src.astype(F64) - c) @ M[:3, :3].T + c + M[:3, 3] + off).astype(F32)
+    out = rng.permutation(n)[:int(round(outliers * n))]
+    tgt_of[out] = (rng.uniform(0.0, 10.0, (len(out), 3)) + WC.FAR_DIR * far + M[:3, 3]).astype(F32)
+    perm = rng.permutation(n).astype(np.int32)
+    tgt = np.empty((n, 3), F32)
+    tgt[perm] = tgt_of
+    m = perm.copy()
+    if shared:
+        k = np.arange(0, n - 1, 5)
+        m[k + 1] = m[k]
+    q = np.arange(n, dtype=np.int32)
+    d = ((src - tgt[m]).astype(F32) ** 2).sum(1).astype(F32)
+    src, tgt = _cloud(src), _cloud(tgt)
+    if non_finite:
+        vals = np.array([np.nan, np.inf, -np.inf], F32)
+        bad_s, bad_t = rng.permutation(n - 1)[:n // 16], rng.permutation(n)[:n // 16]
+        src[bad_s, rng.integers(0, 3, len(bad_s))] = vals[rng.integers(0, 3, len(bad_s))]
+        tgt[bad_t, rng.integers(0, 3, len(bad_t))] = vals[rng.integers(0, 3, len(bad_t))]
+        src[n - 1, 1] = np.nan
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = M[:3, :3], c + M[:3, 3] - M[:3, :3] @ c
+    return dict(src=src, tgt=tgt, q=q, m=m, d=d, value=value, max_iterations=0, refine=False, seed=rej_seed, planted=None, check_c=True, found=True,
+                motion=T, far=far)
+
+
+SMALL_MAX_DIST = 1.0
+SMALL_VALUE0 = 0.1
+SMALL_SEED, SMALL_REJ_SEED = 51, 5      # attempt 1 of this rejector seed samples a pair that is 0.2 mm off: attempt 0 wins by far
+SMALL_TIGHT, SMALL_TIGHT_CAP = 0.002, 300      # a threshold under which a fifth of the pairs count at best: the loop runs to this cap
+
+
+def small_motion(seed, side=12, step=2.0, centre=(0.0, 0.0, 900.0)):
+    """the pair on which the SEARCH returns the planted pairs: a lattice of side^3 points of `step` mm, jittered by up to 0.3 mm,
+    centred 900 mm from the origin as the project's scans are; the target = the source turned by a fraction of a degree about the
+    centre and shifted by a few tenths of a millimetre, plus an offset of random direction: up to 0.01 mm for 96 of 100 pairs, up
+    to 0.3 mm for the others.  Two source points are at least 1.4 mm apart and no pair moves by more than 0.7 mm, so every source
+    point's nearest target within SMALL_MAX_DIST is its planted one (the host test asserts it by brute force).  -> the clouds and
+    `match_of`, the planted target of every source point"""
+    rng = np.random.default_rng(seed)
+    g = (np.stack(np.meshgrid(*[np.arange(side)] * 3, indexing="ij"), -1).reshape(-1, 3) - (side - 1) / 2.0) * step
+    n = len(g)
+    c = np.asarray(centre, F64)
+    src = (g + rng.uniform(-0.3, 0.3, (n, 3)) + c).astype(F32)
+    a = _unit(rng, 1)[0]
+    ang = math.radians(0.3)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    Rm = np.eye(3) + math.sin(ang) * K + (1 - math.cos(ang)) * (K @ K)
+    shift = _unit(rng, 1)[0] * 0.3
+    mag = np.where(rng.uniform(0, 1, n) < 0.96, rng.uniform(0.0, 0.01, n), rng.uniform(0.0, 0.3, n))
+    tgt_of = ((src.astype(F64) - c) @ Rm.T + c + shift + _unit(rng, n) * mag[:, None]).astype(F32)
+    perm = rng.permutation(n).astype(np.int32)
+    tgt = np.empty((n, 3), F32)
+    tgt[perm] = tgt_of
+    return dict(src=_cloud(src), tgt=_cloud(tgt), match_of=perm, max_dist=SMALL_MAX_DIST, value=SMALL_VALUE0, seed=SMALL_REJ_SEED)
+
+
+def small_list(pair):
+    """the list the search must return on small_motion, computed here: (q, m, d) with d the f32 distance the library's search
+    takes without fma"""
+    s, t = pair["src"][:, :3], pair["tgt"][pair["match_of"], :3]
+    dx, dy, dz = (s[:, k] - t[:, k] for k in range(3))
+    return np.arange(len(s), dtype=np.int32), pair["match_of"].copy(), ((dx * dx + dy * dy) + dz * dz).astype(F32)
+
+
+def creeping(n, seed, value, n_fringe, band=(0.7, 1.3), shed=False, n_push=0, rej_seed=0, max_iterations=0):
+    """C10 round by round.  A core of exact rigid copies (to f32 rounding) and a FRINGE of n_fringe pairs whose targets are all
+    offset along one direction u by band x value.  The part of the fringe below the threshold is in I_0; every refit drags T
+    along u and pulls in more of it.  shed = True puts the band's offsets along -u instead and adds n_push pairs offset along +u by
+    [0.3, 0.6] value: these are inliers throughout and drag T along u, away from the band, whose pairs just inside the threshold
+    are then SHED round after round -- rounds in which the set only loses pairs."""
+    rng = np.random.default_rng(seed)
+    src = rng.uniform(0.0, 10.0, (n, 3)).astype(F32)
+    T = _motion(rng)
+    u = _unit(rng, 1)[0]
+    off = np.zeros((n, 3))
+    pick = rng.permutation(n)
+    fringe, push = pick[:n_fringe], pick[n_fringe:n_fringe + n_push]
+    off[fringe] = (-1.0 if shed else 1.0) * u * (rng.uniform(band[0], band[1], n_fringe) * value)[:, None]
+    off[push] = u * (rng.uniform(0.3, 0.6, n_push) * value)[:, None]
+    tgt_of = (src.astype(F64) @ T[:3, :3].T + T[:3, 3] + off).astype(F32)
+    perm = rng.permutation(n).astype(np.int32)
+    tgt = np.empty((n, 3), F32)
+    tgt[perm] = tgt_of
+    q = np.arange(n, dtype=np.int32)
+    d = ((src - tgt[perm]).astype(F32) ** 2).sum(1).astype(F32)
+    return dict(src=_cloud(src), tgt=_cloud(tgt), q=q, m=perm, d=d, value=value, max_iterations=max_iterations, refine=True, seed=rej_seed,
+                planted=None, check_c=True, found=True, motion=T, fringe=np.sort(fringe))
+
+
+def rounding_level(n, seed):
+    """exact rigid copies 900 mm out under a threshold of 2^-14 mm, one ulp of a coordinate there: which pairs count is decided by
+    the rounding of the copies and of C4, and a refit can leave fewer inliers than it was made from"""
+    rng = np.random.default_rng(seed)
+    src = (rng.uniform(-5.0, 5.0, (n, 3)) + np.array([0.0, 0.0, 900.0])).astype(F32)
+    T = _motion(rng)
+    tgt_of = (src.astype(F64) @ T[:3, :3].T + T[:3, 3]).astype(F32)
+    perm = rng.permutation(n).astype(np.int32)
+    tgt = np.empty((n, 3), F32)
+    tgt[perm] = tgt_of
+    q = np.arange(n, dtype=np.int32)
+    d = ((src - tgt[perm]).astype(F32) ** 2).sum(1).astype(F32)
+    return dict(src=_cloud(src), tgt=_cloud(tgt), q=q, m=perm, d=d, value=2.0 ** -14, max_iterations=50, refine=True, seed=1, planted=None,
+                check_c=False, found=True, motion=T)
+
+
+def scaled(case, k):
+    """the case in another unit of length: the points, the threshold by 2^k, d by 2^2k, all exact"""
+    f = F32(2.0) ** k
+    src, tgt = case["src"].copy(), case["tgt"].copy()
+    src[:, :3] *= f
+    tgt[:, :3] *= f
+    return dict(case, src=src, tgt=tgt, d=(case["d"] * f * f).astype(F32), value=case["value"] * 2.0 ** k)
+
+
+FARS = (0.0, 1e3, 1e5, 1e6)
+GRADED_NAMES = tuple("graded_%g" % f for f in FARS)
+EDGE_NAMES = ("planted_1023", "planted_1024", "planted_2048", "planted_2049")
+HARD_NAMES = GRADED_NAMES + ("graded_shared", "graded_non_finite") + EDGE_NAMES + ("creeping", "shedding", "rounding_level")
+UNITS = (-20, -7, 7, 20)
+_hard = {}
+
+
+def build_hard():
+    """name -> hardening case.  The committed seeds are chosen on the reference (tests/test_reject_sac_host.py asserts what they
+    were chosen for)."""
+    if _hard:
+        return _hard
+    h = _hard
+    for far, name in zip(FARS, GRADED_NAMES):
+        h[name] = graded(3000, 21, far, GRADED_VALUE[far], rej_seed=1)
+    h["graded_shared"] = graded(3000, 22, 1e3, GRADED_VALUE[1e3], rej_seed=2, shared=True)
+    h["graded_non_finite"] = graded(3000, 23, 1e3, GRADED_VALUE[1e3], rej_seed=3, non_finite=True)
+    for k, name in enumerate(EDGE_NAMES):
+        h[name] = planted(int(name.split("_")[1]), 30 + k, rej_seed=10 + k)
+    # the issue's band of [0.7, 1.3] value with 90 fringe pairs converges in one or two rounds for every seed tried; a denser fringe
+    # just around the threshold takes three rounds that change the set and a fourth that does not
+    h["creeping"] = creeping(3000, 3, THRESHOLD, 100, band=(0.97, 1.06))
+    h["shedding"] = creeping(3000, 10, THRESHOLD, 60, band=(0.93, 1.0), shed=True, n_push=300)
+    h["rounding_level"] = rounding_level(1500, 41)
+    return h

@@ -1,7 +1,8 @@
 """CPU tests of the sample-consensus rejector: the numpy reference (tests/reject_sac_ref.py) against itself on the planted cases
 of tests/reject_sac_cases.py -- the planted pairs recovered, the loop's arithmetic, the share of well-conditioned samples that
 check (c) of the GPU test relies on --, the layout of the new and the extended structs against the Python bindings, the
-arguments refused before any device is touched, and the exported symbols.  No GPU compute here."""
+arguments refused before any device is touched, and the exported symbols; and what each hardening case of
+reject_sac_cases.build_hard was built for (the second half of the file).  No GPU compute here."""
 import ctypes as C
 import importlib
 import math
@@ -194,3 +195,176 @@ def test_kernels_use_no_scratch_and_fit_four_blocks_per_cu(built, tmp_path):
     assert count == [256, 256, 512, 512, 1024, 1024]  # one counter per attempt of the chunk
     # four blocks of 256 threads per CU are four waves per SIMD: 512 / 4 = 128 VGPRs a wave
     assert all(v <= 128 for _, v, _, _ in use)
+
+
+# ------------------------------------------------------------------ the hardening cases: what they were chosen for, on the reference alone
+
+def ref_run(c, **kw):
+    a = dict(value=c["value"], max_iterations=c["max_iterations"], refine=c["refine"], seed=c["seed"])
+    a.update(kw)
+    return R.run(c["src"], c["tgt"], c["q"], c["m"], c["d"], **a)
+
+
+@pytest.fixture(scope="module")
+def hard():
+    return SC.build_hard()
+
+
+@pytest.fixture(scope="module")
+def hard_ran(hard):
+    return {name: ref_run(c, check_margin=name != "rounding_level") for name, c in hard.items()}
+
+
+def test_hard_case_names_and_shapes(hard, hard_ran):
+    assert tuple(hard) == SC.HARD_NAMES
+    for name in SC.GRADED_NAMES + ("graded_shared", "graded_non_finite"):
+        c, r = hard[name], hard_ran[name]
+        assert len(c["q"]) == 3000 and r["found"] and r["min_margin"] >= K_MARGIN, name
+        # the loop reads every register of the counting kernel's chunk; about a fifth of the pairs count at best
+        assert r["attempts"] > 256 and 0.15 < r["ransac_inliers"] / r["valid"] < 0.3, (name, r["attempts"], r["ransac_inliers"])
+    sh = hard["graded_shared"]
+    assert len(np.unique(sh["q"])) == 3000 and len(np.unique(sh["m"])) == 3000 - 600 and np.array_equal(sh["m"][0::5], sh["m"][1::5])
+    nf, rn = hard["graded_non_finite"], hard_ran["graded_non_finite"]
+    assert rn["valid"] < rn["live"] == 3000 and not np.isfinite(nf["src"][nf["q"][-1], :3]).all() and nf["q"][-1] == nf["q"].max()
+    for name in SC.EDGE_NAMES:
+        c, r = hard[name], hard_ran[name]
+        assert r["valid"] == r["live"] == len(c["q"]) == int(name.split("_")[1]) and r["min_margin"] >= K_MARGIN
+        q, m, d = R.sort_list(c["q"], c["m"], c["d"])
+        assert np.array_equal(r["q"], q[c["planted"]]) and r["well"] >= 0.9, name
+
+
+@pytest.mark.parametrize("far", [f for f in SC.FARS if f > 0])
+def test_far_frames_tell_the_rule_from_contracted_arithmetic(hard, hard_ran, far):
+    """the point of the far cases: on at least one counted attempt the loop consumes, C4 as the rule writes it and C4 with its
+    products contracted into fmas give different counts; near the origin (and on every earlier case) they give the same"""
+    c, r = hard["graded_%g" % far], hard_ran["graded_%g" % far]
+    q, m, _ = R.sort_list(c["q"], c["m"], c["d"])
+    P, Q = c["src"][q, :3], c["tgt"][m, :3]
+    flipped = attempts = 0
+    for st, T, n in zip(r["status"], r["Ts"], r["counts"]):
+        if st != R.COUNTED:
+            continue
+        a, b = R.inlier_mask(T, P, Q, c["value"]), R.inlier_mask(T, P, Q, c["value"], contracted=True)
+        assert a.sum() == n
+        flipped += int((a != b).sum())
+        attempts += int(a.sum() != b.sum())
+    print("far %g: %d decisions flipped, the count of %d of %d attempts changed" % (far, flipped, attempts, r["iterations"]))
+    assert attempts >= 1, far
+
+
+def test_contracted_reference_is_what_it_says():
+    rng = np.random.default_rng(1)
+    P = (rng.uniform(0, 10, (40, 3)) + 1e5).astype(np.float32)
+    T = np.eye(4, dtype=np.float32)
+    T[:3] = rng.standard_normal((3, 4)).astype(np.float32)
+    x = R.transform_f32(T, P, contracted=True)[0]
+    L, f = np.longdouble, np.float32
+    for i in (0, 13, 39):
+        inner = f(L(T[0, 1]) * L(P[i, 1]) + L(f(T[0, 0] * P[i, 0])))
+        assert x[i] == f(f(L(T[0, 2]) * L(P[i, 2]) + L(inner)) + T[0, 3])
+    assert (np.stack(R.transform_f32(T, P)) != np.stack(R.transform_f32(T, P, contracted=True))).any()
+
+
+def _small(hard=None):
+    pair = SC.small_motion(SC.SMALL_SEED)
+    q, m, d = SC.small_list(pair)
+    return pair, q, m, d
+
+
+def test_small_motion_pairs_are_the_nearest_neighbours():
+    pair, q, m, d = _small()
+    s, t = pair["src"][:, :3].astype(np.float64), pair["tgt"][:, :3].astype(np.float64)
+    D = ((s[:, None, :] - t[None, :, :]) ** 2).sum(2)
+    assert 1600 < len(s) < 1800 and np.array_equal(D.argmin(1), pair["match_of"])
+    two = np.partition(D, 1, axis=1)
+    # the planted target within the search distance by a wide margin, every other target beyond it
+    assert np.sqrt(two[:, 0].max()) < 0.7 * pair["max_dist"] and np.sqrt(two[:, 1].min()) > pair["max_dist"]
+    assert 890.0 < np.linalg.norm(s.mean(0)) < 910.0
+
+
+def test_thresholds_on_a_d2_exist_and_split_the_arithmetics():
+    """section 3's searches on the reference's own T of attempt 0: an exact tie, and a threshold between a pair's plain and fma
+    d2; at both the loop consumes the same two attempts, attempt 0 wins by far and no stop decision is near k"""
+    pair, q, m, d = _small()
+    P, Q = pair["src"][q, :3], pair["tgt"][m, :3]
+    r0 = R.run(pair["src"], pair["tgt"], q, m, d, pair["value"], 0, False, pair["seed"])
+    assert r0["attempts"] == 2 and r0["best_attempt"] == 0 and r0["ransac_inliers"] >= 0.966 * len(q)
+    T0, T1 = r0["Ts"]
+    plain, fused = R.d2_f32(T0, P, Q), R.d2_f32(T0, P, Q, fma=True)
+    differ = int((R.bits(plain) != R.bits(fused)).sum())
+    among = R.candidates(plain)
+    assert differ >= 10 and len(among) >= 20
+    i, value = R.find_tie(plain, among)
+    assert value * value == float(plain[i])                       # the tie exists
+    up = float(np.nextafter(value, np.inf))
+    assert not R.inlier_mask(T0, P, Q, value)[i] and R.inlier_mask(T0, P, Q, up)[i]
+    assert R.inlier_mask(T0, P, Q, up).sum() - R.inlier_mask(T0, P, Q, value).sum() == (R.bits(plain) == R.bits(plain[i:i + 1])[0]).sum()
+    j, between = R.find_between(plain, fused, among)
+    a, b = R.inlier_mask(T0, P, Q, between), R.inlier_mask(T0, P, Q, between, fma=True)
+    assert a[j] != b[j] and a.sum() != b.sum()                     # the two reference answers differ
+    print("small motion: %d of %d pairs differ between plain and fma; tie on pair %d at %.17g, between on pair %d at %.17g"
+          % (differ, len(q), i, value, j, between))
+    for v in (value, up, between):
+        for fma in (False, True):
+            counts = [int(R.inlier_mask(T, P, Q, v, fma).sum()) for T in (T0, T1)]
+            lp = R.replay_loop([1, 1], counts, len(q), 1000)
+            assert lp["best"] == 0 and lp["attempts"] == 2 and lp["min_margin"] >= K_MARGIN, (v, fma, counts)
+            assert counts[0] >= 0.966 * len(q) and counts[0] - counts[1] >= 20, (v, fma, counts)
+    # the tight threshold: both arithmetics run to the cap, so the fma route consumes the attempts the dedicated entry traces
+    for fma in (False, True):
+        rt = R.run(pair["src"], pair["tgt"], q, m, d, SC.SMALL_TIGHT, SC.SMALL_TIGHT_CAP, False, pair["seed"], fma=fma)
+        assert rt["attempts"] == rt["iterations"] == SC.SMALL_TIGHT_CAP + 1 and rt["k"] > SC.SMALL_TIGHT_CAP + 50 and rt["found"], (fma, rt["k"])
+
+
+def _set_changes(r):
+    return [(int((b & ~a).sum()), int((a & ~b).sum())) for (_, a), (_, b) in zip(r["rounds"], r["rounds"][1:])]
+
+
+def _decision_margin(c, r):
+    q, m, _ = R.sort_list(c["q"], c["m"], c["d"])
+    P, Q = c["src"][q, :3], c["tgt"][m, :3]
+    return min(float(np.abs(np.sqrt(R.d2_f32(T, P, Q).astype(np.float64)) - c["value"]).min()) for T, _ in r["rounds"])
+
+
+@pytest.mark.parametrize("name", ["creeping", "shedding"])
+def test_refinement_takes_rounds_that_change_the_set(hard, hard_ran, name):
+    c, r = hard[name], hard_ran[name]
+    ch = _set_changes(r)
+    rounds = r["refine_rounds"]
+    print(name, "rounds", rounds, "gained / lost per round", ch, "sizes", [int(k.sum()) for _, k in r["rounds"]])
+    assert len(r["rounds"]) == rounds + 1 and rounds >= 4
+    assert all(g + l > 0 for g, l in ch[:-1]) and ch[-1] == (0, 0)          # at least three rounds change the set; the last does not
+    if name == "shedding":      # rounds in which the set only loses pairs, before the last: what the "entries that differ" counter must see
+        assert sum(1 for g, l in ch[:-1] if g == 0 and l > 0) >= 2
+    else:
+        assert sum(1 for g, l in ch[:-1] if g > 0) >= 3
+    # no pair of any round within a cast's reach of the threshold: the rounds do not depend on the estimator's last bit
+    assert _decision_margin(c, r) >= R.cast_bar(r["T"], c["src"][:, :3]), name
+    assert r["min_margin"] >= K_MARGIN and r["ransac_inliers"] >= 0.966 * len(c["q"])
+    # the identical loop for every cap; the cap of the loop is the cap of the rounds
+    for cap in (1, 2, 3, 4, 5, 6, 8, 1000):
+        rc = ref_run(c, max_iterations=cap)
+        assert (rc["attempts"], rc["iterations"], rc["best_attempt"], rc["ransac_inliers"]) == (r["attempts"], r["iterations"], r["best_attempt"], r["ransac_inliers"])
+        assert rc["attempts"] <= 2 and rc["min_margin"] >= K_MARGIN and rc["refine_rounds"] == min(cap, rounds), (name, cap)
+        Tc, Ic = r["rounds"][min(cap, rounds)]
+        assert np.array_equal(R.bits(rc["T"]), R.bits(Tc)) and rc["inliers"] == Ic.sum()
+
+
+def test_rounding_level_case_goes_where_no_other_does(hard, hard_ran):
+    c, r = hard["rounding_level"], hard_ran["rounding_level"]
+    assert c["value"] == 2.0 ** -14 == float(np.spacing(np.float32(900.0))) and c["refine"]
+    sizes = [int(k.sum()) for _, k in r["rounds"]]
+    print("rounding level:", r["attempts"], "attempts,", r["refine_rounds"], "rounds, sizes", sizes)
+    assert r["found"] and r["refine_rounds"] >= 2 and min(sizes) < 0.5 * max(sizes)      # a refit that loses most of what it was made from
+
+
+def test_units_scale_exactly(hard):
+    for name in ("planted_257", "graded_100000", "creeping"):
+        c = SC.build()[name] if name == "planted_257" else hard[name]
+        for k in SC.UNITS:
+            s = SC.scaled(c, k)
+            f = 2.0 ** k
+            assert np.array_equal(s["src"][:, :3].astype(np.float64), c["src"][:, :3].astype(np.float64) * f)
+            assert np.array_equal(s["tgt"][:, :3].astype(np.float64), c["tgt"][:, :3].astype(np.float64) * f)
+            assert np.array_equal(s["d"].astype(np.float64), c["d"].astype(np.float64) * f * f) and s["value"] == c["value"] * f
+            assert np.array_equal(s["src"][:, 3], c["src"][:, 3]) and (s["value"] * s["value"]) == (c["value"] * c["value"]) * f * f
