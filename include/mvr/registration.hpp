@@ -1380,6 +1380,138 @@ class ExtractIndices {
   bool negative_ = false;
 };
 
+// ---------------------------------------------------------------- Euclidean cluster extraction
+namespace detail {
+// one call of mvr_cloud_euclidean_clusters on an uploaded slot -> PCL's vector of PointIndices (largest cluster first, members
+// ascending); index null: every point
+inline void clusters_of_slot(Device &d, int slot, size_t n, const mvr_cluster_params &p, const std::vector<uint32_t> *index,
+                             std::vector<PointIndices> &clusters, mvr_cluster_result &result)
+{
+  std::vector<uint32_t> offset(n + 2), member(n ? n : 1);
+  const uint32_t none = 0;
+  const uint32_t *idx = index ? (index->empty() ? &none : index->data()) : nullptr;
+  d.check(mvr_cloud_euclidean_clusters(d.ctx(), -1, slot, &p, idx, index ? index->size() : 0, &result, nullptr, offset.data(), offset.size(),
+                                       member.data(), nullptr), "mvr_cloud_euclidean_clusters");
+  clusters.resize(result.n_clusters);
+  for (uint32_t c = 0; c < result.n_clusters; ++c) clusters[c].indices.assign(member.begin() + offset[c], member.begin() + offset[c + 1]);
+}
+}  // namespace detail
+
+// pcl::EuclideanClusterExtraction<PointT> (segmentation/extract_clusters.h): setClusterTolerance, setMinClusterSize,
+// setMaxClusterSize, setSearchMethod (accepted and unused), setInputCloud, setIndices, extract, with PCL's defaults (min 1, max
+// INT_MAX; the tolerance must be set).  Semantics: mvr_cloud_euclidean_clusters (mvr_hip.h, rules E1-E8) -- one call on the
+// GPU per extract(): the clusters largest first, members in ascending index; two points link at d2 <= tolerance^2 (FLANN's
+// radius search is strict).  As PCL, a missing input, a tolerance that is not finite and > 0 or an index outside the cloud
+// prints an error and leaves `clusters` empty.
+template <typename PointT>
+class EuclideanClusterExtraction {
+ public:
+  typedef PointCloud<PointT> PointCloudT;
+  typedef typename PointCloudT::ConstPtr PointCloudConstPtr;
+  typedef search::KdTree<PointT> KdTree;
+  typedef typename KdTree::Ptr KdTreePtr;
+  typedef std::shared_ptr<const std::vector<int> > IndicesConstPtr;
+
+  void setInputCloud(const PointCloudConstPtr &c) { input_ = c; }
+  PointCloudConstPtr getInputCloud() const { return input_; }
+  void setIndices(const PointIndices::ConstPtr &i) { indices_ = i ? std::make_shared<const std::vector<int> >(i->indices) : IndicesConstPtr(); }
+  void setIndices(const PointIndices::Ptr &i) { setIndices(PointIndices::ConstPtr(i)); }
+  void setIndices(const IndicesConstPtr &i) { indices_ = i; }
+  IndicesConstPtr getIndices() const { return indices_; }
+  void setSearchMethod(const KdTreePtr &tree) { tree_ = tree; }
+  KdTreePtr getSearchMethod() const { return tree_; }
+  void setClusterTolerance(double tolerance) { p_.tolerance = tolerance; }
+  double getClusterTolerance() const { return p_.tolerance; }
+  void setMinClusterSize(int n) { p_.min_size = n > 0 ? (uint32_t)n : 0u; }
+  int getMinClusterSize() const { return (int)p_.min_size; }
+  void setMaxClusterSize(int n) { p_.max_size = n > 0 ? (uint32_t)n : 0u; }
+  int getMaxClusterSize() const { return (int)p_.max_size; }
+  const mvr_cluster_result &getResult() const { return result_; }      // ours: components, the ones too small and too large
+
+  void extract(std::vector<PointIndices> &clusters)
+  {
+    static_assert(sizeof(PointT) % 4 == 0 && sizeof(PointT) >= 12, "points that begin with x, y, z expected");
+    clusters.clear();
+    result_ = mvr_cluster_result();
+    if (!input_) { std::fprintf(stderr, "[pcl::EuclideanClusterExtraction::extract] No input dataset given!\n"); return; }
+    if (!(std::isfinite(p_.tolerance) && p_.tolerance > 0.0)) {
+      std::fprintf(stderr, "[pcl::EuclideanClusterExtraction::extract] The cluster tolerance (%f) must be finite and > 0.\n", p_.tolerance);
+      return;
+    }
+    const size_t n = input_->size();
+    std::vector<uint32_t> index;
+    if (indices_) {
+      index.reserve(indices_->size());
+      for (const int i : *indices_) {
+        if (i < 0 || (size_t)i >= n) {
+          std::fprintf(stderr, "[pcl::EuclideanClusterExtraction::extract] The index %d is outside the input dataset of %zu points!\n", i, n);
+          return;
+        }
+        index.push_back((uint32_t)i);
+      }
+    }
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.check(mvr_cloud_upload(d.ctx(), s.s, n ? input_->points[0].data : nullptr, n, sizeof(PointT)), "mvr_cloud_upload");
+    detail::clusters_of_slot(d, s.s, n, p_, indices_ ? &index : nullptr, clusters, result_);
+  }
+
+ private:
+  PointCloudConstPtr input_;
+  IndicesConstPtr indices_;
+  KdTreePtr tree_;
+  mvr_cluster_params p_ = {0.0, 1u, 0x7FFFFFFFu, 0, 0.0, 0, 1u, 0};
+  mvr_cluster_result result_ = mvr_cluster_result();
+};
+
+// pcl::extractEuclideanClusters(cloud, normals, tolerance, tree, clusters, eps_angle, min_pts, max_pts)
+// (segmentation/extract_clusters.h): two points link when they are within the tolerance AND their normals are less than
+// eps_angle apart (rule E3).  The tree is accepted and unused.  As PCL, clouds of different sizes print an error and leave
+// `clusters` empty; so do a tolerance or an angle outside their ranges ((0, inf), (0, pi]).
+template <typename PointT, typename NormalT>
+void extractEuclideanClusters(const PointCloud<PointT> &cloud, const PointCloud<NormalT> &normals, float tolerance,
+                              const typename search::KdTree<PointT>::Ptr & /*tree*/, std::vector<PointIndices> &clusters, double eps_angle,
+                              unsigned int min_pts_per_cluster = 1, unsigned int max_pts_per_cluster = 0x7FFFFFFFu)
+{
+  static_assert(sizeof(PointT) % 4 == 0 && sizeof(PointT) >= 12, "points that begin with x, y, z expected");
+  clusters.clear();
+  const size_t n = cloud.size();
+  if (normals.size() != n) {
+    std::fprintf(stderr, "[pcl::extractEuclideanClusters] Number of points in the input point cloud (%zu) different than normals (%zu)!\n", n, normals.size());
+    return;
+  }
+  if (!(std::isfinite(tolerance) && tolerance > 0.f) || !(eps_angle > 0.0 && eps_angle <= 3.14159265358979323846)) {
+    std::fprintf(stderr, "[pcl::extractEuclideanClusters] The tolerance (%f) must be finite and > 0, the angle (%f) in (0, pi].\n", (double)tolerance, eps_angle);
+    return;
+  }
+  if (!n) return;
+  Device &d = Device::instance();
+  SlotGuard s;
+  std::vector<float> xyz(4 * n), nrm(4 * n);
+  for (size_t i = 0; i < n; ++i) {
+    const PointT &v = cloud.points[i];
+    xyz[4 * i] = v.x; xyz[4 * i + 1] = v.y; xyz[4 * i + 2] = v.z; xyz[4 * i + 3] = 1.f;
+  }
+  d.check(mvr_cloud_upload(d.ctx(), s.s, xyz.data(), n, 16), "mvr_cloud_upload");
+  for (size_t i = 0; i < n; ++i) {
+    const NormalT &q = normals.points[i];
+    nrm[4 * i] = q.normal_x; nrm[4 * i + 1] = q.normal_y; nrm[4 * i + 2] = q.normal_z; nrm[4 * i + 3] = 0.f;
+  }
+  d.check(mvr_cloud_upload_normals(d.ctx(), s.s, nrm.data(), n, 16), "mvr_cloud_upload_normals");
+  mvr_cluster_params p = {(double)tolerance, min_pts_per_cluster, max_pts_per_cluster, 1, eps_angle, 0, 1u, 0};
+  mvr_cluster_result result;
+  detail::clusters_of_slot(d, s.s, n, p, nullptr, clusters, result);
+}
+// a PointNormal cloud carries its own normals
+template <typename PointT>
+typename std::enable_if<detail::has_normal<PointT>::value>::type
+extractEuclideanClusters(const PointCloud<PointT> &cloud, float tolerance, const typename search::KdTree<PointT>::Ptr &tree,
+                         std::vector<PointIndices> &clusters, double eps_angle, unsigned int min_pts_per_cluster = 1,
+                         unsigned int max_pts_per_cluster = 0x7FFFFFFFu)
+{
+  extractEuclideanClusters(cloud, cloud, tolerance, tree, clusters, eps_angle, min_pts_per_cluster, max_pts_per_cluster);
+}
+
 // ---------------------------------------------------------------- sample-consensus alignment
 // pcl::SampleConsensusPrerejective<PointSource, PointTarget, FeatureT> (registration/sample_consensus_prerejective.h):
 // setInputSource, setInputTarget, setSourceFeatures, setTargetFeatures, setMaximumIterations, setNumberOfSamples,

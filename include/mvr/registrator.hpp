@@ -346,6 +346,61 @@ class ScanCloud {
     return before - kept;
   }
 
+  // EXTENSION (pcl::EuclideanClusterExtraction on the raw points, on the GPU; rules E1-E8: mvr_cloud_euclidean_clusters in
+  // mvr_hip.h): what is left once the platter is out is the object plus whatever stood beside it.  extractClusters fills the
+  // clusters' indices -- largest first, members ascending -- and changes nothing; keepLargestClusters keeps the points of the
+  // first `keep` clusters in their original order, `rich` following as in removePlane, and returns the number of points it
+  // dropped.  With eps_angle > 0 the normals of `rich` must agree too (one record per point, as computeFPFH).  Parameters
+  // outside their range print an error and change nothing (extractClusters then returns false).
+  struct ClusterParams {
+    double tolerance = 2.5;
+    uint32_t min_size = 1, max_size = 0x7FFFFFFFu;
+    double eps_angle = 0.0;                // > 0: extractEuclideanClusters with the normals of `rich`, in (0, pi]
+  };
+  bool extractClusters(const ClusterParams &cp, std::vector<std::vector<uint32_t> > &clusters, mvr_cluster_result *result = nullptr) const
+  {
+    clusters.clear();
+    mvr_cluster_params p;
+    if (!clusterParams(cp, 1, p)) return false;
+    Device &d = Device::instance();
+    SlotGuard s;
+    const size_t n = points.size();
+    uploadForClusters(d, s.s, p);
+    std::vector<uint32_t> offset(n + 2), member(n ? n : 1);
+    mvr_cluster_result r;
+    d.check(mvr_cloud_euclidean_clusters(d.ctx(), -1, s.s, &p, nullptr, 0, &r, nullptr, offset.data(), offset.size(), member.data(), nullptr),
+            "mvr_cloud_euclidean_clusters");
+    if (result) *result = r;
+    clusters.resize(r.n_clusters);
+    for (uint32_t c = 0; c < r.n_clusters; ++c) clusters[c].assign(member.begin() + offset[c], member.begin() + offset[c + 1]);
+    return true;
+  }
+  size_t keepLargestClusters(const ClusterParams &cp, uint32_t keep = 1, mvr_cluster_result *result = nullptr)
+  {
+    mvr_cluster_params p;
+    if (!clusterParams(cp, keep, p)) return 0;
+    Device &d = Device::instance();
+    SlotGuard s;
+    const size_t before = points.size();
+    uploadForClusters(d, s.s, p);
+    std::vector<uint32_t> label(before ? before : 1);
+    mvr_cluster_result r;
+    size_t kept = 0;
+    d.check(mvr_cloud_euclidean_clusters(d.ctx(), s.s, s.s, &p, nullptr, 0, &r, &kept, nullptr, 0, nullptr, label.data()), "mvr_cloud_euclidean_clusters");
+    if (result) *result = r;
+    if (kept == before) return 0;
+    d.download(s.s, points);
+    if (rich.size() == before) {                   // colours and normals follow their points
+      io::RichCloud out(kept);
+      size_t w = 0;
+      for (size_t i = 0; i < before; ++i)
+        if (label[i] < keep) out[w++] = rich[i];
+      rich.swap(out);
+    }
+    touch();
+    return before - kept;
+  }
+
   // EXTENSION (pcl::FPFHEstimation on the raw points, on the GPU; rules: mvr_cloud_fpfh in mvr_hip.h): one 33-bin signature per
   // point from every neighbour within `radius`, with the normals of `rich` (estimateNormals, smooth with compute_normals, or
   // a file that carries them).  Without one rich record per point, or with a radius that is not finite and > 0, it prints an
@@ -607,6 +662,26 @@ class ScanCloud {
       return false;
     }
     return true;
+  }
+
+  // ClusterParams -> mvr_cluster_params, checked as the C-ABI checks them (E8); normals need one rich record per point
+  bool clusterParams(const ClusterParams &cp, uint32_t keep, mvr_cluster_params &p) const
+  {
+    p.tolerance = cp.tolerance; p.min_size = cp.min_size; p.max_size = cp.max_size; p.use_normals = cp.eps_angle > 0.0 ? 1 : 0;
+    p.eps_angle = cp.eps_angle; p.negative = 0; p.keep = keep; p.fma_dist = 0;
+    if (!(std::isfinite(p.tolerance) && p.tolerance > 0.0) || keep == 0 || !(cp.eps_angle >= 0.0 && cp.eps_angle <= 3.14159265358979323846) ||
+        (p.use_normals && rich.size() != points.size())) {
+      std::fprintf(stderr, "[ScanCloud::extractClusters] The tolerance (%f) must be finite and > 0, keep (%u) >= 1, the angle (%f) 0 (no normals) or in (0, pi] with one rich record per point.\n",
+                   p.tolerance, keep, cp.eps_angle);
+      return false;
+    }
+    if (points.size() == 0) p.use_normals = 0;      // (an empty slot has no normals to offer)
+    return true;
+  }
+  void uploadForClusters(Device &d, int slot, const mvr_cluster_params &p) const
+  {
+    d.upload(slot, points);
+    if (p.use_normals) uploadRichNormals(d, slot);
   }
 
   // one of the two filters (the other pointer null) in place on `points`; `rich` follows through kept_index
@@ -886,6 +961,19 @@ class Registrator {
   bool getPlatterRemoval() const { return platter_on_; }
   size_t lastPlatterPoints() const { return platter_removed_; }      // what the last saveRegisteredPoints took out
 
+  // EXTENSION, off by default: every saveRegisteredPoints below keeps only the `keep` largest Euclidean clusters of the merged
+  // cloud (ScanCloud::keepLargestClusters: points within `tolerance` of each other, clusters of at least min_size points) --
+  // the object without the clamp, the pot rim and the speckle that stood beside it -- right after the platter removal step and
+  // before any smoothing or downsampling.  tolerance 0 switches it off again.  A merged cloud without a cluster of min_size
+  // points is written empty.
+  void setObjectIsolation(double tolerance, uint32_t min_size, uint32_t keep = 1)
+  {
+    isolation_.tolerance = tolerance; isolation_.min_size = min_size; isolation_keep_ = keep;
+    isolation_on_ = tolerance != 0.0;
+  }
+  bool getObjectIsolation() const { return isolation_on_; }
+  size_t lastIsolationDropped() const { return isolation_dropped_; }      // what the last saveRegisteredPoints took out
+
   // ---- the merged object (registrator.cpp:344-400, the step registration() ends with, :719-744): every registered
   // view's points (and normals) moved by its pose -- the normals by the FULL affine including the translation, as
   // the reference does -- concatenated in view order and written as <folder>/points.pcd
@@ -895,11 +983,13 @@ class Registrator {
   {
     io::RichCloud merged;
     mergeRegisteredPoints(object, merged);
-    if (platter_on_) {
+    isolation_dropped_ = 0;
+    if (platter_on_ || isolation_on_) {
       ScanCloud whole;
       whole.rich.swap(merged);
       for (const io::RichPoint &q : whole.rich) whole.points.push_back(PCLPoint(q.x, q.y, q.z));
       removePlatter(whole);
+      isolateObject(whole);
       merged.swap(whole.rich);
     }
     const bool ok = io::savePCDFile(folder + "/points.pcd", merged, io::PCD_BINARY_COMPRESSED) && io::savePointsASC(folder + "/points.asc", merged);
@@ -918,6 +1008,7 @@ class Registrator {
     mergeRegisteredPoints(object, merged.rich);
     for (const io::RichPoint &q : merged.rich) merged.points.push_back(PCLPoint(q.x, q.y, q.z));
     removePlatter(merged);
+    isolateObject(merged);
     merged.voxelDownsample(leaf_size);
     const bool ok = io::savePCDFile(folder + "/points.pcd", merged.rich, io::PCD_BINARY_COMPRESSED) &&
                     io::savePointsASC(folder + "/points.asc", merged.rich);
@@ -944,6 +1035,7 @@ class Registrator {
     mergeRegisteredPoints(object, merged.rich);
     for (const io::RichPoint &q : merged.rich) merged.points.push_back(PCLPoint(q.x, q.y, q.z));
     removePlatter(merged);
+    isolateObject(merged);
     merged.smooth(mls_radius, polynomial_order, false);
     if (leaf_size > 0.f) merged.voxelDownsample(leaf_size);
     const bool ok = io::savePCDFile(folder + "/points.pcd", merged.rich, io::PCD_BINARY_COMPRESSED) &&
@@ -1007,6 +1099,14 @@ class Registrator {
     platter_removed_ = merged.removePlane(platter_);
   }
 
+  // setObjectIsolation's step on a merged cloud (points and rich records, one per point)
+  void isolateObject(ScanCloud &merged)
+  {
+    isolation_dropped_ = 0;
+    if (!isolation_on_) return;
+    isolation_dropped_ = merged.keepLargestClusters(isolation_, isolation_keep_);
+  }
+
   // raw scans -> device slots (once per object and per revision of its clouds); posed copies get slots of their own
   void ensureResident(int object)
   {
@@ -1035,6 +1135,10 @@ class Registrator {
   ScanCloud::PlaneParams platter_;      // setPlatterRemoval
   bool platter_on_ = false;
   size_t platter_removed_ = 0;
+  ScanCloud::ClusterParams isolation_;  // setObjectIsolation
+  uint32_t isolation_keep_ = 1;
+  bool isolation_on_ = false;
+  size_t isolation_dropped_ = 0;
   int resident_object_ = -1;
   unsigned long long resident_rev_ = 0;
   std::vector<std::unique_ptr<SlotGuard> > raw_guard_, posed_guard_;

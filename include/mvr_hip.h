@@ -681,7 +681,7 @@ int  mvr_cloud_boundary(mvr_ctx *ctx, int slot, const mvr_boundary_params *p, ui
  *      cloud above 0x7FFFFFF0 points, or a cloud whose points are stale because a pipelined run is in flight.  An empty cloud
  *      is MVR_OK with found = 0.  Bit-identical from run to run: integer atomics only, every f64 sum in the order of P10.
  * Out of scope: other models (sphere, cylinder, line, normal plane), other estimators (LMedS, MSAC, PROSAC),
- * setSamplesMaxDist, setIndices on the segmentation, Euclidean cluster extraction. */
+ * setSamplesMaxDist, setIndices on the segmentation. */
 typedef struct {
   int      model;            /* 0: SACMODEL_PLANE, 1: SACMODEL_PERPENDICULAR_PLANE */
   double   threshold;        /* setDistanceThreshold: finite, > 0 */
@@ -706,6 +706,64 @@ int  mvr_cloud_segment_plane(mvr_ctx *ctx, int dst_slot /* -1: none */, int src_
  * ctx, a bad slot, a NULL index with count > 0, an index out of range, or a stale or oversized cloud. */
 int  mvr_cloud_extract_indices(mvr_ctx *ctx, int dst_slot, int src_slot, const uint32_t *index, size_t count, int negative,
                                size_t *n_out);
+
+/* ---- Euclidean cluster extraction (EXTENSION: pcl::EuclideanClusterExtraction, pcl::extractEuclideanClusters with normals) --
+ * What is left of a scan once the platter is out (mvr_cloud_segment_plane) is the object plus whatever stood beside it; this
+ * call reports the clusters of a cloud, largest first, and can keep the first few.  PCL was not at hand; the model is
+ * pcl/segmentation/impl/extract_clusters.hpp and extract_clusters.h, as published; where PCL differs the rule here is the
+ * library's and the deviation is marked.  One thread per point walks the cloud's own grid (the walks of rules N, B and K) and
+ * unites linked points in a lock-free union-find; see csrc/mvr_cluster.hip.
+ *  E1. Active points: with index == NULL every point is active, whatever `negative` says.  Otherwise the listed points are
+ *      active (host, index_count entries, any order, repeats allowed, each below the source size; index_count may be 0), or
+ *      with `negative` all the others.  An inactive point links to nothing and is reported nowhere; its label is UINT32_MAX.
+ *  E2. Link: two active points with finite coordinates link iff d2 <= (float)(tolerance * tolerance), d2 the library's f32
+ *      distance ((dx dx + dy dy) + dz dz, every operation rounded; with fma_dist the fma chain, as everywhere).  The same
+ *      ball as B1 and K2.  DEVIATION: FLANN's radius search is strict (d2 < r2).
+ *  E3. With use_normals the link also needs dot > cos(eps_angle), dot = ((double)a.x * b.x + (double)a.y * b.y) +
+ *      (double)a.z * b.z from the slot's f32 normals, every f64 operation rounded on its own, the cosine taken once on the
+ *      host.  This is PCL's fabs(acos(dot)) < eps_angle: opposite normals do not link, even under eps_angle = pi.  DEVIATION: a
+ *      dot that rounding pushed above 1 links here (PCL's acos gives NaN there, which fails its test).  A NaN dot links
+ *      nothing.  The rule is symmetric in the pair, so the clusters are the connected components of the link graph; PCL's
+ *      flood fill finds the same components (a point may be reached through any chain of links).
+ *  E4. A point with a non-finite x, y or z links to nothing and is a component of one point (as D1, D2); it takes no part in
+ *      sizing the grid.  A cloud with no finite point gives components of size 1 and MVR_OK.
+ *  E5. A component is a cluster iff max(min_size, 1) <= size <= max_size.  too_small counts the components below
+ *      max(min_size, 1), too_large those of the others above max_size.  min_size > max_size gives no cluster and MVR_OK.
+ *  E6. Order: clusters by size descending (PCL's order), equal sizes by their smallest member index ascending (PCL's
+ *      std::sort leaves that open); the members of a cluster in ascending index (as PCL sorts them).
+ *  E7. Outputs (host, each optional): cluster_index = the concatenated member lists, n_clustered entries (capacity: the
+ *      source size); cluster_offset[c] and cluster_offset[c + 1] bound cluster c in it -- only the first m = min(n_clusters,
+ *      offset_cap - 1) clusters get offsets (m + 1 entries written, none with offset_cap = 0), result->n_clusters is always
+ *      the full number, so a caller sees a truncation; label[i] (one per source point) = the rank of point i's cluster, else
+ *      UINT32_MAX.  result: n_active (E1), n_components (of the active points), n_clusters, n_clustered (points in
+ *      clusters), largest (size of cluster 0; 0 without one), too_small, too_large.  dst_slot receives the union of the first
+ *      min(keep, n_clusters) clusters in ascending original index, normals following, a NEW point set as in P11's tail; it
+ *      may equal src_slot; dst_slot == -1 touches no slot.  *n_out (optional) = the points dst_slot received (0 without one).
+ *  E8. MVR_E_ARG, before any GPU work and with nothing written, for a NULL ctx / params / result, a bad slot, dst_slot < -1,
+ *      a tolerance that is non-finite or <= 0, keep == 0 with dst_slot >= 0, use_normals on a slot without normals or with
+ *      an eps_angle outside (0, pi], a NULL index with index_count > 0, an index out of range, a cloud above 0x7FFFFFF0
+ *      points, or a cloud whose points are stale because a pipelined run is in flight.  An empty cloud is MVR_OK with zeros.
+ *      Bit-identical from run to run and for every grid resolution: integer atomics only, and the root of a component is its
+ *      smallest member whatever the order of the unions.
+ * Out of scope: pcl::ConditionalEuclideanClustering, region growing, labelled (per-label) clustering. */
+typedef struct {
+  double   tolerance;     /* setClusterTolerance: finite, > 0 */
+  uint32_t min_size;      /* setMinClusterSize (0 is 1) */
+  uint32_t max_size;      /* setMaxClusterSize */
+  int      use_normals;   /* extractEuclideanClusters(cloud, normals, ...) */
+  double   eps_angle;     /* with use_normals: in (0, pi] */
+  int      negative;      /* how `index` is read, as in mvr_cloud_extract_indices */
+  uint32_t keep;          /* dst_slot: the first `keep` clusters (>= 1) */
+  int      fma_dist;
+} mvr_cluster_params;
+typedef struct { uint32_t n_active, n_components, n_clusters, n_clustered, largest, too_small, too_large; } mvr_cluster_result;
+void mvr_cluster_default_params(mvr_cluster_params *p);   /* PCL's: min 1, max INT32_MAX, no normals, keep 1; tolerance 0 (to be set) */
+int  mvr_cloud_euclidean_clusters(mvr_ctx *ctx, int dst_slot /* -1: none */, int src_slot, const mvr_cluster_params *p,
+                                  const uint32_t *index, size_t index_count,      /* setIndices; NULL: every point */
+                                  mvr_cluster_result *result, size_t *n_out,
+                                  uint32_t *cluster_offset, size_t offset_cap,    /* optional */
+                                  uint32_t *cluster_index /* cap = source size, optional */,
+                                  uint32_t *label /* one per source point, optional */);
 
 /* CorrespondenceEstimation::determineReciprocalCorrespondences(corrs, max_d)
  * (registrator.cpp:496-502, 644-649); reciprocal = 0 gives

@@ -225,6 +225,18 @@ class SacTrace(C.Structure):
                 ("k", C.c_double)]
 
 
+class ClusterParams(C.Structure):
+    """mvr_cluster_params"""
+    _fields_ = [("tolerance", C.c_double), ("min_size", C.c_uint32), ("max_size", C.c_uint32), ("use_normals", C.c_int),
+                ("eps_angle", C.c_double), ("negative", C.c_int), ("keep", C.c_uint32), ("fma_dist", C.c_int)]
+
+
+class ClusterResult(C.Structure):
+    """mvr_cluster_result"""
+    _fields_ = [("n_active", C.c_uint32), ("n_components", C.c_uint32), ("n_clusters", C.c_uint32), ("n_clustered", C.c_uint32),
+                ("largest", C.c_uint32), ("too_small", C.c_uint32), ("too_large", C.c_uint32)]
+
+
 SAC_MODELS = {"plane": 0, "perpendicular_plane": 1}   # mvr_sac_params.model: SACMODEL_PLANE, SACMODEL_PERPENDICULAR_PLANE
 BOUNDARY_MIN_ANGLE = math.pi / 4   # MVR_BOUNDARY_MIN_ANGLE: the smallest angle_threshold the boundary rule accepts
 FPFH_BINS = 11          # MVR_FPFH_BINS: a signature is 3 * 11 = 33 floats
@@ -282,6 +294,9 @@ SIGNATURES = {
     "mvr_cloud_segment_plane": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(SacParams), C.POINTER(SacResult), C.POINTER(_sz), _u32p, _u8p,
                                           C.POINTER(SacTrace), _sz]),
     "mvr_cloud_extract_indices": (C.c_int, [_vp, C.c_int, C.c_int, _u32p, _sz, C.c_int, C.POINTER(_sz)]),
+    "mvr_cluster_default_params": (None, [C.POINTER(ClusterParams)]),
+    "mvr_cloud_euclidean_clusters": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(ClusterParams), _u32p, _sz, C.POINTER(ClusterResult),
+                                               C.POINTER(_sz), _u32p, _sz, _u32p, _u32p]),
     "mvr_feature_knn": (C.c_int, [_vp, _fp, _sz, _fp, _sz, C.c_int, C.c_int, _u32p, _fp]),
     "mvr_pose_scores": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _sz, C.c_double, C.c_int, _u32p, _dp]),
     "mvr_align_prerejective": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, C.POINTER(PrerejParams), _fp, C.POINTER(PrerejResult),
@@ -961,6 +976,43 @@ class Context:
         _chk(_lib.mvr_cloud_extract_indices(self._h, int(dst), int(src), _p(idx, C.c_uint32) if len(idx) else None, len(idx),
                                             int(bool(negative)), C.byref(n_out)), self._h)
         return n_out.value
+
+    def euclidean_clusters(self, dst, src, tolerance, min_size=1, max_size=2**31 - 1, eps_angle=None, index=None, negative=False,
+                           keep=1, fma=False, return_lists=False, return_labels=False):
+        """pcl::EuclideanClusterExtraction of slot src (rules E1-E8: mvr_cloud_euclidean_clusters in mvr_hip.h): the connected
+        components of the points within `tolerance` of each other whose size lies in [min_size, max_size], largest first;
+        with eps_angle (radians) the slot's normals must also agree (pcl::extractEuclideanClusters with normals).  index
+        (setIndices; None: every point) restricts the clustering to the listed points, or with negative to the others.  Slot
+        dst (may be src; -1: no output slot) gets the first `keep` clusters in ascending original index.  Returns a
+        dict(n_active, n_components, n_clusters, n_clustered, largest, too_small, too_large, n_out), followed with
+        return_lists by the list of the clusters' index arrays (uint32, ascending) and with return_labels by the rank of every
+        point's cluster (uint32; UINT32_MAX: in none)."""
+        n = self.size(src)
+        p = ClusterParams(float(tolerance), int(min_size), int(max_size), int(eps_angle is not None),
+                          0.0 if eps_angle is None else float(eps_angle), int(bool(negative)), int(keep), int(bool(fma)))
+        idx, count = None, 0
+        if index is not None:
+            idx = np.ascontiguousarray(index, np.uint32).ravel()
+            count = len(idx)
+            if count == 0:
+                idx = np.zeros(1, np.uint32)      # an empty list is still a list (E1): the pointer must not be NULL
+        res = ClusterResult()
+        n_out = _sz()
+        off = np.empty(n + 2, np.uint32) if return_lists else None
+        cidx = np.empty(max(n, 1), np.uint32) if return_lists else None
+        lab = np.empty(max(n, 1), np.uint32) if return_labels else None
+        _chk(_lib.mvr_cloud_euclidean_clusters(self._h, int(dst), int(src), C.byref(p), _p(idx, C.c_uint32) if idx is not None else None, count,
+                                               C.byref(res), C.byref(n_out), _p(off, C.c_uint32) if return_lists else None,
+                                               n + 2 if return_lists else 0, _p(cidx, C.c_uint32) if return_lists else None,
+                                               _p(lab, C.c_uint32) if return_labels else None), self._h)
+        out = [dict(n_active=int(res.n_active), n_components=int(res.n_components), n_clusters=int(res.n_clusters),
+                    n_clustered=int(res.n_clustered), largest=int(res.largest), too_small=int(res.too_small), too_large=int(res.too_large),
+                    n_out=n_out.value)]
+        if return_lists:
+            out.append([cidx[off[k]:off[k + 1]].copy() for k in range(res.n_clusters)])
+        if return_labels:
+            out.append(lab[:n].copy())
+        return out[0] if len(out) == 1 else tuple(out)
 
     def feature_knn(self, q, t, k):
         """exact k nearest neighbours of every row of q among the rows of t in feature space (33 floats per row, FLANN's

@@ -11,7 +11,7 @@
 //
 //   1. uniform grid with cells >= r (10 bits per axis), points radix-sorted by cell key z|y|x: the 27
 //      neighbouring cells of a point are 9 contiguous key ranges of the sorted array;
-//   2. lock-free union-find (hook the larger root under the smaller with atomicCAS, path halving): one thread
+//   2. lock-free union-find (mvr_union_find.h: hook the larger root under the smaller with atomicCAS, path halving): one thread
 //      per point walks its 9 ranges and unites with every earlier point within r (distance in double, the
 //      reference's `sqrt(squared_distance) > threshold -> skip`);
 //   3. labels = roots = smallest index of each component (boost::connected_components numbers components by
@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "mvr_internal.h"
+#include "mvr_union_find.h"
 
 namespace mvr {
 namespace {
@@ -81,27 +82,6 @@ __global__ void key_kernel(const float4 *__restrict__ p, size_t n, Grid g, uint3
   idx[i] = (uint32_t)i;
 }
 
-__device__ __forceinline__ uint32_t uf_find(uint32_t *parent, uint32_t x)
-{
-  for (;;) {
-    const uint32_t p = __atomic_load_n(&parent[x], __ATOMIC_RELAXED);
-    if (p == x) return x;
-    const uint32_t gp = __atomic_load_n(&parent[p], __ATOMIC_RELAXED);
-    if (gp != p) __atomic_store_n(&parent[x], gp, __ATOMIC_RELAXED);       // path halving: any ancestor is a valid parent
-    x = p;
-  }
-}
-
-__device__ __forceinline__ void uf_unite(uint32_t *parent, uint32_t a, uint32_t b)
-{
-  for (;;) {
-    a = uf_find(parent, a); b = uf_find(parent, b);
-    if (a == b) return;
-    if (a < b) { const uint32_t t = a; a = b; b = t; }
-    if (atomicCAS(&parent[a], a, b) == a) return;             // the larger root goes under the smaller one
-  }
-}
-
 __global__ void unite_kernel(const float4 *__restrict__ p, const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
                              size_t n, double r, uint32_t *__restrict__ parent)
 {
@@ -139,16 +119,11 @@ __global__ void iota_kernel(uint32_t *__restrict__ v, size_t n)
   if (i < n) v[i] = (uint32_t)i;
 }
 
-// One round of pointer jumping: every node adopts its grandparent.  All depths halve at once, with independent
-// gathers instead of the dependent walk of a find -- the object is one giant component whose tree comes out of the
-// union pass thousands of links deep, and 200k concurrent finds through it took 2.3 ms.
+// one round of pointer jumping (uf_jump in mvr_union_find.h)
 __global__ void jump_kernel(uint32_t *__restrict__ parent, size_t n)
 {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t p = __atomic_load_n(&parent[i], __ATOMIC_RELAXED);
-  const uint32_t gp = __atomic_load_n(&parent[p], __ATOMIC_RELAXED);
-  if (gp != p) __atomic_store_n(&parent[i], gp, __ATOMIC_RELAXED);       // any ancestor is a valid parent
+  if (i < n) uf_jump(parent, i);
 }
 
 __global__ void label_kernel(uint32_t *__restrict__ parent, size_t n, uint32_t *__restrict__ label, uint32_t *__restrict__ size,
