@@ -840,7 +840,7 @@ int  mvr_pair_moments2_from_keys(mvr_ctx *ctx, int src_slot, int tgt_slot, const
                                  double max_dist, int reciprocal, int fma_dist, const double origin[3],
                                  double *dev_out);
 
-/* The native host of that loop (csrc/mvr_ctx.hip, collectives in csrc/mvr_world.cpp).  mvr_seq_align_sharded: ONE
+/* The native host of that loop (csrc/mvr_align.hip, collectives in csrc/mvr_world.cpp).  mvr_seq_align_sharded: ONE
  * IterativeClosestPoint::align (registrator.cpp:569) of the full source in src_slot against the sharded target in tgt_slot
  * (this rank's shard), collectives on the context's communicator (mvr_ctx_comm_init / mvr_world_create; none = a world of
  * one): per iteration ncclAllReduce(ncclInt64, ncclMin) of the Ns keys and ncclAllReduce(ncclDouble, ncclSum) of the sums, on

@@ -528,8 +528,6 @@ using namespace mvr;
 
 extern "C" {
 
-#define API __attribute__((visibility("default")))
-
 API int mvr_umeyama_from_moments(const mvr_pair_moments_t *mom, float T[16], double sv[3])
 {
   if (!mom || !T) return MVR_E_ARG;

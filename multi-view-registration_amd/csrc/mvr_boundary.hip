@@ -171,11 +171,9 @@ bool boundary_angle_ok(double t) { return std::isfinite(t) && t >= MVR_BOUNDARY_
 
 using namespace mvr;
 
-#define API __attribute__((visibility("default")))
-
 API int mvr_cloud_boundary(mvr_ctx *ctx, int slot, const mvr_boundary_params *p, uint8_t *boundary, float *max_gap, uint32_t *neighbor_count)
 {
-  if (!ctx || !p || !knn_slot_ok(slot)) return MVR_E_ARG;
+  if (!ctx || !p || !slot_ok(slot)) return MVR_E_ARG;
   if (!(std::isfinite(p->radius) && p->radius > 0.0) || p->min_neighbors < 0 || !boundary_angle_ok(p->angle_threshold)) return MVR_E_ARG;
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   MVR_HIP_TRY(c, hipSetDevice(c->device));

@@ -290,8 +290,6 @@ int cluster_cloud(Ctx *c, Cloud *dst, Cloud &src, const mvr_cluster_params &p, c
 
 using namespace mvr;
 
-#define API __attribute__((visibility("default")))
-
 API void mvr_cluster_default_params(mvr_cluster_params *p)
 {
   if (!p) return;
@@ -306,7 +304,7 @@ API int mvr_cloud_euclidean_clusters(mvr_ctx *ctx, int dst_slot, int src_slot, c
                                      mvr_cluster_result *result, size_t *n_out, uint32_t *cluster_offset, size_t offset_cap, uint32_t *cluster_index,
                                      uint32_t *label)
 {
-  if (!ctx || !p || !result || !knn_slot_ok(src_slot) || !(dst_slot == -1 || knn_slot_ok(dst_slot))) return MVR_E_ARG;
+  if (!ctx || !p || !result || !slot_ok(src_slot) || !(dst_slot == -1 || slot_ok(dst_slot))) return MVR_E_ARG;
   if (!(std::isfinite(p->tolerance) && p->tolerance > 0.0)) return MVR_E_ARG;
   if (dst_slot >= 0 && p->keep == 0) return MVR_E_ARG;
   if (p->use_normals && !(p->eps_angle > 0.0 && p->eps_angle <= M_PI)) return MVR_E_ARG;

@@ -482,8 +482,6 @@ int align_prerejective(Ctx *c, Cloud &src, Cloud &tgt, const float *src_feat, co
 
 using namespace mvr;
 
-#define API __attribute__((visibility("default")))
-
 API int mvr_feature_knn(mvr_ctx *ctx, const float *q, size_t nq, const float *t, size_t nt, int dim, int k, uint32_t *idx, float *d2)
 {
   if (!ctx || dim != kFeatDim || k < 1 || k > MVR_MAX_KNN || (!q && nq) || (!t && nt)) return MVR_E_ARG;
@@ -506,7 +504,7 @@ API int mvr_feature_knn(mvr_ctx *ctx, const float *q, size_t nq, const float *t,
 API int mvr_pose_scores(mvr_ctx *ctx, int src_slot, int tgt_slot, const float *T, size_t count, double max_dist, int fma_dist,
                         uint32_t *inliers, double *error)
 {
-  if (!ctx || !knn_slot_ok(src_slot) || !knn_slot_ok(tgt_slot) || (!T && count) || !(std::isfinite(max_dist) && max_dist > 0.0)) return MVR_E_ARG;
+  if (!ctx || !slot_ok(src_slot) || !slot_ok(tgt_slot) || (!T && count) || !(std::isfinite(max_dist) && max_dist > 0.0)) return MVR_E_ARG;
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   MVR_HIP_TRY(c, hipSetDevice(c->device));
   if (count == 0) return MVR_OK;
@@ -525,7 +523,7 @@ API int mvr_pose_scores(mvr_ctx *ctx, int src_slot, int tgt_slot, const float *T
 API int mvr_align_prerejective(mvr_ctx *ctx, int src_slot, int tgt_slot, const float *src_feat, const float *tgt_feat,
                                const mvr_prerej_params *p, const float *guess, mvr_prerej_result *result, mvr_prerej_trace *trace)
 {
-  if (!ctx || !p || !result || !src_feat || !tgt_feat || !knn_slot_ok(src_slot) || !knn_slot_ok(tgt_slot)) return MVR_E_ARG;
+  if (!ctx || !p || !result || !src_feat || !tgt_feat || !slot_ok(src_slot) || !slot_ok(tgt_slot)) return MVR_E_ARG;
   if (p->max_iterations < 0 || p->nr_samples < 3 || p->nr_samples > kMaxSamples || p->k < 1 || p->k > MVR_MAX_KNN) return MVR_E_ARG;
   if (!(p->similarity >= 0.0 && p->similarity < 1.0) || !(std::isfinite(p->max_dist) && p->max_dist > 0.0) ||
       !(p->inlier_fraction > 0.0 && p->inlier_fraction <= 1.0)) return MVR_E_ARG;

@@ -211,11 +211,9 @@ int fpfh_cloud(Ctx *c, Cloud &cl, const mvr_fpfh_params &p, float *fpfh, float *
 
 using namespace mvr;
 
-#define API __attribute__((visibility("default")))
-
 API int mvr_cloud_fpfh(mvr_ctx *ctx, int slot, const mvr_fpfh_params *p, float *fpfh, float *spfh, uint32_t *neighbor_count)
 {
-  if (!ctx || !p || !knn_slot_ok(slot)) return MVR_E_ARG;
+  if (!ctx || !p || !slot_ok(slot)) return MVR_E_ARG;
   if (!(std::isfinite(p->radius) && p->radius > 0.0)) return MVR_E_ARG;
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   MVR_HIP_TRY(c, hipSetDevice(c->device));

@@ -395,6 +395,11 @@ int set_error(Ctx *c, int status, const char *what, hipError_t e = hipSuccess);
 // host-side stopwatch for the set-up phases (MVR_TRACE_HOST=1): prints the milliseconds since the previous mark to stderr
 void host_mark(const char *what);
 
+// an entry point of the C-ABI, and its context
+#define API __attribute__((visibility("default")))
+#define CTX(p) reinterpret_cast<Ctx *>(p)
+bool slot_ok(int s);                          // (mvr_ctx.hip) a caller's slot number
+
 #define MVR_HIP_TRY(ctx, expr)                                               \
   do {                                                                       \
     hipError_t _e = (expr);                                                  \
@@ -876,6 +881,20 @@ int read_gicp_state(Ctx *c);                       // state block -> Ctx::gicp_h
 // the whole inner optimisation (G7) from X = I; `ride` (optional) queues the caller's own copies before the first round trip
 int gicp_optimise(Ctx *c, const float4 *src, const float4 *snrm, const float4 *tgt, const float4 *tnrm, const int32_t *match,
                   const uint32_t *qperm, size_t q_begin, size_t q_count, const mvr_gicp_params *p, int (*ride)(Ctx *));
+// ---- the search of one pair (mvr_ctx.hip), as the aligns of mvr_align.hip drive it
+// what a search leaves for pass 1.  qperm / tinv: the culled mode's orderings; slot / count: the brute-force mode's compacted
+// reverse queries (the culled mode searches the flagged targets in place: reverse keys are indexed by sorted target position)
+struct SearchPlan { const uint32_t *qperm = nullptr; const uint32_t *tinv = nullptr; const uint32_t *slot = nullptr; const uint32_t *count = nullptr; };
+int run_search(Ctx *c, Cloud &src, Cloud &tgt, size_t qb, size_t qn, double max_dist, bool reciprocal, bool fma, double *evals, SearchPlan *plan);
+int pair_common(Ctx *c, int ss, int ts, double max_dist, int reciprocal, int fma, size_t qb, size_t qn, double *evals, SearchPlan *plan);
+int forward_keys_impl(Ctx *c, Cloud &s, Cloud &t, double max_dist, int fma, long long *dev_keys);
+int moments2_from_keys_impl(Ctx *c, Cloud &s, Cloud &t, const long long *dev_keys, double max_dist, int reciprocal, int fma,
+                            const double origin[3], double *dev_out);
+float cap_from_max2(double max2);             // smallest float bound that admits every float d2 with (double)d2 <= max2
+int read_moments(Ctx *c, size_t n_doubles);   // Ctx::moments -> h_moments, synchronised
+int ensure_align_row(Ctx *c);                 // the mapped pinned row an align's last sums launch writes itself ...
+int spin_moments(Ctx *c, uint32_t seq, size_t n_doubles);      // ... and the wait for its word `seq`; the row lands in h_moments
+double now_ms();
 int launch_rotate_normals_f32(Ctx *c, const float4 *in, float4 *out, size_t n, const float T[16]);
 int launch_rotate_normals_f64(Ctx *c, const float4 *in, float4 *out, size_t n, const double T[16]);
 int launch_fitness(Ctx *c, const nnkey_t *keys, size_t n, double max_range, double *moments);

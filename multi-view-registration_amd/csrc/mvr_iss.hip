@@ -139,13 +139,11 @@ int iss_cloud(Ctx *c, Cloud *dst, Cloud &src, const mvr_iss_params &p, const mvr
 
 using namespace mvr;
 
-#define API __attribute__((visibility("default")))
-
 API int mvr_cloud_iss_keypoints_border(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_iss_params *p, const mvr_iss_border_params *b,
                                        size_t *n_out, uint32_t *kept_index, double *saliency, uint32_t *salient_count, uint32_t *nms_count,
                                        uint8_t *edge, uint8_t *border)
 {
-  if (!ctx || !p || !knn_slot_ok(src_slot) || !(dst_slot == -1 || knn_slot_ok(dst_slot))) return MVR_E_ARG;
+  if (!ctx || !p || !slot_ok(src_slot) || !(dst_slot == -1 || slot_ok(dst_slot))) return MVR_E_ARG;
   if (!(std::isfinite(p->salient_radius) && p->salient_radius > 0.0) || !(std::isfinite(p->non_max_radius) && p->non_max_radius > 0.0))
     return MVR_E_ARG;
   if (!std::isfinite(p->gamma_21) || !std::isfinite(p->gamma_32) || p->min_neighbors < 0) return MVR_E_ARG;

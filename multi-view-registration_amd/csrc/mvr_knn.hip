@@ -184,12 +184,9 @@ int run_batches(Ctx *c, std::vector<KnnSlot> &all, KnnBatch proto, int kmax, int
 
 using namespace mvr;
 
-#define API __attribute__((visibility("default")))
-#define CTX(p) reinterpret_cast<Ctx *>(p)
-
 API int mvr_knn(mvr_ctx *ctx, int qs, int ts, int k, int fma, uint32_t *idx, float *d2)
 {
-  if (!ctx || !knn_slot_ok(qs) || !knn_slot_ok(ts) || k < 1 || k > MVR_MAX_KNN) return MVR_E_ARG;
+  if (!ctx || !slot_ok(qs) || !slot_ok(ts) || k < 1 || k > MVR_MAX_KNN) return MVR_E_ARG;
   Ctx *c = CTX(ctx);
   MVR_HIP_TRY(c, hipSetDevice(c->device));
   Cloud &q = c->slots[qs], &t = c->slots[ts];
@@ -230,7 +227,7 @@ API int mvr_cloud_estimate_normals(mvr_ctx *ctx, int count, const int *slots, co
   if (kmode == rmode || p->k < 0 || p->k > MVR_MAX_KNN || !(p->radius >= 0.0) || std::isinf(p->radius)) return MVR_E_ARG;
   for (int j = 0; j < 3; ++j) if (!std::isfinite(p->viewpoint[j])) return MVR_E_ARG;
   for (int i = 0; i < count; ++i) {
-    if (!knn_slot_ok(slots[i])) return MVR_E_ARG;
+    if (!slot_ok(slots[i])) return MVR_E_ARG;
     for (int j = 0; j < i; ++j) if (slots[j] == slots[i]) return MVR_E_ARG;
   }
   Ctx *c = CTX(ctx);

@@ -210,8 +210,6 @@ __device__ __forceinline__ bool knn_ball_any(const KnnSlot &S, const float4 q, c
 }
 
 // ---- the host side
-inline bool knn_slot_ok(int s) { return s >= 0 && s < MVR_MAX_SLOTS; }
-
 // (float)(radius * radius), kept finite: a d2 of +inf -- a non-finite neighbour, or an f32 overflow -- is never <= r2
 inline float clamp_r2(double radius) { return (float)std::min(radius * radius, (double)std::numeric_limits<float>::max()); }
 

@@ -229,11 +229,9 @@ int mls_cloud(Ctx *c, Cloud &dst, Cloud &src, const mvr_mls_params &p, size_t *n
 
 using namespace mvr;
 
-#define API __attribute__((visibility("default")))
-
 API int mvr_cloud_mls(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_mls_params *p, size_t *n_out, uint32_t *kept_index, float *curvature)
 {
-  if (!ctx || !p || !knn_slot_ok(dst_slot) || !knn_slot_ok(src_slot)) return MVR_E_ARG;
+  if (!ctx || !p || !slot_ok(dst_slot) || !slot_ok(src_slot)) return MVR_E_ARG;
   if (!(std::isfinite(p->radius) && p->radius > 0.0) || !(std::isfinite(p->sqr_gauss_param) && p->sqr_gauss_param >= 0.0)) return MVR_E_ARG;
   if (p->order < 0 || p->order > 2 || p->orient < 0 || p->orient > 1) return MVR_E_ARG;
   for (int j = 0; j < 3; ++j) if (!std::isfinite(p->viewpoint[j])) return MVR_E_ARG;

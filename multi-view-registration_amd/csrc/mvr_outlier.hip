@@ -306,12 +306,10 @@ int outlier_filter(Ctx *c, Cloud &dst, Cloud &src, int k, double stddev_mul, flo
 
 using namespace mvr;
 
-#define API __attribute__((visibility("default")))
-
 API int mvr_cloud_statistical_outlier_removal(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_sor_params *p, size_t *n_out,
                                               uint32_t *kept_index, float *mean_dist, mvr_sor_stats *stats)
 {
-  if (!ctx || !p || !knn_slot_ok(dst_slot) || !knn_slot_ok(src_slot)) return MVR_E_ARG;
+  if (!ctx || !p || !slot_ok(dst_slot) || !slot_ok(src_slot)) return MVR_E_ARG;
   if (p->mean_k < 1 || p->mean_k > MVR_MAX_KNN || !std::isfinite(p->stddev_mul)) return MVR_E_ARG;
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   MVR_HIP_TRY(c, hipSetDevice(c->device));
@@ -322,7 +320,7 @@ API int mvr_cloud_statistical_outlier_removal(mvr_ctx *ctx, int dst_slot, int sr
 API int mvr_cloud_radius_outlier_removal(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_ror_params *p, size_t *n_out,
                                          uint32_t *kept_index, uint32_t *neighbor_count)
 {
-  if (!ctx || !p || !knn_slot_ok(dst_slot) || !knn_slot_ok(src_slot)) return MVR_E_ARG;
+  if (!ctx || !p || !slot_ok(dst_slot) || !slot_ok(src_slot)) return MVR_E_ARG;
   if (!(std::isfinite(p->radius) && p->radius > 0.0) || p->min_neighbors < 0) return MVR_E_ARG;
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   MVR_HIP_TRY(c, hipSetDevice(c->device));

@@ -153,7 +153,6 @@ hipError_t pool_host_free(void *p) { return release(p, true); }
 }  // namespace mvr
 
 extern "C" {
-#define API __attribute__((visibility("default")))
 // gives every idle block of the library's cache back to the runtime; returns the bytes freed.  stats (may be NULL): {bytes still
 // cached, requests served from the cache, requests that went to the runtime}
 API unsigned long long mvr_pool_trim(unsigned long long stats[3])

@@ -502,12 +502,10 @@ int extract_cloud(Ctx *c, Cloud &dst, Cloud &src, const uint32_t *index, size_t 
 
 using namespace mvr;
 
-#define API __attribute__((visibility("default")))
-
 API int mvr_cloud_segment_plane(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_sac_params *p, mvr_sac_result *result, size_t *n_out,
                                 uint32_t *inlier_index, uint8_t *inlier_flag, mvr_sac_trace *trace, size_t trace_cap)
 {
-  if (!ctx || !p || !result || !knn_slot_ok(src_slot) || !(dst_slot == -1 || knn_slot_ok(dst_slot))) return MVR_E_ARG;
+  if (!ctx || !p || !result || !slot_ok(src_slot) || !(dst_slot == -1 || slot_ok(dst_slot))) return MVR_E_ARG;
   if (p->model < 0 || p->model > 1 || !(std::isfinite(p->threshold) && p->threshold > 0.0)) return MVR_E_ARG;
   if (p->max_iterations < 1 || p->max_iterations > (1 << 24) || !(p->probability > 0.0 && p->probability < 1.0)) return MVR_E_ARG;
   if (p->model == 1) {
@@ -523,7 +521,7 @@ API int mvr_cloud_segment_plane(mvr_ctx *ctx, int dst_slot, int src_slot, const 
 
 API int mvr_cloud_extract_indices(mvr_ctx *ctx, int dst_slot, int src_slot, const uint32_t *index, size_t count, int negative, size_t *n_out)
 {
-  if (!ctx || !knn_slot_ok(src_slot) || !knn_slot_ok(dst_slot) || (!index && count)) return MVR_E_ARG;
+  if (!ctx || !slot_ok(src_slot) || !slot_ok(dst_slot) || (!index && count)) return MVR_E_ARG;
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   MVR_HIP_TRY(c, hipSetDevice(c->device));
   return extract_cloud(c, c->slots[dst_slot], c->slots[src_slot], index, count, negative != 0, n_out);

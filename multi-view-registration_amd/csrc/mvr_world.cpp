@@ -243,9 +243,6 @@ int comm_allreduce(Ctx *c, void *dev_buf, size_t count, int kind)
 
 using namespace mvr;
 
-#define API __attribute__((visibility("default")))
-#define CTX(p) reinterpret_cast<Ctx *>(p)
-
 struct mvr_world {
   std::vector<mvr_ctx *> ctx;
   std::vector<ncclComm_t> comm;        // ncclCommInitAll's communicators (owned here, lent to the contexts)

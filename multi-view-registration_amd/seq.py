@@ -16,7 +16,7 @@ and after the align every rank appends ITS slice of the transformed source to it
 Ties go to the lowest GLOBAL target index, so the correspondences are exactly those of the
 single-GPU / single-process run; the sums differ only in the order of f64 additions.
 
-THE PRODUCT'S HOST FOR THIS MODE IS NATIVE: mvr_seq_run_sharded / mvr_seq_align_sharded (csrc/mvr_ctx.hip, the
+THE PRODUCT'S HOST FOR THIS MODE IS NATIVE: mvr_seq_run_sharded / mvr_seq_align_sharded (csrc/mvr_align.hip, the
 collectives on the library's own RCCL communicator in csrc/mvr_world.cpp), wrapped below as
 NativeShardedSequentialICP -- one rank = one context + its communicator, torch (or any launcher) only carries
 rank 0's 128-byte unique id.

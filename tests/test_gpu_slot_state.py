@@ -24,7 +24,7 @@ Measured on an MI355X: a named scenario takes 0.2 s (median; 0.5 s at most), a r
 with the first import of torch; a fresh context costs about 1 ms, the clean rooms a tenth of a sequence's time.
 
 Found by the shard scenarios: the output slot of an align kept the segment table of the shard it had been (DESIGN.md section 22;
-fixed by finish_align_out in csrc/mvr_ctx.hip)."""
+fixed by finish_align_out in csrc/mvr_align.hip)."""
 import importlib
 import time
 
