@@ -637,6 +637,96 @@ class GeneralizedIterativeClosestPoint {
   SlotGuard src_, tgt_, out_;
 };
 
+// ---------------------------------------------------------------- Normal Distributions Transform
+// pcl::NormalDistributionsTransform over mvr_ndt_align (rules N1-N12 in mvr_hip.h), with PCL's names and PCL's defaults --
+// which are meant for metres: setResolution and setStepSize take the cloud's unit.  DEVIATIONS (N3, N4, N5, N7-N9): C^-1 from
+// the eigen-decomposition instead of a numerical inverse; the guess is applied as a matrix and the pose parametrises the
+// increment on top of it; the 27 neighbouring voxels instead of a radius search over all centroids; a backtracking line search
+// in the place of More-Thuente; the align may stop on its first iteration.  EXTENSIONS: setMinPointsPerVoxel, setRotationOrigin.
+// getSearchMethodTarget is not offered.
+template <typename PointSource, typename PointTarget>
+class NormalDistributionsTransform {
+ public:
+  typedef PointCloud<PointSource> PointCloudSource;
+  typedef PointCloud<PointTarget> PointCloudTarget;
+  typedef typename PointCloudSource::Ptr PointCloudSourcePtr;
+  typedef typename PointCloudTarget::Ptr PointCloudTargetPtr;
+  typedef Mat4<float> Matrix4;
+
+  NormalDistributionsTransform() { mvr_ndt_default_params(&p_); }      // PCL's defaults
+
+  void setInputSource(const PointCloudSourcePtr &c) { input_ = c; }
+  void setInputTarget(const PointCloudTargetPtr &c) { target_ = c; }
+  PointCloudSourcePtr const getInputSource() const { return input_; }
+  PointCloudTargetPtr const getInputTarget() const { return target_; }
+  void setResolution(float r) { p_.resolution = (double)r; }
+  float getResolution() const { return (float)p_.resolution; }
+  void setStepSize(double s) { p_.step_size = s; }
+  double getStepSize() const { return p_.step_size; }
+  void setOulierRatio(double r) { p_.outlier_ratio = r; }               // (PCL's spelling)
+  double getOulierRatio() const { return p_.outlier_ratio; }
+  void setOutlierRatio(double r) { p_.outlier_ratio = r; }              // (newer PCL)
+  double getOutlierRatio() const { return p_.outlier_ratio; }
+  void setTransformationEpsilon(double e) { p_.transformation_epsilon = e; }
+  double getTransformationEpsilon() const { return p_.transformation_epsilon; }
+  void setMaximumIterations(int n) { p_.max_iterations = n; }
+  int getMaximumIterations() const { return p_.max_iterations; }
+  // EXTENSIONS: VoxelGridCovariance's minimum (6), and the point the rotation parameters turn about (N4; PCL: the origin)
+  void setMinPointsPerVoxel(int n) { p_.min_points_per_voxel = n; }
+  int getMinPointsPerVoxel() const { return p_.min_points_per_voxel; }
+  void setRotationOrigin(double x, double y, double z) { p_.origin[0] = x; p_.origin[1] = y; p_.origin[2] = z; }
+
+  void align(PointCloudSource &output) { align(output, nullptr); }
+  // the result is what the align finds on top of `guess`, times guess (N4: the source itself is never moved or re-rounded)
+  void align(PointCloudSource &output, const Matrix4 &guess) { align(output, &guess); }
+
+  Matrix4 getFinalTransformation() const { return final_; }
+  bool hasConverged() const { return converged_; }
+  int getFinalNumIteration() const { return stats_.iterations; }
+  double getTransformationProbability() const { return input_ && !input_->empty() ? stats_.score / (double)input_->size() : 0.0; }
+  const mvr_ndt_stats &getStats() const { return stats_; }
+
+  // as IterativeClosestPoint::getFitnessScore
+  double getFitnessScore(double max_range = DBL_MAX)
+  {
+    Device &d = Device::instance();
+    if (!input_ || !target_) return DBL_MAX;
+    detail::upload_cloud(d, src_.s, *input_);
+    if (!aligned_once_) detail::upload_cloud(d, tgt_.s, *target_);
+    double score = DBL_MAX;
+    d.check(mvr_fitness(d.ctx(), src_.s, tgt_.s, final_.data(), max_range, 0, &score), "mvr_fitness");
+    return score;
+  }
+
+ private:
+  void align(PointCloudSource &output, const Matrix4 *guess)
+  {
+    Device &d = Device::instance();
+    converged_ = false; final_ = guess ? *guess : Matrix4::Identity(); stats_ = mvr_ndt_stats();
+    if (!input_ || !target_) return;
+    detail::upload_cloud(d, src_.s, *input_);
+    detail::upload_cloud(d, tgt_.s, *target_);
+    double G[16];
+    if (guess) for (int k = 0; k < 16; ++k) G[k] = (double)guess->data()[k];
+    float T[16];
+    const int rc = mvr_ndt_align(d.ctx(), src_.s, tgt_.s, out_.s, &p_, guess ? G : nullptr, T, nullptr, &stats_, nullptr, 0);
+    if (rc != MVR_E_NOCORR) d.check(rc, "mvr_ndt_align");
+    else std::fprintf(stderr, "[mvr::NormalDistributionsTransform::computeTransformation] The source overlaps no cell of the target.\n");
+    for (int k = 0; k < 16; ++k) final_.m[k] = T[k];
+    converged_ = stats_.converged != 0;
+    detail::download_cloud(d, out_.s, output);
+    aligned_once_ = true;
+  }
+
+  mvr_ndt_params p_;
+  mvr_ndt_stats stats_ = mvr_ndt_stats();
+  PointCloudSourcePtr input_;
+  PointCloudTargetPtr target_;
+  Matrix4 final_;
+  bool converged_ = false, aligned_once_ = false;
+  SlotGuard src_, tgt_, out_;
+};
+
 // ---------------------------------------------------------------- normals
 namespace search {
 // pcl::search::KdTree: accepted and ignored -- the neighbour search is the library's grid walk on the GPU

@@ -573,6 +573,46 @@ class ScanCloud {
     pose = PclMatrixCaster<RowMatrixd>(Matrix4f(T));
     return true;
   }
+  // EXTENSION (pcl::NormalDistributionsTransform on the raw points, on the GPU; rules N1-N12 at mvr_ndt_align in mvr_hip.h): this
+  // scan against the per-voxel Gaussians of `target`, both as their `points` lie; no correspondence search.  resolution (the
+  // voxel edge) and step_size are in the clouds' unit.  The rotation parameters turn about the centre of the target's bounding
+  // box, whatever params.ndt.origin says (N4: far from the origin the line search wanders otherwise).  On true, `pose` takes this
+  // scan's points onto the target's, wherever the align stopped (`stats`, optional, says where and whether it calls that
+  // converged); false (pose untouched): the source overlaps no cell.  Refused parameters throw.
+  struct NDTParams {
+    mvr_ndt_params ndt;
+    NDTParams() { mvr_ndt_default_params(&ndt); }
+  };
+  bool alignNDT(const ScanCloud &target, double resolution, double step_size, RowMatrixd &pose, mvr_ndt_stats *stats = nullptr) const
+  {
+    NDTParams params;
+    params.ndt.resolution = resolution; params.ndt.step_size = step_size;
+    return alignNDT(target, params, pose, stats);
+  }
+  bool alignNDT(const ScanCloud &target, const NDTParams &params, RowMatrixd &pose, mvr_ndt_stats *stats = nullptr) const
+  {
+    mvr_ndt_params p = params.ndt;
+    double lo[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
+    for (size_t i = 0; i < target.points.size(); ++i) {
+      const auto &q = target.points[i];
+      const double v[3] = {(double)q.x, (double)q.y, (double)q.z};
+      if (!(std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]))) continue;
+      for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], v[a]); hi[a] = std::max(hi[a], v[a]); }
+    }
+    for (int a = 0; a < 3; ++a) p.origin[a] = lo[a] <= hi[a] ? 0.5 * (lo[a] + hi[a]) : 0.0;
+    Device &d = Device::instance();
+    SlotGuard s, t;
+    d.upload(s.s, points);
+    d.upload(t.s, target.points);
+    float T[16];
+    mvr_ndt_stats st = mvr_ndt_stats();
+    const int rc = mvr_ndt_align(d.ctx(), s.s, t.s, -1, &p, nullptr, T, nullptr, &st, nullptr, 0);
+    if (stats) *stats = st;
+    if (rc == MVR_E_NOCORR) return false;
+    d.check(rc, "mvr_ndt_align");
+    pose = PclMatrixCaster<RowMatrixd>(Matrix4f(T));
+    return true;
+  }
   void uploadWithNormals(Device &d, int slot, int k_normals) const
   {
     const size_t n = points.size();

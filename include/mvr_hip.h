@@ -1118,6 +1118,109 @@ int  mvr_gicp_sums(mvr_ctx *ctx, int src_slot, int tgt_slot, const int32_t *quer
 int  mvr_gicp_solve(mvr_ctx *ctx, int src_slot, int tgt_slot, const int32_t *query, const int32_t *match, size_t count,
                     const mvr_gicp_params *params, double X_out[16], mvr_gicp_info *info);
 
+/* ---- Normal Distributions Transform (EXTENSION: pcl::NormalDistributionsTransform) -----------------------------------------
+ * Registration without a correspondence search: the source is scored against one Gaussian per voxel of the target and the
+ * pose takes Newton steps on that score.  The voxel size sets the basin, not a nearest-neighbour cap.  PCL was not at hand;
+ * the model is pcl/registration/ndt.h, impl/ndt.hpp and pcl/filters/voxel_grid_covariance.h as published; deviations are
+ * marked.  Opt-in: no other entry changes.  resolution, step_size and transformation_epsilon are in the cloud's unit (PCL's
+ * defaults are meant for metres).
+ *  N1. Inputs: a source slot and a target slot, points only.  A non-finite target point belongs to no voxel (voxel rule 1); a
+ *      non-finite source point contributes nothing.  All arithmetic after the f32 voxel index is f64.
+ *  N2. Constants, as PCL's init(): c1 = 10 (1 - outlier_ratio), c2 = outlier_ratio / resolution^3, d3 = -log c2,
+ *      d1 = -log(c1 + c2) - d3, d2 = -2 log((-log(c1 exp(-1/2) + c2) - d3) / d1).
+ *  N3. Cells.  The voxel index is rules 2-4 of mvr_cloud_voxel_grid with leaf = (float)resolution on all three axes; where rule
+ *      3 would pass the cloud through (lattice too large) the call returns MVR_E_ARG.  A voxel with n >= min_points_per_voxel
+ *      (default 6, as PCL; values below 3 count as 3) gets its mean m = (sum p) / n, kept in f64, and
+ *      C = ((n - 1) / n) (1 / n) sum (p - m)(p - m)^T -- centred, two passes, fixed order; PCL's uncentred expression has the
+ *      same value, and the odd (n - 1) / n is PCL's.  C is eigen-decomposed by the cyclic Jacobi of the normals; lmax = the
+ *      largest eigenvalue.  The voxel is dropped when lmax is not finite or <= 0.  l'_k = max(l_k, min_covar_eigvalue_mult
+ *      lmax) (default 0.01), C^-1 = V diag(1 / l') V^T.  DEVIATION: PCL rebuilds C and inverts it numerically.  Kept cells are
+ *      stored in ascending voxel index: key, n, m[3], C^-1 (xx xy xz yy yz zz).  A wave sums a voxel (lane l takes sorted
+ *      positions l, l + 64, ...; then a fixed-order wave sum), so a long voxel is not serialised on one thread.
+ *  N4. Pose p = (tx, ty, tz, rx, ry, rz): y = R(r)(x - o) + o + t, R = Rx(rx) Ry(ry) Rz(rz) as PCL; x = G x_raw with G the
+ *      optional 4x4 f64 guess (NULL: I), applied in f64 at every evaluation: the raw source is never re-rounded.  o = origin[3]
+ *      is an EXTENSION (PCL rotates about the frame's origin, o = 0, the default): far from the origin the rotation and
+ *      translation parameters are strongly coupled and the line search of N8 wanders.  DEVIATION: PCL parametrises the guess
+ *      itself by Euler angles; here p is the increment on top of G and the result is X(p) G.  No small-angle shortcut (PCL
+ *      zeroes sines below 1e-5).
+ *  N5. Neighbourhood.  The home voxel of y is h[a] = floor((float)y[a] inv) - min_b[a] by the f32 rule of the voxel index.  The
+ *      candidates are the 27 voxels h + {-1, 0, 1}^3 that lie inside the lattice and hold a kept cell, visited in ascending
+ *      voxel index.  A candidate counts when |y - m|^2 <= resolution^2 in f64 (PCL: radiusSearch over the centroids, in f32).
+ *      DEVIATION: a centroid within the radius whose voxel is not one of the 27 is not seen (it cannot happen for a centroid
+ *      inside its own voxel and a y inside its home voxel, up to f32 rounding of the index).
+ *  N6. The 29 sums, over every counted pair (point, cell): d = y - m, v = C^-1 d, q = d.v, e = exp(-d2 q / 2), w = d2 e.  A
+ *      pair with !(0 <= w <= 1) -- PCL's guard; a NaN too -- is skipped whole and is not counted.  J = [I | D1 x~, D2 x~, D3 x~],
+ *      x~ = x - o, D_k = dR/dr_k; K_ij = (d2R / dr_i dr_j) x~ for angular i, j, else 0; a_i = v.J_i.  Per pair:
+ *      s += -d1 e; g_i += d1 w a_i; H_ij += d1 w (J_i^T C^-1 J_j - d2 a_i a_j + v.K_ij).  The host forms R, the D_k and the six
+ *      second-derivative matrices in f64 as products of the axis rotations and their angle derivatives (the angle shifted by
+ *      pi/2 per derivative order, the constant entries zeroed).  Layout, as G5: 0..20 the upper triangle of H, row-major;
+ *      21..26 g; 27 the number of counted pairs; 28 s.  Fixed order, bit-identical from run to run.  s is to be MAXIMISED.
+ *  N7. Direction: delta = -H^+ g from a cyclic Jacobi eigen-decomposition of the symmetric 6x6 H on the host, in f64;
+ *      eigenvalues with |l| <= 6 * 2^-52 * max|l| are dropped (Eigen's default JacobiSVD threshold, which PCL's solve uses).
+ *      |delta| 0 or not finite: stop MVR_NDT_FLAT.  u = delta / |delta|, phi'0 = -g.u; phi'0 > 0: u = -u, phi'0 = -phi'0
+ *      (PCL's reversal); phi'0 == 0: stop MVR_NDT_FLAT.
+ *  N8. Step length.  DEVIATION: PCL runs More-Thuente with interpolation and a curvature condition; here it is backtracking
+ *      with PCL's mu = 1e-4 and PCL's bounds.  a = min(|delta|, step_size).  Up to max_line_evals trials (default 10, PCL's
+ *      max_step_iterations), each: evaluate N6 at p + a u; accept at the first trial with -s(a) <= -s(0) + mu a phi'0;
+ *      otherwise remember the trial with the largest s among those with s(a) > s(0); then halve a and leave the loop when
+ *      a < transformation_epsilon / 2.  No trial accepted: the remembered one is taken with its own a (the trace's `fallback`);
+ *      none remembered: stop MVR_NDT_NO_DECREASE with the pose as it was.  (The score is only piecewise smooth, cells enter
+ *      and leave the radius, and plain Armijo stalls short of the optimum.)
+ *  N9. Stops.  After a taken step p += a u and ++iterations; the sums of the taken trial become the current ones (no
+ *      re-evaluation).  a < transformation_epsilon: MVR_NDT_STEP, converged.  iterations >= max_iterations:
+ *      MVR_NDT_ITERATIONS, converged, as PCL.  A count of 0 at the starting pose (an empty source or cell set too):
+ *      MVR_E_NOCORR with stop MVR_NDT_NO_OVERLAP and T = G.  DEVIATION: PCL never stops on its first iteration.  PCL's
+ *      defaults: resolution 1, step_size 0.1, outlier_ratio 0.55, transformation_epsilon 0.1, max_iterations 35.
+ *  N10. Outputs: X_out = X(p) G, f64 4x4 column-major; T_out the same rounded to f32; out_slot (-1: none) = the source under
+ *      T_out, exactly as the other aligns write theirs.  Stats: iterations, stop, converged, evaluations, n_cells, n_pairs
+ *      (sum 27 at the end), score, ms.  trace[k], k < trace_cap: a, |delta|, trials, the reversed and fallback flags, score,
+ *      count and p[6] after iteration k (an iteration that stopped without a step records the pose as it was).
+ *  N11. MVR_E_ARG before any GPU work, with nothing written, for: a NULL ctx or params, a bad slot, an output slot equal to
+ *      the source or the target slot; a resolution, step_size, transformation_epsilon or min_covar_eigvalue_mult that is not finite and
+ *      > 0; an outlier_ratio outside (0, 1); d1 or d2 not finite, d1 >= 0 or d2 <= 0; max_iterations < 1 or max_line_evals < 1;
+ *      a non-finite origin or G.  mvr_ndt_constants runs exactly these parameter checks on the host (no context) and returns
+ *      d1, d2, d3.
+ *  N12. The cells are built once per call and live in the context's scratch arena; nothing is cached on a slot.
+ * Lookup: a dense uint32 table voxel -> cell when the lattice has at most "ndt_dense_max" entries (mvr_ctx_tune, default
+ * 1 << 24; 0 forces the other route), else a binary search of the kept keys per (j, k) row; both give the same bits.
+ * mvr_ndt_cells builds the cells of a target and downloads them (host arrays optional, `cap` entries each; *n = the number of
+ * cells).  mvr_ndt_sums is N6 at the pose p.  mvr_ndt_direction is N7 on the host: MVR_OK with delta[6], or MVR_E_SINGULAR
+ * where N7 says FLAT on |delta|.
+ * Out of scope: More-Thuente interpolation, a device-side Newton loop, cached cells, NDT in the ring / sequential / sharded
+ * drivers, multi-resolution schedules. */
+enum { MVR_NDT_NOT = 0, MVR_NDT_STEP = 1, MVR_NDT_ITERATIONS = 2, MVR_NDT_FLAT = 3, MVR_NDT_NO_DECREASE = 4, MVR_NDT_NO_OVERLAP = 5 };
+typedef struct {
+  double resolution;               /* setResolution: the voxel edge (PCL: 1)                                             */
+  double step_size;                /* setStepSize: the longest step of the line search (0.1)                             */
+  double outlier_ratio;            /* setOulierRatio (0.55)                                                              */
+  double transformation_epsilon;   /* setTransformationEpsilon (0.1)                                                     */
+  double min_covar_eigvalue_mult;  /* VoxelGridCovariance::setMinimumPointNumberPerVoxel's companion (0.01)              */
+  double origin[3];                /* N4: the point the rotation turns about (0, 0, 0)                                   */
+  int    max_iterations;           /* setMaximumIterations (35)                                                          */
+  int    max_line_evals;           /* N8: trials per line search (10)                                                    */
+  int    min_points_per_voxel;     /* setMinPointPerVoxel (6; below 3 counts as 3)                                       */
+} mvr_ndt_params;
+void mvr_ndt_default_params(mvr_ndt_params *p);
+typedef struct {
+  int      iterations, stop /* MVR_NDT_* */, converged, evaluations;
+  uint32_t n_cells;
+  double   n_pairs, score, ms;
+} mvr_ndt_stats;
+typedef struct {
+  double a, delta_norm;
+  int    trials, reversed, fallback, stop;
+  double score, count, p[6];
+} mvr_ndt_iter_trace;
+int  mvr_ndt_constants(const mvr_ndt_params *params, const double *guess /* optional, 16 */, double d123[3]);
+int  mvr_ndt_direction(const double sums[29], double delta[6]);
+int  mvr_ndt_cells(mvr_ctx *ctx, int tgt_slot, const mvr_ndt_params *params, size_t cap, uint64_t *key, uint32_t *count,
+                   double *mean /* 3 per cell */, double *icov /* 6 per cell */, size_t *n);
+int  mvr_ndt_sums(mvr_ctx *ctx, int src_slot, int tgt_slot, const mvr_ndt_params *params, const double *guess /* optional, 16 */,
+                  const double p[6], double out[29]);
+int  mvr_ndt_align(mvr_ctx *ctx, int src_slot, int tgt_slot, int out_slot, const mvr_ndt_params *params,
+                   const double *guess /* optional, 16 */, float T_out[16], double X_out[16], mvr_ndt_stats *stats,
+                   mvr_ndt_iter_trace *trace /* optional */, int trace_cap);
+
 /* Registration::getFitnessScore(max_range) (registrator.cpp:572,923,1015):
  * mean squared distance of T*input to its unbounded 1-NN in the target.
  * DBL_MAX when no point qualifies. */

@@ -142,6 +142,28 @@ class GicpInfo(C.Structure):
     _fields_ = [("evaluations", C.c_uint32), ("accepted", C.c_uint32), ("lambda_", C.c_double), ("f0", C.c_double), ("f1", C.c_double)]
 
 
+NDT_STOPS = ("NOT", "STEP", "ITERATIONS", "FLAT", "NO_DECREASE", "NO_OVERLAP")      # MVR_NDT_*
+
+
+class NdtParams(C.Structure):
+    """mvr_ndt_params"""
+    _fields_ = [("resolution", C.c_double), ("step_size", C.c_double), ("outlier_ratio", C.c_double), ("transformation_epsilon", C.c_double),
+                ("min_covar_eigvalue_mult", C.c_double), ("origin", C.c_double * 3), ("max_iterations", C.c_int), ("max_line_evals", C.c_int),
+                ("min_points_per_voxel", C.c_int)]
+
+
+class NdtStats(C.Structure):
+    """mvr_ndt_stats"""
+    _fields_ = [("iterations", C.c_int), ("stop", C.c_int), ("converged", C.c_int), ("evaluations", C.c_int), ("n_cells", C.c_uint32),
+                ("n_pairs", C.c_double), ("score", C.c_double), ("ms", C.c_double)]
+
+
+class NdtIterTrace(C.Structure):
+    """mvr_ndt_iter_trace"""
+    _fields_ = [("a", C.c_double), ("delta_norm", C.c_double), ("trials", C.c_int), ("reversed", C.c_int), ("fallback", C.c_int),
+                ("stop", C.c_int), ("score", C.c_double), ("count", C.c_double), ("p", C.c_double * 6)]
+
+
 class PairMoments(C.Structure):
     _fields_ = [("n", C.c_double), ("mean_src", C.c_double * 3), ("mean_tgt", C.c_double * 3),
                 ("mse", C.c_double), ("sigma", C.c_double * 9)]
@@ -352,6 +374,14 @@ SIGNATURES = {
                                      C.POINTER(IcpStats), C.POINTER(GicpIterTrace), C.c_int]),
     "mvr_gicp_sums": (C.c_int, [_vp, C.c_int, C.c_int, _i32p, _i32p, _sz, _dp, C.c_double, _dp]),
     "mvr_gicp_solve": (C.c_int, [_vp, C.c_int, C.c_int, _i32p, _i32p, _sz, C.POINTER(GicpParams), _dp, C.POINTER(GicpInfo)]),
+    "mvr_ndt_default_params": (None, [C.POINTER(NdtParams)]),
+    "mvr_ndt_constants": (C.c_int, [C.POINTER(NdtParams), _dp, _dp]),
+    "mvr_ndt_direction": (C.c_int, [_dp, _dp]),
+    "mvr_ndt_cells": (C.c_int, [_vp, C.c_int, C.POINTER(NdtParams), _sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), _dp, _dp,
+                                C.POINTER(_sz)]),
+    "mvr_ndt_sums": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(NdtParams), _dp, _dp, _dp]),
+    "mvr_ndt_align": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(NdtParams), _dp, _fp, _dp, C.POINTER(NdtStats),
+                                C.POINTER(NdtIterTrace), C.c_int]),
     "mvr_fitness": (C.c_int, [_vp, C.c_int, C.c_int, _fp, C.c_double, C.c_int, _dp]),
     "mvr_lum_edge_from_moments": (C.c_int, [C.POINTER(PairMoments2), _dp, _dp, _dp, _dp, _dp]),
     "mvr_lum_edge_from_moments_x4": (C.c_int, [C.POINTER(PairMoments2), _dp, _dp, _dp, _dp, _dp]),
@@ -469,6 +499,39 @@ def gicp_params(**kw) -> GicpParams:
             raise TypeError("gicp_params: no field %r" % k)
         setattr(p, k, float(v) if names[k] is C.c_double else int(v))
     return p
+
+
+def ndt_params(**kw) -> NdtParams:
+    """mvr_ndt_params with PCL's defaults (mvr_ndt_default_params; they are meant for metres: resolution and step_size are in
+    the cloud's unit); keywords = the fields: resolution, step_size, outlier_ratio, transformation_epsilon,
+    min_covar_eigvalue_mult, origin (3 values), max_iterations, max_line_evals, min_points_per_voxel."""
+    p = NdtParams()
+    _lib.mvr_ndt_default_params(C.byref(p))
+    names = {f[0]: f[1] for f in NdtParams._fields_}
+    for k, v in kw.items():
+        if k not in names:
+            raise TypeError("ndt_params: no field %r" % k)
+        if k == "origin":
+            p.origin[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, float(v) if names[k] is C.c_double else int(v))
+    return p
+
+
+def ndt_constants(params: NdtParams, guess=None):
+    """mvr_ndt_constants: rule N11's parameter checks on the host -> (d1, d2, d3) of rule N2; raises MvrError(E_ARG)"""
+    d = np.empty(3, np.float64)
+    G = None if guess is None else to_cm(guess, np.float64)
+    _chk(_lib.mvr_ndt_constants(C.byref(params), None if G is None else _p(G, C.c_double), _p(d, C.c_double)))
+    return tuple(d)
+
+
+def ndt_direction(sums):
+    """mvr_ndt_direction: rule N7's delta = -H^+ g from the 29 sums -> (delta float64[6], rc); rc is OK or E_SINGULAR"""
+    s, d = np.ascontiguousarray(sums, np.float64), np.empty(6, np.float64)
+    assert s.shape == (29,)
+    rc = _chk(_lib.mvr_ndt_direction(_p(s, C.c_double), _p(d, C.c_double)), allow=(E_SINGULAR,))
+    return d, rc
 
 
 def _chain(chain):
@@ -1203,6 +1266,50 @@ class Context:
                                       C.byref(info)), self._h, allow=(E_NOCORR, E_SINGULAR))
         return from_cm(X), {"evaluations": info.evaluations, "accepted": info.accepted, "lambda": info.lambda_, "f0": info.f0,
                             "f1": info.f1}, rc
+
+    def ndt_cells(self, tgt, params: NdtParams):
+        """mvr_ndt_cells: the kept cells of rule N3 in ascending voxel index -> dict(key uint64[n], count uint32[n],
+        mean float64[n, 3], icov float64[n, 6] (xx xy xz yy yz zz))"""
+        n = _sz()
+        _chk(_lib.mvr_ndt_cells(self._h, tgt, C.byref(params), 0, None, None, None, None, C.byref(n)), self._h)
+        m = n.value
+        key, cnt = np.empty(max(m, 1), np.uint64), np.empty(max(m, 1), np.uint32)
+        mean, icov = np.empty((max(m, 1), 3), np.float64), np.empty((max(m, 1), 6), np.float64)
+        _chk(_lib.mvr_ndt_cells(self._h, tgt, C.byref(params), m, _p(key, C.c_uint64), _p(cnt, C.c_uint32), _p(mean, C.c_double),
+                                _p(icov, C.c_double), C.byref(n)), self._h)
+        assert n.value == m
+        return dict(key=key[:m], count=cnt[:m], mean=mean[:m], icov=icov[:m])
+
+    def ndt_sums(self, src, tgt, params: NdtParams, p=None, guess=None):
+        """mvr_ndt_sums: the 29 sums of rule N6 at the pose p (6 values, zero by default) on top of the guess ((4,4) float64,
+        identity by default) -> float64[29]"""
+        x = np.ascontiguousarray(np.zeros(6) if p is None else p, np.float64)
+        assert x.shape == (6,)
+        G = None if guess is None else to_cm(guess, np.float64)
+        out = np.empty(29, np.float64)
+        _chk(_lib.mvr_ndt_sums(self._h, src, tgt, C.byref(params), None if G is None else _p(G, C.c_double), _p(x, C.c_double),
+                               _p(out, C.c_double)), self._h)
+        return out
+
+    def ndt_align(self, src, tgt, out, params: NdtParams, guess=None, return_trace=False):
+        """mvr_ndt_align -> (T (4,4) float32, X (4,4) float64, stats dict, rc[, trace]); rc is OK or E_NOCORR (no overlap at the
+        start).  trace: one dict per iteration (a, delta_norm, trials, reversed, fallback, stop, score, count, p float64[6])."""
+        T, X, st = np.empty(16, np.float32), np.empty(16, np.float64), NdtStats()
+        G = None if guess is None else to_cm(guess, np.float64)
+        cap = max(1, int(params.max_iterations)) + 1 if return_trace else 0
+        tr = (NdtIterTrace * max(1, cap))()
+        rc = _chk(_lib.mvr_ndt_align(self._h, src, tgt, out, C.byref(params), None if G is None else _p(G, C.c_double), _p(T, C.c_float),
+                                     _p(X, C.c_double), C.byref(st), tr if return_trace else None, cap), self._h, allow=(E_NOCORR,))
+        stats = dict(iterations=st.iterations, stop=NDT_STOPS[st.stop], converged=bool(st.converged), evaluations=st.evaluations,
+                     n_cells=st.n_cells, n_pairs=st.n_pairs, score=st.score, ms=st.ms)
+        if not return_trace:
+            return from_cm(T), from_cm(X), stats, rc
+        # (an iteration that stopped without a step -- FLAT, NO_DECREASE -- leaves a record too)
+        n_it = st.iterations + (1 if st.stop in (3, 4) else 0)
+        trace = [dict(a=tr[k].a, delta_norm=tr[k].delta_norm, trials=tr[k].trials, reversed=bool(tr[k].reversed),
+                      fallback=bool(tr[k].fallback), stop=NDT_STOPS[tr[k].stop], score=tr[k].score, count=tr[k].count,
+                      p=np.array(tr[k].p, np.float64)) for k in range(min(cap, n_it))]
+        return from_cm(T), from_cm(X), stats, rc, trace
 
     def pair_batch_correspondences(self, k, cap):
         """(query, match, d2) of pair k of the last fused batch / ring step (mvr_pair_batch_correspondences)"""

@@ -522,6 +522,133 @@ static bool solve_chain6(int nb, double *D, double *O, double *b)
   return true;
 }
 
+// ---- Normal Distributions Transform: the host's share of rules N2, N4, N6, N7 and N11 (mvr_hip.h)
+int ndt_args(const mvr_ndt_params *p, const double *guess, double d123[3], const char **why)
+{
+  const auto refuse = [&](const char *what) { if (why) *why = what; return (int)MVR_E_ARG; };
+  const auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+  if (!pos(p->resolution) || !pos(p->step_size) || !pos(p->transformation_epsilon) || !pos(p->min_covar_eigvalue_mult))
+    return refuse("NDT: resolution, step_size, transformation_epsilon or min_covar_eigvalue_mult is not finite and > 0");
+  if (!(p->outlier_ratio > 0.0 && p->outlier_ratio < 1.0)) return refuse("NDT: outlier_ratio outside (0, 1)");
+  if (p->max_iterations < 1 || p->max_line_evals < 1) return refuse("NDT: max_iterations < 1 or max_line_evals < 1");
+  for (int k = 0; k < 3; ++k) if (!std::isfinite(p->origin[k])) return refuse("NDT: origin is not finite");
+  if (guess) for (int k = 0; k < 16; ++k) if (!std::isfinite(guess[k])) return refuse("NDT: the guess is not finite");
+  // N2, as PCL's init()
+  const double c1 = 10.0 * (1.0 - p->outlier_ratio), c2 = p->outlier_ratio / (p->resolution * p->resolution * p->resolution);
+  const double d3 = -std::log(c2), d1 = -std::log(c1 + c2) - d3;
+  const double d2 = -2.0 * std::log((-std::log(c1 * std::exp(-0.5) + c2) - d3) / d1);
+  if (!std::isfinite(d1) || !std::isfinite(d2) || !(d1 < 0.0) || !(d2 > 0.0)) return refuse("NDT: the constants d1, d2 of this resolution and outlier_ratio are not usable");
+  d123[0] = d1; d123[1] = d2; d123[2] = d3;
+  return MVR_OK;
+}
+
+namespace {
+// the rotation about axis `ax` by `a`, differentiated `order` times: the angle shifted by order * pi / 2 (taken exactly:
+// (c, s) -> (-s, c) -> (-c, -s)) and, for order > 0, the constant entries zeroed
+void ndt_axis(int ax, double a, int order, double M[9])
+{
+  const double c0 = std::cos(a), s0 = std::sin(a);
+  const double c = order == 0 ? c0 : (order == 1 ? -s0 : -c0), s = order == 0 ? s0 : (order == 1 ? c0 : -s0);
+  const double one = order == 0 ? 1.0 : 0.0;
+  for (int k = 0; k < 9; ++k) M[k] = 0.0;
+  const int i = (ax + 1) % 3, j = (ax + 2) % 3;
+  M[4 * ax] = one;
+  M[3 * i + i] = c; M[3 * i + j] = -s;
+  M[3 * j + i] = s; M[3 * j + j] = c;
+}
+void mul3(const double A[9], const double B[9], double C[9])
+{
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) C[3 * r + c] = (A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c]) + A[3 * r + 2] * B[6 + c];
+}
+void ndt_rot(const double r[3], int ox, int oy, int oz, double M[9])
+{
+  double X[9], Y[9], Z[9], XY[9];
+  ndt_axis(0, r[0], ox, X); ndt_axis(1, r[1], oy, Y); ndt_axis(2, r[2], oz, Z);
+  mul3(X, Y, XY);
+  mul3(XY, Z, M);
+}
+}  // namespace
+
+void ndt_pose(const mvr_ndt_params *p, const double d123[3], const double *guess, const double x[6], NdtPose *P)
+{
+  const double I[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+  for (int k = 0; k < 12; ++k) P->G[k] = I[k];
+  if (guess) for (int r = 0; r < 3; ++r) { for (int k = 0; k < 3; ++k) P->G[3 * r + k] = guess[r + 4 * k]; P->G[9 + r] = guess[r + 12]; }
+  for (int k = 0; k < 3; ++k) { P->o[k] = p->origin[k]; P->t[k] = x[k]; }
+  const double *r = x + 3;
+  ndt_rot(r, 0, 0, 0, P->R);
+  ndt_rot(r, 1, 0, 0, P->D[0]); ndt_rot(r, 0, 1, 0, P->D[1]); ndt_rot(r, 0, 0, 1, P->D[2]);
+  ndt_rot(r, 2, 0, 0, P->DD[0]); ndt_rot(r, 1, 1, 0, P->DD[1]); ndt_rot(r, 1, 0, 1, P->DD[2]);
+  ndt_rot(r, 0, 2, 0, P->DD[3]); ndt_rot(r, 0, 1, 1, P->DD[4]); ndt_rot(r, 0, 0, 2, P->DD[5]);
+  P->d1 = d123[0]; P->d2 = d123[1]; P->r2 = p->resolution * p->resolution;
+}
+
+// X(p) G: y = R (x - o) + o + t, x = G x_raw
+void ndt_matrix(const NdtPose &P, double X[16])
+{
+  double t[3];
+  for (int r = 0; r < 3; ++r) t[r] = (P.o[r] + P.t[r]) - ((P.R[3 * r] * P.o[0] + P.R[3 * r + 1] * P.o[1]) + P.R[3 * r + 2] * P.o[2]);
+  for (int k = 0; k < 16; ++k) X[k] = 0.0;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) X[r + 4 * c] = (P.R[3 * r] * P.G[c] + P.R[3 * r + 1] * P.G[3 + c]) + P.R[3 * r + 2] * P.G[6 + c];
+    X[r + 12] = ((P.R[3 * r] * P.G[9] + P.R[3 * r + 1] * P.G[10]) + P.R[3 * r + 2] * P.G[11]) + t[r];
+  }
+  X[15] = 1.0;
+}
+
+// N7: delta = -H^+ g through the cyclic Jacobi eigen-decomposition of the symmetric 6 x 6 H
+int ndt_direction(const double sums[29], double delta[6])
+{
+  double A[6][6], V[6][6];
+  int t = 0;
+  for (int r = 0; r < 6; ++r)
+    for (int c = r; c < 6; ++c) { A[r][c] = sums[t]; A[c][r] = sums[t]; ++t; }
+  for (int r = 0; r < 6; ++r)
+    for (int c = 0; c < 6; ++c) V[r][c] = r == c ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    double off = 0.0, dia = 0.0;
+    for (int r = 0; r < 6; ++r) { dia += A[r][r] * A[r][r]; for (int c = r + 1; c < 6; ++c) off += A[r][c] * A[r][c]; }
+    if (!(off > 1.0e-40 * dia)) break;                      // (an all-zero or a non-finite matrix ends here too)
+    for (int p = 0; p < 5; ++p)
+      for (int q = p + 1; q < 6; ++q) {
+        const double apq = A[p][q];
+        if (apq == 0.0) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+        const double tt = std::fabs(theta) > 1.0e150 ? 0.5 / theta : std::copysign(1.0, theta) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double cs = 1.0 / std::sqrt(tt * tt + 1.0), sn = tt * cs;
+        A[p][p] -= tt * apq;
+        A[q][q] += tt * apq;
+        A[p][q] = A[q][p] = 0.0;
+        for (int r = 0; r < 6; ++r) {
+          if (r != p && r != q) {
+            const double arp = A[r][p], arq = A[r][q];
+            A[r][p] = A[p][r] = cs * arp - sn * arq;
+            A[r][q] = A[q][r] = sn * arp + cs * arq;
+          }
+          const double vp = V[r][p], vq = V[r][q];
+          V[r][p] = cs * vp - sn * vq;
+          V[r][q] = sn * vp + cs * vq;
+        }
+      }
+  }
+  double lmax = 0.0;
+  for (int k = 0; k < 6; ++k) lmax = std::max(lmax, std::fabs(A[k][k]));
+  const double thr = 6.0 * 0x1p-52 * lmax;
+  for (int r = 0; r < 6; ++r) delta[r] = 0.0;
+  for (int k = 0; k < 6; ++k) {
+    const double l = A[k][k];
+    if (!(std::fabs(l) > thr)) continue;
+    double vg = 0.0;
+    for (int r = 0; r < 6; ++r) vg += V[r][k] * sums[21 + r];
+    for (int r = 0; r < 6; ++r) delta[r] -= V[r][k] * (vg / l);
+  }
+  double n2 = 0.0;
+  for (int r = 0; r < 6; ++r) n2 += delta[r] * delta[r];
+  if (!std::isfinite(lmax)) { for (int r = 0; r < 6; ++r) delta[r] = NAN; return MVR_E_SINGULAR; }
+  return (std::isfinite(n2) && n2 > 0.0) ? (int)MVR_OK : (int)MVR_E_SINGULAR;
+}
+
 }  // namespace mvr
 
 using namespace mvr;

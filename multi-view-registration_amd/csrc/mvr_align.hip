@@ -709,6 +709,164 @@ API int mvr_icp_align_gicp(mvr_ctx *ctx, int ss, int ts, int os, const mvr_gicp_
   return run.finish(c, os, ss, true, T_out, st);
 }
 
+// ---- Normal Distributions Transform (rules N1-N12 in mvr_hip.h; kernels in mvr_ndt.hip, the host's matrices and the 6x6
+// eigen-decomposition in host_math.cpp).  An evaluation is two launches and a 232-byte read-back; the Newton loop with its
+// backtracking line search runs here.
+API void mvr_ndt_default_params(mvr_ndt_params *p)
+{
+  if (!p) return;
+  p->resolution = 1.0; p->step_size = 0.1; p->outlier_ratio = 0.55; p->transformation_epsilon = 0.1; p->min_covar_eigvalue_mult = 0.01;
+  p->origin[0] = p->origin[1] = p->origin[2] = 0.0;
+  p->max_iterations = 35; p->max_line_evals = 10; p->min_points_per_voxel = 6;
+}
+
+namespace {
+// N11's parameter checks, with the refusal in the context's error text
+int ndt_check(Ctx *c, const mvr_ndt_params *p, const double *guess, double d123[3])
+{
+  const char *why = "";
+  const int rc = ndt_args(p, guess, d123, &why);
+  return rc == MVR_OK ? MVR_OK : set_error(c, rc, why);
+}
+}  // namespace
+
+API int mvr_ndt_constants(const mvr_ndt_params *p, const double *guess, double d123[3])
+{
+  if (!p || !d123) return MVR_E_ARG;
+  double d[3];
+  if (int rc = ndt_args(p, guess, d, nullptr)) return rc;
+  std::memcpy(d123, d, sizeof d);
+  return MVR_OK;
+}
+
+API int mvr_ndt_direction(const double sums[29], double delta[6])
+{
+  if (!sums || !delta) return MVR_E_ARG;
+  return ndt_direction(sums, delta);
+}
+
+API int mvr_ndt_cells(mvr_ctx *ctx, int ts, const mvr_ndt_params *p, size_t cap, uint64_t *key, uint32_t *count, double *mean, double *icov,
+                      size_t *n)
+{
+  if (!ctx || !slot_ok(ts) || !p || !n) return MVR_E_ARG;
+  Ctx *c = CTX(ctx);
+  double d[3];
+  if (int rc = ndt_check(c, p, nullptr, d)) return rc;
+  MVR_HIP_TRY(c, hipSetDevice(c->device));
+  NdtCells cells;
+  if (int rc = ndt_build_cells(c, c->slots[ts], p, &cells)) return rc;
+  *n = cells.n;
+  const size_t m = std::min<size_t>(cap, cells.n);
+  if (m) {
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "cell keys");
+    if (key) MVR_HIP_TRY(c, hipMemcpyAsync(key, cells.key, m * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (count) MVR_HIP_TRY(c, hipMemcpyAsync(count, cells.count, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (mean) MVR_HIP_TRY(c, hipMemcpyAsync(mean, cells.mean, 3 * m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (icov) MVR_HIP_TRY(c, hipMemcpyAsync(icov, cells.icov, 6 * m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return MVR_OK;
+}
+
+API int mvr_ndt_sums(mvr_ctx *ctx, int ss, int ts, const mvr_ndt_params *p, const double *guess, const double x[6], double out[29])
+{
+  if (!ctx || !slot_ok(ss) || !slot_ok(ts) || !p || !x || !out) return MVR_E_ARG;
+  Ctx *c = CTX(ctx);
+  double d[3];
+  if (int rc = ndt_check(c, p, guess, d)) return rc;
+  for (int k = 0; k < 6; ++k) if (!std::isfinite(x[k])) return set_error(c, MVR_E_ARG, "NDT: the pose is not finite");
+  MVR_HIP_TRY(c, hipSetDevice(c->device));
+  NdtCells cells;
+  if (int rc = ndt_build_cells(c, c->slots[ts], p, &cells)) return rc;
+  NdtPose P;
+  ndt_pose(p, d, guess, x, &P);
+  return ndt_eval(c, c->slots[ss], cells, P, out);
+}
+
+API int mvr_ndt_align(mvr_ctx *ctx, int ss, int ts, int os, const mvr_ndt_params *p, const double *guess, float T_out[16], double X_out[16],
+                      mvr_ndt_stats *st, mvr_ndt_iter_trace *trace, int trace_cap)
+{
+  if (!ctx || !slot_ok(ss) || !slot_ok(ts) || (os >= 0 && (!slot_ok(os) || os == ss || os == ts)) || !p || !T_out || (trace && trace_cap < 0))
+    return MVR_E_ARG;
+  Ctx *c = CTX(ctx);
+  double d[3];
+  if (int rc = ndt_check(c, p, guess, d)) return rc;
+  MVR_HIP_TRY(c, hipSetDevice(c->device));
+  const double t0 = now_ms();
+  const Cloud &src = c->slots[ss];
+  NdtCells cells;
+  if (int rc = ndt_build_cells(c, c->slots[ts], p, &cells)) return rc;
+  double x[6] = {0, 0, 0, 0, 0, 0}, cur[29], trial[29], best[29];
+  NdtPose P;
+  ndt_pose(p, d, guess, x, &P);
+  int iters = 0, evals = 0, stop = MVR_NDT_NOT, status = MVR_OK;
+  if (int rc = ndt_eval(c, src, cells, P, cur)) return rc;
+  ++evals;
+  if (!(cur[27] > 0.0)) { stop = MVR_NDT_NO_OVERLAP; status = MVR_E_NOCORR; }      // N9 (an empty source or cell set too)
+  const double mu = 1e-4;
+  while (stop == MVR_NDT_NOT) {
+    mvr_ndt_iter_trace *tk = (trace && iters < trace_cap) ? &trace[iters] : nullptr;
+    if (tk) std::memset(tk, 0, sizeof *tk);
+    const auto record = [&](double a, double dn, int trials, int reversed, int fallback) {
+      if (!tk) return;
+      tk->a = a; tk->delta_norm = dn; tk->trials = trials; tk->reversed = reversed; tk->fallback = fallback; tk->stop = stop;
+      tk->score = cur[28]; tk->count = cur[27];
+      std::memcpy(tk->p, x, sizeof x);
+    };
+    // N7
+    double delta[6], u[6], dn = 0.0, dphi = 0.0;
+    (void)ndt_direction(cur, delta);
+    for (int k = 0; k < 6; ++k) dn += delta[k] * delta[k];
+    dn = std::sqrt(dn);
+    if (!(std::isfinite(dn) && dn > 0.0)) { stop = MVR_NDT_FLAT; record(0.0, dn, 0, 0, 0); break; }
+    for (int k = 0; k < 6; ++k) { u[k] = delta[k] / dn; dphi -= cur[21 + k] * u[k]; }
+    int reversed = 0;
+    if (dphi > 0.0) { for (int k = 0; k < 6; ++k) u[k] = -u[k]; dphi = -dphi; reversed = 1; }
+    if (!(dphi < 0.0)) { stop = MVR_NDT_FLAT; record(0.0, dn, 0, reversed, 0); break; }      // (0, or not a number)
+    // N8
+    double a = std::min(dn, p->step_size), a_taken = 0.0, a_best = 0.0;
+    bool accepted = false, have_best = false;
+    int trials = 0;
+    while (trials < p->max_line_evals) {
+      double xa[6];
+      for (int k = 0; k < 6; ++k) xa[k] = x[k] + a * u[k];
+      ndt_pose(p, d, guess, xa, &P);
+      if (int rc = ndt_eval(c, src, cells, P, trial)) return rc;
+      ++evals; ++trials;
+      if (-trial[28] <= -cur[28] + mu * a * dphi) { accepted = true; a_taken = a; break; }
+      if (trial[28] > cur[28] && (!have_best || trial[28] > best[28])) { have_best = true; a_best = a; std::memcpy(best, trial, sizeof best); }
+      a *= 0.5;
+      if (a < p->transformation_epsilon / 2.0) break;
+    }
+    int fallback = 0;
+    if (!accepted) {
+      if (!have_best) { stop = MVR_NDT_NO_DECREASE; record(0.0, dn, trials, reversed, 0); break; }
+      fallback = 1; a_taken = a_best; std::memcpy(trial, best, sizeof trial);
+    }
+    // N9
+    for (int k = 0; k < 6; ++k) x[k] += a_taken * u[k];
+    std::memcpy(cur, trial, sizeof cur);
+    ++iters;
+    if (a_taken < p->transformation_epsilon) stop = MVR_NDT_STEP;
+    else if (iters >= p->max_iterations) stop = MVR_NDT_ITERATIONS;
+    record(a_taken, dn, trials, reversed, fallback);
+  }
+  // N10
+  ndt_pose(p, d, guess, x, &P);
+  double X[16];
+  float T[16];
+  ndt_matrix(P, X);
+  for (int k = 0; k < 16; ++k) T[k] = (float)X[k];
+  if (os >= 0) { if (int rc = finish_align_out(c, os, ss, T, false)) return rc; }
+  std::memcpy(T_out, T, sizeof T);
+  if (X_out) std::memcpy(X_out, X, sizeof X);
+  if (st) {
+    st->iterations = iters; st->stop = stop; st->converged = (stop == MVR_NDT_STEP || stop == MVR_NDT_ITERATIONS) ? 1 : 0; st->evaluations = evals;
+    st->n_cells = cells.n; st->n_pairs = cur[27]; st->score = cur[28]; st->ms = now_ms() - t0;
+  }
+  return status;
+}
+
 // ---- sequential mode with the growing target SHARDED by points over the ranks (registrator.cpp:563-577 is
 // loop-carried and does not shard by pair).  One IterativeClosestPoint::align of the full source (every rank holds it)
 // against the distributed target, as one native loop per rank:

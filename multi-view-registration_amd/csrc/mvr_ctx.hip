@@ -474,7 +474,7 @@ API int mvr_ctx_destroy(mvr_ctx *ctx)
   c->orders.clear(); c->grids.clear();
   if (c->order_pool) c->order_pool->close();          // orderings that outlive the context free their buffers themselves
   void *bufs[] = {c->keys, c->rkeys, c->slot, c->list, c->match, c->flags, c->count, c->evals, c->partials, c->moments,
-                  c->codes_a, c->codes_b, c->idx_a, c->cub_tmp, c->bbox, c->batch_table, c->bkeys, c->brkeys, c->bbound, c->bound, c->dn_arena, c->bpartials, c->blist, c->bslot, c->bchunks, c->dist_table, c->bheavy, c->bwide, c->bwide_count, c->bcull_sets};
+                  c->codes_a, c->codes_b, c->idx_a, c->cub_tmp, c->bbox, c->batch_table, c->bkeys, c->brkeys, c->bbound, c->bound, c->dn_arena, c->bpartials, c->blist, c->bslot, c->bchunks, c->dist_table, c->bheavy, c->bwide, c->bwide_count, c->bcull_sets, c->ndt_table};
   for (void *b : bufs) if (b) (void)hipFree(b);
   if (c->stage_stat) (void)hipFree(c->stage_stat);
   if (c->proj_rows) (void)hipFree(c->proj_rows);
@@ -2044,6 +2044,7 @@ API int mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value)
   else if (!std::strcmp(key, "score_chunk")) { if (value < 1 || value > 65535) return MVR_E_ARG; c->score_chunk = value; }
   else if (!std::strcmp(key, "sac_chunk")) { if (value < 0 || value > 256) return MVR_E_ARG; c->sac_chunk = value; }
   else if (!std::strcmp(key, "rej_sac_chunk")) { if (value < 0 || value > 256) return MVR_E_ARG; c->rej_sac_chunk = value; }
+  else if (!std::strcmp(key, "ndt_dense_max")) { if (value < 0) return MVR_E_ARG; c->ndt_dense_max = value; }
   else if (!std::strcmp(key, "posed_refresh")) c->posed_refresh = value != 0;
   else if (!std::strcmp(key, "pair_groups")) { if (value < 1 || value > 8) return MVR_E_ARG; c->pair_groups = value; }
   else if (!std::strcmp(key, "inplace_ratio")) c->inplace_ratio = value;
@@ -2083,6 +2084,7 @@ API int mvr_ctx_stat(mvr_ctx *ctx, const char *key, double *value)
   else if (!std::strcmp(key, "lean_passes")) *value = (double)c->lean_passes;
   else if (!std::strcmp(key, "blocking_events")) *value = (double)c->blocking_events;
   else if (!std::strcmp(key, "pipeline")) *value = (double)c->pipeline;
+  else if (!std::strcmp(key, "n_cu")) *value = (double)c->n_cu;      // compute units: the reduction kernels' grid-stride loops lap beyond 256 n_cu items
   else if (!std::strcmp(key, "prerej_match_ms")) *value = c->prerej_ms[0];
   else if (!std::strcmp(key, "prerej_hypotheses_ms")) *value = c->prerej_ms[1];
   else if (!std::strcmp(key, "prerej_score_ms")) *value = c->prerej_ms[2];

@@ -289,6 +289,8 @@ struct Ctx {
   mvr_rej_sac_result last_sac = {}; bool last_sac_set = false;      // the last sample-consensus stage that ran on this context (mvr_ctx_last_sample_consensus)
   int sac_chunk = 0;                                     // mvr_cloud_segment_plane: attempts per chunk (0: 64 for a call's first chunk, 256 from then on); results never depend on it
   char *dn_arena = nullptr; size_t dn_arena_cap = 0;     // scratch of mvr_cloud_denoise and mvr_cloud_voxel_grid (one buffer, carved per call)
+  int ndt_dense_max = 1 << 24;                           // NDT: the largest lattice (voxels) that gets the dense voxel -> cell table; above it the kept keys are searched (same bits)
+  uint32_t *ndt_table = nullptr; size_t ndt_table_cap = 0;      // that table
   double *h_table = nullptr; size_t h_table_cap = 0;     // pinned host memory the final kernels of mvr_ring_step write straight into (zero-copy)
   // workspace of the fused batch (culled mode): forward keys of all pairs, reverse keys + flags, per-pair partial rows
   nnkey_t *bkeys = nullptr; size_t bkeys_cap = 0;
@@ -811,6 +813,19 @@ void finish_dst(Ctx *c, Cloud &dst, size_t n, bool normals);
 // centroids as a new point set
 int voxel_grid_cloud(Ctx *c, Cloud &dst, Cloud &src, const float leaf[3], unsigned min_points, size_t *n_out, uint32_t *voxel_of,
                      int *passthrough);
+// the first four steps of voxel_grid_cloud for a cubic leaf (mvr_voxel.hip), for the callers that need the voxels' members and
+// not their centroids (mvr_ndt.hip): the lattice, then the finite points sorted by 64-bit voxel index (stable: a voxel's members
+// in ascending point order), the segment heads and their inclusive scan, all carved from `s` (voxel_sorted_plan sizes them).
+struct VoxLattice {
+  float inv[3], minbf[3];
+  unsigned long long div[3], sentinel;      // div0 div1 div2 <= sentinel: one past the largest index
+  size_t nf;                                // finite points (0: no voxel; the rest is not set)
+  bool pass;                                // rule 3: the lattice is too large
+  int bits;
+};
+struct VoxSorted { const unsigned long long *key; const uint32_t *idx, *head, *vid; };
+void voxel_sorted_plan(Ctx *c, size_t n, Carver &plan);
+int voxel_sorted_index(Ctx *c, const Cloud &src, float leaf, Carver &s, VoxLattice *lat, VoxSorted *out);
 int launch_fill_u64(Ctx *c, nnkey_t *p, size_t n, nnkey_t v);
 // keys with LOCAL target indices <-> signed 64-bit keys with GLOBAL target indices (what a MIN all-reduce over
 // ranks combines; "no neighbour" = INT64_MAX).  import keeps only the matches this shard owns.
@@ -881,6 +896,23 @@ int read_gicp_state(Ctx *c);                       // state block -> Ctx::gicp_h
 // the whole inner optimisation (G7) from X = I; `ride` (optional) queues the caller's own copies before the first round trip
 int gicp_optimise(Ctx *c, const float4 *src, const float4 *snrm, const float4 *tgt, const float4 *tnrm, const int32_t *match,
                   const uint32_t *qperm, size_t q_begin, size_t q_count, const mvr_gicp_params *p, int (*ride)(Ctx *));
+// ---- Normal Distributions Transform (mvr_ndt.hip; rules N1-N12 at mvr_ndt_align in mvr_hip.h)
+// the kept cells of a target, in the context's arena (valid until the next call that carves it), and how to find one
+struct NdtCells {
+  const unsigned long long *key = nullptr; const uint32_t *count = nullptr; const double *mean = nullptr, *icov = nullptr;
+  uint32_t n = 0;
+  const uint32_t *table = nullptr;          // dense route: voxel -> cell or kNone; null: search `key`
+  VoxLattice lat;
+};
+// what an evaluation needs besides the cells: G (R row-major, t), o, t, R, the three first and six second derivatives of R
+// (rx, ry, rz; then xx xy xz yy yz zz), the constants of N2 and the squared radius
+struct NdtPose { double G[12], o[3], t[3], R[9], D[3][9], DD[6][9], d1, d2, r2; };
+int ndt_args(const mvr_ndt_params *p, const double *guess, double d123[3], const char **why);      // N11's parameter checks (host_math.cpp; why: what was refused)
+void ndt_pose(const mvr_ndt_params *p, const double d123[3], const double *guess, const double x[6], NdtPose *P);
+void ndt_matrix(const NdtPose &P, double X[16]);                                         // X(p) G, column-major
+int ndt_build_cells(Ctx *c, const Cloud &tgt, const mvr_ndt_params *p, NdtCells *cells);
+int ndt_eval(Ctx *c, const Cloud &src, const NdtCells &cells, const NdtPose &P, double out[29]);      // two launches and one read-back
+int ndt_direction(const double sums[29], double delta[6]);                               // N7 (host_math.cpp)
 // ---- the search of one pair (mvr_ctx.hip), as the aligns of mvr_align.hip drive it
 // what a search leaves for pass 1.  qperm / tinv: the culled mode's orderings; slot / count: the brute-force mode's compacted
 // reverse queries (the culled mode searches the flagged targets in place: reverse keys are indexed by sorted target position)

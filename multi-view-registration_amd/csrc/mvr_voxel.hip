@@ -316,6 +316,74 @@ size_t sort_temp_bytes(Ctx *c, size_t n)
 
 }  // namespace
 
+// steps 1-3 of voxel_grid_cloud: the finite box and count (the one read-back before the sort), PCL's overflow rule and the
+// geometry of the index.  part / box: 8 * kBoxBlocks and 8 floats of scratch.
+static int voxel_lattice(Ctx *c, const Cloud &src, const float inv[3], float *part, float *box, VoxLattice *L)
+{
+  const size_t n = src.n;
+  // 1. finite box + count
+  const int bb = (int)std::min<size_t>(kBoxBlocks, blocks_for(n, kVoxThreads));
+  hipLaunchKernelGGL(vox_box_partial_kernel, dim3(bb), dim3(kVoxThreads), 0, c->stream, src.pts, n, part);
+  hipLaunchKernelGGL(vox_box_final_kernel, dim3(1), dim3(kVoxThreads), 0, c->stream, part, bb, box);
+  MVR_HIP_TRY(c, hipGetLastError());
+  float hb[8];
+  MVR_HIP_TRY(c, hipMemcpyAsync(hb, box, sizeof hb, hipMemcpyDeviceToHost, c->stream));
+  MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  uint32_t nf32;
+  std::memcpy(&nf32, &hb[6], 4);
+  L->nf = nf32;
+  L->pass = false;
+  if (nf32 == 0) return MVR_OK;
+  // 2. PCL's overflow rule, in f32 as PCL computes it: (max_p - min_p) * inv per axis, truncated, + 1.  A product that is not
+  // below 2^31 (NaN included), or a bound product whose integer does not fit in 62 bits, takes the same exit (no cast overflows)
+  bool pass = false;
+  long long d[3], min_b[3], max_b[3];
+  for (int a = 0; a < 3; ++a) {
+    const float range = hb[3 + a] - hb[a], prod = range * inv[a];
+    const float lo = hb[a] * inv[a], hi = hb[3 + a] * inv[a];
+    if (!(prod < 0x1p31f) || !(std::fabs(lo) < 0x1p62f) || !(std::fabs(hi) < 0x1p62f)) { pass = true; break; }
+    d[a] = (long long)prod + 1;
+    min_b[a] = (long long)std::floor(lo);
+    max_b[a] = (long long)std::floor(hi);
+  }
+  if (!pass && (d[0] * d[1] > 2147483647ll || d[0] * d[1] * d[2] > 2147483647ll)) pass = true;
+  // 3. geometry of the index: div = max_b - min_b + 1; the largest ijk of an axis is the f32 difference of its bounds (a
+  // point's difference cannot exceed it: the f32 operations are monotonic).  Two distinct f32 bounds differ by at least half an
+  // ulp of the larger, and each bound product is rounded by at most half an ulp, so div[a] stays within a small multiple of
+  // d[a] (about 5 d[a] + 3): with d0 d1 d2 <= 2^31 the index needs about 40 bits.  An index that would not fit in 64 bits
+  // takes the pass-through exit all the same (the last guard of rule 3 in mvr_hip.h) rather than wrap.
+  unsigned __int128 max_key = 0, div[3] = {1, 1, 1}, top[3] = {0, 0, 0};
+  if (!pass) {
+    for (int a = 0; a < 3; ++a) {
+      L->inv[a] = inv[a];
+      L->minbf[a] = (float)min_b[a];
+      div[a] = (unsigned __int128)(max_b[a] - min_b[a] + 1);
+      top[a] = (unsigned __int128)(unsigned long long)((float)max_b[a] - (float)min_b[a]);
+    }
+    max_key = top[0] + top[1] * div[0] + top[2] * div[0] * div[1];
+    if (max_key + 1 >= ((unsigned __int128)1 << 64)) pass = true;
+  }
+  L->pass = pass;
+  if (pass) return MVR_OK;
+  for (int a = 0; a < 3; ++a) L->div[a] = (unsigned long long)div[a];
+  L->sentinel = (unsigned long long)(max_key + 1);      // non-finite points: behind every voxel
+  L->bits = 1;
+  while (L->bits < 64 && (L->sentinel >> L->bits) != 0) ++L->bits;
+  return MVR_OK;
+}
+
+namespace {
+VoxGeom geom_of(const VoxLattice &L)
+{
+  VoxGeom g;
+  for (int a = 0; a < 3; ++a) { g.inv[a] = L.inv[a]; g.minbf[a] = L.minbf[a]; }
+  g.div0 = L.div[0];
+  g.div01 = L.div[0] * L.div[1];
+  g.sentinel = L.sentinel;
+  return g;
+}
+}  // namespace
+
 int voxel_grid_cloud(Ctx *c, Cloud &dst, Cloud &src, const float leaf[3], unsigned min_points, size_t *n_out, uint32_t *voxel_of,
                      int *passthrough)
 {
@@ -351,18 +419,10 @@ int voxel_grid_cloud(Ctx *c, Cloud &dst, Cloud &src, const float leaf[3], unsign
   Carver s; s.base = c->dn_arena;
   float *part = s.take<float>(8 * kBoxBlocks), *box = s.take<float>(8);
   uint32_t *counters = s.take<uint32_t>(4);
-  // 1. finite box + count
-  const int bb = (int)std::min<size_t>(kBoxBlocks, blocks_for(n, kVoxThreads));
   MVR_HIP_TRY(c, hipMemsetAsync(counters, 0, 4 * sizeof(uint32_t), c->stream));
-  hipLaunchKernelGGL(vox_box_partial_kernel, dim3(bb), dim3(kVoxThreads), 0, c->stream, src.pts, n, part);
-  hipLaunchKernelGGL(vox_box_final_kernel, dim3(1), dim3(kVoxThreads), 0, c->stream, part, bb, box);
-  MVR_HIP_TRY(c, hipGetLastError());
-  float hb[8];
-  MVR_HIP_TRY(c, hipMemcpyAsync(hb, box, sizeof hb, hipMemcpyDeviceToHost, c->stream));
-  MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  uint32_t nf32;
-  std::memcpy(&nf32, &hb[6], 4);
-  const size_t nf = nf32;
+  VoxLattice lat;
+  if (int rc = voxel_lattice(c, src, inv, part, box, &lat)) return rc;
+  const size_t nf = lat.nf;
   if (nf == 0) {                                        // no finite point: no voxel
     finish_dst(c, dst, 0, false);
     if (voxel_of) std::fill(voxel_of, voxel_of + n, kNone);
@@ -370,36 +430,7 @@ int voxel_grid_cloud(Ctx *c, Cloud &dst, Cloud &src, const float leaf[3], unsign
     if (passthrough) *passthrough = 0;
     return MVR_OK;
   }
-  // 2. PCL's overflow rule, in f32 as PCL computes it: (max_p - min_p) * inv per axis, truncated, + 1.  A product that is not
-  // below 2^31 (NaN included), or a bound product whose integer does not fit in 62 bits, takes the same exit (no cast overflows)
-  bool pass = false;
-  long long d[3], min_b[3], max_b[3];
-  for (int a = 0; a < 3; ++a) {
-    const float range = hb[3 + a] - hb[a], prod = range * inv[a];
-    const float lo = hb[a] * inv[a], hi = hb[3 + a] * inv[a];
-    if (!(prod < 0x1p31f) || !(std::fabs(lo) < 0x1p62f) || !(std::fabs(hi) < 0x1p62f)) { pass = true; break; }
-    d[a] = (long long)prod + 1;
-    min_b[a] = (long long)std::floor(lo);
-    max_b[a] = (long long)std::floor(hi);
-  }
-  if (!pass && (d[0] * d[1] > 2147483647ll || d[0] * d[1] * d[2] > 2147483647ll)) pass = true;
-  // 3. geometry of the index: div = max_b - min_b + 1; the largest ijk of an axis is the f32 difference of its bounds (a
-  // point's difference cannot exceed it: the f32 operations are monotonic).  Two distinct f32 bounds differ by at least half an
-  // ulp of the larger, and each bound product is rounded by at most half an ulp, so div[a] stays within a small multiple of
-  // d[a] (about 5 d[a] + 3): with d0 d1 d2 <= 2^31 the index needs about 40 bits.  An index that would not fit in 64 bits
-  // takes the pass-through exit all the same (the last guard of rule 3 in mvr_hip.h) rather than wrap.
-  VoxGeom g;
-  unsigned __int128 max_key = 0, div[3] = {1, 1, 1}, top[3] = {0, 0, 0};
-  if (!pass) {
-    for (int a = 0; a < 3; ++a) {
-      g.inv[a] = inv[a];
-      g.minbf[a] = (float)min_b[a];
-      div[a] = (unsigned __int128)(max_b[a] - min_b[a] + 1);
-      top[a] = (unsigned __int128)(unsigned long long)((float)max_b[a] - (float)min_b[a]);
-    }
-    max_key = top[0] + top[1] * div[0] + top[2] * div[0] * div[1];
-    if (max_key + 1 >= ((unsigned __int128)1 << 64)) pass = true;
-  }
+  const bool pass = lat.pass;
   if (pass) {                                           // a copy of the input: every point, normals included
     if (!same) {
       dst.n = 0;
@@ -416,11 +447,8 @@ int voxel_grid_cloud(Ctx *c, Cloud &dst, Cloud &src, const float leaf[3], unsign
     if (passthrough) *passthrough = 1;
     return MVR_OK;
   }
-  g.div0 = (unsigned long long)div[0];
-  g.div01 = (unsigned long long)(div[0] * div[1]);
-  g.sentinel = (unsigned long long)(max_key + 1);       // non-finite points: behind every voxel
-  int bits = 1;
-  while (bits < 64 && (g.sentinel >> bits) != 0) ++bits;
+  const VoxGeom g = geom_of(lat);
+  const int bits = lat.bits;
   const bool k32 = g.sentinel <= 0xFFFFFFFFull;
   float4 *out = nullptr, *onrm = nullptr;
   uint32_t *d_map = nullptr;
@@ -451,6 +479,45 @@ int voxel_grid_cloud(Ctx *c, Cloud &dst, Cloud &src, const float leaf[3], unsign
   finish_dst(c, dst, kept, normals);
   if (n_out) *n_out = kept;
   if (passthrough) *passthrough = 0;
+  return MVR_OK;
+}
+
+// ---- steps 1-4 alone, for a cubic leaf and always with 64-bit keys (mvr_internal.h)
+void voxel_sorted_plan(Ctx *c, size_t n, Carver &plan)
+{
+  size_t scan_bytes = 0;
+  (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, n, c->stream);
+  plan.plan<float>(8 * kBoxBlocks); plan.plan<float>(8);
+  plan.plan<unsigned long long>(n); plan.plan<unsigned long long>(n);
+  for (int k = 0; k < 4; ++k) plan.plan<uint32_t>(n);
+  plan.plan<char>(std::max(sort_temp_bytes<unsigned long long>(c, n), scan_bytes));
+}
+
+int voxel_sorted_index(Ctx *c, const Cloud &src, float leaf, Carver &s, VoxLattice *lat, VoxSorted *out)
+{
+  const size_t n = src.n;
+  if (n == 0 || n > 0xFFFFFFF0ull) return set_error(c, MVR_E_ARG, "voxel index: an empty cloud, or one too large for 32-bit indices");
+  if (src.pts_stale) return set_error(c, MVR_E_ARG, "voxel index: the cloud's points are not current (pipelined run)");
+  const float i1 = 1.0f / leaf, inv[3] = {i1, i1, i1};
+  size_t scan_bytes = 0;
+  MVR_HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, n, c->stream));
+  size_t sort_bytes = sort_temp_bytes<unsigned long long>(c, n);
+  float *part = s.take<float>(8 * kBoxBlocks), *box = s.take<float>(8);
+  unsigned long long *key_a = s.take<unsigned long long>(n), *key_b = s.take<unsigned long long>(n);
+  uint32_t *idx_a = s.take<uint32_t>(n), *idx_b = s.take<uint32_t>(n), *head = s.take<uint32_t>(n), *vid = s.take<uint32_t>(n);
+  char *tmp = s.take<char>(std::max(sort_bytes, scan_bytes));
+  MVR_MAY_BLOCK(c, "the voxel index reads back");
+  if (int rc = voxel_lattice(c, src, inv, part, box, lat)) return rc;
+  out->key = key_b; out->idx = idx_b; out->head = head; out->vid = vid;
+  if (lat->nf == 0 || lat->pass) return MVR_OK;
+  const size_t nf = lat->nf;
+  hipLaunchKernelGGL(vox_key_kernel<unsigned long long>, dim3(blocks_for(n, kVoxThreads)), dim3(kVoxThreads), 0, c->stream, src.pts, n,
+                     geom_of(*lat), key_a, idx_a);
+  MVR_HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, key_a, key_b, idx_a, idx_b, n, 0, lat->bits, c->stream));
+  hipLaunchKernelGGL(vox_head_kernel<unsigned long long>, dim3(blocks_for(nf, kVoxThreads)), dim3(kVoxThreads), 0, c->stream, key_b, nf, head);
+  size_t b = scan_bytes;
+  MVR_HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(tmp, b, head, vid, nf, c->stream));
+  MVR_HIP_TRY(c, hipGetLastError());
   return MVR_OK;
 }
 
