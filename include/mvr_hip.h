@@ -1157,8 +1157,8 @@ int  mvr_gicp_solve(mvr_ctx *ctx, int src_slot, int tgt_slot, const int32_t *que
  *      21..26 g; 27 the number of counted pairs; 28 s.  Fixed order, bit-identical from run to run.  s is to be MAXIMISED.
  *  N7. Direction: delta = -H^+ g from a cyclic Jacobi eigen-decomposition of the symmetric 6x6 H on the host, in f64;
  *      eigenvalues with |l| <= 6 * 2^-52 * max|l| are dropped (Eigen's default JacobiSVD threshold, which PCL's solve uses).
- *      |delta| 0 or not finite: stop MVR_NDT_FLAT.  u = delta / |delta|, phi'0 = -g.u; phi'0 > 0: u = -u, phi'0 = -phi'0
- *      (PCL's reversal); phi'0 == 0: stop MVR_NDT_FLAT.
+ *      A non-finite entry of H or g makes delta not a number.  |delta| 0 or not finite: stop MVR_NDT_FLAT.  u = delta /
+ *      |delta|, phi'0 = -g.u; phi'0 > 0: u = -u, phi'0 = -phi'0 (PCL's reversal); phi'0 == 0: stop MVR_NDT_FLAT.
  *  N8. Step length.  DEVIATION: PCL runs More-Thuente with interpolation and a curvature condition; here it is backtracking
  *      with PCL's mu = 1e-4 and PCL's bounds.  a = min(|delta|, step_size).  Up to max_line_evals trials (default 10, PCL's
  *      max_step_iterations), each: evaluate N6 at p + a u; accept at the first trial with -s(a) <= -s(0) + mu a phi'0;
@@ -1171,10 +1171,13 @@ int  mvr_gicp_solve(mvr_ctx *ctx, int src_slot, int tgt_slot, const int32_t *que
  *      MVR_NDT_ITERATIONS, converged, as PCL.  A count of 0 at the starting pose (an empty source or cell set too):
  *      MVR_E_NOCORR with stop MVR_NDT_NO_OVERLAP and T = G.  DEVIATION: PCL never stops on its first iteration.  PCL's
  *      defaults: resolution 1, step_size 0.1, outlier_ratio 0.55, transformation_epsilon 0.1, max_iterations 35.
+ *      The loop of N7-N9 is mvr_ndt_newton, host code that takes the evaluation of N6 as a callback: mvr_ndt_align passes the
+ *      GPU's, a test may pass a script.  The order of the stops is: STEP before ITERATIONS (a short last step says STEP).
  *  N10. Outputs: X_out = X(p) G, f64 4x4 column-major; T_out the same rounded to f32; out_slot (-1: none) = the source under
  *      T_out, exactly as the other aligns write theirs.  Stats: iterations, stop, converged, evaluations, n_cells, n_pairs
  *      (sum 27 at the end), score, ms.  trace[k], k < trace_cap: a, |delta|, trials, the reversed and fallback flags, score,
- *      count and p[6] after iteration k (an iteration that stopped without a step records the pose as it was).
+ *      count and p[6] after iteration k (an iteration that stopped without a step records the pose as it was).  A trace_cap
+ *      shorter than the run changes nothing else: records from trace_cap on are not written.
  *  N11. MVR_E_ARG before any GPU work, with nothing written, for: a NULL ctx or params, a bad slot, an output slot equal to
  *      the source or the target slot; a resolution, step_size, transformation_epsilon or min_covar_eigvalue_mult that is not finite and
  *      > 0; an outlier_ratio outside (0, 1); d1 or d2 not finite, d1 >= 0 or d2 <= 0; max_iterations < 1 or max_line_evals < 1;
@@ -1185,7 +1188,10 @@ int  mvr_gicp_solve(mvr_ctx *ctx, int src_slot, int tgt_slot, const int32_t *que
  * 1 << 24; 0 forces the other route), else a binary search of the kept keys per (j, k) row; both give the same bits.
  * mvr_ndt_cells builds the cells of a target and downloads them (host arrays optional, `cap` entries each; *n = the number of
  * cells).  mvr_ndt_sums is N6 at the pose p.  mvr_ndt_direction is N7 on the host: MVR_OK with delta[6], or MVR_E_SINGULAR
- * where N7 says FLAT on |delta|.
+ * where N7 says FLAT on |delta|.  mvr_ndt_newton runs N7-N9 from p = 0 on the sums `eval` returns (0: fine; anything else is
+ * returned at once, with no output written): p_out, sums_out (optional: the sums at p_out), the stats' iterations, stop,
+ * converged, evaluations, n_pairs and score (n_cells and ms are left alone) and the trace; it returns MVR_OK, MVR_E_NOCORR
+ * (stop MVR_NDT_NO_OVERLAP) or MVR_E_ARG (N11's parameter checks, a NULL params, eval or p_out).  No context, no GPU.
  * Out of scope: More-Thuente interpolation, a device-side Newton loop, cached cells, NDT in the ring / sequential / sharded
  * drivers, multi-resolution schedules. */
 enum { MVR_NDT_NOT = 0, MVR_NDT_STEP = 1, MVR_NDT_ITERATIONS = 2, MVR_NDT_FLAT = 3, MVR_NDT_NO_DECREASE = 4, MVR_NDT_NO_OVERLAP = 5 };
@@ -1213,6 +1219,9 @@ typedef struct {
 } mvr_ndt_iter_trace;
 int  mvr_ndt_constants(const mvr_ndt_params *params, const double *guess /* optional, 16 */, double d123[3]);
 int  mvr_ndt_direction(const double sums[29], double delta[6]);
+typedef int (*mvr_ndt_eval_fn)(void *user, const double p[6], double sums[29]);
+int  mvr_ndt_newton(const mvr_ndt_params *params, mvr_ndt_eval_fn eval, void *user, double p_out[6], double sums_out[29],
+                    mvr_ndt_stats *stats, mvr_ndt_iter_trace *trace /* optional */, int trace_cap);
 int  mvr_ndt_cells(mvr_ctx *ctx, int tgt_slot, const mvr_ndt_params *params, size_t cap, uint64_t *key, uint32_t *count,
                    double *mean /* 3 per cell */, double *icov /* 6 per cell */, size_t *n);
 int  mvr_ndt_sums(mvr_ctx *ctx, int src_slot, int tgt_slot, const mvr_ndt_params *params, const double *guess /* optional, 16 */,

@@ -164,6 +164,9 @@ class NdtIterTrace(C.Structure):
                 ("stop", C.c_int), ("score", C.c_double), ("count", C.c_double), ("p", C.c_double * 6)]
 
 
+NDT_EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double))      # mvr_ndt_eval_fn
+
+
 class PairMoments(C.Structure):
     _fields_ = [("n", C.c_double), ("mean_src", C.c_double * 3), ("mean_tgt", C.c_double * 3),
                 ("mse", C.c_double), ("sigma", C.c_double * 9)]
@@ -377,6 +380,7 @@ SIGNATURES = {
     "mvr_ndt_default_params": (None, [C.POINTER(NdtParams)]),
     "mvr_ndt_constants": (C.c_int, [C.POINTER(NdtParams), _dp, _dp]),
     "mvr_ndt_direction": (C.c_int, [_dp, _dp]),
+    "mvr_ndt_newton": (C.c_int, [C.POINTER(NdtParams), NDT_EVAL_FN, _vp, _dp, _dp, C.POINTER(NdtStats), C.POINTER(NdtIterTrace), C.c_int]),
     "mvr_ndt_cells": (C.c_int, [_vp, C.c_int, C.POINTER(NdtParams), _sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), _dp, _dp,
                                 C.POINTER(_sz)]),
     "mvr_ndt_sums": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(NdtParams), _dp, _dp, _dp]),
@@ -532,6 +536,51 @@ def ndt_direction(sums):
     assert s.shape == (29,)
     rc = _chk(_lib.mvr_ndt_direction(_p(s, C.c_double), _p(d, C.c_double)), allow=(E_SINGULAR,))
     return d, rc
+
+
+def _ndt_trace(tr, n):
+    return [dict(a=tr[k].a, delta_norm=tr[k].delta_norm, trials=tr[k].trials, reversed=bool(tr[k].reversed),
+                 fallback=bool(tr[k].fallback), stop=NDT_STOPS[tr[k].stop], score=tr[k].score, count=tr[k].count,
+                 p=np.array(tr[k].p, np.float64)) for k in range(n)]
+
+
+def ndt_newton(params: NdtParams, fn, trace_cap=None):
+    """mvr_ndt_newton: rules N7-N9 on the host, from p = 0, on the sums fn(p float64[6]) returns (29 values; an int instead is
+    a status: non-zero ends the run at once and comes back as rc) -> dict(rc, stop, converged, iterations, evaluations, p,
+    sums, trace); rc is OK, E_NOCORR (stop NO_OVERLAP) or fn's status, and after fn's status only rc is there.  trace_cap:
+    the records to keep (default: all)."""
+    raised, said = [], []
+
+    def call(user, p, out):
+        try:
+            r = fn(np.array(p[:6], np.float64))
+            if isinstance(r, (int, np.integer)):
+                if int(r) == OK:
+                    raise ValueError("ndt_newton: fn returned OK without sums")
+                said.append(int(r))
+                return int(r)
+            r = np.asarray(r, np.float64)
+            assert r.shape == (29,)
+            for k in range(29):
+                out[k] = r[k]
+            return OK
+        except BaseException as e:      # (an exception must not cross the C frames)
+            raised.append(e)
+            return E_ARG
+    cb = NDT_EVAL_FN(call)
+    x, sums, st = np.empty(6, np.float64), np.empty(29, np.float64), NdtStats()
+    cap = max(1, int(params.max_iterations)) + 1 if trace_cap is None else int(trace_cap)
+    tr = (NdtIterTrace * max(1, cap))()
+    rc = _lib.mvr_ndt_newton(C.byref(params), cb, None, _p(x, C.c_double), _p(sums, C.c_double), C.byref(st), tr, cap)
+    if raised:
+        raise raised[0]
+    if rc not in (OK, E_NOCORR):
+        if not (said and said[-1] == rc):
+            _chk(rc)
+        return dict(rc=rc)
+    n_it = st.iterations + (1 if st.stop in (3, 4) else 0)
+    return dict(rc=rc, stop=NDT_STOPS[st.stop], converged=bool(st.converged), iterations=st.iterations, evaluations=st.evaluations,
+                p=x, sums=sums, score=st.score, count=st.n_pairs, trace=_ndt_trace(tr, min(cap, n_it)))
 
 
 def _chain(chain):
@@ -1291,12 +1340,13 @@ class Context:
                                _p(out, C.c_double)), self._h)
         return out
 
-    def ndt_align(self, src, tgt, out, params: NdtParams, guess=None, return_trace=False):
+    def ndt_align(self, src, tgt, out, params: NdtParams, guess=None, return_trace=False, trace_cap=None):
         """mvr_ndt_align -> (T (4,4) float32, X (4,4) float64, stats dict, rc[, trace]); rc is OK or E_NOCORR (no overlap at the
-        start).  trace: one dict per iteration (a, delta_norm, trials, reversed, fallback, stop, score, count, p float64[6])."""
+        start).  trace: one dict per iteration (a, delta_norm, trials, reversed, fallback, stop, score, count, p float64[6]),
+        the first trace_cap of them (default: all)."""
         T, X, st = np.empty(16, np.float32), np.empty(16, np.float64), NdtStats()
         G = None if guess is None else to_cm(guess, np.float64)
-        cap = max(1, int(params.max_iterations)) + 1 if return_trace else 0
+        cap = (max(1, int(params.max_iterations)) + 1 if trace_cap is None else int(trace_cap)) if return_trace else 0
         tr = (NdtIterTrace * max(1, cap))()
         rc = _chk(_lib.mvr_ndt_align(self._h, src, tgt, out, C.byref(params), None if G is None else _p(G, C.c_double), _p(T, C.c_float),
                                      _p(X, C.c_double), C.byref(st), tr if return_trace else None, cap), self._h, allow=(E_NOCORR,))
@@ -1306,10 +1356,7 @@ class Context:
             return from_cm(T), from_cm(X), stats, rc
         # (an iteration that stopped without a step -- FLAT, NO_DECREASE -- leaves a record too)
         n_it = st.iterations + (1 if st.stop in (3, 4) else 0)
-        trace = [dict(a=tr[k].a, delta_norm=tr[k].delta_norm, trials=tr[k].trials, reversed=bool(tr[k].reversed),
-                      fallback=bool(tr[k].fallback), stop=NDT_STOPS[tr[k].stop], score=tr[k].score, count=tr[k].count,
-                      p=np.array(tr[k].p, np.float64)) for k in range(min(cap, n_it))]
-        return from_cm(T), from_cm(X), stats, rc, trace
+        return from_cm(T), from_cm(X), stats, rc, _ndt_trace(tr, min(cap, n_it))
 
     def pair_batch_correspondences(self, k, cap):
         """(query, match, d2) of pair k of the last fused batch / ring step (mvr_pair_batch_correspondences)"""

@@ -602,6 +602,10 @@ int ndt_direction(const double sums[29], double delta[6])
 {
   double A[6][6], V[6][6];
   int t = 0;
+  // a non-finite entry of H or g: delta is not a number (the sweeps below end at once on a NaN off the diagonal and would
+  // answer from the diagonal alone)
+  for (int k = 0; k < 27; ++k)
+    if (!std::isfinite(sums[k])) { for (int r = 0; r < 6; ++r) delta[r] = NAN; return MVR_E_SINGULAR; }
   for (int r = 0; r < 6; ++r)
     for (int c = r; c < 6; ++c) { A[r][c] = sums[t]; A[c][r] = sums[t]; ++t; }
   for (int r = 0; r < 6; ++r)
@@ -649,11 +653,86 @@ int ndt_direction(const double sums[29], double delta[6])
   return (std::isfinite(n2) && n2 > 0.0) ? (int)MVR_OK : (int)MVR_E_SINGULAR;
 }
 
+// N7-N9: the Newton loop with its backtracking line search, on whatever `eval` says the 29 sums at a pose are (mvr_ndt_align:
+// ndt_pose + ndt_eval; a test: a script).  No HIP here.  A non-zero status of `eval` is returned at once, with nothing written.
+int ndt_newton(const mvr_ndt_params *p, mvr_ndt_eval_fn eval, void *user, double p_out[6], double sums_out[29], mvr_ndt_stats *st,
+               mvr_ndt_iter_trace *trace, int trace_cap)
+{
+  double x[6] = {0, 0, 0, 0, 0, 0}, cur[29], trial[29], best[29];
+  int iters = 0, evals = 0, stop = MVR_NDT_NOT, status = MVR_OK;
+  if (int rc = eval(user, x, cur)) return rc;
+  ++evals;
+  if (!(cur[27] > 0.0)) { stop = MVR_NDT_NO_OVERLAP; status = MVR_E_NOCORR; }      // N9 (an empty source or cell set too)
+  const double mu = 1e-4;
+  while (stop == MVR_NDT_NOT) {
+    mvr_ndt_iter_trace *tk = (trace && iters < trace_cap) ? &trace[iters] : nullptr;
+    if (tk) std::memset(tk, 0, sizeof *tk);
+    const auto record = [&](double a, double dn, int trials, int reversed, int fallback) {
+      if (!tk) return;
+      tk->a = a; tk->delta_norm = dn; tk->trials = trials; tk->reversed = reversed; tk->fallback = fallback; tk->stop = stop;
+      tk->score = cur[28]; tk->count = cur[27];
+      std::memcpy(tk->p, x, sizeof x);
+    };
+    // N7
+    double delta[6], u[6], dn = 0.0, dphi = 0.0;
+    (void)ndt_direction(cur, delta);
+    for (int k = 0; k < 6; ++k) dn += delta[k] * delta[k];
+    dn = std::sqrt(dn);
+    if (!(std::isfinite(dn) && dn > 0.0)) { stop = MVR_NDT_FLAT; record(0.0, dn, 0, 0, 0); break; }
+    for (int k = 0; k < 6; ++k) { u[k] = delta[k] / dn; dphi -= cur[21 + k] * u[k]; }
+    int reversed = 0;
+    if (dphi > 0.0) { for (int k = 0; k < 6; ++k) u[k] = -u[k]; dphi = -dphi; reversed = 1; }
+    if (!(dphi < 0.0)) { stop = MVR_NDT_FLAT; record(0.0, dn, 0, reversed, 0); break; }      // (0, or not a number)
+    // N8
+    double a = std::min(dn, p->step_size), a_taken = 0.0, a_best = 0.0;
+    bool accepted = false, have_best = false;
+    int trials = 0;
+    while (trials < p->max_line_evals) {
+      double xa[6];
+      for (int k = 0; k < 6; ++k) xa[k] = x[k] + a * u[k];
+      if (int rc = eval(user, xa, trial)) return rc;
+      ++evals; ++trials;
+      if (-trial[28] <= -cur[28] + mu * a * dphi) { accepted = true; a_taken = a; break; }
+      if (trial[28] > cur[28] && (!have_best || trial[28] > best[28])) { have_best = true; a_best = a; std::memcpy(best, trial, sizeof best); }
+      a *= 0.5;
+      if (a < p->transformation_epsilon / 2.0) break;
+    }
+    int fallback = 0;
+    if (!accepted) {
+      if (!have_best) { stop = MVR_NDT_NO_DECREASE; record(0.0, dn, trials, reversed, 0); break; }
+      fallback = 1; a_taken = a_best; std::memcpy(trial, best, sizeof trial);
+    }
+    // N9
+    for (int k = 0; k < 6; ++k) x[k] += a_taken * u[k];
+    std::memcpy(cur, trial, sizeof cur);
+    ++iters;
+    if (a_taken < p->transformation_epsilon) stop = MVR_NDT_STEP;
+    else if (iters >= p->max_iterations) stop = MVR_NDT_ITERATIONS;
+    record(a_taken, dn, trials, reversed, fallback);
+  }
+  std::memcpy(p_out, x, sizeof x);
+  if (sums_out) std::memcpy(sums_out, cur, sizeof cur);
+  if (st) {
+    st->iterations = iters; st->stop = stop; st->converged = (stop == MVR_NDT_STEP || stop == MVR_NDT_ITERATIONS) ? 1 : 0; st->evaluations = evals;
+    st->n_pairs = cur[27]; st->score = cur[28];
+  }
+  return status;
+}
+
 }  // namespace mvr
 
 using namespace mvr;
 
 extern "C" {
+
+API int mvr_ndt_newton(const mvr_ndt_params *p, mvr_ndt_eval_fn eval, void *user, double p_out[6], double sums_out[29], mvr_ndt_stats *st,
+                       mvr_ndt_iter_trace *trace, int trace_cap)
+{
+  if (!p || !eval || !p_out || (trace && trace_cap < 0)) return MVR_E_ARG;
+  double d[3];
+  if (int rc = ndt_args(p, nullptr, d, nullptr)) return rc;
+  return ndt_newton(p, eval, user, p_out, sums_out, st, trace, trace_cap);
+}
 
 API int mvr_umeyama_from_moments(const mvr_pair_moments_t *mom, float T[16], double sv[3])
 {

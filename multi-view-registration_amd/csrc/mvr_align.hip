@@ -796,61 +796,19 @@ API int mvr_ndt_align(mvr_ctx *ctx, int ss, int ts, int os, const mvr_ndt_params
   const Cloud &src = c->slots[ss];
   NdtCells cells;
   if (int rc = ndt_build_cells(c, c->slots[ts], p, &cells)) return rc;
-  double x[6] = {0, 0, 0, 0, 0, 0}, cur[29], trial[29], best[29];
+  // N7-N9: the loop is host_math.cpp's ndt_newton; an evaluation is the pose's matrices, two launches and a read-back
+  struct Eval { Ctx *c; const Cloud *src; const NdtCells *cells; const mvr_ndt_params *p; const double *d, *guess; } ev = {c, &src, &cells, p, d, guess};
+  const mvr_ndt_eval_fn eval = [](void *user, const double xp[6], double sums[29]) -> int {
+    const Eval *e = static_cast<const Eval *>(user);
+    NdtPose Q;
+    ndt_pose(e->p, e->d, e->guess, xp, &Q);
+    return ndt_eval(e->c, *e->src, *e->cells, Q, sums);
+  };
+  double x[6], cur[29];
+  mvr_ndt_stats run = {};
+  const int status = ndt_newton(p, eval, &ev, x, cur, &run, trace, trace_cap);
+  if (status != MVR_OK && status != MVR_E_NOCORR) return status;
   NdtPose P;
-  ndt_pose(p, d, guess, x, &P);
-  int iters = 0, evals = 0, stop = MVR_NDT_NOT, status = MVR_OK;
-  if (int rc = ndt_eval(c, src, cells, P, cur)) return rc;
-  ++evals;
-  if (!(cur[27] > 0.0)) { stop = MVR_NDT_NO_OVERLAP; status = MVR_E_NOCORR; }      // N9 (an empty source or cell set too)
-  const double mu = 1e-4;
-  while (stop == MVR_NDT_NOT) {
-    mvr_ndt_iter_trace *tk = (trace && iters < trace_cap) ? &trace[iters] : nullptr;
-    if (tk) std::memset(tk, 0, sizeof *tk);
-    const auto record = [&](double a, double dn, int trials, int reversed, int fallback) {
-      if (!tk) return;
-      tk->a = a; tk->delta_norm = dn; tk->trials = trials; tk->reversed = reversed; tk->fallback = fallback; tk->stop = stop;
-      tk->score = cur[28]; tk->count = cur[27];
-      std::memcpy(tk->p, x, sizeof x);
-    };
-    // N7
-    double delta[6], u[6], dn = 0.0, dphi = 0.0;
-    (void)ndt_direction(cur, delta);
-    for (int k = 0; k < 6; ++k) dn += delta[k] * delta[k];
-    dn = std::sqrt(dn);
-    if (!(std::isfinite(dn) && dn > 0.0)) { stop = MVR_NDT_FLAT; record(0.0, dn, 0, 0, 0); break; }
-    for (int k = 0; k < 6; ++k) { u[k] = delta[k] / dn; dphi -= cur[21 + k] * u[k]; }
-    int reversed = 0;
-    if (dphi > 0.0) { for (int k = 0; k < 6; ++k) u[k] = -u[k]; dphi = -dphi; reversed = 1; }
-    if (!(dphi < 0.0)) { stop = MVR_NDT_FLAT; record(0.0, dn, 0, reversed, 0); break; }      // (0, or not a number)
-    // N8
-    double a = std::min(dn, p->step_size), a_taken = 0.0, a_best = 0.0;
-    bool accepted = false, have_best = false;
-    int trials = 0;
-    while (trials < p->max_line_evals) {
-      double xa[6];
-      for (int k = 0; k < 6; ++k) xa[k] = x[k] + a * u[k];
-      ndt_pose(p, d, guess, xa, &P);
-      if (int rc = ndt_eval(c, src, cells, P, trial)) return rc;
-      ++evals; ++trials;
-      if (-trial[28] <= -cur[28] + mu * a * dphi) { accepted = true; a_taken = a; break; }
-      if (trial[28] > cur[28] && (!have_best || trial[28] > best[28])) { have_best = true; a_best = a; std::memcpy(best, trial, sizeof best); }
-      a *= 0.5;
-      if (a < p->transformation_epsilon / 2.0) break;
-    }
-    int fallback = 0;
-    if (!accepted) {
-      if (!have_best) { stop = MVR_NDT_NO_DECREASE; record(0.0, dn, trials, reversed, 0); break; }
-      fallback = 1; a_taken = a_best; std::memcpy(trial, best, sizeof trial);
-    }
-    // N9
-    for (int k = 0; k < 6; ++k) x[k] += a_taken * u[k];
-    std::memcpy(cur, trial, sizeof cur);
-    ++iters;
-    if (a_taken < p->transformation_epsilon) stop = MVR_NDT_STEP;
-    else if (iters >= p->max_iterations) stop = MVR_NDT_ITERATIONS;
-    record(a_taken, dn, trials, reversed, fallback);
-  }
   // N10
   ndt_pose(p, d, guess, x, &P);
   double X[16];
@@ -861,8 +819,8 @@ API int mvr_ndt_align(mvr_ctx *ctx, int ss, int ts, int os, const mvr_ndt_params
   std::memcpy(T_out, T, sizeof T);
   if (X_out) std::memcpy(X_out, X, sizeof X);
   if (st) {
-    st->iterations = iters; st->stop = stop; st->converged = (stop == MVR_NDT_STEP || stop == MVR_NDT_ITERATIONS) ? 1 : 0; st->evaluations = evals;
-    st->n_cells = cells.n; st->n_pairs = cur[27]; st->score = cur[28]; st->ms = now_ms() - t0;
+    *st = run;
+    st->n_cells = cells.n; st->ms = now_ms() - t0;
   }
   return status;
 }

@@ -913,6 +913,8 @@ void ndt_matrix(const NdtPose &P, double X[16]);                                
 int ndt_build_cells(Ctx *c, const Cloud &tgt, const mvr_ndt_params *p, NdtCells *cells);
 int ndt_eval(Ctx *c, const Cloud &src, const NdtCells &cells, const NdtPose &P, double out[29]);      // two launches and one read-back
 int ndt_direction(const double sums[29], double delta[6]);                               // N7 (host_math.cpp)
+int ndt_newton(const mvr_ndt_params *p, mvr_ndt_eval_fn eval, void *user, double p_out[6], double sums_out[29], mvr_ndt_stats *st,
+               mvr_ndt_iter_trace *trace, int trace_cap);                                  // N7-N9 on a callback's sums (host_math.cpp)
 // ---- the search of one pair (mvr_ctx.hip), as the aligns of mvr_align.hip drive it
 // what a search leaves for pass 1.  qperm / tinv: the culled mode's orderings; slot / count: the brute-force mode's compacted
 // reverse queries (the culled mode searches the flagged targets in place: reverse keys are indexed by sorted target position)

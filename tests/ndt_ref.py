@@ -42,8 +42,10 @@ def lattice(tgt, resolution):
 def voxel_of(points, lat):
     """ijk (int64, may lie outside the lattice) of f64 or f32 points, by the f32 rule"""
     inv, min_b, _ = lat
-    f = np.floor(np.asarray(points).astype(np.float32) * inv) - min_b.astype(np.float32)
-    return f.astype(np.int64)
+    with np.errstate(over="ignore", invalid="ignore"):      # (a finite point far beyond the int64 range: some index outside)
+        f = np.floor(np.asarray(points).astype(np.float32) * inv) - min_b.astype(np.float32)
+        far = ~(np.abs(f) < 2.0 ** 62)
+        return np.where(far, -(2 ** 62), np.where(far, 0.0, f).astype(np.int64))
 
 
 def build_cells(tgt, prm):
@@ -211,12 +213,20 @@ def direction(s29):
 
 
 # ---- N7-N9
-def align(src, cells, prm, G=None):
-    """-> dict(stop, converged, iterations, evaluations, p, X, score, count, trace, margins); margins: for every decision of the
-    line search, |lhs - rhs| / |s(0)| (test_ndt_host.py asks that none is a near-tie)"""
+def align(src, cells, prm, G=None, evaluate=None):
+    """-> dict(stop, converged, iterations, evaluations, p, X, score, count, sums, trace, margins); margins: for every decision
+    of the line search, |lhs - rhs| / |s(0)| (test_ndt_host.py asks that none is a near-tie).  evaluate(p) -> the 29 sums, in
+    place of sums(src, cells, prm, p, G): the loop on a script (src and cells are then not looked at)"""
+    if evaluate is None:
+        evaluate = lambda q: sums(src, cells, prm, q, G)
+    with np.errstate(all="ignore"):          # (a scripted score may be 0, infinite or not a number: the margins are then, too)
+        return _newton(prm, G, evaluate)
+
+
+def _newton(prm, G, evaluate):
     eps, step = prm["transformation_epsilon"], prm["step_size"]
     p = np.zeros(6)
-    cur = sums(src, cells, prm, p, G)
+    cur = np.asarray(evaluate(p.copy()), np.float64)
     evals, iters, stop, trace, margins = 1, 0, "NOT", [], []
     if not cur[27] > 0.0:
         stop = "NO_OVERLAP"
@@ -237,7 +247,7 @@ def align(src, cells, prm, G=None):
         if stop == "NOT":
             a, taken, best = min(dn, step), None, None
             while rec["trials"] < prm["max_line_evals"]:
-                tr = sums(src, cells, prm, p + a * u, G)
+                tr = np.asarray(evaluate(p + a * u), np.float64)
                 evals += 1; rec["trials"] += 1
                 s0, sa = cur[28], tr[28]
                 margins.append(abs((-s0 + MU * a * dphi) - (-sa)) / abs(s0))
@@ -268,4 +278,4 @@ def align(src, cells, prm, G=None):
         rec.update(stop=stop, score=cur[28], count=cur[27], p=p.copy())
         trace.append(rec)
     return dict(stop=stop, converged=stop in ("STEP", "ITERATIONS"), iterations=iters, evaluations=evals, p=p,
-                X=pose_matrix(p, prm["origin"], G), score=cur[28], count=cur[27], trace=trace, margins=margins)
+                X=pose_matrix(p, prm["origin"], G), score=cur[28], count=cur[27], sums=cur, trace=trace, margins=margins)

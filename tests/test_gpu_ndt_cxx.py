@@ -46,20 +46,23 @@ def direct(mvr):
 
 
 @pytest.fixture(scope="module")
-def driven(built, direct, tmp_path_factory):
+def ndt_exe(built, tmp_path_factory):
     built.build_hip()
-    tmp = tmp_path_factory.mktemp("ndt_cxx")
-    exe = str(tmp / "ndt_driver")
+    exe = str(tmp_path_factory.mktemp("ndt_cxx_exe") / "ndt_driver")
     pkg = os.path.join(ROOT, PKG)
     r = subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cxx", "ndt_driver.cpp"),
                         "-o", exe, "-L" + pkg, "-lmvr_hip", "-Wl,-rpath," + pkg], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout
-    case, files = direct["case"], []
+    return exe
+
+
+def drive(exe, tmp, case, guess):
+    files = []
     for key in ("src", "tgt"):
         files.append(str(tmp / (key + ".f32")))
         np.ascontiguousarray(case[key], np.float32).tofile(files[-1])
     files.append(str(tmp / "guess.f32"))
-    np.ascontiguousarray(direct["guess"].T).reshape(16).tofile(files[-1])
+    np.ascontiguousarray(guess.T).reshape(16).tofile(files[-1])
     prm = case["prm"]
     env = dict(os.environ)
     env.pop("MVR_RCCL_LIB", None)
@@ -67,6 +70,11 @@ def driven(built, direct, tmp_path_factory):
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=env)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     return json.loads(r.stdout), r.stderr
+
+
+@pytest.fixture(scope="module")
+def driven(ndt_exe, direct, tmp_path_factory):
+    return drive(ndt_exe, tmp_path_factory.mktemp("ndt_cxx"), direct["case"], direct["guess"])
 
 
 def from_words(words):
@@ -119,3 +127,24 @@ def test_scan_cloud_align_ndt(driven, direct):
     prm = R.params(origin=tuple(0.5 * (t.min(0) + t.max(0))), **case["prm"])
     ref = R.align(case["src"], R.build_cells(case["tgt"], prm), prm)
     assert NC.residual(pose, case) <= 2 * NC.residual(ref["X"], case)
+
+
+def test_flat_stop_through_the_class(ndt_exe, mvr, tmp_path_factory):
+    """the one-cell case `flat-0` of tests/ndt_cases.py (the source's one point on the cell's mean: g = 0): the class reports
+    what Context.ndt_align reports -- not converged, 0 iterations, 1 evaluation, stop FLAT, the final transformation the
+    guess (here I) and `out` the source --, and so does ScanCloud::alignNDT, which turns about that same point"""
+    case = [c for c in NC.branch_cases() if c["name"] == "flat-0"][0]
+    flat = mvr.NDT_STOPS.index("FLAT")
+    prm = dict(case["prm"], origin=(0.0, 0.0, 0.0), min_points_per_voxel=6)          # what the class sets
+    with mvr.Context(0) as ctx:
+        ctx.upload(0, case["src"])
+        ctx.upload(1, case["tgt"])
+        T, X, st, rc = ctx.ndt_align(0, 1, -1, mvr.ndt_params(**prm))
+    assert rc == 0 and (st["stop"], st["converged"], st["iterations"], st["evaluations"]) == ("FLAT", False, 0, 1) and np.array_equal(X, np.eye(4))
+    out, _ = drive(ndt_exe, tmp_path_factory.mktemp("ndt_cxx_flat"), case, np.eye(4, dtype=np.float32))
+    assert out["api"] == [0, 0, 1, 1, flat] and out["guess_api"] == [0, 0, 1, 1, flat]
+    assert np.array_equal(from_words(out["T"]), np.eye(4)) and np.array_equal(from_words(out["guess_T"]), np.eye(4))
+    assert out["score"] == st["score"] and out["probability"] == st["score"]
+    assert np.array_equal(np.asarray(out["out"], np.uint32).view(np.float32), case["src"][0, [0, 2]])
+    assert out["none_api"] == [0, 0, mvr.NDT_STOPS.index("NO_OVERLAP")]
+    assert out["scan_ok"][1:] == [0, flat] and np.array_equal(np.asarray(out["scan_pose"]).reshape(4, 4), np.eye(4))
