@@ -47,12 +47,6 @@ struct ClusterArgs {
   double cos_eps;
 };
 
-__global__ void __launch_bounds__(kClThreads) cl_mark_kernel(const uint32_t *__restrict__ index, size_t count, uint8_t v, uint8_t *__restrict__ active)
-{
-  const size_t k = (size_t)blockIdx.x * kClThreads + threadIdx.x;
-  if (k < count) active[index[k]] = v;          // (repeats store the same byte)
-}
-
 __global__ void __launch_bounds__(kClThreads) cl_iota_kernel(uint32_t *__restrict__ v, size_t n)
 {
   const size_t i = (size_t)blockIdx.x * kClThreads + threadIdx.x;
@@ -234,8 +228,7 @@ int cluster_cloud(Ctx *c, Cloud *dst, Cloud &src, const mvr_cluster_params &p, c
     MVR_HIP_TRY(c, hipMemsetAsync(active, (!index || negative) ? 1 : 0, n, c->stream));
     if (index && index_count) {
       MVR_HIP_TRY(c, hipMemcpyAsync(d_in, index, index_count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-      hipLaunchKernelGGL(cl_mark_kernel, dim3(blocks_for(index_count, kClThreads)), block, 0, c->stream, d_in, index_count, (uint8_t)(negative ? 0 : 1), active);
-      MVR_HIP_TRY(c, hipGetLastError());
+      if (int rc = launch_mark(c, d_in, index_count, (uint8_t)(negative ? 0 : 1), active)) return rc;
     }
     // 2. links
     ClusterArgs a{};

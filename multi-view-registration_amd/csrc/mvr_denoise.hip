@@ -173,9 +173,23 @@ __global__ void gather_kernel(const float4 *__restrict__ in, const unsigned long
   if (index_out) index_out[k] = i;
 }
 
+__global__ void __launch_bounds__(256) mark_index_kernel(const uint32_t *__restrict__ index, size_t count, uint8_t value, uint8_t *__restrict__ flags)
+{
+  const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (k < count) flags[index[k]] = value;      // (a repeated index stores the same byte again)
+}
+
 }  // namespace
 
 // ---- the tail of a filter that keeps a subset (declared in mvr_internal.h)
+int launch_mark(Ctx *c, const uint32_t *d_index, size_t count, uint8_t value, uint8_t *flags)
+{
+  if (!count) return MVR_OK;
+  hipLaunchKernelGGL(mark_index_kernel, dim3(blocks_for(count, 256)), dim3(256), 0, c->stream, d_index, count, value, flags);
+  MVR_HIP_TRY(c, hipGetLastError());
+  return MVR_OK;
+}
+
 int select_flagged(Ctx *c, void *tmp, size_t &tmp_bytes, const uint8_t *flags, size_t n, unsigned long long *list, uint32_t *count)
 {
   size_t b = tmp_bytes;

@@ -447,7 +447,7 @@ int ensure(Ctx *c, T *&p, size_t &cap, size_t want)
   return MVR_OK;
 }
 
-// rule A2's draws (mvr_hip.h): mvr_align_prerejective (mvr_feature.hip) and mvr_cloud_segment_plane (mvr_sac.hip, rule P2)
+// rule A2's draws (mvr_hip.h): mvr_align_prerejective (mvr_feature.hip) and ransac_draw3 (mvr_ransac.h, rules P2 / C2)
 __host__ __device__ inline uint64_t prerej_mix(uint64_t z)
 {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -797,6 +797,8 @@ int cloud_reserve(Ctx *c, Cloud &cl, size_t cap, bool keep);
 int denoise_cloud(Ctx *c, Cloud &cl, int segment_threshold, double triangle_length, size_t *n_kept, size_t *n_components,
                   uint32_t *host_index);
 // ---- the tail of a filter that keeps a subset (mvr_denoise.hip), in the order its callers run it
+// mark_index_kernel: flags[d_index[k]] = value for k < count, a caller's index list (on the device) into a flag per point
+int launch_mark(Ctx *c, const uint32_t *d_index, size_t count, uint8_t value, uint8_t *flags);
 // flags -> list[] = the indices of the set flags, ascending, and *count (a device word) = how many: hipCUB's
 // DeviceSelect::Flagged.  tmp null: only tmp_bytes = the temporary storage a call over n flags needs
 int select_flagged(Ctx *c, void *tmp, size_t &tmp_bytes, const uint8_t *flags, size_t n, unsigned long long *list, uint32_t *count);

@@ -2,50 +2,33 @@
 // written next to mvr_reject_sample_consensus in mvr_hip.h.
 //
 // A stage of the rejector chain (mvr_reject.hip) that works on the same table -- match[i] = the live match of source point i or
-// -1 -- but needs the points, and a RANSAC loop whose length depends on what its attempts find.  The shape is mvr_sac.hip's: the
-// attempts do not depend on each other (C2: attempt t's samples are a pure function of the seed and t), so they are generated and
-// scored a CHUNK at a time and the host replays PCL's loop over the chunk's counts (C7).
+// -1 -- but needs the points, and a RANSAC loop whose length depends on what its attempts find.  The chunked RANSAC -- the
+// draws, the counting kernel, the host's replay of PCL's loop -- is mvr_ransac.h, shared with mvr_sac.hip; what this file adds:
 //   1. rsac_valid_kernel + select_flagged + rsac_gather_kernel, once per stage: the valid live pairs (C1) in ascending query
 //      index, gathered into a dense array of two 16-byte records per pair, (p_i, bits of i) and (q_j, bits of j).  The random
 //      gather of q_j is paid here once, not once per chunk.  nv and the number live come home in one read-back.
 //   2. per chunk: rsac_hypotheses_kernel, one thread per attempt -- the draws of C2 through the compacted pairs, the three pairs'
 //      coordinates and indices --; ONE read-back; the host solves the attempts (C3: the estimator of the ICP, host SVD) and
-//      uploads the chunk's matrices as one block, three float4 rows each, padded with NaN matrices to a multiple of
-//      kRsHypPerStep (a skipped attempt is a NaN matrix too: nobody's inlier); rsac_count_kernel, the hot path; ONE read-back
-//      of the counts.
-//      rsac_count_kernel scores every compacted pair against every attempt of the chunk in one pass: a thread keeps kRsPpt pairs
-//      in registers (six floats each; a tile of 1024 pairs per block).  The twelve floats of an attempt are the same for every
-//      lane and their address depends on the loop counter alone, so they are scalar loads into scalar registers, kRsHypPerStep
-//      attempts per step.  The inliers of a wave are counted by a ballot and a scalar population count per pair; lane
-//      (attempt mod 64) keeps the running count of that attempt in a register, one register per 64 attempts of the chunk (the
-//      template parameter G).  After a block's last tile the waves add their registers into LDS (one integer LDS atomic per wave
-//      and 64 attempts) and the block adds the non-zero sums to the global counts (one integer atomic per block and attempt).
-//      No floating-point atomics, no scratch memory.  The pairs that pad the last tile are NaN and fail the comparison.
+//      uploads the chunk's matrices as one block, padded with NaN matrices (a skipped attempt is a NaN matrix too: nobody's
+//      inlier); the counting kernel over RigidModel (an item is a compacted pair, six floats; a hypothesis the three float4
+//      rows of T, two per step); ONE read-back of the counts.
 //   3. rsac_flag_kernel: C9 / C10 for ONE T read from device memory, over the table itself (an invalid pair gives a non-finite
 //      d2 and fails): the table of the survivors, their number, and how many entries differ from the round before.  The refit
 //      of C10 is launch_moments2 over that table -- the sums the align entries take -- and the host SVD.
 //   4. the surviving table replaces match[], and the stage's W_OUT word is copied from the device counter: the stage record
 //      rides to the host with the others.
 // Everything runs on the context's stream; the work arrays come out of the context's arena (Ctx::dn_arena).
-#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "mvr_internal.h"
+#include "mvr_ransac.h"
 
 namespace mvr {
 namespace {
 
-constexpr int kRsThreads = 256, kRsPpt = 4, kRsTile = kRsThreads * kRsPpt;
-constexpr int kRsMaxChunk = 256;       // 64 attempts per register of rsac_count_kernel, at most 4 of them
-// "rej_sac_chunk" = 0: 64 attempts for a stage's first chunk, 256 from then on.  Measured (profiles/reject_sac_bench.json): a
-// chunk's cost is its two round trips, not its attempts, until the list has millions of pairs; an all-inlier list stops after
-// one attempt, which is what the short first chunk is for.
-constexpr int kRsFirstChunk = 64;
-constexpr int kRsHypPerStep = 2;       // matrices read per step of the counting kernel's attempt loop
-static_assert(kRsMaxChunk % kRsHypPerStep == 0 && 64 % kRsHypPerStep == 0, "the padded chunk fits the arrays and the registers");
-inline uint32_t rsac_padded(uint32_t count) { return (count + kRsHypPerStep - 1u) / kRsHypPerStep * kRsHypPerStep; }
+constexpr int kRsThreads = 256;      // the block of this file's own kernels
 
 // what the host reads back of an attempt: the three sampled pairs, in sample order
 struct RsacHyp { float p[9], q[9]; uint32_t query[3], match[3]; };
@@ -108,15 +91,8 @@ rsac_hypotheses_kernel(const float4 *__restrict__ pairs, uint32_t nv, uint64_t s
 {
   const uint32_t h = blockIdx.x * 64 + threadIdx.x;
   if (h >= count) return;
-  const uint64_t t = t0 + h;
-  const uint32_t r0 = prerej_draw(seed, t, 0, (uint64_t)nv);
-  uint32_t r1 = prerej_draw(seed, t, 1, (uint64_t)(nv - 1u));
-  if (r1 >= r0) ++r1;
-  const uint32_t lo = r0 < r1 ? r0 : r1, hi = r0 < r1 ? r1 : r0;
-  uint32_t r2 = prerej_draw(seed, t, 2, (uint64_t)(nv - 2u));
-  if (r2 >= lo) ++r2;
-  if (r2 >= hi) ++r2;
-  const uint32_t r[3] = {r0, r1, r2};
+  uint32_t r[3];
+  ransac_draw3(seed, t0 + h, nv, r);
   RsacHyp out;
 #pragma unroll
   for (int s = 0; s < 3; ++s) {
@@ -142,55 +118,26 @@ __device__ __forceinline__ float rsac_d2(const float4 r0, const float4 r1, const
   return (dx * dx + dy * dy) + dz * dz;
 }
 
-template <int G, bool FMA>
-__global__ void __launch_bounds__(kRsThreads) rsac_count_kernel(const float4 *__restrict__ pairs, uint32_t nv, const float4 *__restrict__ rows,
-                                                                uint32_t n_hyp, uint32_t n_pad, float bound, uint32_t *__restrict__ counts)
-{
-  __shared__ uint32_t s_cnt[G * 64];
-  const uint32_t tid = threadIdx.x, lane = tid & 63u;
-  for (uint32_t k = tid; k < (uint32_t)(G * 64); k += kRsThreads) s_cnt[k] = 0u;
-  uint32_t acc[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) acc[g] = 0u;
-  const uint32_t tiles = (nv + (uint32_t)kRsTile - 1u) / (uint32_t)kRsTile;
-  for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    // eight independent loads, none behind a branch: past the end the last pair is read and replaced by NaN (never an inlier)
-    float px[kRsPpt], py[kRsPpt], pz[kRsPpt], qx[kRsPpt], qy[kRsPpt], qz[kRsPpt];
-#pragma unroll
-    for (int j = 0; j < kRsPpt; ++j) {
-      const uint32_t k = tile * (uint32_t)kRsTile + (uint32_t)j * kRsThreads + tid;
-      const size_t kk = k < nv ? k : nv - 1u;
-      const float4 p = pairs[2 * kk], q = pairs[2 * kk + 1];
-      px[j] = k < nv ? p.x : NAN; py[j] = p.y; pz[j] = p.z; qx[j] = q.x; qy[j] = q.y; qz[j] = q.z;
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const uint32_t h0 = (uint32_t)g * 64u, hn = n_pad > h0 ? (n_pad - h0 < 64u ? n_pad - h0 : 64u) : 0u;
-      for (uint32_t hh = 0; hh < hn; hh += kRsHypPerStep) {
-        float4 r[kRsHypPerStep][3];      // the same addresses in every lane: scalar loads, all issued before the first is used
-#pragma unroll
-        for (int u = 0; u < kRsHypPerStep; ++u)
-#pragma unroll
-          for (int e = 0; e < 3; ++e) r[u][e] = rows[(size_t)(h0 + hh + (uint32_t)u) * 3u + (uint32_t)e];
-#pragma unroll
-        for (int u = 0; u < kRsHypPerStep; ++u) {
-          uint32_t cnt = 0u;
-#pragma unroll
-          for (int j = 0; j < kRsPpt; ++j)
-            cnt += (uint32_t)__popcll(__ballot(rsac_d2<FMA>(r[u][0], r[u][1], r[u][2], px[j], py[j], pz[j], qx[j], qy[j], qz[j]) < bound));
-          acc[g] += lane == hh + (uint32_t)u ? cnt : 0u;
-        }
-      }
-    }
+// the rigid motion to the counting kernel of mvr_ransac.h
+struct RigidModel {
+  static constexpr int kHypPerStep = 2, kBlocksPerCu = 4;
+  struct Item { float px, py, pz, qx, qy, qz; };
+  struct Hyp { float4 r0, r1, r2; };
+  static __device__ __forceinline__ Item item(const float4 *__restrict__ pairs, uint32_t k, bool pad)
+  {
+    const float4 p = pairs[2 * (size_t)k], q = pairs[2 * (size_t)k + 1];
+    return {pad ? NAN : p.x, p.y, p.z, q.x, q.y, q.z};
   }
-  __syncthreads();
-#pragma unroll
-  for (int g = 0; g < G; ++g)
-    if (acc[g]) atomicAdd(&s_cnt[g * 64 + (int)lane], acc[g]);
-  __syncthreads();
-  for (uint32_t k = tid; k < n_hyp; k += kRsThreads)
-    if (s_cnt[k]) atomicAdd(&counts[k], s_cnt[k]);
-}
+  static __device__ __forceinline__ Hyp hyp(const float4 *__restrict__ rows, uint32_t h)
+  {
+    return {rows[(size_t)h * 3u], rows[(size_t)h * 3u + 1u], rows[(size_t)h * 3u + 2u]};
+  }
+  template <bool FMA>
+  static __device__ __forceinline__ bool inlier(const Hyp T, const Item m, float bound)
+  {
+    return rsac_d2<FMA>(T.r0, T.r1, T.r2, m.px, m.py, m.pz, m.qx, m.qy, m.qz) < bound;
+  }
+};
 
 // C9 / C10 for the T at `rows`: m_out = the table of its inliers; cnt[0] += their number, cnt[1] += the entries that differ from m_prev
 template <bool FMA>
@@ -207,7 +154,7 @@ rsac_flag_kernel(const float4 *__restrict__ src, const float4 *__restrict__ tgt,
     int32_t o = -1;
     if (j >= 0) {
       const float4 p = src[i], q = tgt[j];
-      if (rsac_d2<FMA>(r0, r1, r2, p.x, p.y, p.z, q.x, q.y, q.z) < bound) { o = j; ++kept; }
+      if (RigidModel::inlier<FMA>({r0, r1, r2}, {p.x, p.y, p.z, q.x, q.y, q.z}, bound)) { o = j; ++kept; }
     }
     m_out[i] = o;
     if (m_prev && m_prev[i] != o) ++diff;
@@ -217,26 +164,6 @@ rsac_flag_kernel(const float4 *__restrict__ src, const float4 *__restrict__ tgt,
 
 inline unsigned stride_blocks(size_t n) { return (unsigned)std::min<size_t>(std::max<size_t>((n + kRsThreads - 1) / kRsThreads, 1), 1024); }
 
-template <int G>
-void launch_count_g(Ctx *c, bool fma, unsigned blocks, const float4 *pairs, uint32_t nv, const float4 *rows, uint32_t n_hyp, uint32_t n_pad,
-                    float bound, uint32_t *counts)
-{
-  if (fma) hipLaunchKernelGGL((rsac_count_kernel<G, true>), dim3(blocks), dim3(kRsThreads), 0, c->stream, pairs, nv, rows, n_hyp, n_pad, bound, counts);
-  else hipLaunchKernelGGL((rsac_count_kernel<G, false>), dim3(blocks), dim3(kRsThreads), 0, c->stream, pairs, nv, rows, n_hyp, n_pad, bound, counts);
-}
-
-int launch_count(Ctx *c, bool fma, const float4 *pairs, uint32_t nv, const float4 *rows, uint32_t n_hyp, float bound, uint32_t *counts)
-{
-  const size_t tiles = ((size_t)nv + kRsTile - 1) / kRsTile;
-  const unsigned blocks = (unsigned)std::min<size_t>(tiles, (size_t)std::max(c->n_cu, 1) * 4);
-  const uint32_t n_pad = rsac_padded(n_hyp);
-  if (n_hyp <= 64u) launch_count_g<1>(c, fma, blocks, pairs, nv, rows, n_hyp, n_pad, bound, counts);
-  else if (n_hyp <= 128u) launch_count_g<2>(c, fma, blocks, pairs, nv, rows, n_hyp, n_pad, bound, counts);
-  else launch_count_g<4>(c, fma, blocks, pairs, nv, rows, n_hyp, n_pad, bound, counts);
-  MVR_HIP_TRY(c, hipGetLastError());
-  return MVR_OK;
-}
-
 int launch_flags(Ctx *c, bool fma, const float4 *src, const float4 *tgt, const int32_t *match, size_t ns, const float4 *rows, float bound,
                  int32_t *m_out, const int32_t *m_prev, uint32_t *cnt)
 {
@@ -245,14 +172,6 @@ int launch_flags(Ctx *c, bool fma, const float4 *src, const float4 *tgt, const i
   else hipLaunchKernelGGL(rsac_flag_kernel<false>, dim3(stride_blocks(ns)), dim3(kRsThreads), 0, c->stream, src, tgt, match, ns, rows, bound, m_out, m_prev, cnt);
   MVR_HIP_TRY(c, hipGetLastError());
   return MVR_OK;
-}
-
-// the smallest f32 that is >= t: for an f32 v, (double)v < t  <=>  v < that
-float f32_at_least(double t)
-{
-  float f = (float)t;
-  if ((double)f < t) f = std::nextafterf(f, INFINITY);
-  return f;
 }
 
 // C3: rule A5's estimator on the three pairs in sample order
@@ -305,10 +224,10 @@ int reject_sac_stage(Ctx *c, const mvr_rejector &r, bool fma, const float4 *src,
 
   size_t sel_bytes = 0;
   if (int rc = select_flagged(c, nullptr, sel_bytes, nullptr, ns, nullptr, nullptr)) return rc;
-  constexpr size_t kRowsPerChunk = (size_t)kRsMaxChunk * 3;
+  constexpr size_t kRowsPerChunk = (size_t)kRansacMaxChunk * 3;
   Carver plan;
   plan.plan<uint8_t>(ns); plan.plan<unsigned long long>(ns); plan.plan<float4>(2 * ns); plan.plan<int32_t>(ns); plan.plan<int32_t>(ns);
-  plan.plan<char>(kRsMaxChunk * (sizeof(RsacHyp) + sizeof(uint32_t))); plan.plan<float4>(kRowsPerChunk); plan.plan<uint32_t>(C_WORDS);
+  plan.plan<char>(RansacChunk<RsacHyp>::kBytes); plan.plan<float4>(kRowsPerChunk); plan.plan<uint32_t>(C_WORDS);
   plan.plan<float4>(3); plan.plan<double>(32); plan.plan<char>(sel_bytes);
   if (int rc = ensure(c, c->dn_arena, c->dn_arena_cap, plan.off + 256)) return rc;
   Carver s; s.base = c->dn_arena;
@@ -317,9 +236,7 @@ int reject_sac_stage(Ctx *c, const mvr_rejector &r, bool fma, const float4 *src,
   float4 *pairs = s.take<float4>(2 * ns);
   int32_t *m_tab[2] = {s.take<int32_t>(ns), nullptr};
   m_tab[1] = s.take<int32_t>(ns);
-  char *chunk_dev = s.take<char>(kRsMaxChunk * (sizeof(RsacHyp) + sizeof(uint32_t)));      // the records, then the counts
-  RsacHyp *d_hyp = reinterpret_cast<RsacHyp *>(chunk_dev);
-  uint32_t *d_counts = reinterpret_cast<uint32_t *>(chunk_dev + kRsMaxChunk * sizeof(RsacHyp));
+  const RansacChunk<RsacHyp> dev(s.take<char>(RansacChunk<RsacHyp>::kBytes));
   float4 *d_rows = s.take<float4>(kRowsPerChunk);
   uint32_t *words = s.take<uint32_t>(C_WORDS);
   float4 *d_T = s.take<float4>(3);
@@ -341,80 +258,57 @@ int reject_sac_stage(Ctx *c, const mvr_rejector &r, bool fma, const float4 *src,
   R.live = hw[C_LIVE]; R.valid = nv;
 
   // C7 over the chunks
-  long long best_count = -1, best = -1;
+  RansacLoop loop(max_it, std::log(1.0 - 0.99), nv, c->rej_sac_chunk);
   float best_T[16];
   RsacHyp best_hyp;
   std::memset(best_T, 0, sizeof best_T);
   std::memset(&best_hyp, 0, sizeof best_hyp);
   if (nv >= 3u) {
-    std::vector<char> host(kRsMaxChunk * (sizeof(RsacHyp) + sizeof(uint32_t)));
-    const RsacHyp *h_hyp = reinterpret_cast<const RsacHyp *>(host.data());
-    const uint32_t *h_counts = reinterpret_cast<const uint32_t *>(host.data() + kRsMaxChunk * sizeof(RsacHyp));
-    std::vector<float> h_T((size_t)kRsMaxChunk * 16);
-    std::vector<int> h_status(kRsMaxChunk);
+    std::vector<char> host_mem(RansacChunk<RsacHyp>::kBytes);
+    const RansacChunk<RsacHyp> host(host_mem.data());
+    std::vector<float> h_T((size_t)kRansacMaxChunk * 16);
+    std::vector<int> h_status(kRansacMaxChunk);
     std::vector<float4> h_rows(kRowsPerChunk);
-    const long long max_skip = 10ll * max_it;
-    const double log_p = std::log(1.0 - 0.99);
-    long long iterations = 0, skipped = 0, attempt = 0;
-    double k = 1.0;
-    bool stop = false, first = true;
-    while (!stop && (double)iterations < k && skipped < max_skip) {
-      // no chunk is longer than what the loop can still consume
-      const long long room = (max_it + 1 - iterations) + (max_skip - skipped);
-      const long long want = c->rej_sac_chunk > 0 ? c->rej_sac_chunk : (first ? kRsFirstChunk : kRsMaxChunk);
-      const uint32_t count = (uint32_t)std::min<long long>(want, room), n_pad = rsac_padded(count);
-      first = false;
+    while (loop.more()) {
+      const uint32_t count = loop.next_chunk(), n_pad = ransac_padded<RigidModel>(count);
       hipLaunchKernelGGL(rsac_hypotheses_kernel, dim3(blocks_for(count, 64)), dim3(64), 0, c->stream, (const float4 *)pairs, nv, (uint64_t)r.seed,
-                         (uint64_t)attempt, count, d_hyp, d_counts);
+                         (uint64_t)loop.attempt, count, dev.rec, dev.counts);
       MVR_HIP_TRY(c, hipGetLastError());
-      MVR_HIP_TRY(c, hipMemcpyAsync(host.data(), d_hyp, (size_t)count * sizeof(RsacHyp), hipMemcpyDeviceToHost, c->stream));
+      MVR_HIP_TRY(c, hipMemcpyAsync(host.rec, dev.rec, (size_t)count * sizeof(RsacHyp), hipMemcpyDeviceToHost, c->stream));
       MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
       for (uint32_t h = 0; h < n_pad; ++h) {      // C3
         float *T = &h_T[(size_t)h * 16];
         bool ok = false;
-        if (h < count) { pose_from_samples(h_hyp[h], T); ok = finite16(T); h_status[h] = ok ? 1 : 0; }
+        if (h < count) { pose_from_samples(host.rec[h], T); ok = finite16(T); h_status[h] = ok ? 1 : 0; }
         if (ok) rows_of(T, &h_rows[(size_t)h * 3]);
         else for (int e = 0; e < 3; ++e) h_rows[(size_t)h * 3 + e] = make_float4(NAN, NAN, NAN, NAN);
       }
       MVR_HIP_TRY(c, hipMemcpyAsync(d_rows, h_rows.data(), (size_t)n_pad * 3 * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-      if (int rc = launch_count(c, fma, pairs, nv, d_rows, count, bound, d_counts)) return rc;
-      MVR_HIP_TRY(c, hipMemcpyAsync(host.data() + kRsMaxChunk * sizeof(RsacHyp), d_counts, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+      if (int rc = ransac_launch_count<RigidModel>(c, fma, pairs, nv, d_rows, count, bound, dev.counts)) return rc;
+      MVR_HIP_TRY(c, hipMemcpyAsync(host.counts, dev.counts, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
       MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
-      for (uint32_t h = 0; h < count && (double)iterations < k && skipped < max_skip; ++h, ++attempt) {
-        const RsacHyp &H = h_hyp[h];
-        const int status = h_status[h];
-        const uint32_t cnt = status == 1 ? h_counts[h] : 0u;
-        if (status == 0) ++skipped;
-        else {
-          if ((long long)cnt > best_count) {
-            best_count = cnt; best = attempt; best_hyp = H;
-            std::memcpy(best_T, &h_T[(size_t)h * 16], sizeof best_T);
-            const double w = (double)best_count / (double)nv;
-            const double pno = std::min(std::max(1.0 - w * w * w, DBL_EPSILON), 1.0 - DBL_EPSILON);
-            k = log_p / std::log(pno);
-          }
-          ++iterations;
-          if (iterations > max_it) stop = true;
-        }
-        if (trace && (size_t)attempt < trace_cap) {
-          mvr_rej_sac_trace &Tr = trace[attempt];
-          std::memset(&Tr, 0, sizeof Tr);
-          Tr.status = status;
-          for (int j = 0; j < 3; ++j) { Tr.query[j] = H.query[j]; Tr.match[j] = H.match[j]; }
-          if (status == 1) { std::memcpy(Tr.T, &h_T[(size_t)h * 16], sizeof Tr.T); Tr.inliers = cnt; }
-          Tr.k = k;
-        }
-        if (stop) { ++attempt; break; }
-      }
+      loop.replay(
+          count, [&](uint32_t h) { return h_status[h]; }, [&](uint32_t h) { return host.counts[h]; },
+          [&](uint32_t h) { best_hyp = host.rec[h]; std::memcpy(best_T, &h_T[(size_t)h * 16], sizeof best_T); },
+          [&](uint32_t h, long long attempt, int status, uint32_t cnt, double k) {
+            if (!trace || (size_t)attempt >= trace_cap) return;
+            const RsacHyp &H = host.rec[h];
+            mvr_rej_sac_trace &Tr = trace[attempt];
+            std::memset(&Tr, 0, sizeof Tr);
+            Tr.status = status;
+            for (int j = 0; j < 3; ++j) { Tr.query[j] = H.query[j]; Tr.match[j] = H.match[j]; }
+            if (status == 1) { std::memcpy(Tr.T, &h_T[(size_t)h * 16], sizeof Tr.T); Tr.inliers = cnt; }
+            Tr.k = k;
+          });
     }
-    R.iterations = (int)iterations; R.skipped = (int)skipped; R.attempts = (int)attempt; R.k = k;
   }
-  R.found = best_count >= 3 ? 1 : 0;      // C8
+  R.iterations = (int)loop.iterations; R.skipped = (int)loop.skipped; R.attempts = (int)loop.attempt; R.k = loop.k;
+  R.found = loop.best_count >= 3 ? 1 : 0;      // C8
   if (!R.found) {
     R.inliers = R.live;
     MVR_HIP_TRY(c, hipMemcpyAsync(stage, words + C_LIVE, sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
   } else {
-    R.best_attempt = (int)best;
+    R.best_attempt = (int)loop.best;
     std::memcpy(R.ransac_T, best_T, sizeof best_T);
     std::memcpy(R.T, best_T, sizeof best_T);
     // C9
@@ -426,7 +320,7 @@ int reject_sac_stage(Ctx *c, const mvr_rejector &r, bool fma, const float4 *src,
     if (int rc = launch_flags(c, fma, src, tgt, match, ns, d_T, bound, m_tab[cur], nullptr, words + C_CNT_A)) return rc;
     MVR_HIP_TRY(c, hipMemcpyAsync(hc, words + C_CNT_A, sizeof hc, hipMemcpyDeviceToHost, c->stream));
     MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if ((long long)hc[0] != best_count) return set_error(c, MVR_E_HIP, "sample-consensus rejector: the best attempt's count and its inliers disagree");
+    if ((long long)hc[0] != loop.best_count) return set_error(c, MVR_E_HIP, "sample-consensus rejector: the best attempt's count and its inliers disagree");
     R.ransac_inliers = R.inliers = hc[0];
     if (r.refine) {      // C10
       const double origin[3] = {(double)best_hyp.q[0], (double)best_hyp.q[1], (double)best_hyp.q[2]};

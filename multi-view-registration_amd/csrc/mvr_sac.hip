@@ -1,28 +1,16 @@
 // csrc/mvr_sac.hip -- pcl::SACSegmentation (SACMODEL_PLANE / SACMODEL_PERPENDICULAR_PLANE, SAC_RANSAC) and pcl::ExtractIndices
 // on the GPU (gfx950); the rules P1-P12 are written next to mvr_cloud_segment_plane in mvr_hip.h.
 //
-// RANSAC is a sequential loop over attempts whose length depends on what the attempts find.  The attempts themselves do not
-// depend on each other (rule P2: attempt t's samples are a pure function of the seed and t), so they are generated and scored
-// a CHUNK at a time and the host replays PCL's loop over the chunk's counts (P7); what lies beyond the stopping point is dropped.
+// The chunked RANSAC -- the draws, the counting kernel, the host's replay of PCL's loop -- is mvr_ransac.h; what this file adds:
 //   1. sac_valid_kernel + select_flagged: the valid points' indices, ascending, and their number (one read-back per call).
 //   2. per chunk: sac_hypotheses_kernel, one thread per attempt -- draws, the three points through the list of valid indices,
-//      the plane of P3 and the test of P4 --, then sac_count_kernel, the hot path, then ONE read-back of the chunk's records
-//      and counts.
-//      sac_count_kernel scores every point against every attempt of the chunk in one pass over the cloud: a thread keeps
-//      kSacPpt points in registers (a tile of 1024 per block; x, y, z of the 16-byte records, four loads in flight); the plane of an
-//      attempt is the same for every lane, and its address depends on the loop counter alone, so it is read by a scalar load
-//      into scalar registers, never per lane, four planes per step of the loop (a chunk's planes are padded with NaN planes to
-//      a multiple of four; attempts that are skipped or invalid are NaN planes too, so their device counts are 0).  The inliers of a wave are counted by a ballot and a scalar population count per point, so the count of
-//      (wave, attempt) is a scalar; lane (attempt mod 64) of the wave keeps the running count of that attempt in a register,
-//      one register per 64 attempts of the chunk (the template parameter G).  After a block's last tile the waves add their
-//      registers into LDS (one integer LDS atomic per wave and 64 attempts) and the block adds the non-zero sums to the global
-//      counts (one integer atomic per block and attempt).  No floating-point atomics, no scratch memory.  An invalid point has
-//      a non-finite distance and fails the comparison by itself, and so do the NaN points that pad the last tile.
+//      the plane of P3 and the test of P4 --, then the counting kernel over PlaneModel (an item is a point's x, y, z of its
+//      16-byte record, a hypothesis one float4 plane, four per step; an invalid point has a non-finite distance), then ONE
+//      read-back of the chunk's records and counts.
 //   3. sac_flag_kernel: P5 for one plane, read from device memory (the refined plane never visits the host in between);
 //      sac_moments_kernel + sac_fit_kernel: the fixed-order f64 sums of P10 and the Jacobi fit of mvr_plane.h.
 //   4. the tail of every filter that keeps a subset: select_flagged, gather_kept, finish_dst (mvr_denoise.hip).
 // Everything runs on the context's stream; the work arrays come out of the context's arena (Ctx::dn_arena).
-#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -30,18 +18,39 @@
 #include "mvr_internal.h"
 #include "mvr_knn_walk.h"
 #include "mvr_plane.h"
+#include "mvr_ransac.h"
 
 namespace mvr {
 namespace {
 
-constexpr int kSacThreads = 256, kSacPpt = 4, kSacTile = kSacThreads * kSacPpt;
-constexpr int kSacMaxChunk = 256;      // 64 attempts per register of sac_count_kernel, at most 4 of them
-constexpr int kSacFirstChunk = 64;     // "sac_chunk" = 0: the first chunk of a call; kSacMaxChunk from then on
+// P5
+template <bool FMA>
+__device__ __forceinline__ float sac_distance(const float ca, const float cb, const float cc, const float cd, const float x, const float y,
+                                              const float z)
+{
+  float t = ca * x;
+  if (FMA) { t = fmaf(cb, y, t); t = fmaf(cc, z, t); }
+  else { t = t + cb * y; t = t + cc * z; }
+  return t + cd;
+}
 
-// the counting kernel reads this many planes per step of its attempt loop; a chunk's planes are padded to a multiple of it
-constexpr int kSacPlanesPerStep = 4;
-static_assert(kSacMaxChunk % kSacPlanesPerStep == 0 && 64 % kSacPlanesPerStep == 0, "the padded chunk fits the arrays and the registers");
-__host__ __device__ inline uint32_t sac_padded(uint32_t count) { return (count + kSacPlanesPerStep - 1u) / kSacPlanesPerStep * kSacPlanesPerStep; }
+// the plane to the counting kernel of mvr_ransac.h
+struct PlaneModel {
+  static constexpr int kHypPerStep = 4, kBlocksPerCu = 8;
+  struct Item { float x, y, z; };
+  using Hyp = float4;
+  static __device__ __forceinline__ Item item(const float4 *__restrict__ pts, uint32_t i, bool pad)
+  {
+    const float4 p = pts[i];
+    return {pad ? NAN : p.x, p.y, p.z};
+  }
+  static __device__ __forceinline__ Hyp hyp(const float4 *__restrict__ coef, uint32_t h) { return coef[h]; }
+  template <bool FMA>
+  static __device__ __forceinline__ bool inlier(const Hyp c, const Item p, float bound)
+  {
+    return fabsf(sac_distance<FMA>(c.x, c.y, c.z, c.w, p.x, p.y, p.z)) < bound;
+  }
+};
 
 // what the host reads back of an attempt
 struct SacHyp { float coef[4]; uint32_t sample[3]; int status; };
@@ -63,21 +72,14 @@ struct HypArgs {
 __global__ void __launch_bounds__(64) sac_hypotheses_kernel(HypArgs a)
 {
   const uint32_t h = blockIdx.x * 64 + threadIdx.x;
-  if (h >= a.count) {      // the planes that pad the chunk to a multiple of kSacPlanesPerStep: nobody's inlier
-    if (h < sac_padded(a.count)) a.coef[h] = make_float4(NAN, NAN, NAN, NAN);
+  if (h >= a.count) {      // the planes that pad the chunk to a multiple of PlaneModel::kHypPerStep: nobody's inlier
+    if (h < ransac_padded<PlaneModel>(a.count)) a.coef[h] = make_float4(NAN, NAN, NAN, NAN);
     return;
   }
-  const uint64_t t = a.t0 + h;
-  // P2
-  const uint32_t r0 = prerej_draw(a.seed, t, 0, (uint64_t)a.nv);
-  uint32_t r1 = prerej_draw(a.seed, t, 1, (uint64_t)(a.nv - 1u));
-  if (r1 >= r0) ++r1;
-  const uint32_t lo = r0 < r1 ? r0 : r1, hi = r0 < r1 ? r1 : r0;
-  uint32_t r2 = prerej_draw(a.seed, t, 2, (uint64_t)(a.nv - 2u));
-  if (r2 >= lo) ++r2;
-  if (r2 >= hi) ++r2;
+  uint32_t r[3];
+  ransac_draw3(a.seed, a.t0 + h, a.nv, r);      // P2
   SacHyp out;
-  out.sample[0] = (uint32_t)a.vlist[r0]; out.sample[1] = (uint32_t)a.vlist[r1]; out.sample[2] = (uint32_t)a.vlist[r2];
+  out.sample[0] = (uint32_t)a.vlist[r[0]]; out.sample[1] = (uint32_t)a.vlist[r[1]]; out.sample[2] = (uint32_t)a.vlist[r[2]];
   const float4 p0 = a.pts[out.sample[0]], p1 = a.pts[out.sample[1]], p2 = a.pts[out.sample[2]];
   // P3
   const float e1x = p1.x - p0.x, e1y = p1.y - p0.y, e1z = p1.z - p0.z, e2x = p2.x - p0.x, e2y = p2.y - p0.y, e2z = p2.z - p0.z;
@@ -99,64 +101,6 @@ __global__ void __launch_bounds__(64) sac_hypotheses_kernel(HypArgs a)
   a.counts[h] = 0u;
 }
 
-// P5
-template <bool FMA>
-__device__ __forceinline__ float sac_distance(const float ca, const float cb, const float cc, const float cd, const float x, const float y,
-                                              const float z)
-{
-  float t = ca * x;
-  if (FMA) { t = fmaf(cb, y, t); t = fmaf(cc, z, t); }
-  else { t = t + cb * y; t = t + cc * z; }
-  return t + cd;
-}
-
-template <int G, bool FMA>
-__global__ void __launch_bounds__(kSacThreads) sac_count_kernel(const float4 *__restrict__ pts, uint32_t n, const float4 *__restrict__ coef,
-                                                                uint32_t n_hyp, float bound, uint32_t *__restrict__ counts)
-{
-  __shared__ uint32_t s_cnt[G * 64];
-  const uint32_t tid = threadIdx.x, lane = tid & 63u;
-  for (uint32_t k = tid; k < (uint32_t)(G * 64); k += kSacThreads) s_cnt[k] = 0u;
-  uint32_t acc[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) acc[g] = 0u;
-  const uint32_t tiles = (n + (uint32_t)kSacTile - 1u) / (uint32_t)kSacTile, n_pad = sac_padded(n_hyp);
-  for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    // four independent loads, none behind a branch: past the end the last point is read and replaced by NaN (never an inlier)
-    float x[kSacPpt], y[kSacPpt], z[kSacPpt];
-#pragma unroll
-    for (int j = 0; j < kSacPpt; ++j) {
-      const uint32_t i = tile * (uint32_t)kSacTile + (uint32_t)j * kSacThreads + tid;
-      const float4 p = pts[i < n ? i : n - 1u];
-      x[j] = i < n ? p.x : NAN; y[j] = p.y; z[j] = p.z;
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const uint32_t h0 = (uint32_t)g * 64u, hn = n_pad > h0 ? (n_pad - h0 < 64u ? n_pad - h0 : 64u) : 0u;
-      for (uint32_t hh = 0; hh < hn; hh += kSacPlanesPerStep) {
-        float4 c[kSacPlanesPerStep];      // the same addresses in every lane: scalar loads, all issued before the first is used
-#pragma unroll
-        for (int u = 0; u < kSacPlanesPerStep; ++u) c[u] = coef[h0 + hh + (uint32_t)u];
-#pragma unroll
-        for (int u = 0; u < kSacPlanesPerStep; ++u) {
-          uint32_t cnt = 0u;
-#pragma unroll
-          for (int j = 0; j < kSacPpt; ++j)
-            cnt += (uint32_t)__popcll(__ballot(fabsf(sac_distance<FMA>(c[u].x, c[u].y, c[u].z, c[u].w, x[j], y[j], z[j])) < bound));
-          acc[g] += lane == hh + (uint32_t)u ? cnt : 0u;
-        }
-      }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int g = 0; g < G; ++g)
-    if (acc[g]) atomicAdd(&s_cnt[g * 64 + (int)lane], acc[g]);
-  __syncthreads();
-  for (uint32_t k = tid; k < n_hyp; k += kSacThreads)
-    if (s_cnt[k]) atomicAdd(&counts[k], s_cnt[k]);
-}
-
 template <bool FMA>
 __global__ void sac_flag_kernel(const float4 *__restrict__ pts, size_t n, const float4 *__restrict__ coef, float bound, uint8_t *__restrict__ flag,
                                 uint8_t *__restrict__ nflag)
@@ -164,7 +108,7 @@ __global__ void sac_flag_kernel(const float4 *__restrict__ pts, size_t n, const 
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float4 c = *coef, p = pts[i];
-  const bool in = fabsf(sac_distance<FMA>(c.x, c.y, c.z, c.w, p.x, p.y, p.z)) < bound;
+  const bool in = PlaneModel::inlier<FMA>(c, {p.x, p.y, p.z}, bound);
   flag[i] = in ? 1 : 0;
   nflag[i] = in ? 0 : 1;
 }
@@ -249,44 +193,12 @@ __global__ void sac_low_words_kernel(const unsigned long long *__restrict__ list
   if (k < n) out[k] = (uint32_t)list[k];
 }
 
-__global__ void sac_mark_kernel(const uint32_t *__restrict__ index, size_t count, uint8_t value, uint8_t *__restrict__ flag)
-{
-  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < count) flag[index[k]] = value;      // (a repeated index stores the same byte again)
-}
-
-template <int G>
-void launch_count_g(Ctx *c, bool fma, unsigned blocks, const float4 *pts, uint32_t n, const float4 *coef, uint32_t n_hyp, float bound, uint32_t *counts)
-{
-  if (fma) hipLaunchKernelGGL((sac_count_kernel<G, true>), dim3(blocks), dim3(kSacThreads), 0, c->stream, pts, n, coef, n_hyp, bound, counts);
-  else hipLaunchKernelGGL((sac_count_kernel<G, false>), dim3(blocks), dim3(kSacThreads), 0, c->stream, pts, n, coef, n_hyp, bound, counts);
-}
-
-int launch_count(Ctx *c, bool fma, const float4 *pts, size_t n, const float4 *coef, uint32_t n_hyp, float bound, uint32_t *counts)
-{
-  const size_t tiles = (n + kSacTile - 1) / kSacTile;
-  const unsigned blocks = (unsigned)std::min<size_t>(tiles, (size_t)std::max(c->n_cu, 1) * 8);
-  if (n_hyp <= 64u) launch_count_g<1>(c, fma, blocks, pts, (uint32_t)n, coef, n_hyp, bound, counts);
-  else if (n_hyp <= 128u) launch_count_g<2>(c, fma, blocks, pts, (uint32_t)n, coef, n_hyp, bound, counts);
-  else launch_count_g<4>(c, fma, blocks, pts, (uint32_t)n, coef, n_hyp, bound, counts);
-  MVR_HIP_TRY(c, hipGetLastError());
-  return MVR_OK;
-}
-
 int launch_flags(Ctx *c, bool fma, const float4 *pts, size_t n, const float4 *coef, float bound, uint8_t *flag, uint8_t *nflag)
 {
   if (fma) hipLaunchKernelGGL(sac_flag_kernel<true>, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, pts, n, coef, bound, flag, nflag);
   else hipLaunchKernelGGL(sac_flag_kernel<false>, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, pts, n, coef, bound, flag, nflag);
   MVR_HIP_TRY(c, hipGetLastError());
   return MVR_OK;
-}
-
-// the smallest f32 that is >= t: for an f32 v, (double)v < t  <=>  v < that
-float f32_at_least(double t)
-{
-  float f = (float)t;
-  if ((double)f < t) f = std::nextafterf(f, INFINITY);
-  return f;
 }
 
 // the arrays of the tail, carved after whatever the caller took
@@ -322,7 +234,7 @@ int segment_cloud(Ctx *c, Cloud *dst, Cloud &src, const mvr_sac_params &p, mvr_s
     const size_t blocks = (n + 255) / 256;
     Carver plan;
     plan.plan<uint8_t>(n); plan.plan<unsigned long long>(n); plan.plan<uint8_t>(n); plan.plan<uint8_t>(n);
-    plan.plan<char>(kSacMaxChunk * (sizeof(SacHyp) + sizeof(uint32_t))); plan.plan<float4>(kSacMaxChunk); plan.plan<double>(blocks * kSacMoments);
+    plan.plan<char>(RansacChunk<SacHyp>::kBytes); plan.plan<float4>(kRansacMaxChunk); plan.plan<double>(blocks * kSacMoments);
     plan.plan<SacFit>(1);
     plan_tail(plan, n, sel_bytes);
     if (int rc = ensure(c, c->dn_arena, c->dn_arena_cap, plan.off + 256)) return rc;
@@ -330,10 +242,9 @@ int segment_cloud(Ctx *c, Cloud *dst, Cloud &src, const mvr_sac_params &p, mvr_s
     uint8_t *valid = s.take<uint8_t>(n);
     unsigned long long *vlist = s.take<unsigned long long>(n);
     uint8_t *flag = s.take<uint8_t>(n), *nflag = s.take<uint8_t>(n);
-    char *chunk_dev = s.take<char>(kSacMaxChunk * (sizeof(SacHyp) + sizeof(uint32_t)));      // the records, then the counts: one copy
-    SacHyp *d_hyp = reinterpret_cast<SacHyp *>(chunk_dev);
-    uint32_t *d_counts = reinterpret_cast<uint32_t *>(chunk_dev + kSacMaxChunk * sizeof(SacHyp));
-    float4 *d_coef = s.take<float4>(kSacMaxChunk);
+    char *chunk_dev = s.take<char>(RansacChunk<SacHyp>::kBytes);
+    const RansacChunk<SacHyp> dev(chunk_dev);
+    float4 *d_coef = s.take<float4>(kRansacMaxChunk);
     double *partials = s.take<double>(blocks * kSacMoments);
     SacFit *d_fit = s.take<SacFit>(1);
     TailArrays t = take_tail(s, n, sel_bytes);
@@ -348,7 +259,7 @@ int segment_cloud(Ctx *c, Cloud *dst, Cloud &src, const mvr_sac_params &p, mvr_s
     MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
 
     // P7 over the chunks of P8
-    long long best_count = -1, best = -1;
+    RansacLoop loop(p.max_iterations, std::log(1.0 - p.probability), nv, c->sac_chunk);
     SacHyp best_hyp;
     std::memset(&best_hyp, 0, sizeof best_hyp);
     if (nv >= 3u) {
@@ -357,59 +268,38 @@ int segment_cloud(Ctx *c, Cloud *dst, Cloud &src, const mvr_sac_params &p, mvr_s
       a.ax = p.axis[0]; a.ay = p.axis[1]; a.az = p.axis[2];
       a.na = p.model == 1 ? std::sqrt((a.ax * a.ax + a.ay * a.ay) + a.az * a.az) : 1.0;
       a.cos_eps = p.model == 1 ? std::cos(p.eps_angle) : 0.0;
-      a.hyp = d_hyp; a.coef = d_coef; a.counts = d_counts;
-      std::vector<char> host(kSacMaxChunk * (sizeof(SacHyp) + sizeof(uint32_t)));
-      const SacHyp *h_hyp = reinterpret_cast<const SacHyp *>(host.data());
-      const uint32_t *h_counts = reinterpret_cast<const uint32_t *>(host.data() + kSacMaxChunk * sizeof(SacHyp));
-      const long long max_skip = 10ll * p.max_iterations;
-      const double log_p = std::log(1.0 - p.probability);
-      long long iterations = 0, skipped = 0, attempt = 0;
-      double k = 1.0;
-      bool stop = false, first = true;
-      while (!stop && (double)iterations < k && skipped < max_skip) {
-        // no chunk is longer than what the loop can still consume
-        const long long room = ((long long)p.max_iterations + 1 - iterations) + (max_skip - skipped);
-        const long long want = c->sac_chunk > 0 ? c->sac_chunk : (first ? kSacFirstChunk : kSacMaxChunk);
-        a.count = (uint32_t)std::min<long long>(want, room);
-        a.t0 = (uint64_t)attempt;
-        first = false;
-        hipLaunchKernelGGL(sac_hypotheses_kernel, dim3(blocks_for(sac_padded(a.count), 64)), dim3(64), 0, c->stream, a);
+      a.hyp = dev.rec; a.coef = d_coef; a.counts = dev.counts;
+      std::vector<char> host_mem(RansacChunk<SacHyp>::kBytes);
+      const RansacChunk<SacHyp> host(host_mem.data());
+      while (loop.more()) {
+        a.count = loop.next_chunk();
+        a.t0 = (uint64_t)loop.attempt;
+        hipLaunchKernelGGL(sac_hypotheses_kernel, dim3(blocks_for(ransac_padded<PlaneModel>(a.count), 64)), dim3(64), 0, c->stream, a);
         MVR_HIP_TRY(c, hipGetLastError());
-        if (int rc = launch_count(c, fma, src.pts, n, d_coef, a.count, bound, d_counts)) return rc;
-        MVR_HIP_TRY(c, hipMemcpyAsync(host.data(), chunk_dev, host.size(), hipMemcpyDeviceToHost, c->stream));
+        if (int rc = ransac_launch_count<PlaneModel>(c, fma, src.pts, n, d_coef, a.count, bound, dev.counts)) return rc;
+        MVR_HIP_TRY(c, hipMemcpyAsync(host_mem.data(), chunk_dev, host_mem.size(), hipMemcpyDeviceToHost, c->stream));
         MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (uint32_t h = 0; h < a.count && (double)iterations < k && skipped < max_skip; ++h, ++attempt) {
-          const SacHyp &H = h_hyp[h];
-          const uint32_t count = H.status == 1 ? h_counts[h] : 0u;
-          if (H.status == 0) ++skipped;
-          else {
-            if ((long long)count > best_count) {
-              best_count = count; best = attempt; best_hyp = H;
-              const double w = (double)best_count / (double)nv;
-              const double pno = std::min(std::max(1.0 - w * w * w, DBL_EPSILON), 1.0 - DBL_EPSILON);
-              k = log_p / std::log(pno);
-            }
-            ++iterations;
-            if (iterations > p.max_iterations) stop = true;
-          }
-          if ((size_t)attempt < trace_cap && trace) {
-            mvr_sac_trace &T = trace[attempt];
-            T.status = H.status;
-            for (int j = 0; j < 3; ++j) T.sample[j] = H.sample[j];
-            for (int j = 0; j < 4; ++j) T.coefficients[j] = H.coef[j];
-            T.inliers = count;
-            T.k = k;
-          }
-          if (stop) { ++attempt; break; }
-        }
+        loop.replay(
+            a.count, [&](uint32_t h) { return host.rec[h].status; }, [&](uint32_t h) { return host.counts[h]; },
+            [&](uint32_t h) { best_hyp = host.rec[h]; },
+            [&](uint32_t h, long long attempt, int status, uint32_t count, double k) {
+              if (!trace || (size_t)attempt >= trace_cap) return;
+              const SacHyp &H = host.rec[h];
+              mvr_sac_trace &T = trace[attempt];
+              T.status = status;
+              for (int j = 0; j < 3; ++j) T.sample[j] = H.sample[j];
+              for (int j = 0; j < 4; ++j) T.coefficients[j] = H.coef[j];
+              T.inliers = count;
+              T.k = k;
+            });
       }
-      R.iterations = (int)iterations; R.skipped = (int)skipped; R.attempts = (int)attempt; R.k = k;
     }
-    R.found = best_count > 0 ? 1 : 0;
+    R.iterations = (int)loop.iterations; R.skipped = (int)loop.skipped; R.attempts = (int)loop.attempt; R.k = loop.k;
+    R.found = loop.best_count > 0 ? 1 : 0;
     SacFit hf;
     std::memset(&hf, 0, sizeof hf);
     if (R.found) {
-      R.best_attempt = (int)best;
+      R.best_attempt = (int)loop.best;
       // P9, P10
       hf.plane[0] = hf.plane[1] = make_float4(best_hyp.coef[0], best_hyp.coef[1], best_hyp.coef[2], best_hyp.coef[3]);
       MVR_HIP_TRY(c, hipMemcpyAsync(d_fit, &hf, sizeof hf, hipMemcpyHostToDevice, c->stream));
@@ -481,8 +371,7 @@ int extract_cloud(Ctx *c, Cloud &dst, Cloud &src, const uint32_t *index, size_t 
     MVR_HIP_TRY(c, hipMemsetAsync(flag, negative ? 1 : 0, n, c->stream));
     if (count) {
       MVR_HIP_TRY(c, hipMemcpyAsync(d_in, index, count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-      hipLaunchKernelGGL(sac_mark_kernel, dim3(blocks_for(count, 256)), dim3(256), 0, c->stream, d_in, count, (uint8_t)(negative ? 0 : 1), flag);
-      MVR_HIP_TRY(c, hipGetLastError());
+      if (int rc = launch_mark(c, d_in, count, (uint8_t)(negative ? 0 : 1), flag)) return rc;
     }
     uint32_t hc = 0;
     if (int rc = select_flagged(c, t.tmp, sel_bytes, flag, n, t.list, t.counters)) return rc;

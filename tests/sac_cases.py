@@ -10,7 +10,7 @@ import numpy as np
 import sac_ref as R
 
 F32 = np.float32
-PPT = 4                      # points per thread of sac_count_kernel (kSacPpt)
+PPT = 4                      # points per thread of ransac_count_kernel (kRansacPpt, csrc/mvr_ransac.h)
 TILE_PLUS_ONE = 4 * 256 * PPT + 1
 
 

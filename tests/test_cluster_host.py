@@ -160,16 +160,22 @@ def test_cluster_kernels_use_no_scratch(built, tmp_path):
     assert '#include "mvr_union_find.h"' in open(src).read()
     den = open(os.path.join(ROOT, PKG, "csrc", "mvr_denoise.hip")).read()
     assert '#include "mvr_union_find.h"' in den and "uint32_t uf_find(" not in den      # one union-find, shared
-    r = subprocess.run([built.HIPCC] + built.HIP_FLAGS + ["-x", "hip", "--cuda-device-only", "-c", src, "-o", str(tmp_path / "mvr_cluster.o"),
-                        "-Rpass-analysis=kernel-resource-usage"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-3000:]
-    blocks = re.split(r"(?=remark: Function Name: )", r.stdout)[1:]
-    use = [(re.search(r"Function Name: (\S+)", b).group(1), int(re.search(r" VGPRs: (\d+)", b).group(1)),
-            int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))) for b in blocks]
+    def usage(path):
+        r = subprocess.run([built.HIPCC] + built.HIP_FLAGS + ["-x", "hip", "--cuda-device-only", "-c", path, "-o", str(tmp_path / "device.o"),
+                            "-Rpass-analysis=kernel-resource-usage"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert r.returncode == 0, r.stdout[-3000:]
+        blocks = re.split(r"(?=remark: Function Name: )", r.stdout)[1:]
+        return [(re.search(r"Function Name: (\S+)", b).group(1), int(re.search(r" VGPRs: (\d+)", b).group(1)),
+                 int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1))) for b in blocks]
+
+    use = usage(src)
     own = [u for u in use if "cl_" in u[0] and "_kernel" in u[0]]
+    # E1's marks are launch_mark of the filter tail (mvr_denoise.hip), shared with mvr_cloud_extract_indices: one mark kernel
+    assert "mark_index_kernel" in den and not any("mark" in n for n, _, _ in use), use
+    own += [u for u in usage(os.path.join(ROOT, PKG, "csrc", "mvr_denoise.hip")) if "mark_index_kernel" in u[0]]
     print(own)
     assert sum("cl_link_kernel" in n for n, _, _ in own) == 4                            # (fma) x (plain, normals)
-    for kernel in ("cl_mark_kernel", "cl_jump_kernel", "cl_label_kernel", "cl_root_key_kernel", "cl_rank_kernel", "cl_point_key_kernel",
+    for kernel in ("mark_index_kernel", "cl_jump_kernel", "cl_label_kernel", "cl_root_key_kernel", "cl_rank_kernel", "cl_point_key_kernel",
                    "cl_offsets_kernel"):
         assert sum(kernel in n for n, _, _ in own) == 1, kernel
     assert all(s == 0 and v <= 64 for _, v, s in own), own                               # no spills; 8 waves per SIMD

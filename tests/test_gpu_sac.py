@@ -103,7 +103,7 @@ def test_fma_distance(ctx):
     p, kw, ref, res, idx, tr = gpu_run(ctx, SC.FMA_CASE, 1, fma=True, optimize=False)
     differ = int((ref["trace"]["inliers"] != plain["trace"]["inliers"]).sum())
     print("fma changes %d of %d counts and %d entries of the inlier mask" % (differ, len(tr["inliers"]), (ref["ransac_mask"] != plain["ransac_mask"]).sum()))
-    assert len(ref["trace"]["inliers"]) == len(plain["trace"]["inliers"]) and differ >= 1                # sac_count_kernel<., true>
+    assert len(ref["trace"]["inliers"]) == len(plain["trace"]["inliers"]) and differ >= 1                # ransac_count_kernel<PlaneModel, ., true>
     assert (ref["ransac_mask"] != plain["ransac_mask"]).any()                                              # sac_flag_kernel<true>
     assert same_bits(tr["coefficients"], ref["trace"]["coefficients"]) and np.array_equal(tr["inliers"], ref["trace"]["inliers"])
     assert (res["iterations"], res["best_attempt"], res["inliers"]) == (ref["iterations"], ref["best_attempt"], int(ref["ransac_mask"].sum()))

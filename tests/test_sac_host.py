@@ -249,9 +249,27 @@ def test_sac_kernels_use_no_scratch(built, tmp_path):
             int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1)), int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1)))
            for b in blocks]
     print(use)
-    for kernel, times in (("sac_hypotheses_kernel", 1), ("sac_count_kernel", 6), ("sac_flag_kernel", 2), ("sac_moments_kernel", 1), ("sac_fit_kernel", 1)):
-        assert sum(kernel in n for n, _, _, _ in use) == times, (kernel, use)      # count: (1, 2, 4 registers) x fma
+    for kernel, times in (("sac_hypotheses_kernel", 1), ("sac_flag_kernel", 2), ("sac_moments_kernel", 1), ("sac_fit_kernel", 1)):
+        assert sum(kernel in n for n, _, _, _ in use) == times, (kernel, use)
+    # the shared counting kernel (mvr_ransac.h) over this file's model: (1, 2, 4 registers) x fma
+    count = sorted(l for n, _, _, l in use if "19ransac_count_kernel" in n and "PlaneModel" in n)
+    assert len(count) == sum("count_kernel" in n for n, _, _, _ in use) == 6, use
     assert all(s == 0 for _, _, s, _ in use), use
-    count = sorted(l for n, _, _, l in use if "sac_count_kernel" in n)
     assert count == [256, 256, 512, 512, 1024, 1024]  # one counter per attempt of the chunk
     assert all(v <= 64 for _, v, _, _ in use)
+
+
+def test_one_ransac_scaffold_shared():
+    """the draws, the counting kernel, the replay of the loop and f32_at_least are mvr_ransac.h's, for both chunked RANSACs; the mark
+    kernel of mvr_cloud_extract_indices is the filter tail's (launch_mark, mvr_denoise.hip), for the cluster extraction too"""
+    csrc = os.path.join(ROOT, PKG, "csrc")
+    text = {name: open(os.path.join(csrc, name)).read() for name in os.listdir(csrc) if name.endswith((".hip", ".h", ".cpp"))}
+    for name in ("mvr_sac.hip", "mvr_reject_sac.hip"):
+        s = text[name]
+        assert '#include "mvr_ransac.h"' in s and "float f32_at_least(" not in s, name
+        assert not re.search(r"__global__[^;{]*count_kernel\s*\(", s), name
+        assert "prerej_draw(" not in s and "ransac_draw3(" in s and ".replay(" in s and "ransac_launch_count<" in s, name
+    for needle in ("float f32_at_least(", "void ransac_draw3(", "void replay(", r"ransac_count_kernel("):
+        assert [name for name, s in text.items() if needle in s] == ["mvr_ransac.h"], needle
+    assert "cl_mark_kernel" not in text["mvr_cluster.hip"] and "sac_mark_kernel" not in text["mvr_sac.hip"]
+    assert "launch_mark(" in text["mvr_cluster.hip"] and "launch_mark(" in text["mvr_sac.hip"]
