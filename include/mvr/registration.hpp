@@ -1132,6 +1132,86 @@ class FPFHEstimation {
   double radius_ = 0.0;
 };
 
+// ---------------------------------------------------------------- point feature histograms
+// pcl::PFHEstimation<PointInT, PointNT, PointOutT> (features/pfh.h), the input cloud its own search surface: setInputCloud,
+// setInputNormals, setSearchMethod, setRadiusSearch or setKSearch (the later call decides the mode, exactly one is in force),
+// setMaximumCacheSize / setUseInternalCache (PCL's cache of pair features: accepted, no effect on the result, as in PCL),
+// compute.  Semantics: mvr_cloud_pfh (mvr_hip.h) -- one call on the GPU per compute().  Points, normals, NaN signatures,
+// is_dense and the error prints are those of FPFHEstimation above; setSearchSurface and setIndices are refused with an exception.
+template <typename PointInT, typename PointNT, typename PointOutT = PFHSignature125>
+class PFHEstimation {
+ public:
+  typedef PointCloud<PointInT> PointCloudIn;
+  typedef typename PointCloudIn::ConstPtr PointCloudConstPtr;
+  typedef PointCloud<PointNT> PointCloudN;
+  typedef typename PointCloudN::ConstPtr PointCloudNConstPtr;
+  typedef PointCloud<PointOutT> PointCloudOut;
+  typedef search::KdTree<PointInT> KdTree;
+  typedef typename KdTree::Ptr KdTreePtr;
+  typedef std::shared_ptr<const std::vector<int> > IndicesConstPtr;
+
+  void setInputCloud(const PointCloudConstPtr &c) { input_ = c; }
+  PointCloudConstPtr getInputCloud() const { return input_; }
+  void setInputNormals(const PointCloudNConstPtr &n) { normals_ = n; }
+  PointCloudNConstPtr getInputNormals() const { return normals_; }
+  void setSearchMethod(const KdTreePtr &tree) { tree_ = tree; }
+  KdTreePtr getSearchMethod() const { return tree_; }
+  void setRadiusSearch(double r) { radius_ = r; if (r != 0.0) k_ = 0; }
+  double getRadiusSearch() const { return radius_; }
+  void setKSearch(int k) { k_ = k; if (k != 0) radius_ = 0.0; }
+  int getKSearch() const { return k_; }
+  void setMaximumCacheSize(unsigned int n) { cache_size_ = n; }
+  unsigned int getMaximumCacheSize() const { return cache_size_; }
+  void setUseInternalCache(bool on) { use_cache_ = on; }
+  bool getUseInternalCache() const { return use_cache_; }
+  void setSearchSurface(const PointCloudConstPtr &) { throw std::invalid_argument("[pcl::PFHEstimation::setSearchSurface] a separate search surface is not offered: the input cloud is its own surface"); }
+  void setIndices(const IndicesConstPtr &) { throw std::invalid_argument("[pcl::PFHEstimation::setIndices] index subsets are not offered: every point gets a signature"); }
+
+  void compute(PointCloudOut &output)
+  {
+    static_assert(sizeof(PointInT) % 4 == 0 && sizeof(PointInT) >= 12, "points that begin with x, y, z expected");
+    static_assert(sizeof(PointOutT) == sizeof(float) * MVR_PFH_DIM, "a 125-float signature expected");
+    output.clear();
+    if (!input_) { std::fprintf(stderr, "[pcl::PFHEstimation::compute] No input dataset was given!\n"); return; }
+    if (!normals_ || normals_->size() != input_->size()) {
+      std::fprintf(stderr, "[pcl::PFHEstimation::compute] The number of points in the input dataset differs from the number of points in the dataset containing the normals!\n");
+      return;
+    }
+    const bool kmode = k_ != 0;
+    if (kmode ? (k_ < 1 || k_ > MVR_MAX_KNN) : !(std::isfinite(radius_) && radius_ > 0.0)) {
+      std::fprintf(stderr, "[pcl::PFHEstimation::compute] The search radius (%f) must be finite and > 0 (setRadiusSearch), or k (%d) in 1..%d (setKSearch).\n",
+                   radius_, k_, MVR_MAX_KNN);
+      return;
+    }
+    const size_t n = input_->size();
+    output.resize(n);
+    if (!n) return;
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.check(mvr_cloud_upload(d.ctx(), s.s, input_->points[0].data, n, sizeof(PointInT)), "mvr_cloud_upload");
+    std::vector<float> nrm(4 * n);
+    for (size_t i = 0; i < n; ++i) {
+      const PointNT &q = normals_->points[i];
+      nrm[4 * i] = q.normal_x; nrm[4 * i + 1] = q.normal_y; nrm[4 * i + 2] = q.normal_z; nrm[4 * i + 3] = 0.f;
+    }
+    d.check(mvr_cloud_upload_normals(d.ctx(), s.s, nrm.data(), n, 16), "mvr_cloud_upload_normals");
+    mvr_pfh_params p;
+    p.radius = kmode ? 0.0 : radius_; p.k = k_; p.fma_dist = 0;
+    d.check(mvr_cloud_pfh(d.ctx(), s.s, &p, output.points[0].histogram, nullptr, nullptr), "mvr_cloud_pfh");
+    for (size_t i = 0; i < n && output.is_dense; ++i)
+      if (std::isnan(output.points[i].histogram[0])) output.is_dense = false;
+  }
+
+ private:
+  PointCloudConstPtr input_;
+  PointCloudNConstPtr normals_;
+  KdTreePtr tree_;
+  double radius_ = 0.0;
+  int k_ = 0;
+  unsigned int cache_size_ = (1u << 31) - 1u;
+  bool use_cache_ = false;
+};
+
 // ---------------------------------------------------------------- boundary points
 // pcl::BoundaryEstimation<PointInT, PointNT, PointOutT> (features/boundary.h) in radius mode, the input cloud its own search
 // surface: setInputCloud, setInputNormals, setSearchMethod, setRadiusSearch, setAngleThreshold / getAngleThreshold (PCL's
@@ -1606,7 +1686,8 @@ extractEuclideanClusters(const PointCloud<PointT> &cloud, float tolerance, const
 // pcl::SampleConsensusPrerejective<PointSource, PointTarget, FeatureT> (registration/sample_consensus_prerejective.h):
 // setInputSource, setInputTarget, setSourceFeatures, setTargetFeatures, setMaximumIterations, setNumberOfSamples,
 // setCorrespondenceRandomness, setSimilarityThreshold, setMaxCorrespondenceDistance, setInlierFraction, align, hasConverged,
-// getFinalTransformation, getFitnessScore, getInliers.  Semantics: mvr_align_prerejective (mvr_hip.h) -- one call per align().
+// getFinalTransformation, getFitnessScore, getInliers.  Semantics: mvr_align_prerejective_dim (mvr_hip.h) -- one call per align();
+// FeatureT is a signature of 33 floats (FPFHSignature33) or of 125 (PFHSignature125).
 // PCL draws with rand(); here the result is a pure function of the inputs and of setSeed (ours).  Defaults are PCL's (3
 // samples, randomness 2, similarity 0.9, inlier fraction 0); an inlier fraction of 0 -- which the C-ABI refuses -- is sent as
 // the smallest positive double, the same test.  As PCL, a missing cloud or feature set, or a feature set of another size than
@@ -1660,7 +1741,8 @@ class SampleConsensusPrerejective {
  private:
   void align(PointCloudSource &output, const Matrix4 &guess, bool with_guess)
   {
-    static_assert(sizeof(FeatureT) == sizeof(float) * 3 * MVR_FPFH_BINS, "a 33-float signature expected");
+    static_assert(sizeof(FeatureT) == sizeof(float) * 3 * MVR_FPFH_BINS || sizeof(FeatureT) == sizeof(float) * MVR_PFH_DIM,
+                  "a 33-float or a 125-float signature expected");
     output.clear(); inliers_.clear();
     result_ = mvr_prerej_result(); result_.best_iteration = -1; result_.error = DBL_MAX;
     final_ = with_guess ? guess : Matrix4::Identity();
@@ -1674,10 +1756,11 @@ class SampleConsensusPrerejective {
     d.upload(tgt_.s, *target_);
     mvr_prerej_params p = p_;
     if (p.inlier_fraction == 0.0) p.inlier_fraction = DBL_MIN;
-    static const float none[33] = {0};
-    d.check(mvr_align_prerejective(d.ctx(), src_.s, tgt_.s, sfeat_->empty() ? none : sfeat_->points[0].histogram,
-                                   tfeat_->empty() ? none : tfeat_->points[0].histogram, &p, with_guess ? guess.data() : nullptr, &result_, nullptr),
-            "mvr_align_prerejective");
+    static const float none[MVR_PFH_DIM] = {0};
+    d.check(mvr_align_prerejective_dim(d.ctx(), src_.s, tgt_.s, sfeat_->empty() ? none : sfeat_->points[0].histogram,
+                                       tfeat_->empty() ? none : tfeat_->points[0].histogram, (int)(sizeof(FeatureT) / sizeof(float)), &p,
+                                       with_guess ? guess.data() : nullptr, &result_, nullptr),
+            "mvr_align_prerejective_dim");
     final_ = Matrix4(result_.T);
     d.check(mvr_cloud_transform_f32(d.ctx(), out_.s, src_.s, result_.T), "mvr_cloud_transform_f32");
     d.download(out_.s, output);

@@ -431,6 +431,32 @@ class ScanCloud {
     return true;
   }
 
+  // EXTENSION (pcl::PFHEstimation on the raw points, on the GPU; rules: mvr_cloud_pfh in mvr_hip.h): one 125-bin signature per
+  // point from every PAIR of its neighbours within `radius`, with the normals of `rich`; refusals as computeFPFH.
+  bool computePFH(double radius, std::vector<PFHSignature125> &out) const
+  {
+    out.clear();
+    const size_t n = points.size();
+    if (rich.size() != n) {
+      std::fprintf(stderr, "[ScanCloud::computePFH] The cloud has no normals (%zu points, %zu records): call estimateNormals first.\n", n, rich.size());
+      return false;
+    }
+    if (!(std::isfinite(radius) && radius > 0.0)) {
+      std::fprintf(stderr, "[ScanCloud::computePFH] The radius (%f) must be finite and > 0.\n", radius);
+      return false;
+    }
+    out.resize(n);
+    if (!n) return true;
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.upload(s.s, points);
+    uploadRichNormals(d, s.s);
+    mvr_pfh_params p;
+    p.radius = radius; p.k = 0; p.fma_dist = 0;
+    d.check(mvr_cloud_pfh(d.ctx(), s.s, &p, out[0].histogram, nullptr, nullptr), "mvr_cloud_pfh");
+    return true;
+  }
+
   // EXTENSION (pcl::BoundaryEstimation on the raw points, on the GPU; rules: mvr_cloud_boundary in mvr_hip.h): one flag per point,
   // whether its neighbours within p.radius, projected onto its tangent plane, leave an angular gap above p.angle_threshold,
   // with the normals of `rich` (estimateNormals, smooth with compute_normals, or a file that carries them).  Without one rich
@@ -533,15 +559,40 @@ class ScanCloud {
     std::vector<FPFHSignature33> sf, tf;
     if (result) { *result = mvr_prerej_result(); result->best_iteration = -1; result->error = DBL_MAX; }
     if (!computeFPFH(params.feature_radius, sf) || !target.computeFPFH(params.feature_radius, tf)) return false;
+    return alignPrerejective(target, params, sf, tf, pose, result);
+  }
+  // the same from PFH descriptors (computePFH of both scans at feature_radius): 125 floats per row through the same matcher
+  // and aligner
+  bool alignPrerejectivePFH(const ScanCloud &target, const PrerejectiveParams &params, RowMatrixd &pose, mvr_prerej_result *result = nullptr) const
+  {
+    std::vector<PFHSignature125> sf, tf;
+    if (result) { *result = mvr_prerej_result(); result->best_iteration = -1; result->error = DBL_MAX; }
+    if (!computePFH(params.feature_radius, sf) || !target.computePFH(params.feature_radius, tf)) return false;
+    return alignPrerejective(target, params, sf, tf, pose, result);
+  }
+  // the aligner on descriptor tables the caller holds, one row per point of this scan (sf) and of `target` (tf), 33 or 125
+  // floats per row; with use_keypoints the rows of the other points are overwritten with NaN first
+  template <typename FeatureT>
+  bool alignPrerejective(const ScanCloud &target, const PrerejectiveParams &params, std::vector<FeatureT> &sf, std::vector<FeatureT> &tf,
+                         RowMatrixd &pose, mvr_prerej_result *result = nullptr) const
+  {
+    static_assert(sizeof(FeatureT) == sizeof(float) * 3 * MVR_FPFH_BINS || sizeof(FeatureT) == sizeof(float) * MVR_PFH_DIM,
+                  "a 33-float or a 125-float signature expected");
+    if (result) { *result = mvr_prerej_result(); result->best_iteration = -1; result->error = DBL_MAX; }
+    if (sf.size() != points.size() || tf.size() != target.points.size()) {
+      std::fprintf(stderr, "[ScanCloud::alignPrerejective] One descriptor row per point expected (%zu rows for %zu points, %zu for %zu).\n",
+                   sf.size(), points.size(), tf.size(), target.points.size());
+      return false;
+    }
     if (params.use_keypoints && (!keepKeypointRows(params.keypoints, params.border, sf) || !target.keepKeypointRows(params.keypoints, params.border, tf))) return false;
     Device &d = Device::instance();
     SlotGuard s, t;
     d.upload(s.s, points);
     d.upload(t.s, target.points);
-    static const float none[33] = {0};
+    static const float none[MVR_PFH_DIM] = {0};
     mvr_prerej_result res;
-    d.check(mvr_align_prerejective(d.ctx(), s.s, t.s, sf.empty() ? none : sf[0].histogram, tf.empty() ? none : tf[0].histogram, &params.align,
-                                   nullptr, &res, nullptr), "mvr_align_prerejective");
+    d.check(mvr_align_prerejective_dim(d.ctx(), s.s, t.s, sf.empty() ? none : sf[0].histogram, tf.empty() ? none : tf[0].histogram,
+                                       (int)(sizeof(FeatureT) / sizeof(float)), &params.align, nullptr, &res, nullptr), "mvr_align_prerejective_dim");
     if (result) *result = res;
     if (!res.converged) return false;
     pose = PclMatrixCaster<RowMatrixd>(Matrix4f(res.T));
@@ -629,12 +680,14 @@ class ScanCloud {
     }
   }
   // the descriptor rows of the points detectKeypoints does not list become NaN (false: the detector refused its parameters)
-  bool keepKeypointRows(const mvr_iss_params &p, std::vector<FPFHSignature33> &feat) const
+  template <typename FeatureT>
+  bool keepKeypointRows(const mvr_iss_params &p, std::vector<FeatureT> &feat) const
   {
     mvr_iss_border_params none = mvr_iss_border_params();
     return keepKeypointRows(p, none, feat);
   }
-  bool keepKeypointRows(const mvr_iss_params &p, const mvr_iss_border_params &b, std::vector<FPFHSignature33> &feat) const
+  template <typename FeatureT>
+  bool keepKeypointRows(const mvr_iss_params &p, const mvr_iss_border_params &b, std::vector<FeatureT> &feat) const
   {
     std::vector<uint32_t> key;
     if (!detectKeypoints(p, b, key)) return false;

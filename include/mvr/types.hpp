@@ -71,6 +71,14 @@ struct FPFHSignature33 {
 };
 static_assert(sizeof(FPFHSignature33) == 132, "FPFHSignature33 must match pcl::FPFHSignature33");
 
+// pcl::PFHSignature125: the 5 x 5 x 5 joint bins of a point feature histogram (mvr_cloud_pfh in mvr_hip.h)
+struct PFHSignature125 {
+  float histogram[125];
+  static int descriptorSize() { return 125; }
+  PFHSignature125() { for (float &h : histogram) h = 0.f; }
+};
+static_assert(sizeof(PFHSignature125) == 500, "PFHSignature125 must match pcl::PFHSignature125");
+
 // pcl::Boundary: whether a point lies on the rim of its surface (mvr_cloud_boundary in mvr_hip.h)
 struct Boundary {
   uint8_t boundary_point;

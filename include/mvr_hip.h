@@ -407,8 +407,9 @@ int  mvr_cloud_mls(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_mls_param
  *      because a pipelined run is in flight.  An empty cloud is MVR_OK.  All three outputs NULL: MVR_OK after the work.
  *  F8. Bit-identical from run to run on one grid: one thread per query, one fixed walk order, no floating-point atomics.
  * The slot is not modified and no descriptor stays on the device after the call.
- * Out of scope: the k-neighbour mode (setKSearch), setSearchSurface / setIndices and PFH.  The matching and the
- * sample-consensus alignment that consume the signatures follow below (mvr_feature_knn, mvr_align_prerejective). */
+ * Out of scope: the k-neighbour mode (setKSearch) and setSearchSurface / setIndices.  PFH is mvr_cloud_pfh below.  The
+ * matching and the sample-consensus alignment that consume the signatures follow below (mvr_feature_knn,
+ * mvr_align_prerejective). */
 #define MVR_FPFH_BINS 11            /* per feature; a signature is 3 * 11 = 33 floats (pcl::FPFHSignature33) */
 typedef struct {
   double radius;        /* setRadiusSearch: finite, > 0 */
@@ -419,6 +420,55 @@ int  mvr_cloud_fpfh(mvr_ctx *ctx, int slot, const mvr_fpfh_params *p,
                     float *spfh,              /* optional host, n * 33: the intermediate SPFH   */
                     uint32_t *neighbor_count  /* optional host, n: n_i of rule F2               */);
 
+/* ---- point feature histograms (EXTENSION: pcl::PFHEstimation) -----------------------------------------------------------
+ * The 125-bin descriptor FPFH approximates: the joint histogram of the three angular features over EVERY pair of a
+ * neighbourhood, n_i (n_i - 1) / 2 pairs per point.  PCL was not at hand; the model is pcl/features/impl/pfh.hpp
+ * (computePointPFHSignature, computeFeature) with nr_subdiv = 5, as published; deviations are marked.
+ *  P1. Input and validity: rule F1.  The cloud in `slot` is input and search surface at once, with its normals.  A point is
+ *      VALID when its three coordinates and its three normal components are finite.  An invalid point gets 125 NaN and
+ *      neighbor_count 0 and is nobody's neighbour.
+ *  P2. Neighbourhood: exactly one of radius / k is set.  Every n_i is allowed: no on-chip capacity caps it (P6 aside).
+ *      Radius mode: N(i) is rule F2 -- the f32 distance, fma_dist as everywhere, i itself included.
+ *      k mode (1 <= k <= MVR_MAX_KNN; offered here, PCL's setKSearch): N(i) = the listed entries of mvr_knn's list of i in its
+ *      own cloud (rules N1-N3, key = (d2 bits, index)) minus the entries whose normal is not finite -- whether or not i itself
+ *      is among them (duplicates with lower indices can push it out).  n_i = |N(i)|.
+ *  P3. Pairs: every unordered pair {a, b} of N(i) is counted once.  N(i) is ordered by the key (bits of the f32 d2 to the
+ *      query, index), ascending -- PCL's list order when FLANN returns sorted lists, ties aside -- and the pair features are
+ *      rule F3, verbatim and in the same f32 arithmetic (one piece of code serves both descriptors), with the LATER member of
+ *      the pair in F3's role of "i" and the EARLIER in the role of "j": PCL calls computePairFeatures(indices[i_idx],
+ *      indices[j_idx]) with j_idx < i_idx.  Nothing is sorted: a pair compares its two keys.
+ *  P4. Bins: F4 with 5 in place of 11: b1, b2, b3 in 0..4; the joint bin is h = b1 + 5 * b2 + 25 * b3.
+ *  P5. Histogram: c_i[h] = the number of pairs that P3 gives features and P4 puts in h, an exact unsigned integer;
+ *      m_i = n_i (n_i - 1) / 2 in 64 bits; out[h] = (float)c * (100.0f / (float)m_i) in f32.  (PCL adds the increment c times
+ *      in f32: a difference of rounding only.)  Pairs without features (f4 == 0 or |v| == 0) still count in m_i, as in PCL.
+ *      n_i == 1: 125 zeros.  n_i == 0 (k mode only): 125 NaN, PCL's "no neighbours".
+ *  P6. Range: a query with n_i > 65 535 makes the call fail with MVR_E_ARG, nothing written; the neighbourhoods are counted
+ *      before any such query's pairs are.  DEVIATION: PCL has no such limit (and would need days for such a point).
+ *  P7. MVR_E_ARG, before any GPU work and with nothing written, for everything F7 lists, for both or neither of radius / k
+ *      set (radius: finite and > 0, or 0; k: 1..MVR_MAX_KNN, or 0).  An empty cloud is MVR_OK.  All three outputs NULL:
+ *      MVR_OK after the work.
+ *  P8. The counts are integers added with integer atomics, so the result does not depend on the order of the pairs, on which
+ *      lane computes which, on the resolution of the grid or on any tune key: bit-identical from run to run, from grid to
+ *      grid, and between the staged and the tiled path.  No floating-point atomics anywhere.
+ * One wave per query: it walks the ball over the cloud's own grid with its lanes over the cells' rows (k mode: it reads the k
+ * list), stages the neighbours in LDS, deals the pairs over its 64 lanes and counts into a 125-bin u32 histogram in LDS.  A
+ * neighbourhood of more than MVR_PFH_STAGE points (tune key "pfh_stage", MVR_MAX_KNN..MVR_PFH_STAGE, lowers the threshold)
+ * goes to device scratch and is processed tile against tile.  mvr_ctx_stat "pfh_tiled_queries" / "pfh_pairs": the queries of
+ * the last call that took the tiled path, and its sum of m_i.
+ * The slot is not modified and nothing stays on the device after the call.
+ * Out of scope: setSearchSurface / setIndices, PFHRGB. */
+#define MVR_PFH_DIM 125             /* 5 * 5 * 5 joint bins (pcl::PFHSignature125) */
+#define MVR_PFH_STAGE 256           /* neighbours of one query staged in LDS; above it the tiled path */
+typedef struct {
+  double radius;        /* setRadiusSearch: finite, > 0, or 0 for k mode                   */
+  int    k;             /* setKSearch: 1..MVR_MAX_KNN, or 0 for radius mode; exactly one set */
+  int    fma_dist;
+} mvr_pfh_params;
+int  mvr_cloud_pfh(mvr_ctx *ctx, int slot, const mvr_pfh_params *p,
+                   float *pfh,               /* host, n * 125, row = point index; may be NULL  */
+                   uint32_t *counts,         /* optional host, n * 125: c_i[h] of rule P5      */
+                   uint32_t *neighbor_count  /* optional host, n: n_i of rule P2               */);
+
 /* ---- feature matching and coarse alignment (EXTENSION: pcl::SampleConsensusPrerejective) -------------------------------
  * What brings a scan without a pose prior within the capture range of mvr_icp_align.  The reference pins no PCL version and
  * PCL was not at hand: the models are pcl/registration/impl/sample_consensus_prerejective.hpp,
@@ -426,9 +476,9 @@ int  mvr_cloud_fpfh(mvr_ctx *ctx, int slot, const mvr_fpfh_params *p,
  * published; deviations are marked.
  *
  * mvr_feature_knn: exact k nearest neighbours in feature space.  q / t: host arrays, row = point, `dim` floats per row.
- * dim must be 33 (3 * MVR_FPFH_BINS; the field is there for later descriptors), 1 <= k <= MVR_MAX_KNN, else MVR_E_ARG
+ * dim must be 33 (3 * MVR_FPFH_BINS) or 125 (MVR_PFH_DIM), 1 <= k <= MVR_MAX_KNN, else MVR_E_ARG
  * before any GPU work.  idx / d2: host, nq * k, row-major (either may be NULL).
- *  M1. Distance, FLANN's L2_Simple: acc = 0; for b = 0..32 { diff = q[b] - t[b]; acc = acc + diff * diff; } -- all f32,
+ *  M1. Distance, FLANN's L2_Simple: acc = 0; for b = 0..dim - 1 { diff = q[b] - t[b]; acc = acc + diff * diff; } -- all f32,
  *      every operation rounded, in this order, never contracted.  There is no fma variant.
  *  M2. Order: the k smallest under the key (d2 bits, index), ascending; ties go to the lower index -- the key of mvr_knn.
  *  M3. Non-finite rows: a target row with a non-finite component is never listed, and neither is a pair whose d2 is not
@@ -473,8 +523,10 @@ int  mvr_cloud_fpfh(mvr_ctx *ctx, int slot, const mvr_fpfh_params *p,
  *  nr_samples outside 3..8, k outside 1..MVR_MAX_KNN, similarity outside [0, 1), max_dist not finite and > 0, or
  *  inlier_fraction outside (0, 1].  The draws, matches and polygon tests of all iterations are one launch; the surviving poses
  *  are solved on the host and scored through the kernel of mvr_pose_scores.
- * Out of scope: SampleConsensusInitialAlignment, descriptors of other lengths.  (CorrespondenceRejectorSampleConsensus over the
- * matches of mvr_feature_knn is mvr_reject_sample_consensus, rules C1-C12.) */
+ * mvr_align_prerejective_dim: the same with `dim` floats per row of the two feature tables, dim = 33 or 125 (else MVR_E_ARG):
+ * rules A1-A6 with "33" read as dim.  mvr_align_prerejective is this with dim = 33.
+ * Out of scope: SampleConsensusInitialAlignment, descriptors of lengths other than 33 and 125.
+ * (CorrespondenceRejectorSampleConsensus over the matches of mvr_feature_knn is mvr_reject_sample_consensus, rules C1-C12.) */
 int  mvr_feature_knn(mvr_ctx *ctx, const float *q, size_t nq, const float *t, size_t nt, int dim, int k,
                      uint32_t *idx /* nq * k */, float *d2 /* nq * k */);
 int  mvr_pose_scores(mvr_ctx *ctx, int src_slot, int tgt_slot, const float *T /* count * 16, column-major */, size_t count,
@@ -507,6 +559,9 @@ typedef struct {
 int  mvr_align_prerejective(mvr_ctx *ctx, int src_slot, int tgt_slot, const float *src_feat, const float *tgt_feat,
                             const mvr_prerej_params *params, const float *guess /* optional, 16 */,
                             mvr_prerej_result *result, mvr_prerej_trace *trace /* optional, max_iterations */);
+int  mvr_align_prerejective_dim(mvr_ctx *ctx, int src_slot, int tgt_slot, const float *src_feat, const float *tgt_feat, int dim,
+                                const mvr_prerej_params *params, const float *guess /* optional, 16 */,
+                                mvr_prerej_result *result, mvr_prerej_trace *trace /* optional, max_iterations */);
 
 /* ---- intrinsic shape signature keypoints (EXTENSION: pcl::ISSKeypoint3D) -----------------------------------------------
  * What chooses the points that carry a descriptor into the matcher: a row of a feature table that is overwritten with NaN is
@@ -1442,7 +1497,8 @@ enum { MVR_K_NN = 0, MVR_K_REDUCE = 1, MVR_K_XFORM = 2, MVR_K_GLUE = 3,
  * same permutations), "pipeline_multi_rank" (1: passes with a collective over more than one rank may be queued ahead of their poses
  * too; 0, default, until a recorded two-GPU run);
  * feature matching and pose scoring: "feat_split" (blocks the target of mvr_feature_knn is split over, 1..64; 0, default: by the
- * launch size), "score_chunk" (poses per launch of mvr_pose_scores, default 256);
+ * launch size), "score_chunk" (poses per launch of mvr_pose_scores, default 256); "pfh_stage" (mvr_cloud_pfh: the neighbourhood
+ * size above which a query takes the tiled path, MVR_MAX_KNN..MVR_PFH_STAGE, default MVR_PFH_STAGE);
  * plane segmentation: "sac_chunk" (attempts generated and scored per chunk, 1..256; 0, default: 64 for the first chunk of a
  * call and 256 from then on);
  * the sample-consensus rejector: "rej_sac_chunk" (attempts generated and scored per chunk, 1..256; 0, default: 64 for the first
@@ -1456,7 +1512,8 @@ int  mvr_ctx_pass_log(mvr_ctx *ctx, double *ms, int cap, int *n);
 /* counters of the context, by name: "piped_passes" (passes of mvr_ring_run / mvr_ring_run_sharded whose launch chain was
  * enqueued ahead of their poses, see "pipeline"), "fused_passes" (fused pair batches run so far), "blocking_events"
  * (times the library waited for its stream or re-allocated a buffer: a pass without any is in steady state),
- * "prerej_match_ms" / "prerej_hypotheses_ms" / "prerej_score_ms" (wall milliseconds of the last mvr_align_prerejective by phase) */
+ * "prerej_match_ms" / "prerej_hypotheses_ms" / "prerej_score_ms" (wall milliseconds of the last mvr_align_prerejective by phase),
+ * "pfh_stage" (the tune key's value), "pfh_tiled_queries" / "pfh_pairs" (of the last mvr_cloud_pfh: see there) */
 int  mvr_ctx_stat(mvr_ctx *ctx, const char *key, double *value);
 /* diagnostics: the ordering of the cloud in `slot` (sorted position -> original index); *n = its length (0: none yet) */
 int  mvr_debug_order(mvr_ctx *ctx, int slot, uint32_t *perm, size_t cap, size_t *n);

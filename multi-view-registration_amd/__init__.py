@@ -214,6 +214,11 @@ class FpfhParams(C.Structure):
     _fields_ = [("radius", C.c_double), ("fma_dist", C.c_int)]
 
 
+class PfhParams(C.Structure):
+    """mvr_pfh_params"""
+    _fields_ = [("radius", C.c_double), ("k", C.c_int), ("fma_dist", C.c_int)]
+
+
 class IssParams(C.Structure):
     """mvr_iss_params"""
     _fields_ = [("salient_radius", C.c_double), ("non_max_radius", C.c_double), ("gamma_21", C.c_double), ("gamma_32", C.c_double),
@@ -265,6 +270,8 @@ class ClusterResult(C.Structure):
 SAC_MODELS = {"plane": 0, "perpendicular_plane": 1}   # mvr_sac_params.model: SACMODEL_PLANE, SACMODEL_PERPENDICULAR_PLANE
 BOUNDARY_MIN_ANGLE = math.pi / 4   # MVR_BOUNDARY_MIN_ANGLE: the smallest angle_threshold the boundary rule accepts
 FPFH_BINS = 11          # MVR_FPFH_BINS: a signature is 3 * 11 = 33 floats
+PFH_DIM = 125           # MVR_PFH_DIM: 5 * 5 * 5 joint bins
+PFH_STAGE = 256         # MVR_PFH_STAGE: neighbours staged on chip; above it the tiled path
 PREREJ_MAX_SAMPLES = 8  # MVR_PREREJ_MAX_SAMPLES
 
 
@@ -312,6 +319,7 @@ SIGNATURES = {
     "mvr_cloud_radius_outlier_removal": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RorParams), C.POINTER(_sz), _u32p, _u32p]),
     "mvr_cloud_mls": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(MlsParams), C.POINTER(_sz), _u32p, _fp]),
     "mvr_cloud_fpfh": (C.c_int, [_vp, C.c_int, C.POINTER(FpfhParams), _fp, _fp, _u32p]),
+    "mvr_cloud_pfh": (C.c_int, [_vp, C.c_int, C.POINTER(PfhParams), _fp, _u32p, _u32p]),
     "mvr_cloud_iss_keypoints": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(IssParams), C.POINTER(_sz), _u32p, _dp, _u32p, _u32p]),
     "mvr_cloud_iss_keypoints_border": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(IssParams), C.POINTER(IssBorderParams), C.POINTER(_sz), _u32p,
                                                  _dp, _u32p, _u32p, _u8p, _u8p]),
@@ -326,6 +334,8 @@ SIGNATURES = {
     "mvr_pose_scores": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _sz, C.c_double, C.c_int, _u32p, _dp]),
     "mvr_align_prerejective": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, C.POINTER(PrerejParams), _fp, C.POINTER(PrerejResult),
                                          C.POINTER(PrerejTrace)]),
+    "mvr_align_prerejective_dim": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, C.c_int, C.POINTER(PrerejParams), _fp, C.POINTER(PrerejResult),
+                                             C.POINTER(PrerejTrace)]),
     "mvr_cloud_set_global_base": (C.c_int, [_vp, C.c_int, _sz]),
     "mvr_cloud_append_range": (C.c_int, [_vp, C.c_int, C.c_int, _sz, _sz, _sz]),
     "mvr_nn_forward_keys": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp]),
@@ -980,6 +990,32 @@ class Context:
             res.append(cnt)
         return res[0] if len(res) == 1 else tuple(res)
 
+    def pfh(self, slot, radius=None, k=None, fma=False, return_counts=False, return_neighbors=False):
+        """pcl::PFHEstimation::compute of slot against itself with the slot's own normals (estimate_normals or upload_normals
+        first), exactly one of radius / k (1..MAX_KNN) set: the (n, 125) float32 signatures, row = point index (rules P1-P8:
+        mvr_cloud_pfh in mvr_hip.h).  A point with a non-finite coordinate or normal gets a NaN row.  Returns the signatures, or
+        (pfh[, counts][, neighbor_count]) with the return_* options: counts = the (n, 125) uint32 pair counts the signatures
+        are scaled from, neighbor_count = one uint32 per point (radius mode: the point itself included)."""
+        if (radius is None) == (k is None):
+            raise ValueError("exactly one of radius / k")
+        if k is not None and not 1 <= int(k) <= MAX_KNN:
+            raise ValueError("k must be in 1..%d" % MAX_KNN)
+        if radius is not None and not (math.isfinite(float(radius)) and float(radius) > 0.0):
+            raise ValueError("radius must be finite and > 0")
+        n = self.size(slot)
+        p = PfhParams(float(radius or 0.0), int(k or 0), int(bool(fma)))
+        out = np.empty((n, PFH_DIM), np.float32)
+        cnt = np.empty((n, PFH_DIM), np.uint32) if return_counts else None
+        nb = np.empty(n, np.uint32) if return_neighbors else None
+        _chk(_lib.mvr_cloud_pfh(self._h, int(slot), C.byref(p), _p(out, C.c_float), _p(cnt, C.c_uint32) if return_counts else None,
+                                _p(nb, C.c_uint32) if return_neighbors else None), self._h)
+        res = [out]
+        if return_counts:
+            res.append(cnt)
+        if return_neighbors:
+            res.append(nb)
+        return res[0] if len(res) == 1 else tuple(res)
+
     def boundary(self, slot, radius, angle_threshold=math.pi / 2, min_neighbors=0, fma=False, return_gap=False, return_counts=False):
         """pcl::BoundaryEstimation::compute of slot against itself, radius mode, with the slot's own normals (estimate_normals or
         upload_normals first): one bool per point, whether the neighbours within radius, projected onto the point's tangent
@@ -1127,7 +1163,7 @@ class Context:
         return out[0] if len(out) == 1 else tuple(out)
 
     def feature_knn(self, q, t, k):
-        """exact k nearest neighbours of every row of q among the rows of t in feature space (33 floats per row, FLANN's
+        """exact k nearest neighbours of every row of q among the rows of t in feature space (33 or 125 floats per row, FLANN's
         L2_Simple in f32; rules M1-M3: mvr_feature_knn in mvr_hip.h): (idx[nq, k] uint32, d2[nq, k] float32), each row ascending
         by (d2, index); UINT32_MAX / +inf for a non-finite query row and beyond the listable targets"""
         q, t = np.ascontiguousarray(q, np.float32), np.ascontiguousarray(t, np.float32)
@@ -1150,20 +1186,21 @@ class Context:
 
     def align_prerejective(self, src, tgt, src_feat, tgt_feat, max_iterations=1000, nr_samples=3, k=2, similarity=0.9,
                            max_dist=4.0, inlier_fraction=0.25, seed=0, fma=False, guess=None, return_trace=False):
-        """pcl::SampleConsensusPrerejective::align of slot src onto slot tgt from their (n, 33) descriptors (rules A1-A6:
+        """pcl::SampleConsensusPrerejective::align of slot src onto slot tgt from their (n, 33) or (n, 125) descriptors (rules A1-A6:
         mvr_align_prerejective in mvr_hip.h; k = setCorrespondenceRandomness).  A pure function of its arguments.  Returns a
         dict(converged, best_iteration, inliers, error, rejected, scored, T (4, 4) float32), or (that, trace) with return_trace:
         trace = dict(status[it], src[it, nr_samples], tgt[it, nr_samples], inliers[it], error[it], T[it, 4, 4])."""
         sf, tf = np.ascontiguousarray(src_feat, np.float32), np.ascontiguousarray(tgt_feat, np.float32)
-        if sf.shape != (self.size(src), 3 * FPFH_BINS) or tf.shape != (self.size(tgt), 3 * FPFH_BINS):
-            raise ValueError("descriptors must be (n, 33) float32 tables, one row per point of the slot")
+        dim = sf.shape[1] if sf.ndim == 2 else 0
+        if dim not in (3 * FPFH_BINS, PFH_DIM) or sf.shape != (self.size(src), dim) or tf.shape != (self.size(tgt), dim):
+            raise ValueError("descriptors must be (n, 33) or (n, 125) float32 tables of one width, one row per point of the slot")
         p = PrerejParams(int(max_iterations), int(nr_samples), int(k), float(similarity), float(max_dist), float(inlier_fraction),
                          int(seed), int(bool(fma)))
         g = to_cm(guess, np.float32) if guess is not None else None
         res = PrerejResult()
         tr = (PrerejTrace * max(int(max_iterations), 1))() if return_trace else None
-        _chk(_lib.mvr_align_prerejective(self._h, int(src), int(tgt), _p(sf, C.c_float), _p(tf, C.c_float), C.byref(p),
-                                         _p(g, C.c_float) if g is not None else None, C.byref(res), tr), self._h)
+        _chk(_lib.mvr_align_prerejective_dim(self._h, int(src), int(tgt), _p(sf, C.c_float), _p(tf, C.c_float), dim, C.byref(p),
+                                             _p(g, C.c_float) if g is not None else None, C.byref(res), tr), self._h)
         out = dict(converged=bool(res.converged), best_iteration=res.best_iteration, inliers=int(res.inliers), error=res.error,
                    rejected=int(res.rejected), scored=int(res.scored), T=from_cm(np.array(res.T, np.float32)))
         if not return_trace:

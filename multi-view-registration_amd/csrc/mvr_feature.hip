@@ -1,10 +1,11 @@
-// csrc/mvr_feature.hip -- what consumes the FPFH signatures (gfx950): exact k-NN in feature space, the scores of many posed
-// copies of one cloud against a target, and pcl::SampleConsensusPrerejective on top of the two.  The rules M1-M3, S1-S2 and
+// csrc/mvr_feature.hip -- what consumes the FPFH and PFH signatures (gfx950): exact k-NN in feature space, the scores of many
+// posed copies of one cloud against a target, and pcl::SampleConsensusPrerejective on top of the two.  The rules M1-M3, S1-S2 and
 // A1-A6 are written next to mvr_feature_knn / mvr_pose_scores / mvr_align_prerejective in mvr_hip.h.
 //
-//   * feature_knn_kernel: an all-pairs distance kernel in 33 dimensions.  One query per thread, its 33 features in registers;
-//     the block stages a tile of target rows in LDS (rows padded to 36 floats, so a row is nine 16-byte reads at an address
-//     the whole wave shares: a broadcast, no bank conflict); the k-best list is the register list of mvr_knn.hip (64-bit keys,
+//   * feature_knn_kernel (mvr_feature_knn.h): an all-pairs distance kernel in DIM = 33 (FPFH) or 125 (PFH) dimensions, a
+//     template of the row length.  One query per thread, its DIM features in registers; the block stages a tile of target rows in LDS (rows padded
+//     to a multiple of four floats, 36 or 128, so a row is nine or thirty-two 16-byte reads at an address the whole wave
+//     shares: a broadcast, no bank conflict); the k-best list is the register list of mvr_knn.hip (64-bit keys,
 //     compile-time indices, bucketed by kmax_bucket).  blockIdx.y splits the TARGET, so that 5 000 queries -- 20 blocks -- still
 //     fill the chip; every split writes its k best keys and feature_merge_kernel merges them under the same total order (the
 //     keys are distinct, so the k smallest of the union do not depend on the split).  A row with a non-finite component gives
@@ -23,15 +24,12 @@
 #include <vector>
 
 #include "mvr_internal.h"
+#include "mvr_feature_knn.h"
 #include "mvr_knn_walk.h"
 
 namespace mvr {
 namespace {
 
-constexpr int kFeatDim = 3 * MVR_FPFH_BINS;      // 33
-constexpr int kFeatPad = 36;                     // floats per staged row: 16-byte aligned
-constexpr int kFeatTile = 64;                    // target rows per LDS tile (9 KiB)
-constexpr int kFeatThreads = 256;
 constexpr int kMaxSplit = 64;
 constexpr int kScoreThreads = kKnnThreads;
 
@@ -46,57 +44,6 @@ struct DevBuf {      // a device allocation that lives as long as a call
 };
 
 // ------------------------------------------------------------------ feature k-NN
-
-// part: [split][nq][k] keys, each list ascending
-template <int KMAX>
-__global__ void __launch_bounds__(kFeatThreads) feature_knn_kernel(const float *__restrict__ q, const uint32_t nq, const float *__restrict__ t,
-                                                                   const uint32_t nt, const uint32_t rows_per_split, const int k,
-                                                                   nnkey_t *__restrict__ part)
-{
-  __shared__ __attribute__((aligned(16))) float tile[kFeatTile * kFeatPad];
-  const uint32_t tid = threadIdx.x, qi = blockIdx.x * kFeatThreads + tid;
-  const bool live = qi < nq;
-  float f[kFeatDim];
-#pragma unroll
-  for (int b = 0; b < kFeatDim; ++b) f[b] = live ? q[(size_t)qi * kFeatDim + b] : 0.f;
-  nnkey_t L[KMAX];
-#pragma unroll
-  for (int i = 0; i < KMAX; ++i) L[i] = i < KMAX - k ? 0ull : kKnnKeyEmpty;
-  const uint32_t t0 = min((uint32_t)blockIdx.y * rows_per_split, nt), t1 = min(t0 + rows_per_split, nt);
-  for (uint32_t base = t0; base < t1; base += kFeatTile) {
-    const uint32_t rows = min((uint32_t)kFeatTile, t1 - base);
-    const float *src = t + (size_t)base * kFeatDim;
-    for (uint32_t e = tid; e < rows * kFeatDim; e += kFeatThreads) tile[(e / kFeatDim) * kFeatPad + e % kFeatDim] = src[e];
-    __syncthreads();
-    if (live) {
-      for (uint32_t r = 0; r < rows; ++r) {
-        const float4 *row4 = reinterpret_cast<const float4 *>(tile + r * kFeatPad);
-        float acc = 0.f;      // M1
-#pragma unroll
-        for (int g = 0; g < kFeatDim / 4; ++g) {
-          const float4 v = row4[g];
-          float d;
-          d = f[4 * g] - v.x;     acc = acc + d * d;
-          d = f[4 * g + 1] - v.y; acc = acc + d * d;
-          d = f[4 * g + 2] - v.z; acc = acc + d * d;
-          d = f[4 * g + 3] - v.w; acc = acc + d * d;
-        }
-        {
-          const float d = f[kFeatDim - 1] - tile[r * kFeatPad + kFeatDim - 1];
-          acc = acc + d * d;
-        }
-        const nnkey_t key = ((nnkey_t)__float_as_uint(acc) << 32) | (nnkey_t)(base + r);
-        if (key < L[KMAX - 1]) knn_insert<KMAX>(L, key);
-      }
-    }
-    __syncthreads();
-  }
-  if (!live) return;
-  nnkey_t *out = part + ((size_t)blockIdx.y * nq + qi) * (size_t)k;
-#pragma unroll
-  for (int i = 0; i < KMAX; ++i)
-    if (i >= KMAX - k) out[i - (KMAX - k)] = L[i];
-}
 
 template <int KMAX>
 __global__ void __launch_bounds__(kFeatThreads) feature_merge_kernel(const nnkey_t *__restrict__ part, const uint32_t nq, const int splits, const int k,
@@ -126,16 +73,14 @@ __global__ void __launch_bounds__(kFeatThreads) feature_merge_kernel(const nnkey
 }
 
 template <int KMAX>
-void launch_feature(hipStream_t st, dim3 grid, const float *q, uint32_t nq, const float *t, uint32_t nt, uint32_t rows_per_split, int k,
-                    nnkey_t *part, uint32_t *oidx, float *od2)
+void launch_merge(hipStream_t st, unsigned qblocks, const nnkey_t *part, uint32_t nq, int splits, int k, uint32_t *oidx, float *od2)
 {
-  hipLaunchKernelGGL(feature_knn_kernel<KMAX>, grid, dim3(kFeatThreads), 0, st, q, nq, t, nt, rows_per_split, k, part);
-  hipLaunchKernelGGL(feature_merge_kernel<KMAX>, dim3(grid.x), dim3(kFeatThreads), 0, st, part, nq, (int)grid.y, k, oidx, od2);
+  hipLaunchKernelGGL(feature_merge_kernel<KMAX>, dim3(qblocks), dim3(kFeatThreads), 0, st, part, nq, splits, k, oidx, od2);
 }
 
-// the k-NN table of nq device rows in nt device rows, into device tables (either may be null); queued on the context's stream
-// (the partial lists are freed after a wait for it)
-int feature_knn_device(Ctx *c, const float *dq, size_t nq, const float *dt, size_t nt, int k, uint32_t *didx, float *dd2)
+// the k-NN table of nq device rows in nt device rows of dim floats (feat_dim_ok), into device tables (either may be null); queued
+// on the context's stream (the partial lists are freed after a wait for it)
+int feature_knn_device(Ctx *c, const float *dq, size_t nq, const float *dt, size_t nt, int dim, int k, uint32_t *didx, float *dd2)
 {
   if (nq == 0) return MVR_OK;
   if (nq > 0x7FFFFFF0ull || nt > 0x7FFFFFF0ull) return set_error(c, MVR_E_ARG, "feature_knn: table too large");
@@ -153,11 +98,14 @@ int feature_knn_device(Ctx *c, const float *dq, size_t nq, const float *dt, size
   if (part.alloc(splits * nq * (size_t)k * sizeof(nnkey_t)) != hipSuccess) return set_error(c, MVR_E_NOMEM, "feature_knn: out of device memory");
   const dim3 grid(qblocks, (unsigned)splits);
   nnkey_t *pp = part.as<nnkey_t>();
+  // (the 125-float instantiations stand in mvr_pfh.hip, beside the descriptor they serve: this file holds the 33-float ones)
+  if (dim == kPfhDim) launch_feature_knn_pfh(c->stream, grid, dq, (uint32_t)nq, dt, (uint32_t)nt, (uint32_t)rows, k, pp);
+  else launch_feature_knn<kFpfhDim>(c->stream, grid, dq, (uint32_t)nq, dt, (uint32_t)nt, (uint32_t)rows, k, pp);
   switch (kmax_bucket(k)) {
-    case 8:  launch_feature<8>(c->stream, grid, dq, (uint32_t)nq, dt, (uint32_t)nt, (uint32_t)rows, k, pp, didx, dd2); break;
-    case 16: launch_feature<16>(c->stream, grid, dq, (uint32_t)nq, dt, (uint32_t)nt, (uint32_t)rows, k, pp, didx, dd2); break;
-    case 32: launch_feature<32>(c->stream, grid, dq, (uint32_t)nq, dt, (uint32_t)nt, (uint32_t)rows, k, pp, didx, dd2); break;
-    default: launch_feature<64>(c->stream, grid, dq, (uint32_t)nq, dt, (uint32_t)nt, (uint32_t)rows, k, pp, didx, dd2); break;
+    case 8:  launch_merge<8>(c->stream, qblocks, pp, (uint32_t)nq, (int)splits, k, didx, dd2); break;
+    case 16: launch_merge<16>(c->stream, qblocks, pp, (uint32_t)nq, (int)splits, k, didx, dd2); break;
+    case 32: launch_merge<32>(c->stream, qblocks, pp, (uint32_t)nq, (int)splits, k, didx, dd2); break;
+    default: launch_merge<64>(c->stream, qblocks, pp, (uint32_t)nq, (int)splits, k, didx, dd2); break;
   }
   MVR_HIP_TRY(c, hipGetLastError());
   MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -350,10 +298,10 @@ double ms_since(const std::chrono::steady_clock::time_point t0)
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-int align_prerejective(Ctx *c, Cloud &src, Cloud &tgt, const float *src_feat, const float *tgt_feat, const mvr_prerej_params &p,
+int align_prerejective(Ctx *c, Cloud &src, Cloud &tgt, const float *src_feat, const float *tgt_feat, const int dim, const mvr_prerej_params &p,
                        const float *guess, mvr_prerej_result *res, mvr_prerej_trace *trace)
 {
-  const size_t ns = src.n, nt = tgt.n, iters = (size_t)p.max_iterations;
+  const size_t ns = src.n, nt = tgt.n, iters = (size_t)p.max_iterations, row_len = (size_t)dim;
   const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   std::memset(res, 0, sizeof *res);
   res->best_iteration = -1;
@@ -379,11 +327,11 @@ int align_prerejective(Ctx *c, Cloud &src, Cloud &tgt, const float *src_feat, co
   std::vector<float> qrows;
   for (size_t i = 0; i < ns; ++i) {
     bool ok = std::isfinite(hp[i].x) && std::isfinite(hp[i].y) && std::isfinite(hp[i].z);
-    const float *row = src_feat + i * kFeatDim;
-    for (int b = 0; b < kFeatDim && ok; ++b) ok = std::isfinite(row[b]);
+    const float *row = src_feat + i * row_len;
+    for (size_t b = 0; b < row_len && ok; ++b) ok = std::isfinite(row[b]);
     if (!ok) continue;
     elig.push_back((uint32_t)i);
-    qrows.insert(qrows.end(), row, row + kFeatDim);
+    qrows.insert(qrows.end(), row, row + row_len);
   }
   const size_t ne = elig.size();
   // the scores of the guess and of the surviving poses: one table, the guess first
@@ -395,14 +343,14 @@ int align_prerejective(Ctx *c, Cloud &src, Cloud &tgt, const float *src_feat, co
     // A3: the k-NN table of the eligible rows
     DevBuf dq, dt, dknn, delig, dstat, dsrc, dtgt, dgs, dgt;
     const size_t hyp = iters * kMaxSamples;
-    if (dq.alloc(ne * kFeatDim * 4) != hipSuccess || dt.alloc(nt * kFeatDim * 4) != hipSuccess || dknn.alloc(ne * (size_t)p.k * 4) != hipSuccess ||
+    if (dq.alloc(ne * row_len * 4) != hipSuccess || dt.alloc(nt * row_len * 4) != hipSuccess || dknn.alloc(ne * (size_t)p.k * 4) != hipSuccess ||
         delig.alloc(ne * 4) != hipSuccess || dstat.alloc(iters * 4) != hipSuccess || dsrc.alloc(hyp * 4) != hipSuccess ||
         dtgt.alloc(hyp * 4) != hipSuccess || dgs.alloc(hyp * sizeof(float4)) != hipSuccess || dgt.alloc(hyp * sizeof(float4)) != hipSuccess)
       return set_error(c, MVR_E_NOMEM, "align_prerejective: out of device memory");
-    MVR_HIP_TRY(c, hipMemcpyAsync(dq.p, qrows.data(), ne * kFeatDim * 4, hipMemcpyHostToDevice, c->stream));
-    if (nt) MVR_HIP_TRY(c, hipMemcpyAsync(dt.p, tgt_feat, nt * kFeatDim * 4, hipMemcpyHostToDevice, c->stream));
+    MVR_HIP_TRY(c, hipMemcpyAsync(dq.p, qrows.data(), ne * row_len * 4, hipMemcpyHostToDevice, c->stream));
+    if (nt) MVR_HIP_TRY(c, hipMemcpyAsync(dt.p, tgt_feat, nt * row_len * 4, hipMemcpyHostToDevice, c->stream));
     MVR_HIP_TRY(c, hipMemcpyAsync(delig.p, elig.data(), ne * 4, hipMemcpyHostToDevice, c->stream));
-    if (int rc = feature_knn_device(c, dq.as<float>(), ne, dt.as<float>(), nt, p.k, dknn.as<uint32_t>(), nullptr)) return rc;
+    if (int rc = feature_knn_device(c, dq.as<float>(), ne, dt.as<float>(), nt, dim, p.k, dknn.as<uint32_t>(), nullptr)) return rc;
     c->prerej_ms[0] = ms_since(t0);
     t0 = std::chrono::steady_clock::now();
     // A2-A4 for every iteration in one launch, the sampled points gathered on the way
@@ -484,18 +432,18 @@ using namespace mvr;
 
 API int mvr_feature_knn(mvr_ctx *ctx, const float *q, size_t nq, const float *t, size_t nt, int dim, int k, uint32_t *idx, float *d2)
 {
-  if (!ctx || dim != kFeatDim || k < 1 || k > MVR_MAX_KNN || (!q && nq) || (!t && nt)) return MVR_E_ARG;
+  if (!ctx || !feat_dim_ok(dim) || k < 1 || k > MVR_MAX_KNN || (!q && nq) || (!t && nt)) return MVR_E_ARG;
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   MVR_HIP_TRY(c, hipSetDevice(c->device));
   if (nq == 0) return MVR_OK;
   MVR_MAY_BLOCK(c, "feature_knn reads back");
-  const size_t m = nq * (size_t)k;
+  const size_t m = nq * (size_t)k, row_len = (size_t)dim;
   DevBuf dq, dt, di, dd;
-  if (dq.alloc(nq * kFeatDim * 4) != hipSuccess || dt.alloc(nt * kFeatDim * 4) != hipSuccess || di.alloc(m * 4) != hipSuccess || dd.alloc(m * 4) != hipSuccess)
+  if (dq.alloc(nq * row_len * 4) != hipSuccess || dt.alloc(nt * row_len * 4) != hipSuccess || di.alloc(m * 4) != hipSuccess || dd.alloc(m * 4) != hipSuccess)
     return set_error(c, MVR_E_NOMEM, "mvr_feature_knn: out of device memory");
-  MVR_HIP_TRY(c, hipMemcpyAsync(dq.p, q, nq * kFeatDim * 4, hipMemcpyHostToDevice, c->stream));
-  if (nt) MVR_HIP_TRY(c, hipMemcpyAsync(dt.p, t, nt * kFeatDim * 4, hipMemcpyHostToDevice, c->stream));
-  if (int rc = feature_knn_device(c, dq.as<float>(), nq, dt.as<float>(), nt, k, di.as<uint32_t>(), dd.as<float>())) return rc;
+  MVR_HIP_TRY(c, hipMemcpyAsync(dq.p, q, nq * row_len * 4, hipMemcpyHostToDevice, c->stream));
+  if (nt) MVR_HIP_TRY(c, hipMemcpyAsync(dt.p, t, nt * row_len * 4, hipMemcpyHostToDevice, c->stream));
+  if (int rc = feature_knn_device(c, dq.as<float>(), nq, dt.as<float>(), nt, dim, k, di.as<uint32_t>(), dd.as<float>())) return rc;
   if (idx) MVR_HIP_TRY(c, hipMemcpy(idx, di.p, m * 4, hipMemcpyDeviceToHost));
   if (d2) MVR_HIP_TRY(c, hipMemcpy(d2, dd.p, m * 4, hipMemcpyDeviceToHost));
   return MVR_OK;
@@ -520,14 +468,20 @@ API int mvr_pose_scores(mvr_ctx *ctx, int src_slot, int tgt_slot, const float *T
   return MVR_OK;
 }
 
-API int mvr_align_prerejective(mvr_ctx *ctx, int src_slot, int tgt_slot, const float *src_feat, const float *tgt_feat,
-                               const mvr_prerej_params *p, const float *guess, mvr_prerej_result *result, mvr_prerej_trace *trace)
+API int mvr_align_prerejective_dim(mvr_ctx *ctx, int src_slot, int tgt_slot, const float *src_feat, const float *tgt_feat, int dim,
+                                   const mvr_prerej_params *p, const float *guess, mvr_prerej_result *result, mvr_prerej_trace *trace)
 {
-  if (!ctx || !p || !result || !src_feat || !tgt_feat || !slot_ok(src_slot) || !slot_ok(tgt_slot)) return MVR_E_ARG;
+  if (!ctx || !p || !result || !src_feat || !tgt_feat || !slot_ok(src_slot) || !slot_ok(tgt_slot) || !feat_dim_ok(dim)) return MVR_E_ARG;
   if (p->max_iterations < 0 || p->nr_samples < 3 || p->nr_samples > kMaxSamples || p->k < 1 || p->k > MVR_MAX_KNN) return MVR_E_ARG;
   if (!(p->similarity >= 0.0 && p->similarity < 1.0) || !(std::isfinite(p->max_dist) && p->max_dist > 0.0) ||
       !(p->inlier_fraction > 0.0 && p->inlier_fraction <= 1.0)) return MVR_E_ARG;
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   MVR_HIP_TRY(c, hipSetDevice(c->device));
-  return align_prerejective(c, c->slots[src_slot], c->slots[tgt_slot], src_feat, tgt_feat, *p, guess, result, trace);
+  return align_prerejective(c, c->slots[src_slot], c->slots[tgt_slot], src_feat, tgt_feat, dim, *p, guess, result, trace);
+}
+
+API int mvr_align_prerejective(mvr_ctx *ctx, int src_slot, int tgt_slot, const float *src_feat, const float *tgt_feat,
+                               const mvr_prerej_params *p, const float *guess, mvr_prerej_result *result, mvr_prerej_trace *trace)
+{
+  return mvr_align_prerejective_dim(ctx, src_slot, tgt_slot, src_feat, tgt_feat, kFpfhDim, p, guess, result, trace);
 }

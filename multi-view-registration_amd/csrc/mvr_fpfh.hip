@@ -4,8 +4,9 @@
 // One thread per query, in the order of the cloud's model grid (ensure_model_grid; the helpers of mvr_knn_walk.h), so the 64
 // lanes of a wave are neighbours on the surface and walk the same cells.  Every table a walk reads lies in GRID order, so a
 // neighbour found at grid position j has its normal and its SPFH row at j and the neighbours of one cell are consecutive rows:
-//   1. fpfh_normals_kernel copies the slot's normals from index order to grid order; w = 1 marks a valid point (finite
-//      coordinates and a finite normal), w = 0 an invalid one, which every later walk skips.
+//   1. valid_normals_kernel (mvr_pair_features.h, where the pair features F3 / F4 stand that mvr_pfh.hip shares) copies the
+//      slot's normals from index order to grid order; w = 1 marks a valid point (finite coordinates and a finite normal),
+//      w = 0 an invalid one, which every later walk skips.
 //   2. fpfh_spfh_kernel: the ball walk (knn_ball_walk) computes the three f32 pair features of every neighbour and counts them
 //      into 3 x 11 bins.  The bin index is a runtime value, and a runtime-indexed private array lives in scratch memory
 //      (mvr_knn.hip), so the 33 u32 counters of a thread lie in LDS as hist[bin][thread]: lane t reads and writes the address
@@ -22,6 +23,7 @@
 
 #include "mvr_internal.h"
 #include "mvr_knn_walk.h"
+#include "mvr_pair_features.h"
 
 namespace mvr {
 namespace {
@@ -38,25 +40,6 @@ struct FpfhArgs {
   uint32_t *count;                 // n_i by index
   float r2;
 };
-
-__device__ __forceinline__ float dot3(const float ax, const float ay, const float az, const float bx, const float by, const float bz)
-{
-  return (ax * bx + ay * by) + az * bz;
-}
-
-// F4: the bin of a scaled coordinate, clamped to 0..10 (a NaN goes to 0)
-__device__ __forceinline__ int fpfh_bin(const double x) { return (int)fmin(fmax(floor((double)kBins * x), 0.0), (double)(kBins - 1)); }
-
-__global__ void __launch_bounds__(kFpfhThreads) fpfh_normals_kernel(FpfhArgs a)
-{
-  const KnnSlot &S = a.S;
-  const uint32_t pos = blockIdx.x * kFpfhThreads + threadIdx.x;
-  if (pos >= S.nq) return;
-  const float4 p = S.qs[pos];
-  const float4 n = a.src_nrm[S.q_by_pos ? pos : __float_as_uint(p.w)];
-  const bool ok = finite3(p) && finite3(n);
-  a.gn[pos] = make_float4(n.x, n.y, n.z, ok ? 1.f : 0.f);
-}
 
 template <bool FMA>
 __global__ void __launch_bounds__(kFpfhThreads) fpfh_spfh_kernel(FpfhArgs a)
@@ -78,33 +61,15 @@ __global__ void __launch_bounds__(kFpfhThreads) fpfh_spfh_kernel(FpfhArgs a)
 #pragma unroll
   for (int k = 0; k < kRow; ++k) hist[k * kFpfhThreads + tid] = 0u;
   uint32_t n = 0;
-  const float d_pi = (float)(1.0 / (2.0 * M_PI));
   knn_ball_walk<FMA>(S, q, a.r2, [&](const float4 p, const uint32_t j) {
     const float4 nj = a.gn[j];
     if (nj.w == 0.f) return;
     ++n;
     if (j == pos) return;
-    // F3
-    float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-    const float f4 = sqrtf(dot3(dx, dy, dz, dx, dy, dz));
-    if (f4 == 0.f) return;
-    const float a1 = dot3(ni.x, ni.y, ni.z, dx, dy, dz) / f4, a2 = dot3(nj.x, nj.y, nj.z, dx, dy, dz) / f4;
-    const bool swap = fabsf(a1) < fabsf(a2);
-    const float n1x = swap ? nj.x : ni.x, n1y = swap ? nj.y : ni.y, n1z = swap ? nj.z : ni.z;
-    const float n2x = swap ? ni.x : nj.x, n2y = swap ? ni.y : nj.y, n2z = swap ? ni.z : nj.z;
-    const float f3 = swap ? -a2 : a1;
-    if (swap) { dx = -dx; dy = -dy; dz = -dz; }
-    float vx = dy * n1z - dz * n1y, vy = dz * n1x - dx * n1z, vz = dx * n1y - dy * n1x;
-    const float vn = sqrtf(dot3(vx, vy, vz, vx, vy, vz));
-    if (vn == 0.f) return;
-    vx /= vn; vy /= vn; vz /= vn;
-    const float wx = n1y * vz - n1z * vy, wy = n1z * vx - n1x * vz, wz = n1x * vy - n1y * vx;
-    const float f2 = dot3(vx, vy, vz, n2x, n2y, n2z);
-    const float f1 = atan2f(dot3(wx, wy, wz, n2x, n2y, n2z), dot3(n1x, n1y, n1z, n2x, n2y, n2z));
-    // F4, F5
-    const int b1 = fpfh_bin(((double)f1 + M_PI) * (double)d_pi);
-    const int b2 = fpfh_bin(((double)f2 + 1.0) * 0.5);
-    const int b3 = fpfh_bin(((double)f3 + 1.0) * 0.5);
+    float f1, f2, f3;
+    if (!pair_features(q, ni, p, nj, &f1, &f2, &f3)) return;      // F3
+    int b1, b2, b3;
+    pair_bins<kBins>(f1, f2, f3, &b1, &b2, &b3);                  // F4, F5
     hist[b1 * kFpfhThreads + tid] += 1u;
     hist[(kBins + b2) * kFpfhThreads + tid] += 1u;
     hist[(2 * kBins + b3) * kFpfhThreads + tid] += 1u;
@@ -187,7 +152,7 @@ int fpfh_cloud(Ctx *c, Cloud &cl, const mvr_fpfh_params &p, float *fpfh, float *
   float *rows = s.take<float>(spfh ? m : 1);
   a.r2 = clamp_r2(p.radius);
   const dim3 grid(blocks_for(n, kFpfhThreads)), block(kFpfhThreads);
-  hipLaunchKernelGGL(fpfh_normals_kernel, grid, block, 0, c->stream, a);
+  hipLaunchKernelGGL(valid_normals_kernel<kFpfhThreads>, grid, block, 0, c->stream, a.S, a.src_nrm, a.gn);
   MVR_HIP_TRY(c, hipGetLastError());
   if (p.fma_dist) hipLaunchKernelGGL(fpfh_spfh_kernel<true>, grid, block, 0, c->stream, a);
   else hipLaunchKernelGGL(fpfh_spfh_kernel<false>, grid, block, 0, c->stream, a);

@@ -284,6 +284,8 @@ struct Ctx {
   // feature matching and pose scoring (mvr_feature.hip): blocks a target is split over (0: by the launch size) and poses per
   // scoring launch -- results never depend on either; wall milliseconds of the last mvr_align_prerejective by phase
   int feat_split = 0, score_chunk = 256;
+  int pfh_stage = MVR_PFH_STAGE;                         // neighbours a PFH query stages in LDS; above it the tiled path (tune "pfh_stage")
+  uint64_t pfh_tiled = 0, pfh_pairs = 0;                 // of the last mvr_cloud_pfh: queries on the tiled path, pairs of all queries
   double prerej_ms[3] = {0.0, 0.0, 0.0};                 // matching, hypothesis generation, scoring
   int rej_sac_chunk = 0;                                 // the sample-consensus rejector: attempts per chunk (0: 64 for a stage's first chunk, 256 from then on -- profiles/reject_sac_bench.json); results never depend on it
   mvr_rej_sac_result last_sac = {}; bool last_sac_set = false;      // the last sample-consensus stage that ran on this context (mvr_ctx_last_sample_consensus)

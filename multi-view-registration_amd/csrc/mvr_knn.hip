@@ -180,6 +180,21 @@ int run_batches(Ctx *c, std::vector<KnnSlot> &all, KnnBatch proto, int kmax, int
 }
 
 }  // namespace
+
+// the k-NN lists of a cloud (n > 0, past knn_cloud_ok) in itself -- what mvr_knn gives for q_slot == t_slot -- into the device
+// tables didx / dd2, [n][k] by index; queued on the context's stream (mvr_pfh.hip: the k-neighbour mode)
+int knn_self_device(Ctx *c, Cloud &cl, int k, bool fma, uint32_t *didx, float *dd2)
+{
+  KnnSlot S{};
+  if (int rc = fill_target(c, cl, S)) return rc;
+  fill_queries(cl, S);
+  S.oidx = didx; S.od2 = dd2;
+  std::vector<KnnSlot> all{S};
+  KnnBatch proto{};
+  proto.k = k;
+  return run_batches(c, all, proto, kmax_bucket(k), 0, fma);
+}
+
 }  // namespace mvr
 
 using namespace mvr;

@@ -251,6 +251,9 @@ inline void fill_queries(const Cloud &q, KnnSlot &S)
   S.nq = (uint32_t)q.n;
 }
 
+// the k-NN lists of a cloud (n > 0, past knn_cloud_ok) in itself into device tables [n][k] by index (mvr_knn.hip); queued
+int knn_self_device(Ctx *c, Cloud &cl, int k, bool fma, uint32_t *didx, float *dd2);
+
 // pcl::BoundaryEstimation over a filled slot (mvr_boundary.hip; rules B1-B5 at mvr_cloud_boundary in mvr_hip.h), queued on the
 // context's stream: flag / max_gap / count by index, flag_grid by the query's grid position (the position a later walk of the
 // same slot finds the point at); each of the four may be null.  nrm: the cloud's normals, by index.
