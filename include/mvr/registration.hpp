@@ -729,14 +729,179 @@ class NormalDistributionsTransform {
 
 // ---------------------------------------------------------------- normals
 namespace search {
-// pcl::search::KdTree: accepted and ignored -- the neighbour search is the library's grid walk on the GPU
+// pcl::search::KdTree: the neighbour search is the library's grid walk on the GPU (mvr_knn, mvr_radius_search in mvr_hip.h), so
+// there is no tree to build: setInputCloud stores the pointer, the first search uploads the cloud into a slot of the thread's
+// context, and later searches reuse it until the next setInputCloud.  The feature classes that take a tree through
+// setSearchMethod go on ignoring it (they upload their own input).  nearestKSearch / radiusSearch have PCL's signatures and
+// return the number of neighbours found; the lists are those of mvr_knn (ascending by (d2, index), cut at the last finite
+// entry) and of mvr_radius_search (rules RS1-RS5: d2 <= r2, not FLANN's <; with setSortedResults(false) and max_nn = 0 the
+// order is unspecified).  The single-point forms upload a one-point query cloud per call: the batch forms are the ones to use.
+// A search before setInputCloud, a k outside 1..MVR_MAX_KNN or a radius that is not finite and > 0 prints an error and finds
+// nothing (0).
 template <typename PointT>
 class KdTree {
  public:
   typedef std::shared_ptr<KdTree<PointT> > Ptr;
   typedef std::shared_ptr<const KdTree<PointT> > ConstPtr;
-  explicit KdTree(bool sorted = true) { (void)sorted; }
-  void setInputCloud(const typename PointCloud<PointT>::ConstPtr &) {}
+  typedef PointCloud<PointT> Cloud;
+  typedef typename Cloud::ConstPtr PointCloudConstPtr;
+
+  explicit KdTree(bool sorted = true) : sorted_(sorted) {}
+  void setInputCloud(const PointCloudConstPtr &cloud) { input_ = cloud; slot_.reset(); }
+  PointCloudConstPtr getInputCloud() const { return input_; }
+  void setSortedResults(bool sorted) { sorted_ = sorted; }
+  bool getSortedResults() const { return sorted_; }
+
+  int nearestKSearch(const PointT &point, int k, std::vector<int> &k_indices, std::vector<float> &k_sqr_distances) const
+  {
+    std::vector<std::vector<int> > vi; std::vector<std::vector<float> > vd;
+    knn(&point, 1, k, vi, vd);
+    return take_first(vi, vd, k_indices, k_sqr_distances);
+  }
+  int nearestKSearch(const Cloud &cloud, int index, int k, std::vector<int> &k_indices, std::vector<float> &k_sqr_distances) const
+  {
+    if (!index_ok(cloud, index, "nearestKSearch")) { k_indices.clear(); k_sqr_distances.clear(); return 0; }
+    return nearestKSearch(cloud.points[(size_t)index], k, k_indices, k_sqr_distances);
+  }
+  int nearestKSearch(int index, int k, std::vector<int> &k_indices, std::vector<float> &k_sqr_distances) const
+  {
+    if (!input_ok("nearestKSearch")) { k_indices.clear(); k_sqr_distances.clear(); return 0; }
+    return nearestKSearch(*input_, index, k, k_indices, k_sqr_distances);
+  }
+  void nearestKSearch(const Cloud &cloud, const std::vector<int> &indices, int k, std::vector<std::vector<int> > &k_indices,
+                      std::vector<std::vector<float> > &k_sqr_distances) const
+  {
+    std::vector<PointT> sel;
+    if (!select(cloud, indices, sel, "nearestKSearch")) { k_indices.clear(); k_sqr_distances.clear(); return; }
+    knn(indices.empty() ? (cloud.empty() ? nullptr : &cloud.points[0]) : sel.data(), indices.empty() ? cloud.size() : sel.size(), k, k_indices,
+        k_sqr_distances);
+  }
+
+  int radiusSearch(const PointT &point, double radius, std::vector<int> &k_indices, std::vector<float> &k_sqr_distances, unsigned int max_nn = 0) const
+  {
+    std::vector<std::vector<int> > vi; std::vector<std::vector<float> > vd;
+    radius_rows(&point, 1, radius, max_nn, vi, vd);
+    return take_first(vi, vd, k_indices, k_sqr_distances);
+  }
+  int radiusSearch(const Cloud &cloud, int index, double radius, std::vector<int> &k_indices, std::vector<float> &k_sqr_distances,
+                   unsigned int max_nn = 0) const
+  {
+    if (!index_ok(cloud, index, "radiusSearch")) { k_indices.clear(); k_sqr_distances.clear(); return 0; }
+    return radiusSearch(cloud.points[(size_t)index], radius, k_indices, k_sqr_distances, max_nn);
+  }
+  int radiusSearch(int index, double radius, std::vector<int> &k_indices, std::vector<float> &k_sqr_distances, unsigned int max_nn = 0) const
+  {
+    if (!input_ok("radiusSearch")) { k_indices.clear(); k_sqr_distances.clear(); return 0; }
+    return radiusSearch(*input_, index, radius, k_indices, k_sqr_distances, max_nn);
+  }
+  void radiusSearch(const Cloud &cloud, const std::vector<int> &indices, double radius, std::vector<std::vector<int> > &k_indices,
+                    std::vector<std::vector<float> > &k_sqr_distances, unsigned int max_nn = 0) const
+  {
+    std::vector<PointT> sel;
+    if (!select(cloud, indices, sel, "radiusSearch")) { k_indices.clear(); k_sqr_distances.clear(); return; }
+    radius_rows(indices.empty() ? (cloud.empty() ? nullptr : &cloud.points[0]) : sel.data(), indices.empty() ? cloud.size() : sel.size(), radius, max_nn,
+                k_indices, k_sqr_distances);
+  }
+
+ private:
+  static int take_first(std::vector<std::vector<int> > &vi, std::vector<std::vector<float> > &vd, std::vector<int> &i, std::vector<float> &d)
+  {
+    i.clear(); d.clear();
+    if (!vi.empty()) { i.swap(vi[0]); d.swap(vd[0]); }
+    return (int)i.size();
+  }
+  bool input_ok(const char *fn) const
+  {
+    if (input_) return true;
+    std::fprintf(stderr, "[search::KdTree::%s] No input dataset was given (setInputCloud)!\n", fn);
+    return false;
+  }
+  bool index_ok(const Cloud &cloud, int index, const char *fn) const
+  {
+    if (index >= 0 && (size_t)index < cloud.size()) return true;
+    std::fprintf(stderr, "[search::KdTree::%s] The index %d is outside the cloud (%zu points).\n", fn, index, cloud.size());
+    return false;
+  }
+  bool select(const Cloud &cloud, const std::vector<int> &indices, std::vector<PointT> &sel, const char *fn) const
+  {
+    sel.reserve(indices.size());
+    for (size_t i = 0; i < indices.size(); ++i) {
+      if (!index_ok(cloud, indices[i], fn)) return false;
+      sel.push_back(cloud.points[(size_t)indices[i]]);
+    }
+    return true;
+  }
+  // the slot that holds the input cloud, uploaded at the first search after setInputCloud
+  int target() const
+  {
+    if (!slot_) {
+      slot_.reset(new SlotGuard());
+      Device::instance().upload(slot_->s, *input_);
+    }
+    return slot_->s;
+  }
+  static void upload_queries(Device &d, int slot, const PointT *q, size_t n)
+  {
+    static_assert(sizeof(PointT) == 16, "16-byte XYZ points expected");
+    d.check(mvr_cloud_upload(d.ctx(), slot, n ? q->data : nullptr, n, sizeof(PointT)), "mvr_cloud_upload");
+  }
+  void knn(const PointT *q, size_t n, int k, std::vector<std::vector<int> > &vi, std::vector<std::vector<float> > &vd) const
+  {
+    vi.clear(); vd.clear();
+    if (!input_ok("nearestKSearch")) return;
+    if (k < 1 || k > MVR_MAX_KNN) {
+      std::fprintf(stderr, "[search::KdTree::nearestKSearch] k = %d is outside 1..%d.\n", k, MVR_MAX_KNN);
+      return;
+    }
+    vi.resize(n); vd.resize(n);
+    if (!n) return;
+    Device &d = Device::instance();
+    const int t = target();
+    SlotGuard qs;
+    upload_queries(d, qs.s, q, n);
+    std::vector<uint32_t> idx(n * (size_t)k);
+    std::vector<float> d2(n * (size_t)k);
+    d.check(mvr_knn(d.ctx(), qs.s, t, k, 0, idx.data(), d2.data()), "mvr_knn");
+    for (size_t i = 0; i < n; ++i) {
+      size_t m = 0;
+      while (m < (size_t)k && idx[i * k + m] != UINT32_MAX) ++m;
+      vi[i].assign(idx.begin() + (ptrdiff_t)(i * k), idx.begin() + (ptrdiff_t)(i * k + m));
+      vd[i].assign(d2.begin() + (ptrdiff_t)(i * k), d2.begin() + (ptrdiff_t)(i * k + m));
+    }
+  }
+  void radius_rows(const PointT *q, size_t n, double radius, unsigned int max_nn, std::vector<std::vector<int> > &vi,
+                   std::vector<std::vector<float> > &vd) const
+  {
+    vi.clear(); vd.clear();
+    if (!input_ok("radiusSearch")) return;
+    if (!(std::isfinite(radius) && radius > 0.0)) {
+      std::fprintf(stderr, "[search::KdTree::radiusSearch] The radius (%f) must be finite and > 0.\n", radius);
+      return;
+    }
+    vi.resize(n); vd.resize(n);
+    if (!n) return;
+    Device &d = Device::instance();
+    const int t = target();
+    SlotGuard qs;
+    upload_queries(d, qs.s, q, n);
+    mvr_radius_params p;
+    mvr_radius_default_params(&p);
+    p.radius = radius; p.max_nn = max_nn; p.sorted = sorted_ ? 1 : 0;
+    std::vector<uint64_t> offsets(n + 1);
+    size_t total = 0;
+    d.check(mvr_radius_search(d.ctx(), qs.s, t, &p, offsets.data(), nullptr, nullptr, 0, &total), "mvr_radius_search");
+    std::vector<uint32_t> idx(total ? total : 1);
+    std::vector<float> d2(total ? total : 1);
+    if (total) d.check(mvr_radius_search(d.ctx(), qs.s, t, &p, offsets.data(), idx.data(), d2.data(), total, &total), "mvr_radius_search");
+    for (size_t i = 0; i < n; ++i) {
+      vi[i].assign(idx.begin() + (ptrdiff_t)offsets[i], idx.begin() + (ptrdiff_t)offsets[i + 1]);
+      vd[i].assign(d2.begin() + (ptrdiff_t)offsets[i], d2.begin() + (ptrdiff_t)offsets[i + 1]);
+    }
+  }
+
+  bool sorted_;
+  PointCloudConstPtr input_;
+  mutable std::shared_ptr<SlotGuard> slot_;      // (copies of a tree share the uploaded cloud until one of them gets another)
 };
 }  // namespace search
 

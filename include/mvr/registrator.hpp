@@ -35,6 +35,15 @@ typedef PointCloud<PCLPoint> PCLPointCloud;      // mvr/include/types.h:17
 
 class Registrator;
 
+// what ScanCloud::radiusSearch returns: the rows of mvr_radius_search (mvr_hip.h) as CSR -- the neighbours of query i are
+// indices[offsets[i] .. offsets[i + 1]) with their squared distances beside them
+struct NeighborLists {
+  std::vector<uint64_t> offsets;
+  std::vector<uint32_t> indices;
+  std::vector<float> sqr_distances;
+  size_t rows() const { return offsets.empty() ? 0 : offsets.size() - 1; }
+};
+
 // One scan: raw points + its pose (osg::Matrix of the reference's
 // osg::MatrixTransform base) + the flags the driver consults.
 class ScanCloud {
@@ -455,6 +464,37 @@ class ScanCloud {
     p.radius = radius; p.k = 0; p.fma_dist = 0;
     d.check(mvr_cloud_pfh(d.ctx(), s.s, &p, out[0].histogram, nullptr, nullptr), "mvr_cloud_pfh");
     return true;
+  }
+
+  // EXTENSION (pcl::search::KdTree::radiusSearch for every point at once, on the GPU; rules RS1-RS11: mvr_radius_search in
+  // mvr_hip.h): the neighbours within `radius` of every raw point of this cloud among its own points -- each row starts with the
+  // point itself -- or of every raw point of `queries` among the points of this cloud; rows ascending by (distance, index), at
+  // most max_nn entries each when max_nn > 0.  A radius that is not finite and > 0 prints an error and returns empty lists.
+  NeighborLists radiusSearch(double radius, unsigned int max_nn = 0) const { return radiusSearch(*this, radius, max_nn); }
+  NeighborLists radiusSearch(const ScanCloud &queries, double radius, unsigned int max_nn = 0) const
+  {
+    NeighborLists out;
+    if (!(std::isfinite(radius) && radius > 0.0)) {
+      std::fprintf(stderr, "[ScanCloud::radiusSearch] The radius (%f) must be finite and > 0.\n", radius);
+      return out;
+    }
+    const size_t n = queries.points.size();
+    out.offsets.assign(n + 1, 0);
+    if (!n) return out;
+    Device &d = Device::instance();
+    SlotGuard t;
+    d.upload(t.s, points);
+    std::unique_ptr<SlotGuard> q;
+    if (&queries != this) { q.reset(new SlotGuard()); d.upload(q->s, queries.points); }
+    const int qs = q ? q->s : t.s;
+    mvr_radius_params p;
+    mvr_radius_default_params(&p);
+    p.radius = radius; p.max_nn = max_nn;
+    size_t total = 0;
+    d.check(mvr_radius_search(d.ctx(), qs, t.s, &p, out.offsets.data(), nullptr, nullptr, 0, &total), "mvr_radius_search");
+    out.indices.resize(total); out.sqr_distances.resize(total);
+    if (total) d.check(mvr_radius_search(d.ctx(), qs, t.s, &p, out.offsets.data(), out.indices.data(), out.sqr_distances.data(), total, &total), "mvr_radius_search");
+    return out;
   }
 
   // EXTENSION (pcl::BoundaryEstimation on the raw points, on the GPU; rules: mvr_cloud_boundary in mvr_hip.h): one flag per point,

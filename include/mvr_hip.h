@@ -264,6 +264,54 @@ typedef struct {
 int  mvr_cloud_estimate_normals(mvr_ctx *ctx, int count, const int *slots, const mvr_normal_params *p,
                                 float *const *curvature);
 
+/* ---- radius search (EXTENSION: pcl::search::KdTree::radiusSearch) as CSR lists -----------------------------------
+ * Every neighbour of every point of q_slot within `radius` in t_slot, as variable-length rows.
+ *  RS1. j is a neighbour of query i iff the f32 d2(i, j) <= (float)(radius * radius), that bound kept finite; d2 is the
+ *       expression of mvr_nn, or the fma chain with fma_dist.  This is the library's own neighbour rule (rule 14 of the
+ *       outlier section, the radius mode of mvr_cloud_estimate_normals, M1, F1, P2 ...): a list returned here IS the
+ *       neighbourhood every other radius-mode entry uses.  DEVIATION: FLANN tests a strict < on its own arithmetic, so
+ *       a point at exactly the radius is listed here and not there.  With q_slot == t_slot a point is in its own row
+ *       (d2 = 0), as in PCL.
+ *  RS2. Non-finite points: N1 and N2 of mvr_knn.  A non-finite target point, or a pair whose f32 d2 is not finite, is in
+ *       no row; a non-finite query has an empty row; an empty target, or one without a finite point, gives empty rows.
+ *  RS3. sorted = 1: a row ascends under the key (d2, index), the key of mvr_knn.  The order is total: exact ties and
+ *       duplicates have one answer.
+ *  RS4. max_nn > 0: a row holds the min(n_i, max_nn) smallest entries under that key, ALWAYS in the order of RS3,
+ *       whatever `sorted` says -- one valid instance of what FLANN may return, and the only deterministic one.  For
+ *       max_nn <= MVR_MAX_KNN the row is exactly the prefix of mvr_knn's list with d2 <= r2.
+ *  RS5. sorted = 0 and max_nn = 0: the same set per row; the order is unspecified, but identical from call to call with
+ *       the same arguments on the same slot state.
+ *  RS6. CSR: offsets[i] .. offsets[i + 1] is the row of query INDEX i; offsets[0] = 0, offsets[n_q] = total; idx and d2
+ *       are parallel.
+ *  RS7. Sizing: offsets (n_q + 1 entries, optional) and *total (optional) are written on every successful count.
+ *       idx == NULL && d2 == NULL is a count-only call, `capacity` is ignored.  Otherwise capacity >= total is required:
+ *       a short capacity returns MVR_E_ARG with *total and offsets written and no entry written; mvr_last_error names
+ *       both numbers.  Either of idx / d2 alone may be NULL.
+ *  RS8. A total above MVR_RADIUS_MAX_TOTAL is refused with MVR_E_ARG, *total (and offsets) still written, so that the
+ *       caller can split the queries over several slots.  The bound is what the 32-bit item count of the segmented sort
+ *       addresses; with max_nn it is also applied to the uncapped lengths of the rows longer than the stage, summed.
+ *  RS9. MVR_E_ARG before any GPU work, writing nothing, with mvr_last_error set wherever there is a ctx: a NULL ctx or
+ *       params, a bad slot, a radius that is not finite and > 0, a cloud too large for the walks or whose points are not
+ *       current.  n_q == 0 is MVR_OK with offsets[0] = 0.
+ * RS10. Neither slot is modified: the target gets its own-coordinates grid as in mvr_knn (and the queries theirs, for the
+ *       walking order); nothing else about a slot changes.
+ * RS11. Results do not depend on the grid's resolution, on the tune key "radius_stage", or on the path a row took.
+ * RS12. (internal) radius_search_device leaves offsets / idx / d2 on the device; this entry is that plus the copies home.
+ * A row of more than MVR_RADIUS_STAGE entries (tune key "radius_stage", MVR_MAX_KNN..MVR_RADIUS_STAGE, lowers the threshold)
+ * is ordered by a segmented radix sort in device memory instead of on chip; mvr_ctx_stat "radius_long_rows" counts them. */
+#define MVR_RADIUS_STAGE 1024                /* entries of one row staged and ordered in LDS; above it the long-row path */
+#define MVR_RADIUS_MAX_TOTAL 0x7FFFFFFFull   /* RS8 */
+typedef struct {
+  double   radius;    /* finite, > 0                                                     */
+  uint32_t max_nn;    /* 0: no cap (PCL's default); else at most max_nn entries per row  */
+  int      sorted;    /* setSortedResults; 1 is PCL's default                            */
+  int      fma_dist;
+} mvr_radius_params;
+void mvr_radius_default_params(mvr_radius_params *p);   /* radius 0 (to be set), max_nn 0, sorted 1, fma_dist 0 */
+int  mvr_radius_search(mvr_ctx *ctx, int q_slot, int t_slot, const mvr_radius_params *p,
+                       uint64_t *offsets /* n_q + 1, or NULL */, uint32_t *idx, float *d2 /* `capacity` entries each, or NULL */,
+                       size_t capacity, size_t *total /* or NULL */);
+
 /* ---- sparse outlier removal (EXTENSION: pcl::StatisticalOutlierRemoval and pcl::RadiusOutlierRemoval) ------------
  * The reference pins no PCL version; where PCL versions differ, or PCL is loose, the rule below is this library's rule.
  * Common to both filters:
@@ -1498,7 +1546,9 @@ enum { MVR_K_NN = 0, MVR_K_REDUCE = 1, MVR_K_XFORM = 2, MVR_K_GLUE = 3,
  * too; 0, default, until a recorded two-GPU run);
  * feature matching and pose scoring: "feat_split" (blocks the target of mvr_feature_knn is split over, 1..64; 0, default: by the
  * launch size), "score_chunk" (poses per launch of mvr_pose_scores, default 256); "pfh_stage" (mvr_cloud_pfh: the neighbourhood
- * size above which a query takes the tiled path, MVR_MAX_KNN..MVR_PFH_STAGE, default MVR_PFH_STAGE);
+ * size above which a query takes the tiled path, MVR_MAX_KNN..MVR_PFH_STAGE, default MVR_PFH_STAGE); "radius_stage"
+ * (mvr_radius_search: the row length above which a row takes the long-row path, MVR_MAX_KNN..MVR_RADIUS_STAGE, default
+ * MVR_RADIUS_STAGE);
  * plane segmentation: "sac_chunk" (attempts generated and scored per chunk, 1..256; 0, default: 64 for the first chunk of a
  * call and 256 from then on);
  * the sample-consensus rejector: "rej_sac_chunk" (attempts generated and scored per chunk, 1..256; 0, default: 64 for the first
@@ -1513,7 +1563,10 @@ int  mvr_ctx_pass_log(mvr_ctx *ctx, double *ms, int cap, int *n);
  * enqueued ahead of their poses, see "pipeline"), "fused_passes" (fused pair batches run so far), "blocking_events"
  * (times the library waited for its stream or re-allocated a buffer: a pass without any is in steady state),
  * "prerej_match_ms" / "prerej_hypotheses_ms" / "prerej_score_ms" (wall milliseconds of the last mvr_align_prerejective by phase),
- * "pfh_stage" (the tune key's value), "pfh_tiled_queries" / "pfh_pairs" (of the last mvr_cloud_pfh: see there) */
+ * "pfh_stage" (the tune key's value), "pfh_tiled_queries" / "pfh_pairs" (of the last mvr_cloud_pfh: see there),
+ * "radius_stage" (the tune key's value), "radius_long_rows" (of the last mvr_radius_search: rows on the long-row path),
+ * "radius_count_ms" / "radius_fill_ms" / "radius_copy_ms" (wall milliseconds of the last mvr_radius_search by phase: the count up to
+ * the read-back of the total; the fill and the ordering of the rows, with the copy of the offsets; the copies of idx / d2 to the host) */
 int  mvr_ctx_stat(mvr_ctx *ctx, const char *key, double *value);
 /* diagnostics: the ordering of the cloud in `slot` (sorted position -> original index); *n = its length (0: none yet) */
 int  mvr_debug_order(mvr_ctx *ctx, int slot, uint32_t *perm, size_t cap, size_t *n);

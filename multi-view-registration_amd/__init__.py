@@ -219,6 +219,11 @@ class PfhParams(C.Structure):
     _fields_ = [("radius", C.c_double), ("k", C.c_int), ("fma_dist", C.c_int)]
 
 
+class RadiusParams(C.Structure):
+    """mvr_radius_params"""
+    _fields_ = [("radius", C.c_double), ("max_nn", C.c_uint32), ("sorted", C.c_int), ("fma_dist", C.c_int)]
+
+
 class IssParams(C.Structure):
     """mvr_iss_params"""
     _fields_ = [("salient_radius", C.c_double), ("non_max_radius", C.c_double), ("gamma_21", C.c_double), ("gamma_32", C.c_double),
@@ -273,6 +278,8 @@ FPFH_BINS = 11          # MVR_FPFH_BINS: a signature is 3 * 11 = 33 floats
 PFH_DIM = 125           # MVR_PFH_DIM: 5 * 5 * 5 joint bins
 PFH_STAGE = 256         # MVR_PFH_STAGE: neighbours staged on chip; above it the tiled path
 PREREJ_MAX_SAMPLES = 8  # MVR_PREREJ_MAX_SAMPLES
+RADIUS_STAGE = 1024     # MVR_RADIUS_STAGE: entries of a radius-search row ordered on chip; above it the long-row path
+RADIUS_MAX_TOTAL = 0x7FFFFFFF   # MVR_RADIUS_MAX_TOTAL: the most entries one mvr_radius_search returns (rule RS8)
 
 
 class PrerejParams(C.Structure):
@@ -320,6 +327,8 @@ SIGNATURES = {
     "mvr_cloud_mls": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(MlsParams), C.POINTER(_sz), _u32p, _fp]),
     "mvr_cloud_fpfh": (C.c_int, [_vp, C.c_int, C.POINTER(FpfhParams), _fp, _fp, _u32p]),
     "mvr_cloud_pfh": (C.c_int, [_vp, C.c_int, C.POINTER(PfhParams), _fp, _u32p, _u32p]),
+    "mvr_radius_default_params": (None, [C.POINTER(RadiusParams)]),
+    "mvr_radius_search": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RadiusParams), C.POINTER(C.c_uint64), _u32p, _fp, _sz, C.POINTER(_sz)]),
     "mvr_cloud_iss_keypoints": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(IssParams), C.POINTER(_sz), _u32p, _dp, _u32p, _u32p]),
     "mvr_cloud_iss_keypoints_border": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(IssParams), C.POINTER(IssBorderParams), C.POINTER(_sz), _u32p,
                                                  _dp, _u32p, _u32p, _u8p, _u8p]),
@@ -845,6 +854,31 @@ class Context:
         idx, d2 = np.empty((n, k), np.uint32), np.empty((n, k), np.float32)
         _chk(_lib.mvr_knn(self._h, q_slot, t_slot, int(k), int(fma), _p(idx, C.c_uint32), _p(d2, C.c_float)), self._h)
         return idx, d2
+
+    def radius_search(self, q_slot, t_slot, radius, max_nn=0, sorted=True, fma=False, count_only=False):
+        """pcl::search::KdTree::radiusSearch of every point of q_slot in t_slot, as CSR lists (rules RS1-RS11: mvr_radius_search
+        in mvr_hip.h): (offsets uint64[n + 1], idx uint32[total], d2 float32[total]), the row of query i at offsets[i] ..
+        offsets[i + 1], ascending by (d2, index) when sorted or capped by max_nn > 0.  count_only: (offsets, total)."""
+        if not (math.isfinite(float(radius)) and float(radius) > 0.0):
+            raise ValueError("radius must be finite and > 0")
+        if not 0 <= int(max_nn) <= 0xFFFFFFFF:
+            raise ValueError("max_nn must be in 0..2^32 - 1")
+        for s in (q_slot, t_slot):
+            if not 0 <= int(s) < MAX_SLOTS:
+                raise ValueError("bad slot %r" % (s,))
+        n = self.size(int(q_slot))
+        p = RadiusParams(float(radius), int(max_nn), int(bool(sorted)), int(bool(fma)))
+        offsets = np.empty(n + 1, np.uint64)
+        total = _sz(0)
+        _chk(_lib.mvr_radius_search(self._h, int(q_slot), int(t_slot), C.byref(p), _p(offsets, C.c_uint64), None, None, 0, C.byref(total)), self._h)
+        if count_only:
+            return offsets, int(total.value)
+        m = int(total.value)
+        idx, d2 = np.empty(m, np.uint32), np.empty(m, np.float32)
+        if m:
+            _chk(_lib.mvr_radius_search(self._h, int(q_slot), int(t_slot), C.byref(p), _p(offsets, C.c_uint64), _p(idx, C.c_uint32),
+                                        _p(d2, C.c_float), m, C.byref(total)), self._h)
+        return offsets, idx, d2
 
     def estimate_normals(self, slots, k=None, radius=None, viewpoint=(0.0, 0.0, 0.0), curvature=False, fma=False):
         """pcl::NormalEstimation of every slot against itself (one call): the normals go into the slots (download_normals,

@@ -2042,6 +2042,7 @@ API int mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value)
   else if (!std::strcmp(key, "pair_fused")) c->pair_fused = value != 0;
   else if (!std::strcmp(key, "feat_split")) { if (value < 0 || value > 64) return MVR_E_ARG; c->feat_split = value; }
   else if (!std::strcmp(key, "pfh_stage")) { if (value < MVR_MAX_KNN || value > MVR_PFH_STAGE) return MVR_E_ARG; c->pfh_stage = value; }
+  else if (!std::strcmp(key, "radius_stage")) { if (value < MVR_MAX_KNN || value > MVR_RADIUS_STAGE) return MVR_E_ARG; c->radius_stage = value; }
   else if (!std::strcmp(key, "score_chunk")) { if (value < 1 || value > 65535) return MVR_E_ARG; c->score_chunk = value; }
   else if (!std::strcmp(key, "sac_chunk")) { if (value < 0 || value > 256) return MVR_E_ARG; c->sac_chunk = value; }
   else if (!std::strcmp(key, "rej_sac_chunk")) { if (value < 0 || value > 256) return MVR_E_ARG; c->rej_sac_chunk = value; }
@@ -2089,6 +2090,11 @@ API int mvr_ctx_stat(mvr_ctx *ctx, const char *key, double *value)
   else if (!std::strcmp(key, "pfh_stage")) *value = (double)c->pfh_stage;
   else if (!std::strcmp(key, "pfh_tiled_queries")) *value = (double)c->pfh_tiled;
   else if (!std::strcmp(key, "pfh_pairs")) *value = (double)c->pfh_pairs;
+  else if (!std::strcmp(key, "radius_stage")) *value = (double)c->radius_stage;
+  else if (!std::strcmp(key, "radius_long_rows")) *value = (double)c->radius_long_rows;
+  else if (!std::strcmp(key, "radius_count_ms")) *value = c->radius_ms[0];
+  else if (!std::strcmp(key, "radius_fill_ms")) *value = c->radius_ms[1];
+  else if (!std::strcmp(key, "radius_copy_ms")) *value = c->radius_ms[2];
   else if (!std::strcmp(key, "prerej_match_ms")) *value = c->prerej_ms[0];
   else if (!std::strcmp(key, "prerej_hypotheses_ms")) *value = c->prerej_ms[1];
   else if (!std::strcmp(key, "prerej_score_ms")) *value = c->prerej_ms[2];

@@ -33,16 +33,6 @@ namespace {
 constexpr int kMaxSplit = 64;
 constexpr int kScoreThreads = kKnnThreads;
 
-struct DevBuf {      // a device allocation that lives as long as a call
-  void *p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-  template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 // ------------------------------------------------------------------ feature k-NN
 
 template <int KMAX>

@@ -285,6 +285,9 @@ struct Ctx {
   // scoring launch -- results never depend on either; wall milliseconds of the last mvr_align_prerejective by phase
   int feat_split = 0, score_chunk = 256;
   int pfh_stage = MVR_PFH_STAGE;                         // neighbours a PFH query stages in LDS; above it the tiled path (tune "pfh_stage")
+  int radius_stage = MVR_RADIUS_STAGE;                   // neighbours a radius-search row stages (and orders) in LDS; above it the long-row path (tune "radius_stage")
+  uint64_t radius_long_rows = 0;                         // of the last mvr_radius_search: rows on the long-row path
+  double radius_ms[3] = {0.0, 0.0, 0.0};                 // ... and its wall milliseconds: the count (to the read-back of the total), the fill and ordering, the copies home
   uint64_t pfh_tiled = 0, pfh_pairs = 0;                 // of the last mvr_cloud_pfh: queries on the tiled path, pairs of all queries
   double prerej_ms[3] = {0.0, 0.0, 0.0};                 // matching, hypothesis generation, scoring
   int rej_sac_chunk = 0;                                 // the sample-consensus rejector: attempts per chunk (0: 64 for a stage's first chunk, 256 from then on -- profiles/reject_sac_bench.json); results never depend on it
@@ -792,6 +795,17 @@ struct Carver {
     return p;
   }
 };
+// a device allocation (through the pool) that lives as long as a call (mvr_feature.hip, mvr_pfh.hip, mvr_radius.hip)
+struct DevBuf {
+  void *p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+  template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
 // grows a cloud's point buffer to `cap` points (keep: its current points are copied over)
 int cloud_reserve(Ctx *c, Cloud &cl, size_t cap, bool keep);
 

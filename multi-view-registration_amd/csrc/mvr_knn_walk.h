@@ -1,6 +1,7 @@
 // csrc/mvr_knn_walk.h -- the walks of a cloud's model grid around a query, each written once, for the kernels that search a
 // neighbourhood (mvr_knn.hip: k-NN lists and normals; mvr_outlier.hip: mean neighbour distances and neighbour counts;
-// mvr_mls.hip: moving least squares; mvr_fpfh.hip: FPFH descriptors; mvr_feature.hip: the scores of posed copies):
+// mvr_mls.hip: moving least squares; mvr_fpfh.hip: FPFH descriptors; mvr_feature.hip: the scores of posed copies;
+// mvr_radius.hip: the radius lists themselves):
 //   * knn_shell_walk: shells of cells outward from the query's cell until a visitor's k-best list is full and every unvisited
 //     cell lies beyond it (the f64 bound of knn_unvisited_bound);
 //   * knn_ball_walk: every point within a radius of the query, in grid order (knn_ball_any: the same ball, left at the first
@@ -253,6 +254,24 @@ inline void fill_queries(const Cloud &q, KnnSlot &S)
 
 // the k-NN lists of a cloud (n > 0, past knn_cloud_ok) in itself into device tables [n][k] by index (mvr_knn.hip); queued
 int knn_self_device(Ctx *c, Cloud &cl, int k, bool fma, uint32_t *didx, float *dd2);
+
+// the radius lists of the points of q in t (both past knn_cloud_ok; rules RS1-RS11 at mvr_radius_search in mvr_hip.h) as CSR
+// tables that stay on the device (mvr_radius.hip): offsets[nq + 1] by query index, idx / d2 [total].  The tables belong to the
+// struct (pool allocations, freed with it); the work is queued on the context's stream, which the call waits for once, to
+// read `total`.
+struct RadiusLists {
+  unsigned long long *offsets = nullptr;
+  uint32_t *idx = nullptr;
+  float *d2 = nullptr;
+  size_t nq = 0, total = 0;
+  bool counted = false;              // offsets and total are valid (also when the call then refused: RS7, RS8)
+  RadiusLists() = default;
+  RadiusLists(const RadiusLists &) = delete;
+  RadiusLists &operator=(const RadiusLists &) = delete;
+  ~RadiusLists();
+};
+// fill false: the count alone (offsets, total).  capacity: the entries the caller has room for (RS7; SIZE_MAX: no limit)
+int radius_search_device(Ctx *c, Cloud &q, Cloud &t, const mvr_radius_params &p, bool fill, size_t capacity, RadiusLists *out);
 
 // pcl::BoundaryEstimation over a filled slot (mvr_boundary.hip; rules B1-B5 at mvr_cloud_boundary in mvr_hip.h), queued on the
 // context's stream: flag / max_gap / count by index, flag_grid by the query's grid position (the position a later walk of the

@@ -258,16 +258,6 @@ __global__ void __launch_bounds__(kLanes) pfh_knn_kernel(PfhArgs a)
   pfh_write_row(a, qi, n, true, hist);
 }
 
-struct DevBuf {      // a device allocation (through the pool) that lives as long as a call
-  void *p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-  template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 int pfh_cloud(Ctx *c, Cloud &cl, const mvr_pfh_params &p, float *pfh, uint32_t *counts, uint32_t *neighbor_count)
 {
   const size_t n = cl.n;
