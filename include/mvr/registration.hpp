@@ -907,7 +907,9 @@ class KdTree {
 
 // pcl::NormalEstimation<PointInT, PointOutT> (features/normal_3d.h): setKSearch XOR setRadiusSearch, setViewPoint, compute.
 // Semantics: mvr_cloud_estimate_normals (mvr_hip.h).  As PCL's Feature::compute, a call with both or neither of k / radius
-// set prints an error and leaves `output` empty.
+// set prints an error and leaves `output` empty.  setSearchSurface / setIndices (Feature's own): the neighbours are taken from
+// the surface, and `output` holds one normal per index, in the order of the indices, or one per input point -- rules Q1-Q8 of
+// mvr_cloud_estimate_normals_at.  An index outside the input cloud prints an error and leaves `output` empty.
 template <typename PointInT, typename PointOutT>
 class NormalEstimation {
  public:
@@ -916,9 +918,14 @@ class NormalEstimation {
   typedef PointCloud<PointOutT> PointCloudOut;
   typedef search::KdTree<PointInT> KdTree;
   typedef typename KdTree::Ptr KdTreePtr;
+  typedef std::shared_ptr<const std::vector<int> > IndicesConstPtr;
 
   void setInputCloud(const PointCloudConstPtr &c) { input_ = c; }
   PointCloudConstPtr getInputCloud() const { return input_; }
+  void setSearchSurface(const PointCloudConstPtr &c) { surface_ = c; }
+  PointCloudConstPtr getSearchSurface() const { return surface_; }
+  void setIndices(const IndicesConstPtr &i) { indices_ = i; }
+  IndicesConstPtr getIndices() const { return indices_; }
   void setSearchMethod(const KdTreePtr &tree) { tree_ = tree; }
   KdTreePtr getSearchMethod() const { return tree_; }
   void setKSearch(int k) { k_ = k; }
@@ -939,11 +946,32 @@ class NormalEstimation {
     Device &d = Device::instance();
     SlotGuard s;
     d.upload(s.s, *input_);
-    const size_t n = input_->size();
-    std::vector<float> curv(n ? n : 1), nrm(4 * (n ? n : 1));
     mvr_normal_params p;
     p.k = k_; p.radius = radius_; p.fma_dist = 0;
     for (int j = 0; j < 3; ++j) p.viewpoint[j] = vp_[j];
+    if (surface_ || indices_) {
+      std::vector<uint32_t> idx;
+      if (indices_)
+        for (int i : *indices_) {
+          if (i < 0 || (size_t)i >= input_->size()) { std::fprintf(stderr, "[NormalEstimation::compute] The index %d lies outside the input cloud (%zu points).\n", i, input_->size()); return; }
+          idx.push_back((uint32_t)i);
+        }
+      std::shared_ptr<SlotGuard> t;
+      if (surface_ && surface_ != input_) { t = std::make_shared<SlotGuard>(); d.upload(t->s, *surface_); }
+      const size_t rows = indices_ ? idx.size() : input_->size();
+      std::vector<float> curv(rows ? rows : 1), nrm(4 * (rows ? rows : 1));
+      static const uint32_t none[1] = {0};
+      d.check(mvr_cloud_estimate_normals_at(d.ctx(), s.s, indices_ ? (idx.empty() ? none : idx.data()) : nullptr, idx.size(), t ? t->s : s.s, &p, 0,
+                                            nrm.data(), curv.data()), "mvr_cloud_estimate_normals_at");
+      output.resize(rows);
+      for (size_t i = 0; i < rows; ++i) {
+        PointOutT &o = output.points[i];
+        o.normal_x = nrm[4 * i]; o.normal_y = nrm[4 * i + 1]; o.normal_z = nrm[4 * i + 2]; o.curvature = curv[i];
+      }
+      return;
+    }
+    const size_t n = input_->size();
+    std::vector<float> curv(n ? n : 1), nrm(4 * (n ? n : 1));
     float *cp = curv.data();
     d.check(mvr_cloud_estimate_normals(d.ctx(), 1, &s.s, &p, &cp), "mvr_cloud_estimate_normals");
     size_t got = 0;
@@ -956,7 +984,8 @@ class NormalEstimation {
   }
 
  private:
-  PointCloudConstPtr input_;
+  PointCloudConstPtr input_, surface_;
+  IndicesConstPtr indices_;
   KdTreePtr tree_;
   int k_ = 0;
   double radius_ = 0.0;
@@ -1231,7 +1260,9 @@ class MovingLeastSquares {
 // (Normal, PointNormal).  A point with a non-finite coordinate or normal gets a NaN signature (PCL does the same) and
 // is_dense is cleared.  As PCL's Feature::compute, a missing input, missing normals, a normal cloud of another size or a
 // radius that is not finite and > 0 prints an error and leaves `output` empty.  What this class cannot do it refuses with an
-// exception, not silently: the k-neighbour mode (setKSearch with a non-zero k), setSearchSurface and setIndices.
+// exception, not silently: the k-neighbour mode (setKSearch with a non-zero k), setSearchSurface and setIndices.  (The two stay
+// refused in this class and in PFHEstimation below: their drivers pin the refusal.  The library itself offers both --
+// mvr_cloud_fpfh_at / mvr_cloud_pfh_at -- and ScanCloud::computeFPFHAt / computePFHAt are their C++ form.)
 template <typename PointInT, typename PointNT, typename PointOutT = FPFHSignature33>
 class FPFHEstimation {
  public:

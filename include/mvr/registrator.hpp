@@ -466,6 +466,52 @@ class ScanCloud {
     return true;
   }
 
+  // EXTENSION (setIndices / setSearchSurface of pcl::FPFHEstimation and pcl::PFHEstimation; rules Q1-Q8: mvr_cloud_fpfh_at /
+  // mvr_cloud_pfh_at in mvr_hip.h): the descriptors at chosen points only.  With `indices`, `out` holds indices.size() rows, row r
+  // the signature of point indices[r] of this cloud, which is its own surface -- bit for bit the row computeFPFH / computePFH
+  // give that point.  With `surface`, every raw point of THIS cloud is a query position (it needs no normals) over the points and
+  // the normals of `surface`, and `out` holds one row per point of this cloud.  Refusals as computeFPFH, of the surface; an
+  // index beyond the cloud prints an error too.
+  bool computeFPFHAt(double radius, const std::vector<uint32_t> &indices, std::vector<FPFHSignature33> &out) const
+  {
+    return featuresAt("computeFPFHAt", radius, nullptr, &indices, out);
+  }
+  bool computePFHAt(double radius, const std::vector<uint32_t> &indices, std::vector<PFHSignature125> &out) const
+  {
+    return featuresAt("computePFHAt", radius, nullptr, &indices, out);
+  }
+  bool computeFPFHAt(const ScanCloud &surface, double radius, std::vector<FPFHSignature33> &out) const
+  {
+    return surface.featuresAt("computeFPFHAt", radius, this, nullptr, out);
+  }
+  bool computePFHAt(const ScanCloud &surface, double radius, std::vector<PFHSignature125> &out) const
+  {
+    return surface.featuresAt("computePFHAt", radius, this, nullptr, out);
+  }
+  // EXTENSION (pcl::NormalEstimation with setSearchSurface; mvr_cloud_estimate_normals_at): estimateNormals with the neighbours
+  // taken from the raw points of `surface` -- the normals of a downsampled cloud from the scan it came from
+  void estimateNormalsFrom(const ScanCloud &surface, int k, double radius = 0.0)
+  {
+    Device &d = Device::instance();
+    SlotGuard s, t;
+    const size_t n = points.size();
+    if (rich.size() != n) {
+      io::RichCloud r(n);
+      for (size_t i = 0; i < n; ++i) { r[i].x = points.points[i].x; r[i].y = points.points[i].y; r[i].z = points.points[i].z; }
+      rich.swap(r);
+    }
+    d.upload(s.s, points);
+    d.upload(t.s, surface.points);
+    mvr_normal_params p;
+    p.k = k; p.radius = radius; p.fma_dist = 0;
+    p.viewpoint[0] = p.viewpoint[1] = p.viewpoint[2] = 0.f;
+    std::vector<float> curv(n ? n : 1), nrm(4 * (n ? n : 1));
+    d.check(mvr_cloud_estimate_normals_at(d.ctx(), s.s, nullptr, 0, t.s, &p, 0, nrm.data(), curv.data()), "mvr_cloud_estimate_normals_at");
+    for (size_t i = 0; i < n; ++i) {
+      rich[i].normal_x = nrm[4 * i]; rich[i].normal_y = nrm[4 * i + 1]; rich[i].normal_z = nrm[4 * i + 2]; rich[i].curvature = curv[i];
+    }
+  }
+
   // EXTENSION (pcl::search::KdTree::radiusSearch for every point at once, on the GPU; rules RS1-RS11: mvr_radius_search in
   // mvr_hip.h): the neighbours within `radius` of every raw point of this cloud among its own points -- each row starts with the
   // point itself -- or of every raw point of `queries` among the points of this cloud; rows ascending by (distance, index), at
@@ -578,8 +624,13 @@ class ScanCloud {
   // setMatrix(pose * target.getMatrix()) puts the scan where registrationICPDevice can take over.  false (pose untouched): no
   // normals, a bad radius, or the aligner found no pose that reaches inlier_fraction; `result` (optional) says which.
   // With use_keypoints, detectKeypoints(keypoints) runs on both scans first and the descriptor rows of the other points are
-  // overwritten with NaN: such a row is never sampled (A1) and never matched (M3), so the matcher's work drops from
-  // n_source x n_target pairs to keypoints x n_target while every pose is still scored over all points of the source.
+  // NaN: such a row is never sampled (A1) and never matched (M3), so the matcher's work drops from n_source x n_target pairs to
+  // keypoints x n_target while every pose is still scored over all points of the source.  alignPrerejectivePFH computes its
+  // descriptors AT the keypoints only (computePFHAt, into tables of NaN): by rule Q5 the tables are bit for bit those of the full
+  // computation with the other rows overwritten, at the cost of the keypoints' neighbourhoods (measured: 0.34 ms against 0.53 ms on
+  // the 3k-point recovery pair, 10.2 ms against 138 ms per 200k view at 5 mm; profiles/feature_at_bench.json).  The FPFH overload
+  // still computes every row and overwrites: FPFH at the keypoints needs the SPFH of nearly the whole surface and measured SLOWER
+  // than the whole-cloud call up to 200k points (3.26 ms against 2.22 ms on that pair), so it was not switched.
   // With a border radius (border.border_radius > 0; off by default) the keypoints are those of the detector's border variant.
   struct PrerejectiveParams {
     double feature_radius = 0.0;
@@ -607,6 +658,7 @@ class ScanCloud {
   {
     std::vector<PFHSignature125> sf, tf;
     if (result) { *result = mvr_prerej_result(); result->best_iteration = -1; result->error = DBL_MAX; }
+    if (params.use_keypoints) return alignAtKeypoints("computePFH", target, params, sf, tf, pose, result);
     if (!computePFH(params.feature_radius, sf) || !target.computePFH(params.feature_radius, tf)) return false;
     return alignPrerejective(target, params, sf, tf, pose, result);
   }
@@ -718,6 +770,83 @@ class ScanCloud {
       np.k = k_normals;
       d.check(mvr_cloud_estimate_normals(d.ctx(), 1, &slot, &np, nullptr), "mvr_cloud_estimate_normals");
     }
+  }
+  // what computeFPFH / computePFH (`fn`) refuse, with their texts: a cloud without normals, a radius that is not finite and > 0
+  bool featureInputsOk(const char *fn, double radius) const
+  {
+    const size_t n = points.size();
+    if (rich.size() != n) {
+      std::fprintf(stderr, "[ScanCloud::%s] The cloud has no normals (%zu points, %zu records): call estimateNormals first.\n", fn, n, rich.size());
+      return false;
+    }
+    if (!(std::isfinite(radius) && radius > 0.0)) {
+      std::fprintf(stderr, "[ScanCloud::%s] The radius (%f) must be finite and > 0.\n", fn, radius);
+      return false;
+    }
+    return true;
+  }
+  // the descriptors of the queries over THIS cloud and its normals: the points `indices` of this cloud, or every raw point of
+  // `queries`; 33 or 125 floats per row
+  template <typename FeatureT>
+  bool featuresAt(const char *fn, double radius, const ScanCloud *queries, const std::vector<uint32_t> *indices, std::vector<FeatureT> &out) const
+  {
+    static_assert(sizeof(FeatureT) == sizeof(float) * 3 * MVR_FPFH_BINS || sizeof(FeatureT) == sizeof(float) * MVR_PFH_DIM,
+                  "a 33-float or a 125-float signature expected");
+    out.clear();
+    if (!featureInputsOk(fn, radius)) return false;
+    const size_t n = points.size(), nq = queries ? queries->points.size() : n;
+    if (indices)
+      for (uint32_t i : *indices)
+        if (i >= nq) {
+          std::fprintf(stderr, "[ScanCloud::%s] The index %u lies beyond the cloud (%zu points).\n", fn, i, nq);
+          return false;
+        }
+    const size_t rows = indices ? indices->size() : nq;
+    out.resize(rows);
+    if (!rows) return true;
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.upload(s.s, points);
+    if (n) uploadRichNormals(d, s.s);
+    std::shared_ptr<SlotGuard> q;
+    if (queries && queries != this) { q = std::make_shared<SlotGuard>(); d.upload(q->s, queries->points); }
+    const int qs = q ? q->s : s.s;
+    const uint32_t *ip = indices ? indices->data() : nullptr;
+    if (sizeof(FeatureT) == sizeof(float) * MVR_PFH_DIM) {
+      mvr_pfh_params p;
+      p.radius = radius; p.k = 0; p.fma_dist = 0;
+      d.check(mvr_cloud_pfh_at(d.ctx(), qs, ip, rows, s.s, &p, out[0].histogram, nullptr, nullptr), "mvr_cloud_pfh_at");
+    } else {
+      mvr_fpfh_params p;
+      p.radius = radius; p.fma_dist = 0;
+      d.check(mvr_cloud_fpfh_at(d.ctx(), qs, ip, rows, s.s, &p, out[0].histogram, nullptr), "mvr_cloud_fpfh_at");
+    }
+    return true;
+  }
+  // a descriptor table of this cloud, NaN but for the rows of `key`, which are computed (the table keepKeypointRows leaves)
+  template <typename FeatureT>
+  bool keypointRows(const char *fn, double radius, const std::vector<uint32_t> &key, std::vector<FeatureT> &feat) const
+  {
+    std::vector<FeatureT> rows;
+    if (!featuresAt(fn, radius, nullptr, &key, rows)) return false;
+    FeatureT nan;
+    for (float &v : nan.histogram) v = std::numeric_limits<float>::quiet_NaN();
+    feat.assign(points.size(), nan);
+    for (size_t r = 0; r < key.size(); ++r) feat[key[r]] = rows[r];
+    return true;
+  }
+  // alignPrerejective with use_keypoints and descriptors of its own (`fn`: the call whose refusals come first, as when it ran)
+  template <typename FeatureT>
+  bool alignAtKeypoints(const char *fn, const ScanCloud &target, const PrerejectiveParams &params, std::vector<FeatureT> &sf, std::vector<FeatureT> &tf,
+                        RowMatrixd &pose, mvr_prerej_result *result) const
+  {
+    if (!featureInputsOk(fn, params.feature_radius) || !target.featureInputsOk(fn, params.feature_radius)) return false;
+    std::vector<uint32_t> sk, tk;
+    if (!detectKeypoints(params.keypoints, params.border, sk) || !target.detectKeypoints(params.keypoints, params.border, tk)) return false;
+    if (!keypointRows(fn, params.feature_radius, sk, sf) || !target.keypointRows(fn, params.feature_radius, tk, tf)) return false;
+    PrerejectiveParams rest = params;
+    rest.use_keypoints = false;                          // (the tables hold the keypoints' rows alone already)
+    return alignPrerejective(target, rest, sf, tf, pose, result);
   }
   // the descriptor rows of the points detectKeypoints does not list become NaN (false: the detector refused its parameters)
   template <typename FeatureT>

@@ -455,7 +455,8 @@ int  mvr_cloud_mls(mvr_ctx *ctx, int dst_slot, int src_slot, const mvr_mls_param
  *      because a pipelined run is in flight.  An empty cloud is MVR_OK.  All three outputs NULL: MVR_OK after the work.
  *  F8. Bit-identical from run to run on one grid: one thread per query, one fixed walk order, no floating-point atomics.
  * The slot is not modified and no descriptor stays on the device after the call.
- * Out of scope: the k-neighbour mode (setKSearch) and setSearchSurface / setIndices.  PFH is mvr_cloud_pfh below.  The
+ * Out of scope: the k-neighbour mode (setKSearch).  setSearchSurface / setIndices are mvr_cloud_fpfh_at below (rules Q1-Q8), PFH
+ * is mvr_cloud_pfh below.  The
  * matching and the sample-consensus alignment that consume the signatures follow below (mvr_feature_knn,
  * mvr_align_prerejective). */
 #define MVR_FPFH_BINS 11            /* per feature; a signature is 3 * 11 = 33 floats (pcl::FPFHSignature33) */
@@ -504,7 +505,7 @@ int  mvr_cloud_fpfh(mvr_ctx *ctx, int slot, const mvr_fpfh_params *p,
  * goes to device scratch and is processed tile against tile.  mvr_ctx_stat "pfh_tiled_queries" / "pfh_pairs": the queries of
  * the last call that took the tiled path, and its sum of m_i.
  * The slot is not modified and nothing stays on the device after the call.
- * Out of scope: setSearchSurface / setIndices, PFHRGB. */
+ * setSearchSurface / setIndices are mvr_cloud_pfh_at below (rules Q1-Q8).  Out of scope: PFHRGB. */
 #define MVR_PFH_DIM 125             /* 5 * 5 * 5 joint bins (pcl::PFHSignature125) */
 #define MVR_PFH_STAGE 256           /* neighbours of one query staged in LDS; above it the tiled path */
 typedef struct {
@@ -516,6 +517,58 @@ int  mvr_cloud_pfh(mvr_ctx *ctx, int slot, const mvr_pfh_params *p,
                    float *pfh,               /* host, n * 125, row = point index; may be NULL  */
                    uint32_t *counts,         /* optional host, n * 125: c_i[h] of rule P5      */
                    uint32_t *neighbor_count  /* optional host, n: n_i of rule P2               */);
+
+/* ---- normals, FPFH and PFH at query points over a search surface (EXTENSION: setSearchSurface / setIndices) ---------------
+ * PCL computes descriptors at a few keypoints against the full-resolution scan (setInputCloud(keypoints) with
+ * setSearchSurface(scan), or setIndices), and the normals of a downsampled cloud from the scan it came from.  The three
+ * entries below are the three above with the query separated from the surface; one query convention serves them.
+ *  Q1. Which queries.  indices == NULL: every point of q_slot is a query, rows = n_q, row r answers point r.  Otherwise
+ *      rows = n_indices and row r answers point indices[r] of q_slot; indices may be in any order and may repeat.  An index
+ *      >= n_q is MVR_E_ARG with nothing written.  rows == 0 is MVR_OK.
+ *  Q2. What a query is.  The surface is surface_slot, with that slot's normals (FPFH and PFH need them: F7, P7).  With
+ *      q_slot != surface_slot a query is a POSITION only: valid iff its three coordinates are finite; it needs no normal
+ *      (PCL: with a search surface set, normals_ belong to the surface).  With q_slot == surface_slot query i IS surface
+ *      point i, and F1 / P1 apply to it: a non-finite normal gives a NaN row and count 0.  (Normals need no normal of
+ *      anybody: their queries are positions in either case.)
+ *  Q3. Neighbourhoods: the library's own rule around the query position -- F2 / P2 radius mode, the f32 d2 with <=, fma_dist;
+ *      in k mode (PFH, normals) the mvr_knn(q_slot, surface_slot, k) list of the query, for PFH minus the entries with an
+ *      invalid normal.  A surface point at d2 == 0 is a neighbour like any other.
+ *  Q4. Values.  Normals: the rules of mvr_cloud_estimate_normals, the covariance relative to the query position, the flip at
+ *      the query position, fewer than 3 neighbours NaN.  FPFH: F3-F6; the SPFH of a surface point is its own SPFH in the
+ *      surface (F5 of mvr_cloud_fpfh on surface_slot); F6 runs over the query's neighbours, in walk order, in f64; n_i == 0
+ *      gives 33 NaN (PCL's "no neighbours"; in the self mode a query is always its own neighbour); an invalid query gives 33
+ *      NaN and count 0.  PFH: P3-P6 on the query's neighbourhood; n_i == 0 gives NaN, n_i == 1 zeros; P6's limit holds.
+ *  Q5. Equivalence.  A query exactly at surface point i, valid under F1, with the same parameters and the same state of
+ *      surface_slot, gets a row BIT-IDENTICAL to row i of the existing call -- signature, counts, neighbor_count, normal and
+ *      curvature -- whether it comes through `indices` on the same slot or through a copy of the point in another slot: a
+ *      walk's cells and order depend only on the query position and the surface's grid.  PFH counts are in addition
+ *      independent of the grid's resolution and of the path taken (P8).
+ *  Q6. store_in_slot = 1 (normals) is allowed only with indices == NULL, else MVR_E_ARG; q_slot then gets the normals
+ *      (has_normals set) as from mvr_cloud_estimate_normals, the host arrays staying optional.  With store_in_slot = 0
+ *      neither slot is modified, the own-coordinates grids of RS10 aside.
+ *  Q7. Refusals: everything F7 / P7 list, applied to both slots, the normals requirement to the surface only; all before any
+ *      GPU work, with nothing written.  An empty surface with a non-empty query set is MVR_OK with the
+ *      empty-neighbourhood rows of Q4.
+ *  Q8. Nothing stays on the device after the call.  indices == NULL with q_slot == surface_slot is the existing call (FPFH,
+ *      PFH, and normals with store_in_slot = 1; normals with store_in_slot = 0 take the general path, which leaves the slot
+ *      alone and gives the same bits).
+ * The queries are gathered into an array of positions and sorted by the cell of the surface's grid they fall in (tune key
+ * "at_sort" = 0 leaves the sort out; no result depends on it).  FPFH computes the SPFH on demand: a marking walk flags the
+ * union of the queries' neighbours, a flagged selection lists them, and only those rows are computed (mvr_ctx_stat
+ * "fpfh_at_marked": how many, of the last call).  Out of scope: FPFH in k mode; descriptors kept on the device. */
+int  mvr_cloud_estimate_normals_at(mvr_ctx *ctx, int q_slot, const uint32_t *indices, size_t n_indices, int surface_slot,
+                                   const mvr_normal_params *p, int store_in_slot,
+                                   float *normals   /* optional host, rows * 4: nx ny nz 0 */,
+                                   float *curvature /* optional host, rows                 */);
+int  mvr_cloud_fpfh_at(mvr_ctx *ctx, int q_slot, const uint32_t *indices, size_t n_indices, int surface_slot,
+                       const mvr_fpfh_params *p,
+                       float *fpfh              /* host, rows * 33; may be NULL */,
+                       uint32_t *neighbor_count /* optional host, rows          */);
+int  mvr_cloud_pfh_at(mvr_ctx *ctx, int q_slot, const uint32_t *indices, size_t n_indices, int surface_slot,
+                      const mvr_pfh_params *p,
+                      float *pfh               /* host, rows * 125; may be NULL */,
+                      uint32_t *counts         /* optional host, rows * 125     */,
+                      uint32_t *neighbor_count /* optional host, rows           */);
 
 /* ---- feature matching and coarse alignment (EXTENSION: pcl::SampleConsensusPrerejective) -------------------------------
  * What brings a scan without a pose prior within the capture range of mvr_icp_align.  The reference pins no PCL version and
@@ -1548,7 +1601,9 @@ enum { MVR_K_NN = 0, MVR_K_REDUCE = 1, MVR_K_XFORM = 2, MVR_K_GLUE = 3,
  * launch size), "score_chunk" (poses per launch of mvr_pose_scores, default 256); "pfh_stage" (mvr_cloud_pfh: the neighbourhood
  * size above which a query takes the tiled path, MVR_MAX_KNN..MVR_PFH_STAGE, default MVR_PFH_STAGE); "radius_stage"
  * (mvr_radius_search: the row length above which a row takes the long-row path, MVR_MAX_KNN..MVR_RADIUS_STAGE, default
- * MVR_RADIUS_STAGE);
+ * MVR_RADIUS_STAGE); "at_sort" (the *_at entries: 1, default, sorts the queries by the cell of the surface's grid they fall in;
+ * 0 takes them in the order given; no result depends on it), "at_clock" (1: mvr_cloud_fpfh_at records an event on its stream
+ * around each of its four stages, created and destroyed per call, for the "fpfh_at_*_ms" stats; 0, default: none);
  * plane segmentation: "sac_chunk" (attempts generated and scored per chunk, 1..256; 0, default: 64 for the first chunk of a
  * call and 256 from then on);
  * the sample-consensus rejector: "rej_sac_chunk" (attempts generated and scored per chunk, 1..256; 0, default: 64 for the first
@@ -1564,6 +1619,10 @@ int  mvr_ctx_pass_log(mvr_ctx *ctx, double *ms, int cap, int *n);
  * (times the library waited for its stream or re-allocated a buffer: a pass without any is in steady state),
  * "prerej_match_ms" / "prerej_hypotheses_ms" / "prerej_score_ms" (wall milliseconds of the last mvr_align_prerejective by phase),
  * "pfh_stage" (the tune key's value), "pfh_tiled_queries" / "pfh_pairs" (of the last mvr_cloud_pfh: see there),
+ * "at_sort" (the tune key's value), "fpfh_at_marked" (of the last mvr_cloud_fpfh_at: the surface points whose SPFH row was
+ * computed), "fpfh_at_mark_ms" / "fpfh_at_select_ms" / "fpfh_at_spfh_ms" / "fpfh_at_weight_ms" (device milliseconds of its stages --
+ * the marking walk, the flagged selection with the read-back of its count, the SPFH rows, the weighting -- when the tune key
+ * "at_clock" was 1 during the call, else 0),
  * "radius_stage" (the tune key's value), "radius_long_rows" (of the last mvr_radius_search: rows on the long-row path),
  * "radius_count_ms" / "radius_fill_ms" / "radius_copy_ms" (wall milliseconds of the last mvr_radius_search by phase: the count up to
  * the read-back of the total; the fill and the ordering of the rows, with the copy of the offsets; the copies of idx / d2 to the host) */

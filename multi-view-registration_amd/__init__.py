@@ -327,6 +327,9 @@ SIGNATURES = {
     "mvr_cloud_mls": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(MlsParams), C.POINTER(_sz), _u32p, _fp]),
     "mvr_cloud_fpfh": (C.c_int, [_vp, C.c_int, C.POINTER(FpfhParams), _fp, _fp, _u32p]),
     "mvr_cloud_pfh": (C.c_int, [_vp, C.c_int, C.POINTER(PfhParams), _fp, _u32p, _u32p]),
+    "mvr_cloud_estimate_normals_at": (C.c_int, [_vp, C.c_int, _u32p, C.c_size_t, C.c_int, C.POINTER(NormalParams), C.c_int, _fp, _fp]),
+    "mvr_cloud_fpfh_at": (C.c_int, [_vp, C.c_int, _u32p, C.c_size_t, C.c_int, C.POINTER(FpfhParams), _fp, _u32p]),
+    "mvr_cloud_pfh_at": (C.c_int, [_vp, C.c_int, _u32p, C.c_size_t, C.c_int, C.POINTER(PfhParams), _fp, _u32p, _u32p]),
     "mvr_radius_default_params": (None, [C.POINTER(RadiusParams)]),
     "mvr_radius_search": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RadiusParams), C.POINTER(C.c_uint64), _u32p, _fp, _sz, C.POINTER(_sz)]),
     "mvr_cloud_iss_keypoints": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(IssParams), C.POINTER(_sz), _u32p, _dp, _u32p, _u32p]),
@@ -1043,6 +1046,67 @@ class Context:
         nb = np.empty(n, np.uint32) if return_neighbors else None
         _chk(_lib.mvr_cloud_pfh(self._h, int(slot), C.byref(p), _p(out, C.c_float), _p(cnt, C.c_uint32) if return_counts else None,
                                 _p(nb, C.c_uint32) if return_neighbors else None), self._h)
+        res = [out]
+        if return_counts:
+            res.append(cnt)
+        if return_neighbors:
+            res.append(nb)
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def _at_rows(self, q_slot, indices):
+        """the query convention of the *_at calls (rule Q1): (indices as a contiguous uint32 array or None, its pointer, rows)"""
+        if indices is None:
+            return None, None, self.size(q_slot)
+        a = np.asarray(indices)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError("indices must be a one-dimensional integer array")
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise ValueError("indices must fit 32 unsigned bits")
+        a = np.ascontiguousarray(a, np.uint32)
+        # (a non-NULL pointer also for an empty list: NULL means "every point")
+        return a, (_p(a, C.c_uint32) if a.size else C.cast((C.c_uint32 * 1)(), _u32p)), int(a.size)
+
+    def estimate_normals_at(self, q_slot, surface_slot, indices=None, k=None, radius=None, viewpoint=(0.0, 0.0, 0.0), store=False,
+                            fma=False):
+        """pcl::NormalEstimation at the points `indices` of q_slot (None: all of them) with surface_slot as search surface
+        (setSearchSurface / setIndices; rules Q1-Q8: mvr_cloud_estimate_normals_at in mvr_hip.h).  Exactly one of k / radius.
+        Returns (normals (rows, 3) float32, curvature (rows,) float32); store=True (indices None only) also puts the normals
+        into q_slot."""
+        _, ptr, rows = self._at_rows(q_slot, indices)
+        p = NormalParams(int(k or 0), float(radius or 0.0), (C.c_float * 3)(*[float(v) for v in viewpoint]), int(bool(fma)))
+        nrm = np.empty((rows, 4), np.float32)
+        curv = np.empty(rows, np.float32)
+        _chk(_lib.mvr_cloud_estimate_normals_at(self._h, int(q_slot), ptr, rows if ptr is not None else 0, int(surface_slot), C.byref(p),
+                                                int(bool(store)), _p(nrm, C.c_float), _p(curv, C.c_float)), self._h)
+        return nrm[:, :3].copy(), curv
+
+    def fpfh_at(self, q_slot, surface_slot, radius, indices=None, fma=False, return_counts=False):
+        """pcl::FPFHEstimation at the points `indices` of q_slot (None: all of them) over surface_slot and ITS normals
+        (setSearchSurface / setIndices; rules Q1-Q8: mvr_cloud_fpfh_at in mvr_hip.h): the (rows, 33) float32 signatures, row r
+        for indices[r]; with return_counts also neighbor_count (rows,) uint32.  Only the SPFH rows the queries' neighbours
+        need are computed."""
+        _, ptr, rows = self._at_rows(q_slot, indices)
+        p = FpfhParams(float(radius), int(bool(fma)))
+        out = np.empty((rows, 3 * FPFH_BINS), np.float32)
+        cnt = np.empty(rows, np.uint32) if return_counts else None
+        _chk(_lib.mvr_cloud_fpfh_at(self._h, int(q_slot), ptr, rows if ptr is not None else 0, int(surface_slot), C.byref(p),
+                                    _p(out, C.c_float), _p(cnt, C.c_uint32) if return_counts else None), self._h)
+        return (out, cnt) if return_counts else out
+
+    def pfh_at(self, q_slot, surface_slot, indices=None, radius=None, k=None, fma=False, return_counts=False, return_neighbors=False):
+        """pcl::PFHEstimation at the points `indices` of q_slot (None: all of them) over surface_slot and ITS normals, exactly
+        one of radius / k set (rules Q1-Q8: mvr_cloud_pfh_at in mvr_hip.h): the (rows, 125) float32 signatures, or
+        (pfh[, counts][, neighbor_count]) with the return_* options, as pfh() gives them."""
+        if (radius is None) == (k is None):
+            raise ValueError("exactly one of radius / k")
+        _, ptr, rows = self._at_rows(q_slot, indices)
+        p = PfhParams(float(radius or 0.0), int(k or 0), int(bool(fma)))
+        out = np.empty((rows, PFH_DIM), np.float32)
+        cnt = np.empty((rows, PFH_DIM), np.uint32) if return_counts else None
+        nb = np.empty(rows, np.uint32) if return_neighbors else None
+        _chk(_lib.mvr_cloud_pfh_at(self._h, int(q_slot), ptr, rows if ptr is not None else 0, int(surface_slot), C.byref(p),
+                                   _p(out, C.c_float), _p(cnt, C.c_uint32) if return_counts else None,
+                                   _p(nb, C.c_uint32) if return_neighbors else None), self._h)
         res = [out]
         if return_counts:
             res.append(cnt)

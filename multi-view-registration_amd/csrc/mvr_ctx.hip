@@ -2042,6 +2042,8 @@ API int mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value)
   else if (!std::strcmp(key, "pair_fused")) c->pair_fused = value != 0;
   else if (!std::strcmp(key, "feat_split")) { if (value < 0 || value > 64) return MVR_E_ARG; c->feat_split = value; }
   else if (!std::strcmp(key, "pfh_stage")) { if (value < MVR_MAX_KNN || value > MVR_PFH_STAGE) return MVR_E_ARG; c->pfh_stage = value; }
+  else if (!std::strcmp(key, "at_sort")) c->at_sort = value != 0;
+  else if (!std::strcmp(key, "at_clock")) c->at_clock = value != 0;
   else if (!std::strcmp(key, "radius_stage")) { if (value < MVR_MAX_KNN || value > MVR_RADIUS_STAGE) return MVR_E_ARG; c->radius_stage = value; }
   else if (!std::strcmp(key, "score_chunk")) { if (value < 1 || value > 65535) return MVR_E_ARG; c->score_chunk = value; }
   else if (!std::strcmp(key, "sac_chunk")) { if (value < 0 || value > 256) return MVR_E_ARG; c->sac_chunk = value; }
@@ -2090,6 +2092,12 @@ API int mvr_ctx_stat(mvr_ctx *ctx, const char *key, double *value)
   else if (!std::strcmp(key, "pfh_stage")) *value = (double)c->pfh_stage;
   else if (!std::strcmp(key, "pfh_tiled_queries")) *value = (double)c->pfh_tiled;
   else if (!std::strcmp(key, "pfh_pairs")) *value = (double)c->pfh_pairs;
+  else if (!std::strcmp(key, "at_sort")) *value = (double)c->at_sort;
+  else if (!std::strcmp(key, "fpfh_at_marked")) *value = (double)c->fpfh_at_marked;
+  else if (!std::strcmp(key, "fpfh_at_mark_ms")) *value = (double)c->fpfh_at_ms[0];
+  else if (!std::strcmp(key, "fpfh_at_select_ms")) *value = (double)c->fpfh_at_ms[1];
+  else if (!std::strcmp(key, "fpfh_at_spfh_ms")) *value = (double)c->fpfh_at_ms[2];
+  else if (!std::strcmp(key, "fpfh_at_weight_ms")) *value = (double)c->fpfh_at_ms[3];
   else if (!std::strcmp(key, "radius_stage")) *value = (double)c->radius_stage;
   else if (!std::strcmp(key, "radius_long_rows")) *value = (double)c->radius_long_rows;
   else if (!std::strcmp(key, "radius_count_ms")) *value = c->radius_ms[0];

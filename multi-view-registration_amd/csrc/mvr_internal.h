@@ -289,6 +289,10 @@ struct Ctx {
   uint64_t radius_long_rows = 0;                         // of the last mvr_radius_search: rows on the long-row path
   double radius_ms[3] = {0.0, 0.0, 0.0};                 // ... and its wall milliseconds: the count (to the read-back of the total), the fill and ordering, the copies home
   uint64_t pfh_tiled = 0, pfh_pairs = 0;                 // of the last mvr_cloud_pfh: queries on the tiled path, pairs of all queries
+  int at_sort = 1;                                       // the _at entries sort their queries by the surface's cells (tune "at_sort"); results never depend on it
+  uint64_t fpfh_at_marked = 0;                           // of the last mvr_cloud_fpfh_at: surface points whose SPFH row was computed
+  int at_clock = 0;                                      // tune "at_clock": mvr_cloud_fpfh_at times its stages with events on its stream ...
+  float fpfh_at_ms[4] = {0.f, 0.f, 0.f, 0.f};            // ... mark, select (with the read-back of the count), SPFH, weight; 0 without the key
   double prerej_ms[3] = {0.0, 0.0, 0.0};                 // matching, hypothesis generation, scoring
   int rej_sac_chunk = 0;                                 // the sample-consensus rejector: attempts per chunk (0: 64 for a stage's first chunk, 256 from then on -- profiles/reject_sac_bench.json); results never depend on it
   mvr_rej_sac_result last_sac = {}; bool last_sac_set = false;      // the last sample-consensus stage that ran on this context (mvr_ctx_last_sample_consensus)

@@ -181,6 +181,14 @@ int run_batches(Ctx *c, std::vector<KnnSlot> &all, KnnBatch proto, int kmax, int
 
 }  // namespace
 
+int knn_device(Ctx *c, const KnnSlot &S, int k, bool fma)
+{
+  std::vector<KnnSlot> all{S};
+  KnnBatch proto{};
+  proto.k = k;
+  return run_batches(c, all, proto, kmax_bucket(k), 0, fma);
+}
+
 // the k-NN lists of a cloud (n > 0, past knn_cloud_ok) in itself -- what mvr_knn gives for q_slot == t_slot -- into the device
 // tables didx / dd2, [n][k] by index; queued on the context's stream (mvr_pfh.hip: the k-neighbour mode)
 int knn_self_device(Ctx *c, Cloud &cl, int k, bool fma, uint32_t *didx, float *dd2)
@@ -287,5 +295,54 @@ API int mvr_cloud_estimate_normals(mvr_ctx *ctx, int count, const int *slots, co
   if (e != hipSuccess) return set_error(c, MVR_E_HIP, "mvr_cloud_estimate_normals copy", e);
   if (e2 != hipSuccess) return set_error(c, MVR_E_HIP, "mvr_cloud_estimate_normals sync", e2);
   for (size_t j = 0; j < all.size(); ++j) c->slots[slots[used[j]]].has_normals = true;
+  return MVR_OK;
+}
+
+API int mvr_cloud_estimate_normals_at(mvr_ctx *ctx, int q_slot, const uint32_t *indices, size_t n_indices, int surface_slot,
+                                      const mvr_normal_params *p, int store_in_slot, float *normals, float *curvature)
+{
+  if (!ctx || !p || !slot_ok(q_slot) || !slot_ok(surface_slot)) return MVR_E_ARG;
+  const bool kmode = p->k != 0, rmode = p->radius != 0.0;
+  if (kmode == rmode || p->k < 0 || p->k > MVR_MAX_KNN || !(p->radius >= 0.0) || std::isinf(p->radius)) return MVR_E_ARG;
+  for (int j = 0; j < 3; ++j) if (!std::isfinite(p->viewpoint[j])) return MVR_E_ARG;
+  if (store_in_slot && indices) return MVR_E_ARG;      // Q6
+  Ctx *c = CTX(ctx);
+  MVR_HIP_TRY(c, hipSetDevice(c->device));
+  Cloud &q = c->slots[q_slot], &t = c->slots[surface_slot];
+  if (int rc = knn_cloud_ok(c, q, "mvr_cloud_estimate_normals_at")) return rc;
+  if (int rc = knn_cloud_ok(c, t, "mvr_cloud_estimate_normals_at")) return rc;
+  if (int rc = at_indices_ok(c, q, indices, n_indices, "mvr_cloud_estimate_normals_at")) return rc;
+  const size_t rows = indices ? n_indices : q.n;
+  if (rows == 0) return MVR_OK;
+  if (store_in_slot && q_slot == surface_slot) {      // Q8: the slot against itself, into the slot
+    float *const cv[1] = {curvature};
+    if (int rc = mvr_cloud_estimate_normals(ctx, 1, &q_slot, p, cv)) return rc;
+    if (normals) MVR_HIP_TRY(c, hipMemcpy(normals, q.nrm, rows * sizeof(float4), hipMemcpyDeviceToHost));
+    return MVR_OK;
+  }
+  KnnSlot S{};
+  if (int rc = fill_target(c, t, S)) return rc;
+  AtQueries Q;
+  if (int rc = at_queries(c, q, false, indices, n_indices, S, &Q)) return rc;
+  S.qs = Q.q; S.q_by_pos = 0u; S.nq = (uint32_t)rows;
+  DevBuf out;
+  if (out.alloc(rows * (sizeof(float4) + sizeof(float))) != hipSuccess) return set_error(c, MVR_E_NOMEM, "mvr_cloud_estimate_normals_at: out of device memory");
+  S.curv = reinterpret_cast<float *>(out.as<float4>() + rows);
+  S.nrm = out.as<float4>();
+  if (store_in_slot) {
+    q.has_normals = false;
+    if (int rc = ensure(c, q.nrm, q.nrm_cap, q.n)) return rc;
+    S.nrm = q.nrm;
+  }
+  std::vector<KnnSlot> all{S};
+  KnnBatch proto{};
+  proto.k = p->k;
+  proto.r2 = clamp_r2(p->radius);
+  for (int j = 0; j < 3; ++j) proto.vp[j] = p->viewpoint[j];
+  if (int rc = run_batches(c, all, proto, kmode ? kmax_bucket(p->k) : 8, kmode ? 1 : 2, p->fma_dist != 0)) return rc;
+  if (normals) MVR_HIP_TRY(c, hipMemcpyAsync(normals, S.nrm, rows * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  if (curvature) MVR_HIP_TRY(c, hipMemcpyAsync(curvature, S.curv, rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  MVR_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (store_in_slot) q.has_normals = true;
   return MVR_OK;
 }

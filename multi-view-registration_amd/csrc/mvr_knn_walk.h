@@ -254,6 +254,30 @@ inline void fill_queries(const Cloud &q, KnnSlot &S)
 
 // the k-NN lists of a cloud (n > 0, past knn_cloud_ok) in itself into device tables [n][k] by index (mvr_knn.hip); queued
 int knn_self_device(Ctx *c, Cloud &cl, int k, bool fma, uint32_t *didx, float *dd2);
+// the same for queries that are not the target's own points: the lists of S.qs in S's target into S.oidx / S.od2, [nq][k] by
+// the query's index (w of the query, or its position with q_by_pos); queued
+int knn_device(Ctx *c, const KnnSlot &S, int k, bool fma);
+
+// ---- the query side of the entries that answer chosen queries over a search surface (mvr_at.hip; mvr_cloud_estimate_normals_at,
+// mvr_cloud_fpfh_at, mvr_cloud_pfh_at; rules Q1-Q8 in mvr_hip.h).  A query is a position and the output row it answers: q[r] =
+// {x, y, z, bits of the row}, so every walk kernel takes it as it takes a point of a grid (KnnSlot::qs with q_by_pos = 0).
+// A query that is invalid under Q2 gets NaN coordinates: it walks nothing, and every entry gives an invalid query the row of
+// an empty neighbourhood.  The rows are sorted by the cell of the SURFACE's grid the query falls in (one hipCUB pair sort; tune
+// key "at_sort" = 0 leaves it out), so the lanes of a wave, or consecutive waves, walk the same cells.  The order changes no
+// result: every row is written by its own number.
+struct AtQueries {
+  DevBuf buf;
+  const float4 *q = nullptr;
+  size_t rows = 0;
+};
+// Q1's refusal (an index >= n_q), on the host, before any GPU work
+int at_indices_ok(Ctx *c, const Cloud &q, const uint32_t *indices, size_t n_indices, const char *fn);
+// indices: host, or null for every point of q.  with_normals: Q2's same-slot case (a query with a non-finite normal is invalid).
+// S: the surface (fill_target).  `indices` is copied before the call returns; the kernels are queued on the context's stream.
+int at_queries(Ctx *c, const Cloud &q, bool with_normals, const uint32_t *indices, size_t n_indices, const KnnSlot &S, AtQueries *out);
+// the marking walk: S = the query array over the surface, gn = the surface's normals in the order of S.gt with the validity mark in
+// w; count[row] = the query's valid neighbours, need[j] = 1 at the grid position of each (need: S.nt bytes, cleared by the caller)
+int launch_at_mark(Ctx *c, const KnnSlot &S, const float4 *gn, float r2, bool fma, uint32_t *count, uint8_t *need);
 
 // the radius lists of the points of q in t (both past knn_cloud_ok; rules RS1-RS11 at mvr_radius_search in mvr_hip.h) as CSR
 // tables that stay on the device (mvr_radius.hip): offsets[nq + 1] by query index, idx / d2 [total].  The tables belong to the

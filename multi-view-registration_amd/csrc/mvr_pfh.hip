@@ -43,8 +43,9 @@ struct PfhTotals {
 };
 
 struct PfhArgs {
-  KnnSlot S;                       // the cloud searched against itself (nrm / curv / oidx / od2 unused)
-  const float4 *gn;                // radius mode: normals in the order of S.qs, w = 1 for a valid point, else 0
+  KnnSlot S;                       // the surface as target; its own points as queries, or (at) the query array (nrm / curv / oidx / od2 unused)
+  const float4 *gn;                // radius mode: normals in the order of S.gt, w = 1 for a valid point, else 0
+  int at;                          // the queries are a query array (mvr_cloud_pfh_at): valid iff finite (Q2), rows by w
   const float4 *pts, *nrm;         // k mode: the slot's points and normals by index
   const uint32_t *kidx;            // k mode: [n][k] by index
   const float *kd2;
@@ -157,7 +158,7 @@ __global__ void __launch_bounds__(kLanes) pfh_radius_kernel(PfhArgs a)
   const uint32_t pos = blockIdx.x;
   const float4 q = S.qs[pos];
   const uint32_t qi = S.q_by_pos ? pos : __float_as_uint(q.w);
-  if (a.gn[pos].w == 0.f) {                           // P1 (an invalid query walks nothing)
+  if (a.at ? !finite3(q) : a.gn[pos].w == 0.f) {      // P1 / Q2 (an invalid query walks nothing)
     pfh_write_row(a, qi, 0u, false, hist);
     if (threadIdx.x == 0) a.ncount[qi] = 0u;
     return;
@@ -170,7 +171,7 @@ __global__ void __launch_bounds__(kLanes) pfh_radius_kernel(PfhArgs a)
   if (threadIdx.x == 0) {
     a.ncount[qi] = n;
     atomicMax(&a.totals->max_n, n);
-    atomicAdd(&a.totals->pairs, (unsigned long long)n * (unsigned long long)(n - 1u) / 2ull);      // (n >= 1: the query itself)
+    atomicAdd(&a.totals->pairs, (unsigned long long)n * (unsigned long long)(n > 0u ? n - 1u : 0u) / 2ull);      // (n == 0: a query off the surface)
     if (n > cap) {                                    // the tiled launch takes it
       const uint32_t at = atomicAdd(&a.totals->listed, 1u);
       a.big_pos[at] = pos;
@@ -218,13 +219,13 @@ __global__ void __launch_bounds__(kLanes) pfh_tiled_kernel(PfhArgs a)
   pfh_write_row(a, qi, n, true, hist);
 }
 
-// k mode: block = query INDEX; lane l stages entry l of the query's list
+// k mode: block = query INDEX (at: output row, whose list is row qi of the table); lane l stages entry l of the query's list
 __global__ void __launch_bounds__(kLanes) pfh_knn_kernel(PfhArgs a)
 {
   __shared__ float4 sp[kLanes], sn[kLanes];
   __shared__ uint32_t hist[128];
   const uint32_t qi = blockIdx.x, lane = threadIdx.x;
-  if (!(finite3(a.pts[qi]) && finite3(a.nrm[qi]))) {  // P1
+  if (!a.at && !(finite3(a.pts[qi]) && finite3(a.nrm[qi]))) {  // P1 (at: an invalid query has an empty list, the same row)
     pfh_write_row(a, qi, 0u, false, hist);
     if (lane == 0) a.ncount[qi] = 0u;
     return;
@@ -258,18 +259,24 @@ __global__ void __launch_bounds__(kLanes) pfh_knn_kernel(PfhArgs a)
   pfh_write_row(a, qi, n, true, hist);
 }
 
-int pfh_cloud(Ctx *c, Cloud &cl, const mvr_pfh_params &p, float *pfh, uint32_t *counts, uint32_t *neighbor_count)
+// qc null: every point of the cloud cl against cl itself (mvr_cloud_pfh).  Else the queries of rules Q1 / Q2 -- the points
+// `indices` of qc (null: all of them) -- over the surface cl (mvr_cloud_pfh_at); the refusals of both are the caller's.
+int pfh_cloud(Ctx *c, Cloud &cl, const mvr_pfh_params &p, float *pfh, uint32_t *counts, uint32_t *neighbor_count, const Cloud *qc = nullptr,
+              const uint32_t *indices = nullptr, size_t n_indices = 0)
 {
-  const size_t n = cl.n;
+  const size_t ns = cl.n, n = !qc ? ns : indices ? n_indices : qc->n;      // surface points; queries = output rows
   c->pfh_tiled = c->pfh_pairs = 0;
-  if (!cl.has_normals && n > 0) return set_error(c, MVR_E_ARG, "pfh: the slot has no normals");
+  if (!cl.has_normals && ns > 0) return set_error(c, MVR_E_ARG, "pfh: the slot has no normals");
   if (int rc = knn_cloud_ok(c, cl, "pfh")) return rc;
   if (n == 0) return MVR_OK;
   MVR_MAY_BLOCK(c, "pfh reads back");
   const bool kmode = p.k > 0, fma = p.fma_dist != 0;
   PfhArgs a{};
+  a.at = qc ? 1 : 0;
   DevBuf klist_i, klist_d;
-  if (kmode) {
+  AtQueries Q;
+  KnnSlot self{};                                          // the surface walking itself: the order of gn
+  if (kmode && !qc) {
     const size_t m = n * (size_t)p.k;
     if (klist_i.alloc(m * 4) != hipSuccess || klist_d.alloc(m * 4) != hipSuccess) return set_error(c, MVR_E_NOMEM, "pfh: out of device memory");
     if (int rc = knn_self_device(c, cl, p.k, fma, klist_i.as<uint32_t>(), klist_d.as<float>())) return rc;
@@ -277,15 +284,27 @@ int pfh_cloud(Ctx *c, Cloud &cl, const mvr_pfh_params &p, float *pfh, uint32_t *
   } else {
     if (int rc = fill_target(c, cl, a.S)) return rc;      // (before the arena is carved: the grid build uses the context's buffers)
     fill_queries(cl, a.S);
+    self = a.S;
     a.r2 = clamp_r2(p.radius);
+    if (qc) {
+      if (int rc = at_queries(c, *qc, qc == &cl, indices, n_indices, a.S, &Q)) return rc;
+      a.S.qs = Q.q; a.S.q_by_pos = 0u; a.S.nq = (uint32_t)n;
+    }
+    if (kmode) {                                           // the lists of the queries in the surface, by row
+      const size_t m = n * (size_t)p.k;
+      if (klist_i.alloc(m * 4) != hipSuccess || klist_d.alloc(m * 4) != hipSuccess) return set_error(c, MVR_E_NOMEM, "pfh: out of device memory");
+      a.S.oidx = klist_i.as<uint32_t>(); a.S.od2 = klist_d.as<float>();
+      if (int rc = knn_device(c, a.S, p.k, fma)) return rc;
+      a.pts = cl.pts; a.nrm = cl.nrm; a.kidx = klist_i.as<uint32_t>(); a.kd2 = klist_d.as<float>(); a.k = p.k;
+    }
   }
   const size_t rows = n * (size_t)kDim;
   Carver plan;
-  plan.plan<float4>(n); plan.plan<float>(pfh ? rows : 1); plan.plan<uint32_t>(counts ? rows : 1); plan.plan<uint32_t>(n);
+  plan.plan<float4>(ns); plan.plan<float>(pfh ? rows : 1); plan.plan<uint32_t>(counts ? rows : 1); plan.plan<uint32_t>(n);
   plan.plan<PfhTotals>(1); plan.plan<uint32_t>(n); plan.plan<unsigned long long>(n);
   if (int rc = ensure(c, c->dn_arena, c->dn_arena_cap, plan.off + 256)) return rc;
   Carver s; s.base = c->dn_arena;
-  float4 *gn = s.take<float4>(n);
+  float4 *gn = s.take<float4>(ns);
   a.gn = gn;
   a.out = s.take<float>(pfh ? rows : 1);
   a.counts = s.take<uint32_t>(counts ? rows : 1);
@@ -301,8 +320,10 @@ int pfh_cloud(Ctx *c, Cloud &cl, const mvr_pfh_params &p, float *pfh, uint32_t *
   if (kmode) {
     hipLaunchKernelGGL(pfh_knn_kernel, grid, block, 0, c->stream, a);
   } else {
-    hipLaunchKernelGGL(valid_normals_kernel<kKnnThreads>, dim3(blocks_for(n, kKnnThreads)), dim3(kKnnThreads), 0, c->stream, a.S, cl.nrm, gn);
-    MVR_HIP_TRY(c, hipGetLastError());
+    if (ns > 0) {
+      hipLaunchKernelGGL(valid_normals_kernel<kKnnThreads>, dim3(blocks_for(ns, kKnnThreads)), dim3(kKnnThreads), 0, c->stream, self, cl.nrm, gn);
+      MVR_HIP_TRY(c, hipGetLastError());
+    }
     if (fma) hipLaunchKernelGGL(pfh_radius_kernel<true>, grid, block, 0, c->stream, a);
     else hipLaunchKernelGGL(pfh_radius_kernel<false>, grid, block, 0, c->stream, a);
   }
@@ -348,4 +369,21 @@ API int mvr_cloud_pfh(mvr_ctx *ctx, int slot, const mvr_pfh_params *p, float *pf
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   MVR_HIP_TRY(c, hipSetDevice(c->device));
   return pfh_cloud(c, c->slots[slot], *p, pfh, counts, neighbor_count);
+}
+
+API int mvr_cloud_pfh_at(mvr_ctx *ctx, int q_slot, const uint32_t *indices, size_t n_indices, int surface_slot, const mvr_pfh_params *p, float *pfh,
+                         uint32_t *counts, uint32_t *neighbor_count)
+{
+  if (!ctx || !p || !slot_ok(q_slot) || !slot_ok(surface_slot)) return MVR_E_ARG;
+  const bool kmode = p->k != 0, rmode = p->radius != 0.0;
+  if (kmode == rmode || p->k < 0 || p->k > MVR_MAX_KNN || !(std::isfinite(p->radius) && p->radius >= 0.0)) return MVR_E_ARG;
+  Ctx *c = reinterpret_cast<Ctx *>(ctx);
+  MVR_HIP_TRY(c, hipSetDevice(c->device));
+  Cloud &q = c->slots[q_slot], &t = c->slots[surface_slot];
+  if (!indices && q_slot == surface_slot) return pfh_cloud(c, t, *p, pfh, counts, neighbor_count);      // Q8
+  if (!t.has_normals && t.n > 0) return set_error(c, MVR_E_ARG, "pfh: the surface slot has no normals");
+  if (int rc = knn_cloud_ok(c, q, "pfh")) return rc;
+  if (int rc = knn_cloud_ok(c, t, "pfh")) return rc;
+  if (int rc = at_indices_ok(c, q, indices, n_indices, "pfh")) return rc;
+  return pfh_cloud(c, t, *p, pfh, counts, neighbor_count, &q, indices, n_indices);
 }
