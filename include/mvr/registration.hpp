@@ -1408,6 +1408,171 @@ class PFHEstimation {
   bool use_cache_ = false;
 };
 
+// ---------------------------------------------------------------- SHOT descriptors
+// pcl::SHOTLocalReferenceFrameEstimation<PointInT, PointOutT> (features/shot_lrf.h), the input cloud its own search surface:
+// setInputCloud, setSearchMethod, setRadiusSearch, compute.  Semantics: mvr_cloud_shot_lrf (rules L1-L7 in mvr_hip.h); a point
+// with fewer than five other points within the radius gets nine NaN, and is_dense says so.
+template <typename PointInT, typename PointOutT = ReferenceFrame>
+class SHOTLocalReferenceFrameEstimation {
+ public:
+  typedef PointCloud<PointInT> PointCloudIn;
+  typedef typename PointCloudIn::ConstPtr PointCloudConstPtr;
+  typedef PointCloud<PointOutT> PointCloudOut;
+  typedef search::KdTree<PointInT> KdTree;
+  typedef typename KdTree::Ptr KdTreePtr;
+
+  void setInputCloud(const PointCloudConstPtr &c) { input_ = c; }
+  void setSearchMethod(const KdTreePtr &tree) { tree_ = tree; }
+  void setRadiusSearch(double r) { radius_ = r; }
+  double getRadiusSearch() const { return radius_; }
+
+  void compute(PointCloudOut &output)
+  {
+    static_assert(sizeof(PointInT) % 4 == 0 && sizeof(PointInT) >= 12, "points that begin with x, y, z expected");
+    static_assert(sizeof(PointOutT) == sizeof(float) * 9, "a frame of nine floats expected");
+    output.clear();
+    if (!input_) { std::fprintf(stderr, "[pcl::SHOTLocalReferenceFrameEstimation::compute] No input dataset was given!\n"); return; }
+    if (!(std::isfinite(radius_) && radius_ > 0.0)) {
+      std::fprintf(stderr, "[pcl::SHOTLocalReferenceFrameEstimation::compute] The search radius (%f) must be finite and > 0 (setRadiusSearch).\n", radius_);
+      return;
+    }
+    const size_t n = input_->size();
+    output.resize(n);
+    if (!n) return;
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.check(mvr_cloud_upload(d.ctx(), s.s, input_->points[0].data, n, sizeof(PointInT)), "mvr_cloud_upload");
+    mvr_shot_params p;
+    p.radius = radius_; p.lrf_radius = 0.0; p.fma_dist = 0;
+    d.check(mvr_cloud_shot_lrf(d.ctx(), s.s, &p, output.points[0].rf, nullptr), "mvr_cloud_shot_lrf");
+    for (size_t i = 0; i < n && output.is_dense; ++i)
+      if (std::isnan(output.points[i].rf[0])) output.is_dense = false;
+  }
+
+ private:
+  PointCloudConstPtr input_;
+  KdTreePtr tree_;
+  double radius_ = 0.0;
+};
+
+// pcl::SHOTEstimation<PointInT, PointNT, PointOutT, PointRFT> (features/shot.h): setInputCloud, setInputNormals (the normals of
+// the search surface when one is set, as in PCL, else of the input), setSearchSurface, setIndices, setSearchMethod,
+// setRadiusSearch, setLRFRadius (0, the default: the search radius), setInputReferenceFrames (one frame per output row; no frame
+// is then computed), compute.  Semantics: mvr_cloud_shot / mvr_cloud_shot_at (rules L1-L7, H1-H9 and Q1-Q8 in mvr_hip.h) -- one
+// call on the GPU per compute().  With indices the output holds one row per index; every row carries its frame in rf.
+template <typename PointInT, typename PointNT, typename PointOutT = SHOT352, typename PointRFT = ReferenceFrame>
+class SHOTEstimation {
+ public:
+  typedef PointCloud<PointInT> PointCloudIn;
+  typedef typename PointCloudIn::ConstPtr PointCloudConstPtr;
+  typedef PointCloud<PointNT> PointCloudN;
+  typedef typename PointCloudN::ConstPtr PointCloudNConstPtr;
+  typedef PointCloud<PointRFT> PointCloudRF;
+  typedef typename PointCloudRF::ConstPtr PointCloudRFConstPtr;
+  typedef PointCloud<PointOutT> PointCloudOut;
+  typedef search::KdTree<PointInT> KdTree;
+  typedef typename KdTree::Ptr KdTreePtr;
+  typedef std::shared_ptr<const std::vector<int> > IndicesConstPtr;
+
+  void setInputCloud(const PointCloudConstPtr &c) { input_ = c; }
+  void setInputNormals(const PointCloudNConstPtr &n) { normals_ = n; }
+  void setSearchSurface(const PointCloudConstPtr &c) { surface_ = c; }
+  void setIndices(const IndicesConstPtr &i) { indices_ = i; }
+  void setSearchMethod(const KdTreePtr &tree) { tree_ = tree; }
+  void setRadiusSearch(double r) { radius_ = r; }
+  double getRadiusSearch() const { return radius_; }
+  void setLRFRadius(float r) { lrf_radius_ = r; }
+  float getLRFRadius() const { return lrf_radius_; }
+  void setInputReferenceFrames(const PointCloudRFConstPtr &f) { frames_ = f; }
+
+  void compute(PointCloudOut &output)
+  {
+    static_assert(sizeof(PointInT) % 4 == 0 && sizeof(PointInT) >= 12, "points that begin with x, y, z expected");
+    static_assert(sizeof(PointOutT) == sizeof(float) * (MVR_SHOT_DIM + 9) && sizeof(PointRFT) == sizeof(float) * 9, "SHOT352 and a frame of nine floats expected");
+    output.clear();
+    if (!input_) { std::fprintf(stderr, "[pcl::SHOTEstimation::compute] No input dataset was given!\n"); return; }
+    const PointCloudConstPtr &surface = surface_ ? surface_ : input_;
+    if (!normals_ || normals_->size() != surface->size()) {
+      std::fprintf(stderr, "[pcl::SHOTEstimation::compute] The number of points in the search surface differs from the number of points in the dataset containing the normals!\n");
+      return;
+    }
+    if (!(std::isfinite(radius_) && radius_ > 0.0) || !(std::isfinite(lrf_radius_) && lrf_radius_ >= 0.f)) {
+      std::fprintf(stderr, "[pcl::SHOTEstimation::compute] The search radius (%f) must be finite and > 0 (setRadiusSearch), the LRF radius (%f) finite and >= 0.\n",
+                   radius_, (double)lrf_radius_);
+      return;
+    }
+    std::vector<uint32_t> idx;
+    if (indices_)
+      for (int i : *indices_) {
+        if (i < 0 || (size_t)i >= input_->size()) { std::fprintf(stderr, "[pcl::SHOTEstimation::compute] The index %d lies beyond the input cloud.\n", i); return; }
+        idx.push_back((uint32_t)i);
+      }
+    const size_t rows = indices_ ? idx.size() : input_->size();
+    if (frames_ && frames_->size() != rows) {
+      std::fprintf(stderr, "[pcl::SHOTEstimation::compute] One input reference frame per output row expected (%zu for %zu)!\n", frames_->size(), rows);
+      return;
+    }
+    output.resize(rows);
+    if (!rows) return;
+    Device &d = Device::instance();
+    SlotGuard s;
+    const size_t ns = surface->size();
+    d.check(mvr_cloud_upload(d.ctx(), s.s, ns ? surface->points[0].data : nullptr, ns, sizeof(PointInT)), "mvr_cloud_upload");
+    if (ns) {
+      std::vector<float> nrm(4 * ns);
+      for (size_t i = 0; i < ns; ++i) {
+        const PointNT &q = normals_->points[i];
+        nrm[4 * i] = q.normal_x; nrm[4 * i + 1] = q.normal_y; nrm[4 * i + 2] = q.normal_z; nrm[4 * i + 3] = 0.f;
+      }
+      d.check(mvr_cloud_upload_normals(d.ctx(), s.s, nrm.data(), ns, 16), "mvr_cloud_upload_normals");
+    }
+    std::shared_ptr<SlotGuard> q;
+    if (surface_ && surface_ != input_) {
+      q = std::make_shared<SlotGuard>();
+      d.check(mvr_cloud_upload(d.ctx(), q->s, input_->points[0].data, input_->size(), sizeof(PointInT)), "mvr_cloud_upload");
+    }
+    mvr_shot_params p;
+    p.radius = radius_; p.lrf_radius = (double)lrf_radius_; p.fma_dist = 0;
+    std::vector<float> rowsf(rows * (size_t)MVR_SHOT_DIM), lrf(rows * 9);
+    const float *fin = frames_ ? frames_->points[0].rf : nullptr;
+    if (q || indices_)
+      d.check(mvr_cloud_shot_at(d.ctx(), q ? q->s : s.s, indices_ ? idx.data() : nullptr, idx.size(), s.s, &p, fin, rowsf.data(), lrf.data(), nullptr, nullptr),
+              "mvr_cloud_shot_at");
+    else
+      d.check(mvr_cloud_shot(d.ctx(), s.s, &p, fin, rowsf.data(), lrf.data(), nullptr, nullptr), "mvr_cloud_shot");
+    for (size_t i = 0; i < rows; ++i) {
+      std::memcpy(output.points[i].descriptor, rowsf.data() + i * MVR_SHOT_DIM, sizeof(float) * MVR_SHOT_DIM);
+      std::memcpy(output.points[i].rf, lrf.data() + i * 9, sizeof(float) * 9);
+      if (std::isnan(output.points[i].descriptor[0])) output.is_dense = false;
+    }
+  }
+
+ private:
+  PointCloudConstPtr input_, surface_;
+  PointCloudNConstPtr normals_;
+  PointCloudRFConstPtr frames_;
+  IndicesConstPtr indices_;
+  KdTreePtr tree_;
+  double radius_ = 0.0;
+  float lrf_radius_ = 0.f;
+};
+
+// the rows of a feature cloud as the contiguous table the matcher takes: `dim` floats per row.  A signature that is nothing but
+// its histogram is the table already; pcl::SHOT352 carries its frame behind the descriptor and is packed.
+template <typename FeatureT> struct FeatureRows {
+  enum { dim = sizeof(FeatureT) / sizeof(float) };
+  static const float *table(const std::vector<FeatureT> &f, std::vector<float> &) { return f.empty() ? nullptr : f[0].histogram; }
+};
+template <> struct FeatureRows<SHOT352> {
+  enum { dim = MVR_SHOT_DIM };
+  static const float *table(const std::vector<SHOT352> &f, std::vector<float> &packed)
+  {
+    packed.resize(f.size() * (size_t)MVR_SHOT_DIM);
+    for (size_t i = 0; i < f.size(); ++i) std::memcpy(packed.data() + i * MVR_SHOT_DIM, f[i].descriptor, sizeof(float) * MVR_SHOT_DIM);
+    return f.empty() ? nullptr : packed.data();
+  }
+};
+
 // ---------------------------------------------------------------- boundary points
 // pcl::BoundaryEstimation<PointInT, PointNT, PointOutT> (features/boundary.h) in radius mode, the input cloud its own search
 // surface: setInputCloud, setInputNormals, setSearchMethod, setRadiusSearch, setAngleThreshold / getAngleThreshold (PCL's
@@ -1883,7 +2048,7 @@ extractEuclideanClusters(const PointCloud<PointT> &cloud, float tolerance, const
 // setInputSource, setInputTarget, setSourceFeatures, setTargetFeatures, setMaximumIterations, setNumberOfSamples,
 // setCorrespondenceRandomness, setSimilarityThreshold, setMaxCorrespondenceDistance, setInlierFraction, align, hasConverged,
 // getFinalTransformation, getFitnessScore, getInliers.  Semantics: mvr_align_prerejective_dim (mvr_hip.h) -- one call per align();
-// FeatureT is a signature of 33 floats (FPFHSignature33) or of 125 (PFHSignature125).
+// FeatureT is a signature of 33 floats (FPFHSignature33), of 125 (PFHSignature125) or pcl::SHOT352 (352; FeatureRows above).
 // PCL draws with rand(); here the result is a pure function of the inputs and of setSeed (ours).  Defaults are PCL's (3
 // samples, randomness 2, similarity 0.9, inlier fraction 0); an inlier fraction of 0 -- which the C-ABI refuses -- is sent as
 // the smallest positive double, the same test.  As PCL, a missing cloud or feature set, or a feature set of another size than
@@ -1937,8 +2102,8 @@ class SampleConsensusPrerejective {
  private:
   void align(PointCloudSource &output, const Matrix4 &guess, bool with_guess)
   {
-    static_assert(sizeof(FeatureT) == sizeof(float) * 3 * MVR_FPFH_BINS || sizeof(FeatureT) == sizeof(float) * MVR_PFH_DIM,
-                  "a 33-float or a 125-float signature expected");
+    static_assert(FeatureRows<FeatureT>::dim == 3 * MVR_FPFH_BINS || FeatureRows<FeatureT>::dim == MVR_PFH_DIM || FeatureRows<FeatureT>::dim == MVR_SHOT_DIM,
+                  "a 33-float or a 125-float signature, or SHOT352, expected");
     output.clear(); inliers_.clear();
     result_ = mvr_prerej_result(); result_.best_iteration = -1; result_.error = DBL_MAX;
     final_ = with_guess ? guess : Matrix4::Identity();
@@ -1952,9 +2117,10 @@ class SampleConsensusPrerejective {
     d.upload(tgt_.s, *target_);
     mvr_prerej_params p = p_;
     if (p.inlier_fraction == 0.0) p.inlier_fraction = DBL_MIN;
-    static const float none[MVR_PFH_DIM] = {0};
-    d.check(mvr_align_prerejective_dim(d.ctx(), src_.s, tgt_.s, sfeat_->empty() ? none : sfeat_->points[0].histogram,
-                                       tfeat_->empty() ? none : tfeat_->points[0].histogram, (int)(sizeof(FeatureT) / sizeof(float)), &p,
+    static const float none[MVR_SHOT_DIM] = {0};
+    std::vector<float> spack, tpack;
+    const float *sp = FeatureRows<FeatureT>::table(sfeat_->points, spack), *tp = FeatureRows<FeatureT>::table(tfeat_->points, tpack);
+    d.check(mvr_align_prerejective_dim(d.ctx(), src_.s, tgt_.s, sp ? sp : none, tp ? tp : none, (int)FeatureRows<FeatureT>::dim, &p,
                                        with_guess ? guess.data() : nullptr, &result_, nullptr),
             "mvr_align_prerejective_dim");
     final_ = Matrix4(result_.T);

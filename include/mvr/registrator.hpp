@@ -662,6 +662,101 @@ class ScanCloud {
     if (!computePFH(params.feature_radius, sf) || !target.computePFH(params.feature_radius, tf)) return false;
     return alignPrerejective(target, params, sf, tf, pose, result);
   }
+  // EXTENSION (pcl::SHOTEstimation on the raw points, on the GPU; rules L1-L7 and H1-H9: mvr_cloud_shot in mvr_hip.h): one SHOT352
+  // per point -- 352 unit-norm floats and the local reference frame they were computed in -- with the normals of `rich`;
+  // lrf_radius 0: the radius.  Refusals as computeFPFH.  computeSHOTAt: at the points `indices` of this cloud, or at every raw
+  // point of this cloud over `surface` and its normals (rules Q1-Q8), bit for bit the rows computeSHOT gives those points.
+  bool computeSHOT(double radius, std::vector<SHOT352> &out, double lrf_radius = 0.0) const
+  {
+    return shotAt("computeSHOT", radius, lrf_radius, nullptr, nullptr, out);
+  }
+  bool computeSHOTAt(double radius, const std::vector<uint32_t> &indices, std::vector<SHOT352> &out, double lrf_radius = 0.0) const
+  {
+    return shotAt("computeSHOTAt", radius, lrf_radius, nullptr, &indices, out);
+  }
+  bool computeSHOTAt(const ScanCloud &surface, double radius, std::vector<SHOT352> &out, double lrf_radius = 0.0) const
+  {
+    return surface.shotAt("computeSHOTAt", radius, lrf_radius, this, nullptr, out);
+  }
+  // the coarse alignment from SHOT descriptors (computeSHOT of both scans at feature_radius): 352 floats per row through the
+  // same matcher and aligner; with use_keypoints the descriptors are computed AT the ISS keypoints only, as alignPrerejectivePFH
+  // does it, into tables that are NaN elsewhere
+  bool alignPrerejectiveSHOT(const ScanCloud &target, const PrerejectiveParams &params, RowMatrixd &pose, mvr_prerej_result *result = nullptr) const
+  {
+    if (result) { *result = mvr_prerej_result(); result->best_iteration = -1; result->error = DBL_MAX; }
+    std::vector<float> st, tt;
+    if (params.use_keypoints) {
+      if (!featureInputsOk("computeSHOT", params.feature_radius) || !target.featureInputsOk("computeSHOT", params.feature_radius)) return false;
+      std::vector<uint32_t> sk, tk;
+      if (!detectKeypoints(params.keypoints, params.border, sk) || !target.detectKeypoints(params.keypoints, params.border, tk)) return false;
+      if (!shotTable(params.feature_radius, &sk, st) || !target.shotTable(params.feature_radius, &tk, tt)) return false;
+    } else if (!shotTable(params.feature_radius, nullptr, st) || !target.shotTable(params.feature_radius, nullptr, tt)) {
+      return false;
+    }
+    Device &d = Device::instance();
+    SlotGuard s, t;
+    d.upload(s.s, points);
+    d.upload(t.s, target.points);
+    static const float none[MVR_SHOT_DIM] = {0};
+    mvr_prerej_result res;
+    d.check(mvr_align_prerejective_dim(d.ctx(), s.s, t.s, st.empty() ? none : st.data(), tt.empty() ? none : tt.data(), MVR_SHOT_DIM, &params.align, nullptr,
+                                       &res, nullptr), "mvr_align_prerejective_dim");
+    if (result) *result = res;
+    if (!res.converged) return false;
+    pose = PclMatrixCaster<RowMatrixd>(Matrix4f(res.T));
+    return true;
+  }
+  // the SHOT rows of this cloud as the contiguous table the matcher takes, one row of 352 floats per point; with `key` only
+  // those rows are computed and the others are NaN
+  bool shotTable(double radius, const std::vector<uint32_t> *key, std::vector<float> &table) const
+  {
+    std::vector<SHOT352> rows;
+    if (!shotAt("computeSHOT", radius, 0.0, nullptr, key, rows)) return false;
+    table.assign(points.size() * (size_t)MVR_SHOT_DIM, key ? std::numeric_limits<float>::quiet_NaN() : 0.f);
+    for (size_t r = 0; r < rows.size(); ++r)
+      std::memcpy(table.data() + (size_t)(key ? (*key)[r] : r) * MVR_SHOT_DIM, rows[r].descriptor, sizeof(float) * MVR_SHOT_DIM);
+    return true;
+  }
+  // the SHOT rows of the queries over THIS cloud and its normals: the points `indices` of this cloud, or every raw point of
+  // `queries`, or (both null) every point of this cloud
+  bool shotAt(const char *fn, double radius, double lrf_radius, const ScanCloud *queries, const std::vector<uint32_t> *indices, std::vector<SHOT352> &out) const
+  {
+    out.clear();
+    if (!featureInputsOk(fn, radius)) return false;
+    if (!(std::isfinite(lrf_radius) && lrf_radius >= 0.0)) {
+      std::fprintf(stderr, "[ScanCloud::%s] The LRF radius (%f) must be finite and >= 0.\n", fn, lrf_radius);
+      return false;
+    }
+    const size_t n = points.size(), nq = queries ? queries->points.size() : n;
+    if (indices)
+      for (uint32_t i : *indices)
+        if (i >= nq) {
+          std::fprintf(stderr, "[ScanCloud::%s] The index %u lies beyond the cloud (%zu points).\n", fn, i, nq);
+          return false;
+        }
+    const size_t rows = indices ? indices->size() : nq;
+    out.resize(rows);
+    if (!rows) return true;
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.upload(s.s, points);
+    if (n) uploadRichNormals(d, s.s);
+    std::shared_ptr<SlotGuard> q;
+    if (queries && queries != this) { q = std::make_shared<SlotGuard>(); d.upload(q->s, queries->points); }
+    mvr_shot_params p;
+    p.radius = radius; p.lrf_radius = lrf_radius; p.fma_dist = 0;
+    std::vector<float> table(rows * (size_t)MVR_SHOT_DIM), lrf(rows * 9);
+    if (q || indices)
+      d.check(mvr_cloud_shot_at(d.ctx(), q ? q->s : s.s, indices ? indices->data() : nullptr, rows, s.s, &p, nullptr, table.data(), lrf.data(), nullptr, nullptr),
+              "mvr_cloud_shot_at");
+    else
+      d.check(mvr_cloud_shot(d.ctx(), s.s, &p, nullptr, table.data(), lrf.data(), nullptr, nullptr), "mvr_cloud_shot");
+    for (size_t r = 0; r < rows; ++r) {
+      std::memcpy(out[r].descriptor, table.data() + r * MVR_SHOT_DIM, sizeof(float) * MVR_SHOT_DIM);
+      std::memcpy(out[r].rf, lrf.data() + r * 9, sizeof(float) * 9);
+    }
+    return true;
+  }
   // the aligner on descriptor tables the caller holds, one row per point of this scan (sf) and of `target` (tf), 33 or 125
   // floats per row; with use_keypoints the rows of the other points are overwritten with NaN first
   template <typename FeatureT>

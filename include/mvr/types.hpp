@@ -79,6 +79,27 @@ struct PFHSignature125 {
 };
 static_assert(sizeof(PFHSignature125) == 500, "PFHSignature125 must match pcl::PFHSignature125");
 
+// pcl::ReferenceFrame: a local reference frame, nine floats row-major -- x axis, y axis, z axis (rules L1-L7 at mvr_cloud_shot
+// in mvr_hip.h)
+struct ReferenceFrame {
+  union {
+    float rf[9];
+    struct { float x_axis[3], y_axis[3], z_axis[3]; };
+  };
+  ReferenceFrame() { for (float &v : rf) v = 0.f; }
+};
+static_assert(sizeof(ReferenceFrame) == 36, "ReferenceFrame must match pcl::ReferenceFrame");
+
+// pcl::SHOT352: 32 volumes x 11 shape slots of a signature of histograms of orientations, and the frame it was computed in
+// (mvr_cloud_shot in mvr_hip.h)
+struct SHOT352 {
+  float descriptor[352];
+  float rf[9];
+  static int descriptorSize() { return 352; }
+  SHOT352() { for (float &h : descriptor) h = 0.f; for (float &v : rf) v = 0.f; }
+};
+static_assert(sizeof(SHOT352) == 1444, "SHOT352 must match pcl::SHOT352");
+
 // pcl::Boundary: whether a point lies on the rim of its surface (mvr_cloud_boundary in mvr_hip.h)
 struct Boundary {
   uint8_t boundary_point;

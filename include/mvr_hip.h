@@ -570,6 +570,90 @@ int  mvr_cloud_pfh_at(mvr_ctx *ctx, int q_slot, const uint32_t *indices, size_t 
                       uint32_t *counts         /* optional host, rows * 125     */,
                       uint32_t *neighbor_count /* optional host, rows           */);
 
+/* ---- SHOT descriptors and their local reference frames (EXTENSION: pcl::SHOTEstimation, SHOT352) -------------------------
+ * The 352-float signature of histograms of orientations: 32 volumes (8 azimuth sectors x 2 radial husks x 2 elevation halves)
+ * of a repeatable local reference frame, 11 slots of the cosine between the neighbour's normal and the frame's z axis each;
+ * linear in the neighbourhood.  PCL was not at hand; the models are pcl/features/impl/shot.hpp (interpolateSingleChannel,
+ * normalizeHistogram) and shot_lrf.hpp (getLocalRF), as published; deviations are marked.  A frame is nine f32, row-major:
+ * x axis, y axis, z axis.
+ * Local reference frame:
+ *  L1. A surface point takes part iff its three coordinates are finite; no normal is needed.  A query is a position (Q2); a
+ *      non-finite query gets nine NaN and count 0.
+ *  L2. Neighbourhood: rule F2 at lrf_radius (0: radius) -- f32 d2 <= (float)(R * R), fma_dist as everywhere -- WITHOUT the
+ *      surface points whose three f32 coordinates equal the query's (the query's own point and its exact copies).  FOLLOWING
+ *      THE PUBLISHED FILE: getLocalRF skips them (`if (pt.head<3> () == central_point.head<3> ()) continue;`) in the
+ *      covariance, in the votes and in the count.  n = the number of the others, which mvr_cloud_shot_lrf reports; n < 5 gives
+ *      nine NaN.
+ *  L3. All in f64: v_j = (double)p_j - (double)q per component, d_j = sqrt(v_j . v_j), w_j = R - d_j (a weight that a
+ *      rounding at the rim makes <= 0 is used as it is, as in PCL), M = sum of w_j v_j v_j^T (six sums), W = sum of w_j.
+ *      W == 0 or anything non-finite gives nine NaN.
+ *  L4. C = M / W; the cyclic Jacobi of the normals; z0 = the unit eigenvector of the smallest eigenvalue, x0 that of the
+ *      largest -- always two different columns of the Jacobi basis, so an isotropic neighbourhood still gets an orthonormal frame.
+ *  L5. Sign of a in {x0, z0}: plus = #{j : (v_x a_x + v_y a_y) + v_z a_z >= 0} in f64 over all n neighbours; 2 plus > n keeps
+ *      a, 2 plus < n negates it.  DEVIATION on 2 plus == n: PCL looks at five neighbours around the median of FLANN's
+ *      distance-sorted list, which a streaming walk does not have; here s = sum of w_j (v_j . a) decides, s < 0 negates.
+ *  L6. y = z x x in f64; the nine components are rounded to f32, and the descriptor reads the frame back from those f32: a
+ *      frame passed as lrf_in and the frame computed inside the call give the same bits.
+ *  L7. Each lane adds in walk order, then a fixed tree: frames are bit-identical from run to run on one grid, and agree across
+ *      grid resolutions to rounding.  No floating-point atomics.
+ * Descriptor:
+ *  H1. The surface needs normals (F7); a surface point contributes iff it is valid under F1.  Query validity is Q2; in the
+ *      self mode F1 applies to the query.  An invalid query, or a frame with a NaN (computed or passed in), gives 352 NaN and
+ *      count 0 (and, for an invalid query, a NaN frame in lrf_out unless lrf_in was passed, which is returned as it came).
+ *  H2. N(i) is rule F2 at radius, the query's own point included; n_i = |N(i)| is what neighbor_count reports.  n_i < 5 gives
+ *      352 NaN (THE LIBRARY'S RULE: PCL warns and leaves the row unset).  A neighbour at f64 distance d == 0 adds nothing.
+ *  H3. v and d as in L3.  (x, y, z) = (v . X, v . Y, v . Z) in f64, each (a b + c d) + e f, X / Y / Z the f32 frame; a
+ *      component with |.| < 1e-30 is set to 0.
+ *  H4. Shape: c = n_j . Z in f64, clamped to [-1, 1]; a non-finite c skips the neighbour.  bin = ((1 + c) * 10) / 2,
+ *      step = floor(bin + 0.5) in 0..10, t = bin - step.
+ *  H5. Volume: vol = 4 s + 2 outer + upper, outer = d > R / 2, upper = z > 0, s the azimuth sector: with a = atan2(y, x),
+ *      s = min(7, floor((a + pi) / (pi / 4))), centred on -7 pi / 8 + s pi / 4; x == y == 0 gives s = 0.  The slot of (vol, k)
+ *      is 11 vol + k.  (FOLLOWING THE PUBLISHED FILE: s is computed as PCL computes it, from the signs of x and y and the
+ *      comparison of |x| with |y| -- the same sector, decided without a libm call, so that no rounding of atan2 moves a
+ *      neighbour on a sector border.)
+ *  H6. Amounts of one neighbour; home collects, the side amounts go to one neighbouring slot each.
+ *      (a) shape: home += 1 - |t|; t > 0: t to (vol, (step + 1) % 10); t < 0: -t to (vol, (step + 9) % 10).  (PCL'S PUBLISHED
+ *          QUIRK, kept: the modulus is 10 on 11 slots.)
+ *      (b) radial, outer: u = (d - 3R/4) / (R/2); d > 3R/4: home += 1 - u; else home += 1 + u and -u to (vol - 2, step).
+ *          Inner: u = (d - R/4) / (R/2); d < R/4: home += 1 + u; else home += 1 - u and u to (vol + 2, step).
+ *      (c) elevation, inc = acos(clamp(z / d)).  Lower half (inc > pi/2, or |inc - pi/2| < 1e-30 and z <= 0):
+ *          u = (inc - 3pi/4) / (pi/2); inc > 3pi/4: home += 1 - u; else home += 1 + u and -u to (vol + 1, step).  Upper half:
+ *          u = (inc - pi/4) / (pi/2); inc < pi/4: home += 1 + u; else home += 1 - u and u to (vol - 1, step).
+ *      (d) azimuth, unless x == y == 0: u = (a - centre(s)) / (pi/4) clamped to [-0.5, 0.5]; u > 0: home += 1 - u and u to
+ *          ((vol + 4) % 32, step); else home += 1 + u and -u to ((vol + 28) % 32, step).
+ *      (e) home goes to (vol, step).
+ *      (a) and (d) hand out 1 each; (b) and (c) hand out 1 between the centres of their two halves and 1 - |u| beyond them,
+ *      where no slot further out takes the rest: a neighbour adds at most 4 (3 on the z axis), exactly 4 at the centre of a
+ *      volume.  (As published the scheme is NOT continuous across a border: home carries the other dimensions' shares with
+ *      it from one slot to the next; only the border's own dimension is split half and half.)
+ *  H7. Fixed point: every amount w (a negative rounding is clamped to 0) becomes the integer floor(w 2^32 + 0.5) and is added
+ *      with an integer atomic into S[352], 64 bits wide: S depends on no order, lane assignment, grid resolution or tune key
+ *      (P8's argument).  PCL adds f32 amounts in FLANN's order: a difference of rounding only.
+ *  H8. norm = sqrt(sum over ascending b of ((double)S_b)^2); out_b = (float)((double)S_b / norm).  norm == 0 gives 352 NaN
+ *      (PCL's 0 / 0; M3 then ignores the row).  `sums` of a NaN row of H1 / H2 are zeros.
+ *  H9. Refusals: those of F7 / Q7, plus lrf_radius non-finite or < 0; all before any GPU work, with nothing written.  An
+ *      empty cloud is MVR_OK.  All outputs NULL: MVR_OK after the work.  Neither slot is modified, nothing stays on the device.
+ * mvr_cloud_shot_lrf needs no normals and reports n of L2.  mvr_cloud_shot_at follows Q1-Q8; Q5 holds for the frames, the sums,
+ * the rows and the counts.  One wave per query, three streaming walks (L sums; signs; descriptor), no neighbour list, no cap.
+ * Out of scope: colour SHOT (SHOT1344), the k-neighbour mode, descriptors kept on the device. */
+#define MVR_SHOT_DIM 352            /* 32 volumes x 11 shape slots (pcl::SHOT352) */
+typedef struct {
+  double radius;        /* setRadiusSearch: finite, > 0                                   */
+  double lrf_radius;    /* setLRFRadius: finite, > 0, or 0 = radius                       */
+  int    fma_dist;
+} mvr_shot_params;
+int  mvr_cloud_shot_lrf(mvr_ctx *ctx, int slot, const mvr_shot_params *p, float *lrf /* host, n * 9 */,
+                        uint32_t *neighbor_count /* optional host, n */);
+int  mvr_cloud_shot(mvr_ctx *ctx, int slot, const mvr_shot_params *p,
+                    const float *lrf_in      /* optional host, n * 9: setInputReferenceFrames */,
+                    float *shot              /* host, n * 352; may be NULL                    */,
+                    float *lrf_out           /* optional host, n * 9                          */,
+                    unsigned long long *sums /* optional host, n * 352: S of rule H7          */,
+                    uint32_t *neighbor_count /* optional host, n                              */);
+int  mvr_cloud_shot_at(mvr_ctx *ctx, int q_slot, const uint32_t *indices, size_t n_indices, int surface_slot,
+                       const mvr_shot_params *p, const float *lrf_in /* optional host, rows * 9 */, float *shot, float *lrf_out,
+                       unsigned long long *sums, uint32_t *neighbor_count);
+
 /* ---- feature matching and coarse alignment (EXTENSION: pcl::SampleConsensusPrerejective) -------------------------------
  * What brings a scan without a pose prior within the capture range of mvr_icp_align.  The reference pins no PCL version and
  * PCL was not at hand: the models are pcl/registration/impl/sample_consensus_prerejective.hpp,
@@ -577,7 +661,7 @@ int  mvr_cloud_pfh_at(mvr_ctx *ctx, int q_slot, const uint32_t *indices, size_t 
  * published; deviations are marked.
  *
  * mvr_feature_knn: exact k nearest neighbours in feature space.  q / t: host arrays, row = point, `dim` floats per row.
- * dim must be 33 (3 * MVR_FPFH_BINS) or 125 (MVR_PFH_DIM), 1 <= k <= MVR_MAX_KNN, else MVR_E_ARG
+ * dim must be 33 (3 * MVR_FPFH_BINS), 125 (MVR_PFH_DIM) or 352 (MVR_SHOT_DIM), 1 <= k <= MVR_MAX_KNN, else MVR_E_ARG
  * before any GPU work.  idx / d2: host, nq * k, row-major (either may be NULL).
  *  M1. Distance, FLANN's L2_Simple: acc = 0; for b = 0..dim - 1 { diff = q[b] - t[b]; acc = acc + diff * diff; } -- all f32,
  *      every operation rounded, in this order, never contracted.  There is no fma variant.
@@ -624,9 +708,10 @@ int  mvr_cloud_pfh_at(mvr_ctx *ctx, int q_slot, const uint32_t *indices, size_t 
  *  nr_samples outside 3..8, k outside 1..MVR_MAX_KNN, similarity outside [0, 1), max_dist not finite and > 0, or
  *  inlier_fraction outside (0, 1].  The draws, matches and polygon tests of all iterations are one launch; the surviving poses
  *  are solved on the host and scored through the kernel of mvr_pose_scores.
- * mvr_align_prerejective_dim: the same with `dim` floats per row of the two feature tables, dim = 33 or 125 (else MVR_E_ARG):
+ * mvr_align_prerejective_dim: the same with `dim` floats per row of the two feature tables, dim = 33, 125 or 352 (else MVR_E_ARG):
  * rules A1-A6 with "33" read as dim.  mvr_align_prerejective is this with dim = 33.
- * Out of scope: SampleConsensusInitialAlignment, descriptors of lengths other than 33 and 125.
+ * Out of scope: SampleConsensusInitialAlignment, descriptors of lengths other than 33, 125 and 352; MFMA and the unit-norm
+ * shortcut 2 - 2 q.t for SHOT rows (M1's sum is kept term by term at every length).
  * (CorrespondenceRejectorSampleConsensus over the matches of mvr_feature_knn is mvr_reject_sample_consensus, rules C1-C12.) */
 int  mvr_feature_knn(mvr_ctx *ctx, const float *q, size_t nq, const float *t, size_t nt, int dim, int k,
                      uint32_t *idx /* nq * k */, float *d2 /* nq * k */);

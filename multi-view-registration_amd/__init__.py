@@ -219,6 +219,11 @@ class PfhParams(C.Structure):
     _fields_ = [("radius", C.c_double), ("k", C.c_int), ("fma_dist", C.c_int)]
 
 
+class ShotParams(C.Structure):
+    """mvr_shot_params"""
+    _fields_ = [("radius", C.c_double), ("lrf_radius", C.c_double), ("fma_dist", C.c_int)]
+
+
 class RadiusParams(C.Structure):
     """mvr_radius_params"""
     _fields_ = [("radius", C.c_double), ("max_nn", C.c_uint32), ("sorted", C.c_int), ("fma_dist", C.c_int)]
@@ -276,6 +281,7 @@ SAC_MODELS = {"plane": 0, "perpendicular_plane": 1}   # mvr_sac_params.model: SA
 BOUNDARY_MIN_ANGLE = math.pi / 4   # MVR_BOUNDARY_MIN_ANGLE: the smallest angle_threshold the boundary rule accepts
 FPFH_BINS = 11          # MVR_FPFH_BINS: a signature is 3 * 11 = 33 floats
 PFH_DIM = 125           # MVR_PFH_DIM: 5 * 5 * 5 joint bins
+SHOT_DIM = 352          # MVR_SHOT_DIM: 32 volumes x 11 shape slots
 PFH_STAGE = 256         # MVR_PFH_STAGE: neighbours staged on chip; above it the tiled path
 PREREJ_MAX_SAMPLES = 8  # MVR_PREREJ_MAX_SAMPLES
 RADIUS_STAGE = 1024     # MVR_RADIUS_STAGE: entries of a radius-search row ordered on chip; above it the long-row path
@@ -330,6 +336,10 @@ SIGNATURES = {
     "mvr_cloud_estimate_normals_at": (C.c_int, [_vp, C.c_int, _u32p, C.c_size_t, C.c_int, C.POINTER(NormalParams), C.c_int, _fp, _fp]),
     "mvr_cloud_fpfh_at": (C.c_int, [_vp, C.c_int, _u32p, C.c_size_t, C.c_int, C.POINTER(FpfhParams), _fp, _u32p]),
     "mvr_cloud_pfh_at": (C.c_int, [_vp, C.c_int, _u32p, C.c_size_t, C.c_int, C.POINTER(PfhParams), _fp, _u32p, _u32p]),
+    "mvr_cloud_shot_lrf": (C.c_int, [_vp, C.c_int, C.POINTER(ShotParams), _fp, _u32p]),
+    "mvr_cloud_shot": (C.c_int, [_vp, C.c_int, C.POINTER(ShotParams), _fp, _fp, _fp, C.POINTER(C.c_uint64), _u32p]),
+    "mvr_cloud_shot_at": (C.c_int, [_vp, C.c_int, _u32p, C.c_size_t, C.c_int, C.POINTER(ShotParams), _fp, _fp, _fp,
+                                    C.POINTER(C.c_uint64), _u32p]),
     "mvr_radius_default_params": (None, [C.POINTER(RadiusParams)]),
     "mvr_radius_search": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RadiusParams), C.POINTER(C.c_uint64), _u32p, _fp, _sz, C.POINTER(_sz)]),
     "mvr_cloud_iss_keypoints": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(IssParams), C.POINTER(_sz), _u32p, _dp, _u32p, _u32p]),
@@ -1114,6 +1124,58 @@ class Context:
             res.append(nb)
         return res[0] if len(res) == 1 else tuple(res)
 
+    @staticmethod
+    def _shot_params(radius, lrf_radius, fma):
+        return ShotParams(float(radius), float(radius if lrf_radius is None else lrf_radius), int(bool(fma)))
+
+    def shot_lrf(self, slot, radius, fma=False, return_neighbors=False):
+        """pcl::SHOTLocalReferenceFrameEstimation::compute of slot against itself (rules L1-L7: mvr_cloud_shot in mvr_hip.h; no
+        normals needed): the (n, 9) float32 frames, row-major x, y, z axes, NaN where fewer than 5 OTHER points lie within radius;
+        with return_neighbors also their number, (n,) uint32."""
+        n = self.size(slot)
+        p = self._shot_params(radius, 0.0, fma)
+        out = np.empty((n, 9), np.float32)
+        nb = np.empty(n, np.uint32) if return_neighbors else None
+        _chk(_lib.mvr_cloud_shot_lrf(self._h, int(slot), C.byref(p), _p(out, C.c_float), _p(nb, C.c_uint32) if return_neighbors else None),
+             self._h)
+        return (out, nb) if return_neighbors else out
+
+    def _shot_call(self, rows, call, lrf, return_lrf, return_sums, return_neighbors):
+        fr = None
+        if lrf is not None:
+            fr = np.ascontiguousarray(lrf, np.float32)
+            if fr.shape != (rows, 9):
+                raise ValueError("lrf must be a (rows, 9) float32 table")
+        out = np.empty((rows, SHOT_DIM), np.float32)
+        lo = np.empty((rows, 9), np.float32) if return_lrf else None
+        sm = np.empty((rows, SHOT_DIM), np.uint64) if return_sums else None
+        nb = np.empty(rows, np.uint32) if return_neighbors else None
+        _chk(call(_p(fr, C.c_float) if fr is not None and rows else None, _p(out, C.c_float), _p(lo, C.c_float) if return_lrf else None,
+                  _p(sm, C.c_uint64) if return_sums else None, _p(nb, C.c_uint32) if return_neighbors else None), self._h)
+        res = [out] + [x for x, want in ((lo, return_lrf), (sm, return_sums), (nb, return_neighbors)) if want]
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def shot(self, slot, radius, lrf_radius=None, lrf=None, fma=False, return_lrf=False, return_sums=False, return_neighbors=False):
+        """pcl::SHOTEstimation::compute (SHOT352) of slot against itself with the slot's own normals (rules L1-L7 and H1-H9:
+        mvr_cloud_shot in mvr_hip.h): the (n, 352) float32 unit-norm signatures, row = point index.  lrf_radius (None: radius)
+        is setLRFRadius; lrf, an (n, 9) table, is setInputReferenceFrames (no frame is then computed).  Returns the signatures,
+        or (shot[, lrf][, sums][, neighbor_count]) with the return_* options: lrf = the frames used, sums = the (n, 352) uint64
+        fixed-point sums the rows are normalised from, neighbor_count = one uint32 per point (the point itself included)."""
+        p = self._shot_params(radius, lrf_radius, fma)
+        return self._shot_call(self.size(slot), lambda *a: _lib.mvr_cloud_shot(self._h, int(slot), C.byref(p), *a), lrf, return_lrf,
+                               return_sums, return_neighbors)
+
+    def shot_at(self, q_slot, surface_slot, radius, indices=None, lrf_radius=None, lrf=None, fma=False, return_lrf=False,
+                return_sums=False, return_neighbors=False):
+        """pcl::SHOTEstimation at the points `indices` of q_slot (None: all of them) over surface_slot and ITS normals
+        (setSearchSurface / setIndices; rules Q1-Q8): the (rows, 352) float32 signatures, row r for indices[r], and the
+        return_* options of shot(); lrf is a (rows, 9) table."""
+        _, ptr, rows = self._at_rows(q_slot, indices)
+        p = self._shot_params(radius, lrf_radius, fma)
+        return self._shot_call(rows, lambda *a: _lib.mvr_cloud_shot_at(self._h, int(q_slot), ptr, rows if ptr is not None else 0,
+                                                                       int(surface_slot), C.byref(p), *a), lrf, return_lrf, return_sums,
+                               return_neighbors)
+
     def boundary(self, slot, radius, angle_threshold=math.pi / 2, min_neighbors=0, fma=False, return_gap=False, return_counts=False):
         """pcl::BoundaryEstimation::compute of slot against itself, radius mode, with the slot's own normals (estimate_normals or
         upload_normals first): one bool per point, whether the neighbours within radius, projected onto the point's tangent
@@ -1261,7 +1323,7 @@ class Context:
         return out[0] if len(out) == 1 else tuple(out)
 
     def feature_knn(self, q, t, k):
-        """exact k nearest neighbours of every row of q among the rows of t in feature space (33 or 125 floats per row, FLANN's
+        """exact k nearest neighbours of every row of q among the rows of t in feature space (33, 125 or 352 floats per row, FLANN's
         L2_Simple in f32; rules M1-M3: mvr_feature_knn in mvr_hip.h): (idx[nq, k] uint32, d2[nq, k] float32), each row ascending
         by (d2, index); UINT32_MAX / +inf for a non-finite query row and beyond the listable targets"""
         q, t = np.ascontiguousarray(q, np.float32), np.ascontiguousarray(t, np.float32)
@@ -1284,14 +1346,14 @@ class Context:
 
     def align_prerejective(self, src, tgt, src_feat, tgt_feat, max_iterations=1000, nr_samples=3, k=2, similarity=0.9,
                            max_dist=4.0, inlier_fraction=0.25, seed=0, fma=False, guess=None, return_trace=False):
-        """pcl::SampleConsensusPrerejective::align of slot src onto slot tgt from their (n, 33) or (n, 125) descriptors (rules A1-A6:
+        """pcl::SampleConsensusPrerejective::align of slot src onto slot tgt from their (n, 33), (n, 125) or (n, 352) descriptors (rules A1-A6:
         mvr_align_prerejective in mvr_hip.h; k = setCorrespondenceRandomness).  A pure function of its arguments.  Returns a
         dict(converged, best_iteration, inliers, error, rejected, scored, T (4, 4) float32), or (that, trace) with return_trace:
         trace = dict(status[it], src[it, nr_samples], tgt[it, nr_samples], inliers[it], error[it], T[it, 4, 4])."""
         sf, tf = np.ascontiguousarray(src_feat, np.float32), np.ascontiguousarray(tgt_feat, np.float32)
         dim = sf.shape[1] if sf.ndim == 2 else 0
-        if dim not in (3 * FPFH_BINS, PFH_DIM) or sf.shape != (self.size(src), dim) or tf.shape != (self.size(tgt), dim):
-            raise ValueError("descriptors must be (n, 33) or (n, 125) float32 tables of one width, one row per point of the slot")
+        if dim not in (3 * FPFH_BINS, PFH_DIM, SHOT_DIM) or sf.shape != (self.size(src), dim) or tf.shape != (self.size(tgt), dim):
+            raise ValueError("descriptors must be (n, 33), (n, 125) or (n, 352) float32 tables of one width, one row per point of the slot")
         p = PrerejParams(int(max_iterations), int(nr_samples), int(k), float(similarity), float(max_dist), float(inlier_fraction),
                          int(seed), int(bool(fma)))
         g = to_cm(guess, np.float32) if guess is not None else None

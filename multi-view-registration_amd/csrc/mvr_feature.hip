@@ -88,8 +88,10 @@ int feature_knn_device(Ctx *c, const float *dq, size_t nq, const float *dt, size
   if (part.alloc(splits * nq * (size_t)k * sizeof(nnkey_t)) != hipSuccess) return set_error(c, MVR_E_NOMEM, "feature_knn: out of device memory");
   const dim3 grid(qblocks, (unsigned)splits);
   nnkey_t *pp = part.as<nnkey_t>();
-  // (the 125-float instantiations stand in mvr_pfh.hip, beside the descriptor they serve: this file holds the 33-float ones)
-  if (dim == kPfhDim) launch_feature_knn_pfh(c->stream, grid, dq, (uint32_t)nq, dt, (uint32_t)nt, (uint32_t)rows, k, pp);
+  // (the 125-float instantiations stand in mvr_pfh.hip and the 352-float kernel in mvr_shot.hip, beside the descriptors they
+  // serve: this file holds the 33-float ones)
+  if (dim == kShotDim) launch_feature_knn_shot(c->stream, grid, dq, (uint32_t)nq, dt, (uint32_t)nt, (uint32_t)rows, k, pp);
+  else if (dim == kPfhDim) launch_feature_knn_pfh(c->stream, grid, dq, (uint32_t)nq, dt, (uint32_t)nt, (uint32_t)rows, k, pp);
   else launch_feature_knn<kFpfhDim>(c->stream, grid, dq, (uint32_t)nq, dt, (uint32_t)nt, (uint32_t)rows, k, pp);
   switch (kmax_bucket(k)) {
     case 8:  launch_merge<8>(c->stream, qblocks, pp, (uint32_t)nq, (int)splits, k, didx, dd2); break;

@@ -1,6 +1,7 @@
 // csrc/mvr_feature_knn.h -- the all-pairs distance kernel of mvr_feature_knn (rules M1-M3 in mvr_hip.h), a template of the row
 // length, and its launch by list size.  csrc/mvr_feature.hip, where the kernel is described and its partial lists are merged,
-// instantiates the 33-float rows of FPFH; csrc/mvr_pfh.hip the 125-float rows of PFH.  Not installed.
+// instantiates the 33-float rows of FPFH; csrc/mvr_pfh.hip the 125-float rows of PFH.  The 352-float rows of SHOT have a kernel of
+// their own in csrc/mvr_shot.hip (this one keeps the query row in registers, which does not scale to them).  Not installed.
 #pragma once
 
 #include "mvr_internal.h"
@@ -8,11 +9,11 @@
 
 namespace mvr {
 
-constexpr int kFpfhDim = 3 * MVR_FPFH_BINS, kPfhDim = MVR_PFH_DIM;      // the row lengths served: 33 and 125
+constexpr int kFpfhDim = 3 * MVR_FPFH_BINS, kPfhDim = MVR_PFH_DIM, kShotDim = MVR_SHOT_DIM;      // the row lengths served: 33, 125 and 352
 constexpr int feat_pad(int dim) { return (dim + 3) / 4 * 4; }            // floats per staged row: 16-byte aligned (36, 128)
 constexpr int kFeatTile = 64;                    // target rows per LDS tile (9 KiB at 33 floats, 32 KiB at 125)
 constexpr int kFeatThreads = 256;
-inline bool feat_dim_ok(int dim) { return dim == kFpfhDim || dim == kPfhDim; }
+inline bool feat_dim_ok(int dim) { return dim == kFpfhDim || dim == kPfhDim || dim == kShotDim; }
 
 // part: [split][nq][k] keys, each list ascending
 template <int KMAX, int DIM>
@@ -83,5 +84,8 @@ void launch_feature_knn(hipStream_t st, dim3 grid, const float *q, uint32_t nq, 
 // launch_feature_knn<kPfhDim>, compiled in mvr_pfh.hip
 void launch_feature_knn_pfh(hipStream_t st, dim3 grid, const float *q, uint32_t nq, const float *t, uint32_t nt, uint32_t rows_per_split, int k,
                             nnkey_t *part);
+// the kernel for rows of kShotDim floats, in mvr_shot.hip: the same grid, the same partial lists
+void launch_feature_knn_shot(hipStream_t st, dim3 grid, const float *q, uint32_t nq, const float *t, uint32_t nt, uint32_t rows_per_split, int k,
+                             nnkey_t *part);
 
 }  // namespace mvr
