@@ -7,6 +7,7 @@
 //     size, then an LZF stream of the records re-ordered field by field (all x, all y, ...).
 //   * `points.asc` of saveRegisteredPoints (mvr/src/registrator.cpp:386-395): "%f %f %f %d %d %d\n" per point.
 //   * the dataset tree `points/object_%05d/view_%02d/points.pcd` (mvr/src/file_system_model.cpp:286,300,313).
+//   * ASCII PLY for point clouds (PointCloud::save) and, an extension, for triangle meshes (PolygonMesh: vertex + face elements).
 // PCL is not in this image, so this is a restatement of the published file format, pinned by round trips,
 // hand-written files and an independent Python decoder in tests/ (parity with PCL itself: unpinned).
 #pragma once
@@ -343,6 +344,104 @@ inline bool loadPLYFile(const std::string &filename, PointCloud<PointXYZ> &cloud
   }
   if (!have) return false;
   cloud = out;
+  return true;
+}
+
+// pcl::io::savePLYFile(filename, PolygonMesh): ASCII PLY, a vertex element with float x y z and a `face` element with
+// `property list uchar int vertex_indices` (the layout PCL's mesh writer and every mesh viewer use).  A polygon of more than
+// 255 vertices does not fit the count's type: false.  A mesh without faces writes `element face 0`.
+inline bool savePLYFile(const std::string &filename, const PolygonMesh &mesh)
+{
+  for (const Vertices &p : mesh.polygons) if (p.vertices.size() > 255) return false;
+  FILE *file = std::fopen(filename.c_str(), "w");
+  if (file == NULL) return false;
+  std::fprintf(file, "ply\nformat ascii 1.0\ncomment PCL generated\nelement vertex %zu\n", mesh.cloud.size());
+  std::fprintf(file, "property float x\nproperty float y\nproperty float z\n");
+  std::fprintf(file, "element face %zu\nproperty list uchar int vertex_indices\nend_header\n", mesh.polygons.size());
+  for (size_t i = 0; i < mesh.cloud.size(); ++i) std::fprintf(file, "%.9g %.9g %.9g\n", mesh.cloud.points[i].x, mesh.cloud.points[i].y, mesh.cloud.points[i].z);
+  for (const Vertices &p : mesh.polygons) {
+    std::fprintf(file, "%zu", p.vertices.size());
+    for (uint32_t v : p.vertices) std::fprintf(file, " %u", v);
+    std::fprintf(file, "\n");
+  }
+  const bool ok = std::ferror(file) == 0;
+  std::fclose(file);
+  return ok;
+}
+
+// the matching reader: ASCII PLY with a vertex element that has x y z among its scalar properties and, optionally, a face
+// element whose list property is named vertex_indices or vertex_index; the elements come in the header's order, other
+// elements and other properties (scalar or list) are skipped.  false -- the mesh untouched -- for a malformed, truncated or
+// binary file, a vertex element with a list property or without x y z, or a face that names a vertex that is not there.
+inline bool loadPLYFile(const std::string &filename, PolygonMesh &mesh)
+{
+  std::ifstream f(filename.c_str());
+  if (!f) return false;
+  std::string line;
+  if (!std::getline(f, line) || line.substr(0, 3) != "ply") return false;
+  struct Prop { std::string name; bool list = false; };
+  struct Elem { std::string name; size_t count = 0; std::vector<Prop> props; };
+  std::vector<Elem> elems;
+  bool ascii = false, ended = false;
+  while (std::getline(f, line)) {
+    if (!line.empty() && line[line.size() - 1] == '\r') line.erase(line.size() - 1);
+    std::istringstream ss(line);
+    std::string key; ss >> key;
+    if (key == "format") { std::string fmt; ss >> fmt; ascii = fmt == "ascii"; }
+    else if (key == "element") { Elem e; if (!(ss >> e.name >> e.count)) return false; elems.push_back(e); }
+    else if (key == "property") {
+      Prop p; std::string t;
+      if (!(ss >> t) || elems.empty()) return false;
+      if (t == "list") { std::string tc, ti; if (!(ss >> tc >> ti >> p.name)) return false; p.list = true; }
+      else if (!(ss >> p.name)) return false;
+      elems.back().props.push_back(p);
+    }
+    else if (key == "end_header") { ended = true; break; }
+  }
+  if (!ended || !ascii) return false;
+  PolygonMesh out;
+  bool have = false;
+  for (const Elem &e : elems) {
+    const bool vertex = e.name == "vertex", face = e.name == "face";
+    int ix = -1, iy = -1, iz = -1;
+    for (size_t k = 0; k < e.props.size(); ++k) {
+      if (vertex && e.props[k].list) return false;
+      if (e.props[k].name == "x") ix = (int)k;
+      if (e.props[k].name == "y") iy = (int)k;
+      if (e.props[k].name == "z") iz = (int)k;
+    }
+    if (vertex && (ix < 0 || iy < 0 || iz < 0)) return false;
+    if ((vertex || face) && e.count > (1ull << 32)) return false;
+    for (size_t i = 0; i < e.count; ++i) {
+      if (!std::getline(f, line)) return false;
+      if (!vertex && !face) continue;
+      std::istringstream ss(line);
+      double xyz[3] = {0, 0, 0};
+      for (size_t k = 0; k < e.props.size(); ++k) {
+        if (!e.props[k].list) {
+          double v; if (!(ss >> v)) return false;
+          if (vertex && (int)k == ix) xyz[0] = v;
+          if (vertex && (int)k == iy) xyz[1] = v;
+          if (vertex && (int)k == iz) xyz[2] = v;
+          continue;
+        }
+        long long cnt; if (!(ss >> cnt) || cnt < 0 || cnt > 255) return false;
+        const bool mine = face && (e.props[k].name == "vertex_indices" || e.props[k].name == "vertex_index");
+        Vertices poly;
+        for (long long j = 0; j < cnt; ++j) {
+          if (!mine) { double skip; if (!(ss >> skip)) return false; continue; }
+          long long v; if (!(ss >> v) || v < 0 || v > 0xFFFFFFFFll) return false;
+          poly.vertices.push_back((uint32_t)v);
+        }
+        if (mine) out.polygons.push_back(poly);
+      }
+      if (vertex) out.cloud.push_back(PointXYZ((float)xyz[0], (float)xyz[1], (float)xyz[2]));
+    }
+    have |= vertex;
+  }
+  if (!have) return false;
+  for (const Vertices &p : out.polygons) for (uint32_t v : p.vertices) if (v >= out.cloud.size()) return false;
+  mesh = out;
   return true;
 }
 

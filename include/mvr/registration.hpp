@@ -1253,6 +1253,94 @@ class MovingLeastSquares {
   PointIndicesPtr corresponding_ = std::make_shared<PointIndices>();
 };
 
+// ---------------------------------------------------------------- surface reconstruction
+// pcl::MarchingCubesHoppe<PointNT> (surface/marching_cubes_hoppe.h): setInputCloud, setSearchMethod (accepted, unused: the
+// search is the library's), setGridResolution, setIsoLevel, setPercentageExtendGrid, setDistanceIgnore, reconstruct.  Semantics:
+// mvr_cloud_marching_cubes_hoppe (mvr_hip.h, rules M1-M15) -- one call on the GPU per reconstruct().  PointNT: a point with x, y,
+// z and normal_x / y / z (PointNormal).  reconstruct(PolygonMesh &) fills mesh.cloud (DEVIATION: a PointCloud<PointXYZ>, see
+// PolygonMesh) and mesh.polygons; reconstruct(points, polygons) gives the vertices as PointNT with zero normals, as PCL leaves
+// them.  Without setWeld (EXTENSION, rule M13) polygon t is (3t, 3t + 1, 3t + 2) over a triangle soup, as in PCL.  A missing
+// input or a parameter outside rule M12 prints an error and leaves the outputs empty.
+template <typename PointNT>
+class MarchingCubesHoppe {
+ public:
+  typedef PointCloud<PointNT> PointCloudIn;
+  typedef typename PointCloudIn::ConstPtr PointCloudInConstPtr;
+  typedef search::KdTree<PointNT> KdTree;
+  typedef typename KdTree::Ptr KdTreePtr;
+  typedef std::shared_ptr<MarchingCubesHoppe<PointNT> > Ptr;
+
+  void setInputCloud(const PointCloudInConstPtr &c) { input_ = c; }
+  PointCloudInConstPtr getInputCloud() const { return input_; }
+  void setSearchMethod(const KdTreePtr &tree) { tree_ = tree; }
+  KdTreePtr getSearchMethod() const { return tree_; }
+  void setGridResolution(int res_x, int res_y, int res_z) { p_.res[0] = res_x; p_.res[1] = res_y; p_.res[2] = res_z; }
+  void getGridResolution(int &res_x, int &res_y, int &res_z) const { res_x = p_.res[0]; res_y = p_.res[1]; res_z = p_.res[2]; }
+  void setIsoLevel(float iso_level) { p_.iso_level = iso_level; }
+  float getIsoLevel() const { return p_.iso_level; }
+  void setPercentageExtendGrid(float percentage) { p_.percentage_extend_grid = percentage; }
+  float getPercentageExtendGrid() const { return p_.percentage_extend_grid; }
+  void setDistanceIgnore(float dist_ignore) { p_.dist_ignore = dist_ignore; }
+  float getDistanceIgnore() const { return p_.dist_ignore; }
+  void setWeld(bool weld) { p_.weld = weld ? 1 : 0; }      // EXTENSION
+  bool getWeld() const { return p_.weld != 0; }
+
+  void reconstruct(PolygonMesh &output)
+  {
+    std::vector<float> xyz;
+    run(xyz, output.polygons);
+    output.cloud.clear();
+    output.cloud.resize(xyz.size() / 3);
+    for (size_t i = 0; i < output.cloud.size(); ++i) output.cloud.points[i] = PointXYZ(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+  }
+  void reconstruct(PointCloud<PointNT> &points, std::vector<Vertices> &polygons)
+  {
+    std::vector<float> xyz;
+    run(xyz, polygons);
+    points.clear();
+    points.resize(xyz.size() / 3);
+    for (size_t i = 0; i < points.size(); ++i) points.points[i] = PointNT(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+  }
+
+ private:
+  void run(std::vector<float> &xyz, std::vector<Vertices> &polygons)
+  {
+    static_assert(detail::has_normal<PointNT>::value, "MarchingCubesHoppe needs points that carry normals");
+    xyz.clear();
+    polygons.clear();
+    if (!input_) { std::fprintf(stderr, "[pcl::MarchingCubesHoppe::reconstruct] No input dataset given!\n"); return; }
+    Device &d = Device::instance();
+    SlotGuard s;
+    detail::upload_cloud(d, s.s, *input_);
+    // a first capacity from the lattice's faces; a surface that needs more says how much (rule M11) and is asked again
+    uint64_t nt = 0, nv = 0;
+    size_t cap = 1024;
+    if (p_.res[0] >= 2 && p_.res[1] >= 2 && p_.res[2] >= 2)
+      cap = std::max<size_t>(cap, 8 * ((size_t)p_.res[0] * p_.res[1] + (size_t)p_.res[1] * p_.res[2] + (size_t)p_.res[0] * p_.res[2]));
+    std::vector<uint32_t> idx;
+    for (;;) {
+      xyz.resize(cap * 9);
+      if (p_.weld) idx.resize(cap * 3);
+      const int rc = mvr_cloud_marching_cubes_hoppe(d.ctx(), s.s, &p_, nullptr, xyz.data(), cap, p_.weld ? idx.data() : nullptr, &nt, &nv);
+      if (rc == MVR_E_ARG && nt > cap) { cap = (size_t)nt; continue; }
+      if (rc == MVR_E_ARG) { std::fprintf(stderr, "[pcl::MarchingCubesHoppe::reconstruct] %s\n", mvr_last_error(d.ctx())); xyz.clear(); return; }
+      d.check(rc, "mvr_cloud_marching_cubes_hoppe");
+      break;
+    }
+    xyz.resize((size_t)nv * 3);
+    polygons.resize((size_t)nt);
+    for (size_t t = 0; t < (size_t)nt; ++t) {
+      polygons[t].vertices.resize(3);
+      for (uint32_t k = 0; k < 3; ++k) polygons[t].vertices[k] = p_.weld ? idx[3 * t + k] : (uint32_t)(3 * t + k);
+    }
+  }
+
+  static mvr_mc_params defaults() { mvr_mc_params p; mvr_mc_default_params(&p); return p; }
+  PointCloudInConstPtr input_;
+  KdTreePtr tree_;
+  mvr_mc_params p_ = defaults();
+};
+
 // ---------------------------------------------------------------- fast point feature histograms
 // pcl::FPFHEstimation<PointInT, PointNT, PointOutT> (features/fpfh.h) in radius mode, the input cloud its own search surface:
 // setInputCloud, setInputNormals, setSearchMethod, setRadiusSearch, compute.  Semantics: mvr_cloud_fpfh (mvr_hip.h) -- one call

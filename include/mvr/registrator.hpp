@@ -543,6 +543,84 @@ class ScanCloud {
     return out;
   }
 
+  // EXTENSION (pcl::MarchingCubesHoppe on the raw points, on the GPU; rules M1-M15: mvr_cloud_marching_cubes_hoppe in mvr_hip.h):
+  // the triangle mesh of this cloud from the normals of `rich`, which must be oriented (a scan's are: estimateNormals flips
+  // them towards the sensor).  voxel_size > 0 (an extension of the extension) replaces res by ceil(extent / voxel_size) + 1 per
+  // axis, extent = the finite points' box widened by percentage_extend_grid.  Without one rich record per point, or with a
+  // parameter outside rule M12 (a lattice of more than 2^27 vertices included), it prints an error, leaves `mesh` empty and
+  // returns false.  `points`, `rich` and the pose stay as they are.
+  struct MeshParams {
+    int res[3] = {32, 32, 32};
+    float iso_level = 0.f, percentage_extend_grid = 0.f, dist_ignore = -1.f;
+    bool weld = true;              // one vertex per lattice edge (rule M13); false: PCL's triangle soup
+    double voxel_size = 0.0;       // 0: res as given
+  };
+  bool reconstructMesh(const MeshParams &mp, PolygonMesh &mesh) const
+  {
+    mesh.cloud.clear();
+    mesh.polygons.clear();
+    const size_t n = points.size();
+    if (rich.size() != n) {
+      std::fprintf(stderr, "[ScanCloud::reconstructMesh] The cloud has no normals (%zu points, %zu records): call estimateNormals first.\n", n, rich.size());
+      return false;
+    }
+    mvr_mc_params p;
+    mvr_mc_default_params(&p);
+    for (int k = 0; k < 3; ++k) p.res[k] = mp.res[k];
+    p.iso_level = mp.iso_level; p.percentage_extend_grid = mp.percentage_extend_grid; p.dist_ignore = mp.dist_ignore; p.weld = mp.weld ? 1 : 0;
+    if (mp.voxel_size != 0.0) {
+      if (!(std::isfinite(mp.voxel_size) && mp.voxel_size > 0.0) || !(mp.percentage_extend_grid >= 0.f) || !std::isfinite(mp.percentage_extend_grid)) {
+        std::fprintf(stderr, "[ScanCloud::reconstructMesh] The voxel size (%f) must be finite and > 0, the grid extension (%f) finite and >= 0.\n",
+                     mp.voxel_size, (double)mp.percentage_extend_grid);
+        return false;
+      }
+      double lo[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
+      for (const PCLPoint &q : points.points) {
+        if (!(std::isfinite(q.x) && std::isfinite(q.y) && std::isfinite(q.z))) continue;
+        const double v[3] = {q.x, q.y, q.z};
+        for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], v[k]); hi[k] = std::max(hi[k], v[k]); }
+      }
+      double cells = 1.0;
+      for (int k = 0; k < 3; ++k) {
+        const double extent = hi[k] >= lo[k] ? (hi[k] - lo[k]) * (1.0 + (double)mp.percentage_extend_grid) : 0.0;
+        const double r = std::ceil(extent / mp.voxel_size) + 1.0;
+        cells *= std::max(r, 2.0);
+        p.res[k] = (int)std::min(std::max(r, 2.0), 2147483647.0);
+      }
+      if (cells > (double)MVR_MC_MAX_VERTICES) {
+        std::fprintf(stderr, "[ScanCloud::reconstructMesh] A voxel size of %f gives a lattice of %.0f vertices, above the limit of %llu.\n", mp.voxel_size, cells,
+                     (unsigned long long)MVR_MC_MAX_VERTICES);
+        return false;
+      }
+    }
+    Device &d = Device::instance();
+    SlotGuard s;
+    d.upload(s.s, points);
+    if (n) uploadRichNormals(d, s.s);
+    uint64_t nt = 0, nv = 0;
+    size_t cap = std::max<size_t>(1024, 8 * ((size_t)std::max(p.res[0], 0) * std::max(p.res[1], 0) + (size_t)std::max(p.res[1], 0) * std::max(p.res[2], 0) +
+                                             (size_t)std::max(p.res[0], 0) * std::max(p.res[2], 0)));
+    std::vector<float> xyz;
+    std::vector<uint32_t> idx;
+    for (;;) {      // a first capacity from the lattice's faces; a surface that needs more says how much (rule M11)
+      xyz.resize(cap * 9);
+      if (p.weld) idx.resize(cap * 3);
+      const int rc = mvr_cloud_marching_cubes_hoppe(d.ctx(), s.s, &p, nullptr, xyz.data(), cap, p.weld ? idx.data() : nullptr, &nt, &nv);
+      if (rc == MVR_E_ARG && nt > cap) { cap = (size_t)nt; continue; }
+      if (rc == MVR_E_ARG) { std::fprintf(stderr, "[ScanCloud::reconstructMesh] %s\n", mvr_last_error(d.ctx())); return false; }
+      d.check(rc, "mvr_cloud_marching_cubes_hoppe");
+      break;
+    }
+    mesh.cloud.resize((size_t)nv);
+    for (size_t i = 0; i < (size_t)nv; ++i) mesh.cloud.points[i] = PCLPoint(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+    mesh.polygons.resize((size_t)nt);
+    for (size_t t = 0; t < (size_t)nt; ++t) {
+      mesh.polygons[t].vertices.resize(3);
+      for (uint32_t k = 0; k < 3; ++k) mesh.polygons[t].vertices[k] = p.weld ? idx[3 * t + k] : (uint32_t)(3 * t + k);
+    }
+    return true;
+  }
+
   // EXTENSION (pcl::BoundaryEstimation on the raw points, on the GPU; rules: mvr_cloud_boundary in mvr_hip.h): one flag per point,
   // whether its neighbours within p.radius, projected onto its tangent plane, leave an angular gap above p.angle_threshold,
   // with the normals of `rich` (estimateNormals, smooth with compute_normals, or a file that carries them).  Without one rich
@@ -1305,7 +1383,7 @@ class Registrator {
     return true;
   }
 
-  // EXTENSION, off by default: every saveRegisteredPoints below first takes the platter out of the merged cloud -- the plane
+  // EXTENSION, off by default: every saveRegisteredPoints (and saveRegisteredMesh) below first takes the platter out of the merged cloud -- the plane
   // perpendicular to the turntable axis (getAxisNormal, refined or not) within eps_angle, found by ScanCloud::removePlane with
   // SACMODEL_PERPENDICULAR_PLANE at this distance threshold.  threshold 0 switches it off again.  A merged cloud without such
   // a plane is written as it is.
@@ -1316,9 +1394,9 @@ class Registrator {
     platter_on_ = threshold != 0.0;
   }
   bool getPlatterRemoval() const { return platter_on_; }
-  size_t lastPlatterPoints() const { return platter_removed_; }      // what the last saveRegisteredPoints took out
+  size_t lastPlatterPoints() const { return platter_removed_; }      // what the last saveRegisteredPoints / saveRegisteredMesh took out
 
-  // EXTENSION, off by default: every saveRegisteredPoints below keeps only the `keep` largest Euclidean clusters of the merged
+  // EXTENSION, off by default: every saveRegisteredPoints (and saveRegisteredMesh) below keeps only the `keep` largest Euclidean clusters of the merged
   // cloud (ScanCloud::keepLargestClusters: points within `tolerance` of each other, clusters of at least min_size points) --
   // the object without the clamp, the pot rim and the speckle that stood beside it -- right after the platter removal step and
   // before any smoothing or downsampling.  tolerance 0 switches it off again.  A merged cloud without a cluster of min_size
@@ -1329,7 +1407,7 @@ class Registrator {
     isolation_on_ = tolerance != 0.0;
   }
   bool getObjectIsolation() const { return isolation_on_; }
-  size_t lastIsolationDropped() const { return isolation_dropped_; }      // what the last saveRegisteredPoints took out
+  size_t lastIsolationDropped() const { return isolation_dropped_; }      // what the last saveRegisteredPoints / saveRegisteredMesh took out
 
   // ---- the merged object (registrator.cpp:344-400, the step registration() ends with, :719-744): every registered
   // view's points (and normals) moved by its pose -- the normals by the FULL affine including the translation, as
@@ -1400,6 +1478,37 @@ class Registrator {
     const size_t n = merged.rich.size();
     if (merged_out) merged_out->swap(merged.rich);
     return ok ? n : 0;
+  }
+
+  // EXTENSION: the surface of the merged object -- the merged cloud of saveRegisteredPoints, after the same platter removal and
+  // isolation steps when they are on, put through ScanCloud::reconstructMesh with its merged (full-affine-moved) normals and
+  // written as <folder>/mesh.ply beside points.pcd (io::savePLYFile: ASCII, vertex + face elements).  mesh_out receives the
+  // mesh as written.  Returns the number of triangles written.  NOTE: the merged normals are moved by the FULL affine, as the
+  // reference moves them (mergeRegisteredPoints): a pose with a translation adds it to the normal and so turns it, and the signed
+  // distances of rule M5 are then wrong near that view's points -- the mesh is meaningful for views whose poses are pure rotations
+  // (or whose normals are estimated again on the merged cloud).  A merge without normals -- a registered view that holds XYZ
+  // points only, or no registered view at all -- writes nothing and returns 0, and so does a refusal of reconstructMesh.
+  size_t saveRegisteredMesh(int object, const std::string &folder, const ScanCloud::MeshParams &params, PolygonMesh *mesh_out = nullptr)
+  {
+    bool normals = false;
+    for (int v = 0; v < model_->numViews(); ++v) {
+      const ScanCloud &pc = model_->getPointCloud(object, v);
+      if (!pc.isRegistered()) continue;
+      if (pc.rich.size() != pc.size()) { normals = false; break; }
+      normals = normals || pc.size() > 0;
+    }
+    if (!normals) return 0;
+    ScanCloud merged;
+    mergeRegisteredPoints(object, merged.rich);
+    for (const io::RichPoint &q : merged.rich) merged.points.push_back(PCLPoint(q.x, q.y, q.z));
+    removePlatter(merged);
+    isolateObject(merged);
+    PolygonMesh mesh;
+    if (!merged.reconstructMesh(params, mesh)) return 0;
+    if (!io::savePLYFile(folder + "/mesh.ply", mesh)) return 0;
+    const size_t n = mesh.polygons.size();
+    if (mesh_out) { mesh_out->cloud = mesh.cloud; mesh_out->polygons.swap(mesh.polygons); }
+    return n;
   }
 
   // ---- Registrator::registration (registrator.cpp:719-744): denoise every view, give it its prior, mark it

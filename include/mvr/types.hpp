@@ -161,6 +161,23 @@ class PointCloud {
   Ptr makeShared() const { return Ptr(new PointCloud<PointT>(*this)); }
 };
 
+// pcl::Vertices: the vertex indices of one polygon
+struct Vertices {
+  typedef std::shared_ptr<Vertices> Ptr;
+  typedef std::shared_ptr<const Vertices> ConstPtr;
+  std::vector<uint32_t> vertices;
+};
+
+// pcl::PolygonMesh: a cloud of vertices and the polygons over it (what MarchingCubesHoppe::reconstruct fills,
+// mvr_cloud_marching_cubes_hoppe in mvr_hip.h).  DEVIATION: PCL's `cloud` is a type-erased pcl::PCLPointCloud2 that callers
+// convert with fromPCLPointCloud2; here it is the PointCloud<PointXYZ> that conversion would give.
+struct PolygonMesh {
+  typedef std::shared_ptr<PolygonMesh> Ptr;
+  typedef std::shared_ptr<const PolygonMesh> ConstPtr;
+  PointCloud<PointXYZ> cloud;
+  std::vector<Vertices> polygons;
+};
+
 // pcl::Correspondence {index_query, index_match, distance}; `distance` holds
 // the SQUARED distance, as PCL's correspondence estimation stores it.
 struct Correspondence {

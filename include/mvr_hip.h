@@ -1597,6 +1597,74 @@ int  mvr_world_ring_run(mvr_world *w, int n_steps, int n_views, const int *posed
 /* pcl::getTransformation(x,y,z,roll,pitch,yaw) -> column-major 4x4. */
 void mvr_pose_to_mat4(const double pose[6], double T[16]);
 
+/* ---- surface reconstruction (EXTENSION: pcl::MarchingCubesHoppe) -----------------------------------------------------------
+ * The triangle mesh of a cloud that carries oriented normals: a lattice over the cloud's box, at every lattice vertex the signed
+ * distance to the tangent plane of the nearest point, marching cubes over the lattice.  PCL was not at hand and the reference pins
+ * no version; the rules restate pcl/surface/impl/marching_cubes.hpp and marching_cubes_hoppe.hpp (1.8 and later) as published:
+ * PARITY WITH PCL UNPINNED.
+ *  M1. Input: the cloud in `slot` with its normals.  A slot without normals is MVR_E_ARG before any GPU work; an empty slot is
+ *      MVR_OK with zero triangles (grid_out, when given, is filled with NaN).
+ *  M2. Box: lower / upper = the f32 componentwise min / max over the FINITE points (the library's rule; N5 applies), then
+ *      ext = (0.5f * percentage_extend_grid) * (upper - lower), lower -= ext, upper += ext.  Every operation is rounded to f32 and
+ *      no fma is used anywhere in M2-M8.
+ *  M3. Voxel size: size = (upper - lower) / (float)res per axis -- by res, not res - 1: the lattice stops one voxel short of
+ *      upper (PCL's behaviour, and why callers extend the grid).
+ *  M4. Lattice vertex (x, y, z), 0 <= x < res_x ..., lies at v = lower + size * (float)i per axis (the multiply, then the add);
+ *      its value is grid[x * res_y * res_z + y * res_z + z].
+ *  M5. Value: with (j, d2) = mvr_nn's answer for v in the slot (the library's f32 d2, fma_dist as everywhere, ties to the lowest
+ *      index, N1 for non-finite points) the value is NaN when there is no finite point; when dist_ignore > 0 and not
+ *      d2 < dist_ignore (the SQUARED distance against dist_ignore: PCL's quirk, kept); when n_j.x is NaN; when the f32 norm
+ *      sqrt((nx*nx + ny*ny) + nz*nz) of n_j is not > 0.5f.  Otherwise it is (n.x * dx + n.y * dy) + n.z * dz with d = v - p_j.
+ *  M6. Cells (x, y, z), every index below res - 1, in x-major, z-fastest order.  Corners 0..7 at the offsets (0,0,0) (1,0,0)
+ *      (1,0,1) (0,0,1) (0,1,0) (1,1,0) (1,1,1) (0,1,1).  A cell with a NaN corner emits nothing; cube |= 1 << i when
+ *      value[i] < iso_level.
+ *  M7. Corner positions: c = lower + size * index per axis; a corner is c plus size on the axes its offset is 1 on (one add).
+ *  M8. Edges 0..11 join the corners 0-1 1-2 2-3 3-0 4-5 5-6 6-7 7-4 0-4 1-5 2-6 3-7.  Edge a-b gives
+ *      mu = (iso - va) / (vb - va) and p = pa + mu * (pb - pa) on all three axes, always in that direction: neighbouring cells
+ *      compute a shared edge in opposite directions and may differ in the last bit (PCL's behaviour, kept).
+ *  M9. Output: the triangles of a cell in the case table's order, cells in M6's order; 3 * T vertices (xyz f32), polygon t is
+ *      (3t, 3t + 1, 3t + 2).  A second run gives the same bits; the result depends neither on the resolution of the slot's grid
+ *      nor on a tune key ("mc_route" included).
+ * M10. Case tables: Lorensen / Bourke's edgeTable[256] and triTable[256][16], which PCL carries verbatim, written out once in
+ *      csrc/mvr_mc_tables.h; mvr_mc_case hands a row to the host (what the tests and the numpy reference read).
+ * M11. Sizing (the pattern of RS7): *n_triangles is written by every call that gets as far as the count (64-bit);
+ *      vertices == NULL is a count-only call (*n_vertices = 3 T); capacity_triangles < T returns MVR_E_ARG with the counts
+ *      written and nothing else.  grid_out: optional host array of res_x * res_y * res_z floats that receives the values.
+ * M12. MVR_E_ARG before any GPU work, nothing written: a NULL ctx or params, a bad slot, a res below 2, res_x * res_y * res_z
+ *      above 2^27, a non-finite iso_level or percentage_extend_grid, a negative percentage_extend_grid, a NaN dist_ignore
+ *      (dist_ignore <= 0: no limit; PCL's default is -1), weld with vertices but without indices.
+ * M13. Weld (EXTENSION, weld = 1): soup vertices on the same lattice edge become one; the key is 3 * (the 1-D index of M4 of the
+ *      edge's lower vertex) + axis, not coordinates.  A welded vertex takes the position computed by the first soup corner that
+ *      uses it; welded vertices are numbered in order of first use; polygons keep M9's order with the new indices; a triangle
+ *      whose three indices are not all different is kept.  `vertices` then receives the n_vertices welded positions (it still
+ *      needs room for 3 * capacity_triangles) and `indices` 3 * T u32.  Weld needs 3 * T < 2^31, else MVR_E_ARG after the count.
+ * M14. Neither the slot nor its normals are modified (the slot gets its own-coordinates grid as in mvr_knn).
+ * M15. An axis with upper == lower has size 0: M3-M8 literally, every vertex at the same position on that axis.
+ * The search: tune key "mc_route" 0 (default) takes the walk of the cloud's own grid with a one-entry list that starts at the cap
+ * when dist_ignore > 0, and otherwise the culled search behind mvr_nn over the lattice as query sets of at most 2^23 vertices
+ * (a cloud that holds a non-finite point, for which that search has no rule, and a context in brute-force mode take the tiled
+ * exact search in launches of at most 2^38 point pairs); 1 / 2 / 3 force the walk / the culled / the tiled search.  All give
+ * mvr_nn's (j, d2) wherever the value is not NaN.  HAZARD: "mc_route" 1 WITHOUT a cap sends unbounded queries through the shell
+ * walk -- exact, but a vertex far from the surface looks up millions of cells; it is there for the tests.  mvr_ctx_stat
+ * "mc_route_used", and with tune "mc_clock" = 1 "mc_search_ms" / "mc_values_ms" / "mc_classify_ms" / "mc_emit_ms" /
+ * "mc_weld_ms" / "mc_copy_ms". */
+#define MVR_MC_MAX_VERTICES (1ull << 27)   /* M12: the most lattice vertices of one call */
+typedef struct {
+  int   res[3];                  /* setGridResolution: lattice vertices per axis, >= 2                 */
+  float iso_level;               /* setIsoLevel                                                        */
+  float percentage_extend_grid;  /* setPercentageExtendGrid: finite, >= 0                              */
+  float dist_ignore;             /* setDistanceIgnore: <= 0 no limit; compared with the SQUARED distance */
+  int   weld;                    /* EXTENSION (M13)                                                    */
+  int   fma_dist;
+} mvr_mc_params;
+void mvr_mc_default_params(mvr_mc_params *p);   /* PCL's: 32, 32, 32, 0, 0, -1; weld 0, fma_dist 0 */
+/* row `cube` (0..255) of the case tables: *edges = edgeTable[cube], tri = triTable[cube]; host only, no GPU */
+int  mvr_mc_case(int cube, uint16_t *edges, int8_t tri[16]);
+int  mvr_cloud_marching_cubes_hoppe(mvr_ctx *ctx, int slot, const mvr_mc_params *p, float *grid_out /* or NULL */,
+                                    float *vertices /* 9 * capacity_triangles floats, or NULL */, size_t capacity_triangles,
+                                    uint32_t *indices /* weld only: 3 * capacity_triangles */, uint64_t *n_triangles,
+                                    uint64_t *n_vertices);
+
 /* ---- turntable prior (PointCloud::initRotation point_cloud.cpp:400-413,
  *      Registrator::getRotationMatrix registrator.cpp:331-342) --------------- */
 double mvr_turntable_angle(int view, int n_views);
@@ -1692,7 +1760,11 @@ enum { MVR_K_NN = 0, MVR_K_REDUCE = 1, MVR_K_XFORM = 2, MVR_K_GLUE = 3,
  * plane segmentation: "sac_chunk" (attempts generated and scored per chunk, 1..256; 0, default: 64 for the first chunk of a
  * call and 256 from then on);
  * the sample-consensus rejector: "rej_sac_chunk" (attempts generated and scored per chunk, 1..256; 0, default: 64 for the first
- * chunk of a stage and 256 from then on -- measured, profiles/reject_sac_bench.json).
+ * chunk of a stage and 256 from then on -- measured, profiles/reject_sac_bench.json);
+ * marching cubes: "mc_route" (the search behind the lattice values: 0, default, by dist_ignore; 1 the own-grid walk -- without a
+ * dist_ignore it is slow beyond use on anything but a test cloud --; 2 the culled search; 3 the tiled exact search; see
+ * mvr_cloud_marching_cubes_hoppe), "mc_clock" (1: the call waits after each stage and records its wall milliseconds for the
+ * "mc_*_ms" stats; 0, default: no waits).
  * Results never depend on them. */
 int  mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value);
 /* wall milliseconds of every pass of the LAST mvr_ring_run / mvr_ring_run_sharded on this context (from the end of the

@@ -229,6 +229,12 @@ class RadiusParams(C.Structure):
     _fields_ = [("radius", C.c_double), ("max_nn", C.c_uint32), ("sorted", C.c_int), ("fma_dist", C.c_int)]
 
 
+class McParams(C.Structure):
+    """mvr_mc_params"""
+    _fields_ = [("res", C.c_int * 3), ("iso_level", C.c_float), ("percentage_extend_grid", C.c_float), ("dist_ignore", C.c_float),
+                ("weld", C.c_int), ("fma_dist", C.c_int)]
+
+
 class IssParams(C.Structure):
     """mvr_iss_params"""
     _fields_ = [("salient_radius", C.c_double), ("non_max_radius", C.c_double), ("gamma_21", C.c_double), ("gamma_32", C.c_double),
@@ -285,6 +291,7 @@ SHOT_DIM = 352          # MVR_SHOT_DIM: 32 volumes x 11 shape slots
 PFH_STAGE = 256         # MVR_PFH_STAGE: neighbours staged on chip; above it the tiled path
 PREREJ_MAX_SAMPLES = 8  # MVR_PREREJ_MAX_SAMPLES
 RADIUS_STAGE = 1024     # MVR_RADIUS_STAGE: entries of a radius-search row ordered on chip; above it the long-row path
+MC_MAX_VERTICES = 1 << 27   # MVR_MC_MAX_VERTICES: the most lattice vertices of one marching-cubes call (rule M12)
 RADIUS_MAX_TOTAL = 0x7FFFFFFF   # MVR_RADIUS_MAX_TOTAL: the most entries one mvr_radius_search returns (rule RS8)
 
 
@@ -342,6 +349,10 @@ SIGNATURES = {
                                     C.POINTER(C.c_uint64), _u32p]),
     "mvr_radius_default_params": (None, [C.POINTER(RadiusParams)]),
     "mvr_radius_search": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RadiusParams), C.POINTER(C.c_uint64), _u32p, _fp, _sz, C.POINTER(_sz)]),
+    "mvr_mc_default_params": (None, [C.POINTER(McParams)]),
+    "mvr_mc_case": (C.c_int, [C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_int8)]),
+    "mvr_cloud_marching_cubes_hoppe": (C.c_int, [_vp, C.c_int, C.POINTER(McParams), _fp, _fp, _sz, _u32p, C.POINTER(C.c_uint64),
+                                                 C.POINTER(C.c_uint64)]),
     "mvr_cloud_iss_keypoints": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(IssParams), C.POINTER(_sz), _u32p, _dp, _u32p, _u32p]),
     "mvr_cloud_iss_keypoints_border": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(IssParams), C.POINTER(IssBorderParams), C.POINTER(_sz), _u32p,
                                                  _dp, _u32p, _u32p, _u8p, _u8p]),
@@ -500,6 +511,14 @@ def from_cm(v):
 
 
 # --------------------------------------------------------------- host helpers
+
+def mc_case(cube):
+    """mvr_mc_case: row `cube` (0..255) of the marching-cubes case tables (rule M10) -> (edge bits, int8[16] edge triples,
+    -1 terminated); host only"""
+    e, t = C.c_uint16(), np.empty(16, np.int8)
+    _chk(_lib.mvr_mc_case(int(cube), C.byref(e), _p(t, C.c_int8)))
+    return int(e.value), t
+
 
 def icp_params(reciprocal=True, max_dist=4.0, max_iter=10, teps=1e-6, feps=64.0, fma=False, point_to_plane=False):
     """Defaults = the reference's settings at mvr/src/registrator.cpp:551-560
@@ -867,6 +886,40 @@ class Context:
         idx, d2 = np.empty((n, k), np.uint32), np.empty((n, k), np.float32)
         _chk(_lib.mvr_knn(self._h, q_slot, t_slot, int(k), int(fma), _p(idx, C.c_uint32), _p(d2, C.c_float)), self._h)
         return idx, d2
+
+    def marching_cubes_hoppe(self, slot, res=(32, 32, 32), iso_level=0.0, percentage_extend_grid=0.0, dist_ignore=-1.0, weld=False,
+                             return_grid=False, fma=False, count_only=False):
+        """pcl::MarchingCubesHoppe::reconstruct of the cloud in slot with its normals (rules M1-M15:
+        mvr_cloud_marching_cubes_hoppe in mvr_hip.h) -> (vertices (3 T, 3) float32, polygons (T, 3) uint32[, grid res float32]);
+        polygon t of the soup is (3t, 3t + 1, 3t + 2).  weld: the welded vertices (V, 3) and the polygons over them (M13).
+        count_only: (T[, grid])."""
+        res = tuple(int(r) for r in res)
+        if len(res) != 3:
+            raise ValueError("res must have three entries")
+        p = McParams((C.c_int * 3)(*res), float(iso_level), float(percentage_extend_grid), float(dist_ignore), int(bool(weld)), int(bool(fma)))
+        lattice = res[0] * res[1] * res[2]
+        grid = np.empty(res, np.float32) if return_grid and min(res) >= 2 and lattice <= MC_MAX_VERTICES else None
+        gp = _p(grid, C.c_float) if grid is not None else None
+        T, V = C.c_uint64(0), C.c_uint64(0)
+        if count_only:
+            _chk(_lib.mvr_cloud_marching_cubes_hoppe(self._h, int(slot), C.byref(p), gp, None, 0, None, C.byref(T), C.byref(V)), self._h)
+            return (int(T.value), grid) if return_grid else int(T.value)
+        # a first capacity from the lattice's faces; a surface that needs more says how much (M11) and is asked again
+        cap = max(1024, 8 * (res[0] * res[1] + res[1] * res[2] + res[0] * res[2])) if min(res) >= 2 else 1
+        while True:
+            verts = np.empty((3 * cap, 3), np.float32)
+            idx = np.empty(3 * cap, np.uint32) if weld else None
+            rc = _lib.mvr_cloud_marching_cubes_hoppe(self._h, int(slot), C.byref(p), gp, _p(verts, C.c_float), cap,
+                                                     _p(idx, C.c_uint32) if weld else None, C.byref(T), C.byref(V))
+            if rc == E_ARG and int(T.value) > cap:
+                cap = int(T.value)
+                continue
+            _chk(rc, self._h)
+            break
+        t, v = int(T.value), int(V.value)
+        polys = idx[:3 * t].reshape(t, 3).copy() if weld else np.arange(3 * t, dtype=np.uint32).reshape(t, 3)
+        out = (verts[:v].copy(), polys)
+        return out + (grid,) if return_grid else out
 
     def radius_search(self, q_slot, t_slot, radius, max_nn=0, sorted=True, fma=False, count_only=False):
         """pcl::search::KdTree::radiusSearch of every point of q_slot in t_slot, as CSR lists (rules RS1-RS11: mvr_radius_search

@@ -2045,6 +2045,8 @@ API int mvr_ctx_tune(mvr_ctx *ctx, const char *key, int value)
   else if (!std::strcmp(key, "at_sort")) c->at_sort = value != 0;
   else if (!std::strcmp(key, "at_clock")) c->at_clock = value != 0;
   else if (!std::strcmp(key, "radius_stage")) { if (value < MVR_MAX_KNN || value > MVR_RADIUS_STAGE) return MVR_E_ARG; c->radius_stage = value; }
+  else if (!std::strcmp(key, "mc_route")) { if (value < 0 || value > 3) return MVR_E_ARG; c->mc_route = value; }
+  else if (!std::strcmp(key, "mc_clock")) c->mc_clock = value != 0;
   else if (!std::strcmp(key, "score_chunk")) { if (value < 1 || value > 65535) return MVR_E_ARG; c->score_chunk = value; }
   else if (!std::strcmp(key, "sac_chunk")) { if (value < 0 || value > 256) return MVR_E_ARG; c->sac_chunk = value; }
   else if (!std::strcmp(key, "rej_sac_chunk")) { if (value < 0 || value > 256) return MVR_E_ARG; c->rej_sac_chunk = value; }
@@ -2103,6 +2105,14 @@ API int mvr_ctx_stat(mvr_ctx *ctx, const char *key, double *value)
   else if (!std::strcmp(key, "radius_count_ms")) *value = c->radius_ms[0];
   else if (!std::strcmp(key, "radius_fill_ms")) *value = c->radius_ms[1];
   else if (!std::strcmp(key, "radius_copy_ms")) *value = c->radius_ms[2];
+  else if (!std::strcmp(key, "mc_route")) *value = (double)c->mc_route;
+  else if (!std::strcmp(key, "mc_route_used")) *value = (double)c->mc_route_used;
+  else if (!std::strcmp(key, "mc_search_ms")) *value = c->mc_ms[0];
+  else if (!std::strcmp(key, "mc_values_ms")) *value = c->mc_ms[1];
+  else if (!std::strcmp(key, "mc_classify_ms")) *value = c->mc_ms[2];
+  else if (!std::strcmp(key, "mc_emit_ms")) *value = c->mc_ms[3];
+  else if (!std::strcmp(key, "mc_weld_ms")) *value = c->mc_ms[4];
+  else if (!std::strcmp(key, "mc_copy_ms")) *value = c->mc_ms[5];
   else if (!std::strcmp(key, "prerej_match_ms")) *value = c->prerej_ms[0];
   else if (!std::strcmp(key, "prerej_hypotheses_ms")) *value = c->prerej_ms[1];
   else if (!std::strcmp(key, "prerej_score_ms")) *value = c->prerej_ms[2];

@@ -288,6 +288,12 @@ struct Ctx {
   int radius_stage = MVR_RADIUS_STAGE;                   // neighbours a radius-search row stages (and orders) in LDS; above it the long-row path (tune "radius_stage")
   uint64_t radius_long_rows = 0;                         // of the last mvr_radius_search: rows on the long-row path
   double radius_ms[3] = {0.0, 0.0, 0.0};                 // ... and its wall milliseconds: the count (to the read-back of the total), the fill and ordering, the copies home
+  // marching cubes (mvr_mc.hip): which search answers the lattice vertices (tune "mc_route": 0 = by dist_ignore, 1 = the walk of
+  // the cloud's own grid, 2 = the culled search over slabs of the lattice, 3 = the tiled exact search of mvr_nn.hip; no result
+  // depends on it), the route the last call took, whether the stages are timed (tune "mc_clock"), and their wall milliseconds:
+  // search, values, classify + scan, emit, weld, copies home
+  int mc_route = 0, mc_route_used = 0, mc_clock = 0;
+  double mc_ms[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   uint64_t pfh_tiled = 0, pfh_pairs = 0;                 // of the last mvr_cloud_pfh: queries on the tiled path, pairs of all queries
   int at_sort = 1;                                       // the _at entries sort their queries by the surface's cells (tune "at_sort"); results never depend on it
   uint64_t fpfh_at_marked = 0;                           // of the last mvr_cloud_fpfh_at: surface points whose SPFH row was computed
